@@ -13,7 +13,15 @@ dense Adam over the whole table (run_pipeline_lightgcn.py:117-159).
                          3-layer D=128 (SURVEY 8d "C2": symmetric adjacency nnz=20M, B=16384).  At N>1 every rank
                          owns its own 1M-user / 10M-edge shard of a weak-scaled graph: "scaling": "weak".
 
-The default N=1 run carries, after the timed region, the metric's other configurations as blocks of the same JSON line:
+A plain run does only what the headline needs: it builds the workload, runs W warm-up and K timed steps, writes the last
+step's outputs when --dump-outputs DIR is given, and prints the line.
+
+  --dump-outputs DIR     after the timed steps: DIR/loss.npy (the last step's loss) and DIR/users_emb.npy, DIR/items_emb.npy
+                         (the trained embedding rows, original ids, of a fixed seeded sample of at most DUMP_ROWS rows per
+                         table), float32; the inputs are seeded, so two builds can be compared output for output.
+
+--full adds everything else: the headline's roofline (HIP events around every propagate launch of the timed steps) and, at
+N=1, the metric's other configurations as blocks of the same JSON line, after the timed region:
   "c2"         BASELINE configs[1] on one GPU (--steps/--warmup as the headline; ms/step, positive-edges/s, roofline with
                live PMC traffic, plain_step_ms, cpu_baseline); with --config c2 the side block is "c4_n1"
                                                                                              [--no-side to skip]
@@ -27,11 +35,12 @@ The default N=1 run carries, after the timed region, the metric's other configur
   "map_at_12"  ranking quality on a PLANTED-structure graph (synthetic.SyntheticSpec.communities), layer-0 predictor vs
                propagated embeddings vs popularity                                           [--no-map to skip]
 
-roofline.traffic is measured in THIS invocation: before the parent touches the GPU it runs itself twice per
+With --full, roofline.traffic is measured in THIS invocation: before the parent touches the GPU it runs itself twice per
 configuration as a short child under `rocprofv3 --pmc FETCH_SIZE` / `--pmc WRITE_SIZE` (separate passes, no trace
 domains) and reads the per-dispatch counters of the propagate kernels.                       [--no-pmc to skip]
 
-Launch: python bench.py --gpus N --steps K --warmup W      (N>1: the parent starts N worker processes itself, before
+Launch: python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
+                                                           (N>1: the parent starts N worker processes itself, before
         touching the GPU) or, equivalently, python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 Prints ONE JSON line (rank 0).
 """
@@ -58,6 +67,10 @@ HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md); the guide
 C4_GLOBAL_BATCH = 131072
 # the planted-structure graph of the MAP@12 leg: small enough that 100 steps are a few epochs
 MAP_SPEC = dict(num_users=50_000, num_items=5_000, num_edges=1_000_000, seed=5, communities=32, community_mix=0.9, deg_max=2000)
+# --dump-outputs: rows kept per embedding table (16 MiB per table at D = 128; fewer rows at a larger D), and their seed
+DUMP_ROWS = 32768
+DUMP_BYTES_PER_TABLE = 16 << 20
+DUMP_SEED = 2024
 
 
 def parse_args():
@@ -72,6 +85,12 @@ def parse_args():
     ap.add_argument("--dim", type=int, default=128)
     ap.add_argument("--layers", type=int, default=3)
     ap.add_argument("--batch", type=int, default=None, help="positive edges per GPU (c2) / per job (c4)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: roofline, live PMC traffic, CPU baselines, plain-step leg, the other LightGCN "
+                         "configuration and the ranker / PinSAGE / e2e / top-K / MAP@12 blocks (the --no-* switches below "
+                         "skip parts of it; without --full none of it runs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's loss and a fixed sample of the trained embedding rows to DIR/*.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--plain-leg", action="store_true", help="time the straightforward step as plain_step_ms for --config c4 too")
     ap.add_argument("--plain-step", action="store_true",
@@ -225,14 +244,16 @@ def build_workload(config: str, args, world: int, rank: int, dev, plain: bool = 
                 table0=table0, t_gen=t_gen, strong=strong)
 
 
-def timed_steps(trainer, steps: int, warmup: int, sync):
-    """W untimed + K timed steps bracketed by sync(); returns (elapsed s, per-step ms sorted, spmm events, last loss)."""
+def timed_steps(trainer, steps: int, warmup: int, sync, launch_events: bool = True):
+    """W untimed + K timed steps bracketed by sync(); returns (elapsed s, per-step ms sorted, spmm events, last loss).
+    launch_events=False: no events around the propagate launches (the roofline's input), events is then None."""
     import torch as t
     from laplace_amd import ops
     for _ in range(warmup):
         trainer.step()
     sync()
-    ops.SPMM_EVENTS = []  # (start, end) HIP events around every propagate launch, on the launch stream
+    # (start, end) HIP events around every propagate launch, on the launch stream
+    ops.SPMM_EVENTS = [] if launch_events else None
     marks = [t.cuda.Event(enable_timing=True) for _ in range(steps + 1)]  # per-step spread; no sync inside the loop
     t0 = time.perf_counter()
     marks[0].record()
@@ -245,6 +266,24 @@ def timed_steps(trainer, steps: int, warmup: int, sync):
     per_step = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(steps))
     events, ops.SPMM_EVENTS = ops.SPMM_EVENTS, None
     return elapsed, per_step, events, loss
+
+
+def dump_outputs(out_dir: str, trainer, model, loss) -> None:
+    """--dump-outputs: what a caller of the timed path holds after its last step, as float32 .npy files: the step's loss and
+    the trained parameters (the model's two embedding tables, rows under their original ids).  A table of more than
+    DUMP_ROWS rows is sampled: the same seeded, sorted row set on every run with the same arguments."""
+    import numpy as np
+    import torch as t
+    os.makedirs(out_dir, exist_ok=True)
+    trainer.to_original_order()   # the next step() puts the rows back into training order itself
+    arrays = {"loss": loss.detach().reshape(-1)}
+    for name, w in (("users_emb", model.users_emb.weight), ("items_emb", model.items_emb.weight)):
+        n = w.shape[0]
+        keep = min(n, DUMP_ROWS, DUMP_BYTES_PER_TABLE // (4 * w.shape[1]))
+        rows = t.randperm(n, generator=t.Generator().manual_seed(DUMP_SEED))[:keep].sort().values if keep < n else t.arange(n)
+        arrays[name] = w.detach()[rows.to(w.device)]
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a.to(t.float32).cpu().numpy())
 
 
 def roofline_block(events, nnz: int, n_rows: int, D: int, steps: int, traffic, traffic_src) -> dict:
@@ -554,8 +593,8 @@ def main():
     pmc = {}
     side = "c2" if args.config == "c4" else "c4"     # the other LightGCN configuration rides as a block at N = 1
     custom_size = any(v is not None for v in (args.users, args.items, args.edges, args.batch)) or args.uniform
-    want_side = world_env == 1 and not args.no_side and not args.pmc_child and not args.plain_step and not custom_size
-    if world_env == 1 and not args.no_pmc and not args.pmc_child and not args.plain_step:
+    want_side = args.full and world_env == 1 and not args.no_side and not args.pmc_child and not args.plain_step and not custom_size
+    if args.full and world_env == 1 and not args.no_pmc and not args.pmc_child and not args.plain_step:
         passthrough = []
         for flag, val in (("--users", args.users), ("--items", args.items), ("--edges", args.edges), ("--batch", args.batch)):
             if val is not None:
@@ -589,7 +628,7 @@ def main():
 
     if os.environ.get("LAPLACE_SPMM_TWO_STREAMS") is not None:  # A/B switch
         ops.SPMM_TWO_STREAMS = int(os.environ["LAPLACE_SPMM_TWO_STREAMS"] or 0)   # 1: short rows enqueued first, 2: split rows first
-    want_cpu = rank == 0 and world == 1 and not args.no_cpu_baseline and not args.pmc_child
+    want_cpu = args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not args.pmc_child
     tl = time.perf_counter()
     w = build_workload(args.config, args, world, rank, dev, plain=args.plain_step, want_table0=want_cpu)
     tl = _leg("import_and_graph_setup", tl)
@@ -604,10 +643,13 @@ def main():
             dist.barrier()
         t.cuda.synchronize()
 
-    elapsed, per_step, events, loss = timed_steps(trainer, args.steps, args.warmup, sync)
+    elapsed, per_step, events, loss = timed_steps(trainer, args.steps, args.warmup, sync, launch_events=args.full or args.pmc_child)
     if args.pmc_child:   # the profiler has what it came for
         return
     tl = _leg("trainer_setup_and_timed_region", tl)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, trainer, model, loss)
+        tl = _leg("dump_outputs", tl)
     pct = lambda q: per_step[min(len(per_step) - 1, int(q * len(per_step)))]
     loss_val = float(loss)
 
@@ -623,7 +665,7 @@ def main():
             traffic, _, traffic_src = pmc[args.config]
             if traffic is None:
                 traffic_src = f"live PMC passes failed ({traffic_src})"
-        if traffic is None and world == 1:
+        if args.full and traffic is None and world == 1:
             off, off_src = offline_traffic(default_workload, args.config)
             if off is not None:
                 traffic, traffic_src = off, off_src
@@ -649,15 +691,15 @@ def main():
                                     f"BPR + dense Adam; BASELINE.json configs[1]"),
                        "parallelism": "1 GPU" if world == 1 else f"user-sharded x{world}, items replicated, "
                                                                  f"{'RCCL' if backend == 'nccl' else backend} all-reduce of item rows per layer"},
-            "roofline": roofline_block(events, nnz, n_rows, D, args.steps, traffic, traffic_src),
+            **({"roofline": roofline_block(events, nnz, n_rows, D, args.steps, traffic, traffic_src)} if args.full else {}),
             "step_form": "plain" if args.plain_step else "sparse_batch",
             "node_order": "locality (items by popularity, users by coldest item)" if getattr(trainer, "order", None) is not None else "generator ids",
             "loss": loss_val, "graph_gen_s": round(w["t_gen"], 1), "backend": backend if world > 1 else None,
         }
 
-    # ---- extra legs, N=1 only, after the timed region ------------------------------------------------
+    # ---- extra legs (--full), N=1 only, after the timed region ----------------------------------------
     tl = time.perf_counter()
-    if world == 1 and not args.plain_step and not args.no_plain_leg and (args.config == "c2" or args.plain_leg):
+    if args.full and world == 1 and not args.plain_step and not args.no_plain_leg and (args.config == "c2" or args.plain_leg):
         trainer.to_original_order()  # the second trainer relabels the table itself
         out["plain_step_ms"] = plain_step_leg(model, adj, inter, B, args.steps, args.warmup)
         out["plain_step_positive_edges_per_s"] = B * 1e3 / out["plain_step_ms"]
@@ -666,7 +708,7 @@ def main():
         trainer.finish()
         out["cpu_baseline"] = cpu_baseline_for(args.config, args, ei, U, I, K, B, w["table0"])
         tl = _leg("cpu_baseline", tl)
-    if world == 1 and rank == 0:
+    if args.full and world == 1 and rank == 0:
         # free the headline's state before the other configurations
         del trainer, model, inter, adj, w, events
         t.cuda.empty_cache()

@@ -123,7 +123,7 @@ def test_bench_c4_four_ranks_on_one_card_smoke():
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "LOCAL_WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "4", "--users", "64000", "--items", "2000",
-                        "--edges", "640000", "--batch", "4096", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"],
+                        "--edges", "640000", "--batch", "4096", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--full"],
                        env=env, capture_output=True, text=True, timeout=420)
     assert r.returncode == 0, r.stderr[-2000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]

@@ -2,7 +2,7 @@
 # A/B of the split rows' band rule on BASELINE configs[3] at N = 1 (bench.py --config c4): LAPLACE_SPMM_BAND_MIN_PER = entries a
 # band cut of a split row should hold on average (csrc/spmm.hip, plan_seg_flags_kernel).  tools/ab_c4_band.sh 1 8 32 ...
 for v in "$@"; do
-  LAPLACE_SPMM_BAND_MIN_PER=$v timeout -k 10 240 python3 bench.py --config c4 --steps 10 --warmup 3 --no-cpu-baseline --no-pmc --no-map \
+  LAPLACE_SPMM_BAND_MIN_PER=$v timeout -k 10 240 python3 bench.py --full --config c4 --steps 10 --warmup 3 --no-cpu-baseline --no-pmc --no-map \
       --no-plain-leg --no-ranker --no-pinsage --no-e2e --no-topk > /tmp/ab_c4_$v.log 2>&1
   python3 - <<EOF2
 import json

@@ -1,7 +1,7 @@
 #!/bin/bash
 # A/B of the banded plan's band width (columns) on BASELINE configs[3] at N = 1: tools/ab_c4_bandwidth.sh 2048 4096 8192 ...
 for v in "$@"; do
-  LAPLACE_SPMM_BAND=$v timeout -k 10 240 python3 bench.py --config c4 --steps 10 --warmup 3 --no-cpu-baseline --no-pmc --no-map \
+  LAPLACE_SPMM_BAND=$v timeout -k 10 240 python3 bench.py --full --config c4 --steps 10 --warmup 3 --no-cpu-baseline --no-pmc --no-map \
       --no-plain-leg --no-ranker --no-pinsage --no-e2e --no-topk > /tmp/ab_c4b_$v.log 2>&1
   python3 - <<EOF2
 import json

@@ -1,7 +1,7 @@
 #!/bin/bash
 # A/B of the propagate's stream mode on BASELINE configs[3] at N = 1: tools/ab_c4_streams.sh 0 1 2
 for v in "$@"; do
-  LAPLACE_SPMM_TWO_STREAMS=$v timeout -k 10 240 python3 bench.py --config c4 --steps 10 --warmup 3 --no-cpu-baseline --no-pmc --no-map \
+  LAPLACE_SPMM_TWO_STREAMS=$v timeout -k 10 240 python3 bench.py --full --config c4 --steps 10 --warmup 3 --no-cpu-baseline --no-pmc --no-map \
       --no-plain-leg --no-ranker --no-pinsage --no-e2e --no-topk > /tmp/ab_c4s_$v.log 2>&1
   python3 - <<EOF2
 import json

@@ -5,7 +5,7 @@ export TMPDIR=/tmp
 out=$GRAFT_REPO_ROOT/gpurun_out/final; mkdir -p $out
 timeout -k 10 1000 python -m pytest tests/ -x -q -m gpu > $out/gpu_tests.log 2>&1; echo tests rc=$?; tail -n 3 $out/gpu_tests.log
 timeout -k 10 200 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -n 2
-timeout -k 10 900 python bench.py > $out/bench_line.json 2> $out/bench.err; echo bench rc=$?
+timeout -k 10 900 python bench.py --full > $out/bench_line.json 2> $out/bench.err; echo bench rc=$?
 LAPLACE_SPMM_TWO_STREAMS=0 timeout -k 10 500 bash tools/prof_bench.sh r04_bench_c4_one_stream_final --config c4 --steps 5 > $out/prof_c4.log 2>&1; echo prof rc=$?; cp gpurun_out/r04_bench_c4_one_stream_final/r04_bench_c4_one_stream_final.md $out/ 2>/dev/null; tail -n 2 $out/prof_c4.log
 python3 - <<EOF2
 import json
