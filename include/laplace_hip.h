@@ -939,6 +939,28 @@ int    mi_pinsage_step_check(const mi_pinsage_model* model, const mi_pinsage_ste
 int    mi_pinsage_apply_f32(const mi_pinsage_model* model, const mi_pinsage_grad_list* lists, int32_t n_lists, float grad_scale,
                             mi_stream_t stream);
 
+/* ------------------------------------------------------------------------------------
+ * N5  evaluation: the representation of EVERY item in one call (round 5).
+ * replaces: the evaluation half of pinsage/model.py:120-134 — collate_test's sample_blocks over batches of item ids
+ *           (pinsage/sampler.py:181-185) and model.get_repr per batch, in eval mode (no dropout).
+ * For one (seed, step) an item's top-T neighbours at a sampler layer do not depend on the batch it is in (the walk draws
+ * are keyed on the start item; eval blocks carry no label pairs), so the batched get_repr equals a layer-by-layer pass
+ * over the catalogue: per model layer m, the neighbours of every item at sampler layer n_layers - 1 - m (the draws of
+ * mi_pinsage_neighbors over seeds 0 .. n_items - 1), n = relu(Q h + b_Q) over all items, then one fused kernel per item:
+ * weighted mean of its neighbours' n rows (w / max(sum w, 1), ascending j), W [mean, h] + b_W, relu, L2 normalisation
+ * (norm 0: divided by 1); out = proj + h of the last layer.  Equal to the batched path to rounding (the order of at most
+ * T terms of the mean), not bitwise; deterministic, no atomics, nothing waited on by the host.
+ * Reads of the model descriptor: n_layers, hidden, n_items, proj ([n_items + 1, hidden]; rows 0 .. n_items - 1 used) and
+ * conv[l].q_w / q_b / w_w / w_b; nothing else.  out: [n_items, hidden] fp32.  proj, out and the biases 16-byte aligned.
+ * MI_ERR_UNSUPPORTED (nothing enqueued) unless hidden % 4 == 0, hidden <= 128, 1 <= n_layers <= MI_PINSAGE_MAX_LAYERS,
+ * num_neighbors <= 16 and the walks of one seed fit mi_pinsage_neighbors' block.
+ * ---------------------------------------------------------------------------------- */
+size_t mi_pinsage_embed_items_workspace_bytes(int64_t n_items, int32_t hidden, int32_t num_neighbors);
+int    mi_pinsage_embed_items_f32(const mi_pinsage_model* model, const int32_t* iu_ptr, const int32_t* iu_idx,
+                                  const int32_t* ui_ptr, const int32_t* ui_idx, int32_t walk_length, double restart_prob,
+                                  int32_t num_walks, int32_t num_neighbors, uint64_t seed, uint64_t step, float* out,
+                                  void* ws, size_t ws_bytes, mi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

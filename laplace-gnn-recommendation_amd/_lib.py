@@ -260,6 +260,9 @@ _PROTOTYPES = {
     "mi_pinsage_step_f32": (c_int32, [POINTER(PinsageModel), POINTER(PinsageStepBatch), P, c_size_t, P]),
     "mi_pinsage_step_check": (c_int32, [POINTER(PinsageModel), POINTER(PinsageStepBatch), P, c_size_t]),
     "mi_pinsage_apply_f32": (c_int32, [POINTER(PinsageModel), POINTER(PinsageGradList), c_int32, ctypes.c_float, P]),
+    "mi_pinsage_embed_items_workspace_bytes": (c_size_t, [c_int64, c_int32, c_int32]),
+    "mi_pinsage_embed_items_f32": (c_int32, [POINTER(PinsageModel), P, P, P, P, c_int32, c_double, c_int32, c_int32, c_uint64,
+                                             c_uint64, P, P, c_size_t, P]),
     "mi_adam_dense_f32": (c_int32, [c_int64, c_int64, P, c_int64, P, c_int64, P, P, P,
                                     c_double, c_double, c_double, c_double, c_int64, P]),
 }

@@ -75,7 +75,7 @@ __global__ void neighbors_kernel(int64_t n_seeds, const int32_t* __restrict__ n_
     const bool live = ls < spb && i < n_seeds;
     const int slots = num_walks * walk_length;
     int32_t* vis = nvis + (ls < spb ? ls : 0) * slots;
-    const int32_t s = live ? (int32_t)seeds[i] : 0;
+    const int32_t s = live ? (seeds ? (int32_t)seeds[i] : (int32_t)i) : 0;   // no seed list: seed i is item i
     if (live && wk < num_walks) {
         int32_t cur = s;
         int tr = 0;
@@ -387,6 +387,22 @@ __global__ __launch_bounds__(kBT) void pinsage_block_kernel(int n_max, const int
 }
 
 }  // namespace
+
+// The neighbour table of EVERY item at one sampler layer (seed list = the identity): csrc/pinsage_infer.hip's catalogue pass.
+// Same draws as mi_pinsage_neighbors over seeds 0 .. n_items - 1.  false when the walks of a seed do not fit a block.
+bool pinsage_neighbors_all(int64_t n_items, const int32_t* iu_ptr, const int32_t* iu_idx, const int32_t* ui_ptr,
+                           const int32_t* ui_idx, int walk_length, double restart_prob, int num_walks, int T, int layer,
+                           uint64_t seed, uint64_t step, int64_t* nb, int64_t* wt, hipStream_t stream) {
+    int w_pad, spb;
+    size_t lds;
+    if (!neighbors_launch_shape(num_walks, walk_length, &w_pad, &spb, &lds)) return false;
+    Bip g = {iu_ptr, iu_idx, ui_ptr, ui_idx};
+    const uint32_t thr = (uint32_t)(restart_prob * 4294967296.0);
+    hipLaunchKernelGGL(neighbors_kernel, dim3((unsigned)mi_ceil_div(n_items, spb)), dim3(kNbThreads), lds, stream, n_items,
+                       (const int32_t*)nullptr, (const int64_t*)nullptr, g, walk_length, thr, num_walks, T, layer, seed, step,
+                       w_pad, nb, wt);
+    return true;
+}
 
 extern "C" {
 

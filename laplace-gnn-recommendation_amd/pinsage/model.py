@@ -9,7 +9,7 @@ the per-pair dot products and the hinge are torch ops on [batch]-sized tensors.
 """
 from __future__ import annotations
 
-from typing import List, Tuple
+from typing import List, Optional, Tuple
 
 import torch as t
 import torch.nn.functional as F
@@ -111,6 +111,36 @@ class PinSAGEModel(nn.Module):
         for conv, block in zip(self.convs, blocks):
             h = conv(block, h, h[: block["n_dst"]])
         return h_dst_final + h
+
+    def item_representations(self, sampler, *, step: Optional[int] = None) -> Tensor:
+        """The representation of every item, [n_items, hidden] — the evaluation half of pinsage/model.py:120-134 (get_repr
+        over collate_test's blocks for batches of item ids), in eval mode with no autograd; the module's train / eval mode
+        is restored afterwards.  `step` (default sampler.step) keys the walks with sampler.seed: the same (seed, step)
+        gives the same bits on every call.
+
+        One native call (mi_pinsage_embed_items_f32: a layer-by-layer pass over the catalogue, every item's neighbours
+        sampled once per layer) where the kernel takes the shapes; otherwise the reference-shaped path, sample_blocks +
+        get_repr over batches of sampler.batch_size item ids.  The two agree to rounding (DESIGN §7, N5 evaluation)."""
+        from .native import embed_items
+        step = int(sampler.step if step is None else step)
+        was_training = self.training
+        self.eval()
+        try:
+            with t.no_grad():
+                h = embed_items(self, sampler, step)
+                if h is None:
+                    h = self.batched_item_representations(sampler, step)
+        finally:
+            self.train(was_training)
+        return h
+
+    def batched_item_representations(self, sampler, step: int, batch_size: Optional[int] = None) -> Tensor:
+        """get_repr over sample_blocks(batch, step) for consecutive batches of item ids (pinsage/sampler.py:181-185), as the
+        reference evaluates; the caller sets eval mode and no_grad (item_representations does)."""
+        n_items = self.proj.weight.shape[0] - 1
+        ids = t.arange(n_items, device=self.proj.weight.device)
+        return t.cat([self.get_repr(sampler.sample_blocks(b, step))
+                      for b in ids.split(int(batch_size or sampler.batch_size))], 0)
 
     def score(self, h: Tensor, seeds: Tensor, pair) -> Tensor:
         u, v = pair

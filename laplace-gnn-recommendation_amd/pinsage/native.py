@@ -338,3 +338,42 @@ class NativePinSAGEStep:
             lists[r].bias = base + r * stride + 4 * o_bias
         _lib.check(_lib.lib().mi_pinsage_apply_f32(ctypes.byref(d), lists, world, 1.0 / world, _lib.current_stream()),
                    "mi_pinsage_apply_f32")
+
+
+# ---- evaluation: every item's representation in one C call ------------------------------------------------------------------
+def embed_items(model: PinSAGEModel, sampler, step: int) -> Optional[Tensor]:
+    """PinSAGEModel.get_repr of every item, for the sampler's (seed, step), as one mi_pinsage_embed_items_f32 call
+    (csrc/pinsage_infer.hip): [n_items, hidden] fp32.  None when the model or the sampler lies outside the kernel's shapes
+    (nothing has been enqueued then); the caller takes the batched path.  Eval semantics (no dropout); no autograd."""
+    if not isinstance(model, PinSAGEModel) or not all(hasattr(sampler, a) for a in ("iu_ptr", "ui_ptr", "L", "p", "W", "T")):
+        return None
+    proj = model.proj.weight
+    hidden, n_items = int(proj.shape[1]), int(proj.shape[0]) - 1
+    params = [proj] + [x for cv in model.convs for x in (cv.Q.weight, cv.Q.bias, cv.W.weight, cv.W.bias)]
+    if (hidden % 4 or hidden > 128 or not (1 <= len(model.convs) <= _lib.MI_PINSAGE_MAX_LAYERS) or sampler.T > 16
+            or n_items != sampler.num_items or len(model.convs) != sampler.n_layers):
+        return None
+    if any(x is None or x.dtype != t.float32 or not x.is_cuda or not x.is_contiguous() or x.device != proj.device for x in params):
+        return None
+    for cv in model.convs:
+        if tuple(cv.Q.weight.shape) != (hidden, hidden) or tuple(cv.W.weight.shape) != (hidden, 2 * hidden):
+            return None
+    if sampler.iu_ptr.device != proj.device:
+        return None
+    d = PinsageModel()
+    d.n_layers, d.hidden, d.n_items = len(model.convs), hidden, n_items
+    d.proj = proj.data_ptr()
+    for l, cv in enumerate(model.convs):
+        c = d.conv[l]
+        c.q_w, c.q_b, c.w_w, c.w_b = (x.data_ptr() for x in (cv.Q.weight, cv.Q.bias, cv.W.weight, cv.W.bias))
+    L = _lib.lib()
+    out = t.empty(n_items, hidden, dtype=t.float32, device=proj.device)
+    ws = t.empty(int(L.mi_pinsage_embed_items_workspace_bytes(n_items, hidden, sampler.T)), dtype=t.uint8, device=proj.device)
+    rc = L.mi_pinsage_embed_items_f32(ctypes.byref(d), sampler.iu_ptr.data_ptr(), sampler.iu_idx.data_ptr(),
+                                      sampler.ui_ptr.data_ptr(), sampler.ui_idx.data_ptr(), sampler.L, sampler.p, sampler.W,
+                                      sampler.T, sampler.seed & ((1 << 64) - 1), int(step), out.data_ptr(), ws.data_ptr(),
+                                      ws.numel(), _lib.current_stream())
+    if rc == _lib.MI_ERR_UNSUPPORTED:
+        return None
+    _lib.check(rc, "mi_pinsage_embed_items_f32")
+    return out
