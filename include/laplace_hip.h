@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define MI_ABI_VERSION 9
+#define MI_ABI_VERSION 10
 
 #define MI_ERR_BAD_ARG      (-1)  /* null pointer, negative size, misaligned buffer   */
 #define MI_ERR_TOO_LARGE    (-2)  /* a size does not fit int32 indexing                */
@@ -163,6 +163,15 @@ int    mi_spmm_plan_count(int64_t n_rows, int64_t n_cols, const int32_t* rowptr,
 int    mi_spmm_plan_count_range(int64_t n_rows, int64_t n_cols, const int32_t* rowptr, const int32_t* col,
                                 int32_t chunk, int32_t max_deg, int32_t band, void* ws, size_t ws_bytes,
                                 mi_spmm_plan_info* info, mi_stream_t stream);
+/* The same analysis with a third row class: THIN rows, chunk < degree <= thin_max, get no work items and no partial rows —
+ * only the rows with max(chunk, thin_max) < degree <= max_deg are split (thin_max = 0: mi_spmm_plan_count_range, bit for
+ * bit).  A thin row holds a few entries per band, so as work items it pays a partial row for nearly every gather; it is
+ * summed whole by a wavefront instead (mi_spmm_ex.thin_rows).  The caller lists the thin rows itself (degrees from rowptr),
+ * longest first, marks them with -2 in plan->long_index after mi_spmm_plan_fill, and passes the list with EVERY launch of
+ * the plan: neither the short-row nor the split-row kernels compute them. */
+int    mi_spmm_plan_count_thin(int64_t n_rows, int64_t n_cols, const int32_t* rowptr, const int32_t* col,
+                               int32_t chunk, int32_t thin_max, int32_t max_deg, int32_t band, void* ws, size_t ws_bytes,
+                               mi_spmm_plan_info* info, mi_stream_t stream);
 int    mi_spmm_plan_fill(int64_t n_rows, const int32_t* rowptr, const mi_spmm_plan_info* info,
                          mi_spmm_plan* plan, void* ws, size_t ws_bytes, mi_stream_t stream);
 /* Fills plan->epos / ecol / eval (caller-allocated: n_launch, nnz_long, nnz_long elements; nnz_long from
@@ -271,6 +280,12 @@ typedef struct mi_spmm_ex {
                                        test the bit before the map, gather only the live entries in list order, write no partial
                                        row for a work item without any, and the fix-up skips those — same sums in the same order,
                                        bitwise the result without the hint.  Ignored with a sweep, a row_list or an unpacked plan. */
+    const int32_t* thin_rows;       /* device int32[n_thin], with a plan from mi_spmm_plan_count_thin: its thin rows, longest first.
+                                       Each is summed whole by one wavefront — equal consecutive pieces of the row, one per
+                                       sub-group, added in sub-group order through LDS, one epilogue — as part of
+                                       MI_SPMM_SPLIT_ROWS: no partial rows, no atomics, bitwise reproducible.  Serves every form
+                                       (x_map, addend_map, adam; with row_list the listed rows whose long_index is -2) */
+    int32_t        n_thin;          /* 0 (and a null mi_spmm_ex) = the plan has no thin rows */
 } mi_spmm_ex;
 #define MI_SPMM_SHORT_ROWS 1
 #define MI_SPMM_SPLIT_ROWS 2

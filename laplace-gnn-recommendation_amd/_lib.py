@@ -10,7 +10,7 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 # the package directory is never overwritten by an experiment.  It is still this library or nothing — no fallback.
 LIB_PATH = os.environ.get("LAPLACE_HIP_LIB") or os.path.join(PKG_DIR, "liblaplace_hip.so")
 
-MI_ABI_VERSION = 9
+MI_ABI_VERSION = 10
 MI_SPMM_GROUP = 32
 
 
@@ -47,7 +47,7 @@ class SpmmExStruct(Structure):
     _fields_ = [("x_map", c_void_p), ("addend_map", c_void_p), ("row_list", c_void_p), ("n_list_dev", c_void_p),
                 ("n_list", c_int64), ("adam", POINTER(AdamArgs)), ("parts", c_int32), ("hot_rows", c_int32),
                 ("sweep", POINTER(SpmmSweepStruct)), ("hot_base", c_int32), ("hot_threads", c_int32),
-                ("x_bits", c_void_p)]
+                ("x_bits", c_void_p), ("thin_rows", c_void_p), ("n_thin", c_int32)]
 
 
 MI_SPMM_SHORT_ROWS, MI_SPMM_SPLIT_ROWS = 1, 2
@@ -187,6 +187,7 @@ _PROTOTYPES = {
     "mi_spmm_plan_workspace_bytes": (c_size_t, [c_int64, c_int64]),
     "mi_spmm_plan_count": (c_int32, [c_int64, c_int64, P, P, c_int32, c_int32, P, c_size_t, POINTER(SpmmPlanInfo), P]),
     "mi_spmm_plan_count_range": (c_int32, [c_int64, c_int64, P, P, c_int32, c_int32, c_int32, P, c_size_t, POINTER(SpmmPlanInfo), P]),
+    "mi_spmm_plan_count_thin": (c_int32, [c_int64, c_int64, P, P, c_int32, c_int32, c_int32, c_int32, P, c_size_t, POINTER(SpmmPlanInfo), P]),
     "mi_spmm_plan_fill": (c_int32, [c_int64, P, POINTER(SpmmPlanInfo), POINTER(SpmmPlanStruct), P, c_size_t, P]),
     "mi_spmm_workspace_bytes": (c_size_t, [POINTER(SpmmPlanStruct), c_int64]),
     "mi_spmm_plan_pack_workspace_bytes": (c_size_t, [c_int64]),

@@ -24,6 +24,8 @@
 // user row that the hub items of a recommendation graph make then meet in that XCD's 4 MB L2 instead
 // of each going to HBM.  Measured on C2 (tools/ab_band.py, round 1): 1.20 -> 1.04 ms per launch with
 // one wavefront per item; see DESIGN.md for the final figures.
+// THIN rows of a plan (longer than chunk, but with only a few entries per band) are not split: one wavefront
+// sums each of them whole (spmm_thin_kernel), without partial rows.
 #include "common.hpp"
 #include "pairs.hpp"
 #include <algorithm>
@@ -119,6 +121,8 @@ struct Ex {
     int32_t hot_base, hot_rows, hot_threads;  // persistent short-row launch (host side only): hot_rows 0 = plain launch, > 0 = LDS cache rows, < 0 = no cache
     const uint32_t* x_bits;     // bit c = (x_map[c] >= 0): "live columns are rare" — on a packed plan the work items run as spmm_items_xscan_kernel
     uint8_t* slot_live;         // [plan->n_items], behind the partial rows: 0 = the work item gathered nothing and wrote no partial row
+    const int32_t* thin_rows;   // [n_thin]: the plan's thin rows (chunk < degree <= thin_max), longest first: summed whole by spmm_thin_kernel
+    int32_t n_thin;
 };
 
 // Largest n over the sub-groups of the wavefront (loop bounds must be wave-uniform around __shfl).
@@ -358,7 +362,7 @@ __global__ __launch_bounds__(kBlock) void spmm_rows_pair_kernel(RowsSide a, Rows
     ep.streaming = MI_PICK(ep.streaming);
     ep.p = nullptr; ep.ldp4 = 0; ep.m = nullptr; ep.v = nullptr; ep.reg_w = nullptr;
     ep.adam = MiAdamConsts{};
-    const Ex ex = {nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0, nullptr, nullptr};
+    const Ex ex = {nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0, nullptr, nullptr, nullptr, 0};
     spmm_rows_body<LPR, 1, UNROLL, MI_SPMM_ROWS_RPS, false, false>(first ? blockIdx.x : blockIdx.x - split, first ? split : gridDim.x - split,
                                                                   MI_PICK(n_out), MI_PICK(d4), MI_PICK(rowptr), MI_PICK(col), MI_PICK(val),
                                                                   MI_PICK(X4), MI_PICK(ldx4), ep, INT32_MAX, ex, 1);
@@ -1045,6 +1049,90 @@ __global__ __launch_bounds__(kBlock) void spmm_fixup_kernel(int32_t n_long, int 
     store_epilogue<LPR, VPL, ADAM>(ep, out_row, d4, lane, acc, a);
 }
 
+// THIN split rows (mi_spmm_ex.thin_rows: chunk < degree <= the plan's thin_max), each summed WHOLE.  As banded work items
+// such a row holds one to three entries per band (C4: the 25 K item rows of 257..2 048 entries own 76 % of the 7.7 M work
+// items, tools/thin_rows_table.py), so nearly every gather paid a 512-byte partial row written and read back.  Here
+// `waves` wavefronts (1, 2 or 4 of the workgroup's 4) share one row: its entries are cut into equal consecutive pieces, one
+// per sub-group, each piece is summed in list order by subgroup_accumulate, the pieces are added in sub-group order through
+// LDS and the row's first sub-group applies the epilogue once.  No partial row, no fix-up slot, no atomics: a fixed
+// association, bitwise reproducible.  The rows come longest first, so the grid's tail is made of the short ones.
+// row_list launches run one slot per LIST position and take the rows whose long_index says "thin" (-2).
+#ifndef MI_SPMM_UNROLL_THIN
+#define MI_SPMM_UNROLL_THIN 4   // row loads in flight per lane (VPL = 1).  8 buys nothing: C4 step, separate processes alternated, thin rows up to
+                                // 2 entries per band: 4: 46.80 / 46.81 ms, 8: 46.86 / 46.97; up to 4 per band: 4: 47.08 / 47.11, 8: 47.35 / 47.35
+#endif
+#ifndef MI_SPMM_THIN_WAVES
+#define MI_SPMM_THIN_WAVES 1    // wavefronts per thin row; LAPLACE_SPMM_THIN_WAVES = 1 / 2 / 4 for A/B.  C4 step (D = 128: two sub-groups per
+#endif                          // wavefront), same process, thin rows up to 4 entries per band: 4: 48.60 / 48.72 ms, 2: 48.47, 1: 48.00 / 47.79 /
+                                // 47.66; up to 2 per band: 4: 48.16 / 48.26, 2: 47.53, 1: 47.39 / 47.55 — more rows in flight beat shorter walks
+template <int LPR, int VPL, int UNROLL, bool SPARSE, bool ADAM>
+__global__ __launch_bounds__(kBlock) void spmm_thin_kernel(int64_t n_slots, int32_t waves, int d4,
+                                                           const int32_t* __restrict__ rowptr,
+                                                           const int32_t* __restrict__ col,
+                                                           const float* __restrict__ val,
+                                                           const float4* __restrict__ X4, int64_t ldx4,
+                                                           Epilogue ep, Ex ex) {
+    constexpr int NB = MI_WAVE / LPR, SG = NB * kWavesPerBlock;
+    __shared__ float4 red[SG][VPL][LPR];
+    const int lane = mi_lane();
+    const int li = lane % LPR;
+    const int wave = threadIdx.x / MI_WAVE;
+    const int sgi = wave * NB + lane / LPR;              // sub-group of the workgroup
+    const int pieces = waves * NB;                       // sub-groups per row
+    const int first_sg = (wave / waves) * pieces;        // the row's first sub-group
+    const int piece = sgi - first_sg;
+    const int64_t q = (int64_t)blockIdx.x * (kWavesPerBlock / waves) + wave / waves;
+    const bool listed = SPARSE && ex.row_list != nullptr;
+    int64_t r = 0, out_row = 0, ar = -1;
+    bool mine = q < n_slots;                             // uniform over the row's wavefronts
+    if (mine) {
+        if (listed) {
+            if (ex.n_list_dev && q >= (int64_t)*ex.n_list_dev) mine = false;
+            if (mine) {
+                r = ex.row_list[q];
+                mine = ex.long_index[r] == -2;           // a listed thin row is computed at its list position
+                out_row = ar = q;
+            }
+        } else {
+            r = ex.thin_rows[q];
+            out_row = r;
+            ar = ex.addend_map ? (int64_t)ex.addend_map[r] : r;
+        }
+    }
+    int32_t beg = 0;
+    int n = 0;
+    if (mine) {
+        const int32_t rb = rowptr[r];
+        const int32_t len = rowptr[r + 1] - rb;
+        const int32_t per = (len + pieces - 1) / pieces;
+        const int32_t b = min(piece * per, len);
+        beg = rb + b;
+        n = min(per, len - b);
+    }
+    const int nmax = wave_max_over_subgroups<LPR>(n);
+    float4 acc[VPL];
+    subgroup_accumulate<LPR, VPL, UNROLL, SPARSE>(col, val, X4, ldx4, d4, beg, n, nmax, li, ex.x_map, acc);
+#pragma unroll
+    for (int v = 0; v < VPL; ++v) red[sgi][v][li] = acc[v];
+    __syncthreads();   // reached by every thread of the workgroup exactly once
+    if (!mine || piece != 0) return;
+    float4 a[VPL];
+    load_addend<LPR, VPL>(ep, ar, d4, li, a);
+#pragma unroll
+    for (int v = 0; v < VPL; ++v) {
+        float4 t = red[first_sg][v][li];
+        for (int g = 1; g < pieces; ++g) t = mi_f4_add(t, red[first_sg + g][v][li]);
+        acc[v] = t;
+    }
+    store_epilogue<LPR, VPL, ADAM>(ep, out_row, d4, li, acc, a);
+}
+
+int32_t thin_waves() {
+    const char* e = getenv("LAPLACE_SPMM_THIN_WAVES");   // A/B
+    const int v = e ? atoi(e) : MI_SPMM_THIN_WAVES;
+    return (v == 1 || v == 2) ? v : 4;
+}
+
 // ---- plan construction --------------------------------------------------------------------
 // Phase 1 (mi_spmm_plan_count) keeps its arrays in the caller's workspace; phase 2 (mi_spmm_plan_fill)
 // carves the same layout again from the counts in mi_spmm_plan_info.
@@ -1084,12 +1172,14 @@ bool plan_carve(MiArena& ar, int64_t n_rows, int64_t nnz_total, int64_t n_long, 
     return w.seg_start && w.keys0 && w.keys1;
 }
 
-__global__ void plan_flags_kernel(int64_t n_rows, const int32_t* __restrict__ rowptr, int32_t chunk, int32_t max_deg,
+__global__ void plan_flags_kernel(int64_t n_rows, const int32_t* __restrict__ rowptr, int32_t min_deg, int32_t max_deg,
                                   int32_t* __restrict__ is_long, int32_t* __restrict__ ldeg) {
     int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (r > n_rows) return;
     const int32_t deg = (r < n_rows) ? rowptr[r + 1] - rowptr[r] : 0;
-    const bool lg = deg > chunk && deg <= max_deg;  // rows above max_deg belong to another plan (the SWEEP half of a hybrid)
+    // rows above max_deg belong to another plan (the SWEEP half of a hybrid); min_deg = max(chunk, thin_max): the thin rows
+    // between chunk and thin_max get no work items (spmm_thin_kernel sums them whole)
+    const bool lg = deg > min_deg && deg <= max_deg;
     is_long[r] = lg ? 1 : 0;
     ldeg[r] = lg ? deg : 0;
 }
@@ -1277,6 +1367,7 @@ int launch_spmm_mode(int64_t n_rows, int d4, const int32_t* rowptr, const int32_
                      float4* partial, const Ex& ex, int64_t n_list, hipStream_t s, const mi_spmm_sweep* sweep) {
     constexpr int UNROLL = (VPL == 1) ? MI_SPMM_UNROLL : 4;                                        // work items, sweep
     constexpr int UNROLL_ROWS = (VPL == 1) ? (ADAM ? MI_SPMM_UNROLL_ADAM : MI_SPMM_UNROLL) : 4;   // the short-row kernel (the one that carries the Adam epilogue)
+    constexpr int UNROLL_THIN = (VPL == 1) ? MI_SPMM_UNROLL_THIN : 4;                             // whole thin rows
     constexpr int SG = (MI_WAVE / LPR) * kWavesPerBlock;
     constexpr int ROWS_RPS = MI_SPMM_ROWS_RPS;
 #ifndef MI_SPMM_ITEMS_SLOTS
@@ -1329,6 +1420,14 @@ int launch_spmm_mode(int64_t n_rows, int d4, const int32_t* rowptr, const int32_
             hipLaunchKernelGGL((spmm_items_kernel<LPR, VPL, UNROLL, ITEMS_RPS, SPARSE>), gi, dim3(kBlock), 0, s, n_launch,
                                plan->band > 0 ? 1 : 0, d4, reinterpret_cast<const int4*>(plan->items), plan->epos, ecol, eval,
                                X4, ldx4, partial, ex.x_map, ep.streaming);
+    }
+    if (do_split && ex.n_thin > 0) {
+        const int32_t waves = thin_waves();
+        const int64_t n_slots = listed ? n_list : (int64_t)ex.n_thin;
+        if (n_slots > 0)
+            hipLaunchKernelGGL((spmm_thin_kernel<LPR, VPL, UNROLL_THIN, SPARSE, ADAM>),
+                               dim3((unsigned)mi_ceil_div(n_slots, (int64_t)(kWavesPerBlock / waves))), dim3(kBlock), 0, s, n_slots,
+                               waves, d4, rowptr, col, val, X4, ldx4, ep, ex);
     }
     const int64_t n_out = listed ? n_list : n_rows;
     bool short_done = false;
@@ -1436,7 +1535,15 @@ int mi_spmm_plan_count(int64_t n_rows, int64_t n_cols, const int32_t* rowptr, co
 int mi_spmm_plan_count_range(int64_t n_rows, int64_t n_cols, const int32_t* rowptr, const int32_t* col,
                              int32_t chunk, int32_t max_deg, int32_t band, void* ws, size_t ws_bytes,
                              mi_spmm_plan_info* info, mi_stream_t stream) {
+    return mi_spmm_plan_count_thin(n_rows, n_cols, rowptr, col, chunk, 0, max_deg, band, ws, ws_bytes, info, stream);
+}
+
+int mi_spmm_plan_count_thin(int64_t n_rows, int64_t n_cols, const int32_t* rowptr, const int32_t* col,
+                            int32_t chunk, int32_t thin_max, int32_t max_deg, int32_t band, void* ws, size_t ws_bytes,
+                            mi_spmm_plan_info* info, mi_stream_t stream) {
     MI_CHECK_ARG(n_rows >= 0 && n_cols >= 0 && rowptr && chunk > 0 && max_deg >= chunk && band >= 0 && ws && info);
+    MI_CHECK_ARG(thin_max == 0 || (thin_max >= chunk && thin_max <= max_deg));
+    const int32_t min_deg = std::max(chunk, thin_max);
     if (n_rows >= INT32_MAX || n_cols >= INT32_MAX) return MI_ERR_TOO_LARGE;
     hipStream_t s = (hipStream_t)stream;
     memset(info, 0, sizeof(*info));
@@ -1454,7 +1561,7 @@ int mi_spmm_plan_count_range(int64_t n_rows, int64_t n_cols, const int32_t* rowp
         if (!plan_carve(ar, n_rows, nnz, -1, -1, -1, w)) return MI_ERR_WORKSPACE;
     }
     const int64_t n1 = n_rows + 1;
-    hipLaunchKernelGGL(plan_flags_kernel, plan_grid(n1), dim3(256), 0, s, n_rows, rowptr, chunk, max_deg, w.is_long, w.ldeg);
+    hipLaunchKernelGGL(plan_flags_kernel, plan_grid(n1), dim3(256), 0, s, n_rows, rowptr, min_deg, max_deg, w.is_long, w.ldeg);
     size_t tb = w.tmp_bytes;
     MI_HIP(rocprim::exclusive_scan(w.tmp, tb, w.is_long, w.long_off, 0, (size_t)n1, rocprim::plus<int32_t>(), s));
     tb = w.tmp_bytes;
@@ -1605,7 +1712,7 @@ int mi_spmm_csr_ex_f32(int64_t n_rows, int64_t d, const int32_t* rowptr, const i
     MI_CHECK_ARG(!Y || (ldy % 4 == 0 && ldy >= d && mi_aligned16(Y) && Y != X));
     MI_CHECK_ARG(!S || (lds % 4 == 0 && lds >= d && mi_aligned16(S) && S != X));
     MI_CHECK_ARG(!addend || (lda % 4 == 0 && lda >= d && mi_aligned16(addend)));
-    Ex ex = {nullptr, nullptr, nullptr, nullptr, nullptr, MI_SPMM_SHORT_ROWS | MI_SPMM_SPLIT_ROWS, 0, 0, 0, nullptr, nullptr};
+    Ex ex = {nullptr, nullptr, nullptr, nullptr, nullptr, MI_SPMM_SHORT_ROWS | MI_SPMM_SPLIT_ROWS, 0, 0, 0, nullptr, nullptr, nullptr, 0};
     int64_t n_list = 0;
     if (exh) {
         ex.x_map = exh->x_map;
@@ -1623,10 +1730,15 @@ int mi_spmm_csr_ex_f32(int64_t n_rows, int64_t d, const int32_t* rowptr, const i
             ex.hot_rows = exh->hot_rows;   // the caller's contract: hot_base + max(hot_rows, 0) <= rows of X
             ex.hot_threads = exh->hot_threads;
         }
+        if (exh->n_thin > 0) {   // the plan was counted with thin_max > 0: its thin rows travel with every launch
+            MI_CHECK_ARG(plan && exh->thin_rows);
+            ex.thin_rows = exh->thin_rows;
+            ex.n_thin = exh->n_thin;
+        }
         if (ex.row_list) {
             MI_CHECK_ARG(n_list >= 0 && !ex.addend_map);
             if (n_list == 0) return 0;
-            if (plan && plan->n_long_rows > 0) {
+            if (plan && (plan->n_long_rows > 0 || ex.n_thin > 0)) {
                 MI_CHECK_ARG(plan->long_index);
                 ex.long_index = plan->long_index;
             }

@@ -26,6 +26,15 @@ DEFAULT_CHUNK = 256  # max nnz per work item of a split (hub) row
 # band outgrowing one L2 up to 8 MB of rows.  Widening only the THIN rows' bands is slower (csrc/spmm.hip, plan_seg_flags_kernel).
 DEFAULT_BAND = int(_os_environ.get("LAPLACE_SPMM_BAND", 16384))
 MIN_BANDED_COLS = 131072  # narrower adjacencies keep the row-major plan (nothing to block for)
+# THIN rows of a default banded plan: split rows of at most THIN_PER_BAND * n_bands entries get no work items and are summed
+# whole by a wavefront each (csrc/spmm.hip, spmm_thin_kernel).  Such a row holds THIN_PER_BAND entries per band at most, i.e.
+# it paid a 512-byte partial row, written and read back, for every one or two gathers (C4: 58 % of the 7.7 M work items hold
+# 11 % of the split rows' entries, profiles/thin_rows_c4.md).  A/B on C4 at N = 1 (same process, one graph, 20 steps after 5;
+# ms per step / dense launch / sparse-operand launch): 0: 51.18, 51.57, 50.84 / 9.12 / 5.36, 1: 49.52 / 8.75 / 5.18,
+# 2: 47.39, 47.55 / 8.38 / 4.99, 3: 47.57, 47.28, 4: 47.79, 47.66 / 8.52 / 5.07, 6: 48.70, 8: 49.06 / 8.66 / 5.18 — past ~4 entries per
+# band the lost L2 company of the band costs more than the partial rows did.  0 = no thin rows, the plan of before.
+# LAPLACE_SPMM_THIN overrides for A/B.
+THIN_PER_BAND = int(_os_environ.get("LAPLACE_SPMM_THIN", 2))
 
 # bench.py sets this to a list to collect (start, end, kind) HIP events around every propagate launch,
 # recorded on the stream the kernels are launched on.  None = no timing overhead.
@@ -133,10 +142,21 @@ class SpmmPlan:
     packed: tuple = ()                            # (epos, ecol, eval): the split rows' entries in launch order (mi_spmm_plan_pack_entries)
     packed_of: tuple = ()                         # (val.data_ptr(), val._version) the packed values were copied from
     nnz_long: int = 0
+    thin_rows: Optional[Tensor] = None            # int32: rows with chunk < degree <= thin_max, longest first (mi_spmm_ex.thin_rows)
+    thin_max: int = 0
+
+    @property
+    def n_thin_rows(self) -> int:
+        return int(self.thin_rows.numel()) if self.thin_rows is not None else 0
+
+    @property
+    def n_split_rows(self) -> int:
+        return int(self.struct.n_long_rows)
 
     @property
     def n_long_rows(self) -> int:
-        return int(self.struct.n_long_rows)
+        """Rows with more than `chunk` entries, i.e. not the short-row kernel's: the split rows and the thin rows."""
+        return int(self.struct.n_long_rows) + self.n_thin_rows
 
     @property
     def n_items(self) -> int:
@@ -465,10 +485,14 @@ SWEEP_BAND = int(_os.environ.get("LAPLACE_SWEEP_BAND", SWEEP_BAND))
 SWEEP_PACE = int(_os.environ.get("LAPLACE_SWEEP_PACE", SWEEP_PACE))
 
 
-def build_spmm_plan(a: DeviceCSR, chunk: int = DEFAULT_CHUNK, band: Optional[int] = None, sweep: Optional[bool] = None) -> SpmmPlan:
+def build_spmm_plan(a: DeviceCSR, chunk: int = DEFAULT_CHUNK, band: Optional[int] = None, sweep: Optional[bool] = None,
+                    thin_max: Optional[int] = None) -> SpmmPlan:
     """Split-row plan of an adjacency.  band = columns per band of a banded plan (see include/laplace_hip.h),
     0 = row-major, None = DEFAULT_BAND when the adjacency has at least MIN_BANDED_COLS columns.  sweep (default: the
-    module switch SWEEP, and only when band is not given): the SWEEP form when the adjacency qualifies."""
+    module switch SWEEP, and only when band is not given): the SWEEP form when the adjacency qualifies.
+    thin_max: rows with chunk < degree <= thin_max are THIN rows — no work items, no partial rows, summed whole by a
+    wavefront each (plan.thin_rows, longest first); 0 = none.  None = 0 for every plan whose band is given, for sweep and
+    row-major plans; THIN_PER_BAND * n_bands where the banded default applies."""
     if (SWEEP if sweep is None else sweep) and band is None:
         plan = build_sweep_plan(a, chunk, band=SWEEP_BAND)
         if plan is not None:
@@ -476,11 +500,16 @@ def build_spmm_plan(a: DeviceCSR, chunk: int = DEFAULT_CHUNK, band: Optional[int
     L = _lib.lib()
     if band is None:
         band = DEFAULT_BAND if a.n_cols >= MIN_BANDED_COLS else 0
+        if thin_max is None and band > 0:
+            thin_max = THIN_PER_BAND * ((a.n_cols + band - 1) // band)
+    thin_max = int(thin_max or 0)
+    if thin_max <= chunk:
+        thin_max = 0
     dev = a.device
     ws = _ws(L.mi_spmm_plan_workspace_bytes(a.n_rows, a.nnz), dev)
     info = _lib.SpmmPlanInfo()
-    check(L.mi_spmm_plan_count(a.n_rows, a.n_cols, _ptr(a.rowptr), _ptr(a.col), chunk, band, ws.data_ptr(), ws.numel(),
-                               ctypes.byref(info), _stream()), "mi_spmm_plan_count")
+    check(L.mi_spmm_plan_count_thin(a.n_rows, a.n_cols, _ptr(a.rowptr), _ptr(a.col), chunk, thin_max, 2 ** 31 - 1, band,
+                                    ws.data_ptr(), ws.numel(), ctypes.byref(info), _stream()), "mi_spmm_plan_count_thin")
     nl, nlaunch = int(info.n_long_rows), int(info.n_launch)
     long_rows = t.empty(max(nl, 1), dtype=t.int32, device=dev)
     item_ptr = t.empty(max(nl, 1) + 1, dtype=t.int32, device=dev)
@@ -494,6 +523,14 @@ def build_spmm_plan(a: DeviceCSR, chunk: int = DEFAULT_CHUNK, band: Optional[int
     plan = SpmmPlan(st, long_rows, item_ptr, items, long_index)
     plan.nnz_long = int(info.nnz_long)
     del ws
+    plan.thin_max = thin_max
+    if thin_max > 0 and a.n_rows > 0:
+        deg = a.rowptr[1:] - a.rowptr[:-1]
+        rows = t.nonzero((deg > chunk) & (deg <= thin_max)).view(-1)
+        if rows.numel() > 0:
+            rows = rows[t.argsort(deg[rows], descending=True, stable=True)]
+            long_index[rows] = -2                                   # row_list launches: "thin", neither short nor split
+            plan.thin_rows = rows.to(t.int32).contiguous()
     if PACK_ENTRIES and nlaunch > 0 and plan.nnz_long > 0 and a.val is not None:
         _pack_plan_entries(a, plan, values_only=False)
     return plan
@@ -581,7 +618,7 @@ def spmm(a: DeviceCSR, X: Tensor, *, Y: Optional[Tensor] = None, addend: Optiona
     plan = a.plan
     if plan is not None and plan.sweep is not None and d > 128:  # the sweep form stops at 128 floats per row
         if plan.wide is None:
-            plan.wide = build_spmm_plan(a, chunk=int(plan.struct.chunk), sweep=False)
+            plan.wide = build_spmm_plan(a, chunk=int(plan.struct.chunk), sweep=False, thin_max=0)
         plan = plan.wide
     L = _lib.lib()
     if plan is not None and plan.packed and plan.packed_of != (a.val.data_ptr(), a.val._version):
@@ -615,21 +652,24 @@ def spmm(a: DeviceCSR, X: Tensor, *, Y: Optional[Tensor] = None, addend: Optiona
             x_bits = a._x_bits = t.empty((a.n_cols + 31) // 32, dtype=t.int32, device=a.device)
         check(L.mi_map_live_bits_i32(a.n_cols, _ptr(x_map), _ptr(x_bits), _stream()), "mi_map_live_bits_i32")
 
+    n_thin = plan.n_thin_rows if plan is not None else 0
+
     def launch(parts: int, stream: int) -> None:
         exs = None
         if (x_map is not None or addend_map is not None or row_list is not None or adam_args is not None or parts
-                or sweep is not None or hot_rows != 0 or HOT_THREADS):
+                or sweep is not None or hot_rows != 0 or HOT_THREADS or n_thin):
             exs = SpmmExStruct(_ptr(x_map), _ptr(addend_map), _ptr(row_list), _ptr(n_list_dev),
                                row_list.numel() if row_list is not None else 0,
                                ctypes.pointer(adam_args) if adam_args is not None else None, parts, hot_rows,
-                               ctypes.pointer(sweep) if sweep is not None else None, hot_base, HOT_THREADS, _ptr(x_bits))
+                               ctypes.pointer(sweep) if sweep is not None else None, hot_base, HOT_THREADS, _ptr(x_bits),
+                               _ptr(plan.thin_rows) if n_thin else None, n_thin)
         check(L.mi_spmm_csr_ex_f32(a.n_rows, d, _ptr(a.rowptr), col_ptr, val_ptr, X.data_ptr(), ldx,
                                    _ptr(Y), ldy, _ptr(addend), lda, _ptr(S), lds, float(scale),
                                    ctypes.byref(plan.struct) if plan is not None else None,
                                    ctypes.byref(exs) if exs is not None else None, ws_ptr, ws_bytes,
                                    stream), "mi_spmm_csr_ex_f32")
 
-    if SPMM_TWO_STREAMS and plan is not None and plan.n_items > 0:
+    if SPMM_TWO_STREAMS and plan is not None and (plan.n_items > 0 or n_thin > 0):
         # short rows beside the split rows' work items + fix-up: disjoint output rows, joined before returning
         cur = t.cuda.current_stream()
         side = _side_stream(a.device)
