@@ -215,18 +215,26 @@ class DeviceGraphSampler:
     def iter_users(self, users: Tensor) -> Iterator[HeteroData]:
         """The batches of `users` (int64, in this order, batch_size at a time) through the same pipelined iterator as an epoch:
         batch i is sampled with Philox step self.step + i, exactly what sample(users[i * B:(i + 1) * B], step=self.step + i)
-        returns — evaluation of a subset of the customers (a submission shard, held-out users) without a host wait per batch."""
-        self._order_override = users.detach().to("cpu", t.int64).contiguous()
-        return iter(self)
+        returns — evaluation of a subset of the customers (a submission shard, held-out users) without a host wait per batch.
+        The order belongs to the iterator returned HERE, whichever iterator of this sampler is advanced first.  Ids outside
+        [0, num_users) raise IndexError before anything is uploaded: the walk kernels index with them unchecked."""
+        order = users.detach().to("cpu", t.int64).contiguous().view(-1)
+        if order.numel() and (int(order.min()) < 0 or int(order.max()) >= self.num_users):
+            bad = order[(order < 0) | (order >= self.num_users)]
+            raise IndexError(f"iter_users: {int(bad.numel())} user id(s) outside [0, {self.num_users}), e.g. {int(bad[0])}")
+        return self._epoch(order)
 
     def __iter__(self) -> Iterator[HeteroData]:
         """One epoch: every user once, shuffled (DataLoader(shuffle=True) semantics).  With `prefetch` (default)
         sampling runs three batches ahead on a side stream while the consumer trains on batch i: nothing of the
-        sampler sits between two steps.  Same batches, same order, same Philox steps as the serial loop."""
-        g = t.Generator(device="cpu").manual_seed(self.seed + self.step)
-        order = getattr(self, "_order_override", None)
-        self._order_override = None
+        sampler sits between two steps.  Same batches, same order, same Philox steps as the serial loop.
+        An iterator abandoned mid-epoch (break, close(), dropped) orders the consumer's stream after whatever it had
+        queued on the side stream; self.step counts the batches handed out."""
+        return self._epoch(None)
+
+    def _epoch(self, order: Optional[Tensor]) -> Iterator[HeteroData]:
         if order is None:
+            g = t.Generator(device="cpu").manual_seed(self.seed + self.step)
             order = t.randperm(self.num_users, generator=g) if self.shuffle else t.arange(self.num_users)
         n_order = int(order.numel())
         batches = [order[b:b + self.batch_size] for b in range(0, n_order, self.batch_size)]
@@ -248,6 +256,7 @@ class DeviceGraphSampler:
         # the epoch's seed order goes to the device ONCE (round 4: a 24-element host-to-device copy per batch was 40 us of the
         # loop's host time — the loop is host-bound, tools/prof_host_native.py); a batch's seeds are a view of it
         order_dev = order.to(self.device, t.int64)
+        order_dev.record_stream(side)   # read by the side stream's walks: its memory is not reused before they are done
         batches_dev = [order_dev[b:b + self.batch_size] for b in range(0, n_order, self.batch_size)]
 
         side_raw = side.cuda_stream
@@ -332,13 +341,16 @@ class DeviceGraphSampler:
                 sys.setswitchinterval(interval)
                 t.cuda.current_stream(self.device).wait_stream(side)
             return
-        pend = {j: start(j) for j in range(min(DEPTH, nb))}      # phase A of the first DEPTH batches
-        cur = finish(0, pend.pop(0))
-        for i in range(nb):
-            data, ready = cur
-            if i + 1 < nb:
-                cur = finish(i + 1, pend.pop(i + 1))
-                if i + DEPTH < nb:
-                    pend[i + DEPTH] = start(i + DEPTH)
-            self.step = step0 + i + 1
-            yield hand_out(data, ready)
+        try:
+            pend = {j: start(j) for j in range(min(DEPTH, nb))}      # phase A of the first DEPTH batches
+            cur = finish(0, pend.pop(0))
+            for i in range(nb):
+                data, ready = cur
+                if i + 1 < nb:
+                    cur = finish(i + 1, pend.pop(i + 1))
+                    if i + DEPTH < nb:
+                        pend[i + DEPTH] = start(i + DEPTH)
+                self.step = step0 + i + 1
+                yield hand_out(data, ready)
+        finally:   # an abandoned epoch leaves up to DEPTH walks and an emit queued: the consumer's stream goes after them
+            t.cuda.current_stream(self.device).wait_stream(side)

@@ -76,10 +76,13 @@ _INTER_CACHE: dict = {}
 
 
 def _cached_interactions(edge_index: Tensor, num_users: int, num_items: int) -> Interactions:
-    key = (edge_index.data_ptr(), tuple(edge_index.shape), str(edge_index.device))
-    hit = _INTER_CACHE.get(key)
-    if hit is None:
-        _INTER_CACHE.clear()
-        hit = Interactions(edge_index, num_users, num_items)
-        _INTER_CACHE[key] = hit
-    return hit
+    """One entry: the Interactions of the edge_index last sampled from.  A hit needs the same tensor OBJECT (the entry
+    holds it, so its address is not reused), the _version it had (in-place edits through torch) and the same shape and id
+    ranges.  A caller that rewrites edge_index through a raw pointer or an aliasing tensor passes a fresh tensor or clears
+    _INTER_CACHE."""
+    key = (edge_index._version, tuple(edge_index.shape), num_users, num_items)
+    hit = _INTER_CACHE.get("last")
+    if hit is None or hit[0] is not edge_index or hit[1] != key:
+        hit = (edge_index, key, Interactions(edge_index, num_users, num_items))
+        _INTER_CACHE["last"] = hit
+    return hit[2]

@@ -6,6 +6,7 @@ function requires GPU tensors and raises otherwise — there is no CPU path in t
 from __future__ import annotations
 
 import ctypes
+import itertools
 import os
 from os import environ as _os_environ
 from dataclasses import dataclass, field
@@ -128,6 +129,9 @@ def _ws_reused(nbytes: int, device) -> Tensor:
 # --------------------------------------------------------------------------------------
 # CSR container
 # --------------------------------------------------------------------------------------
+_VAL_GEN = itertools.count(1)
+
+
 @dataclass
 class SpmmPlan:
     struct: SpmmPlanStruct
@@ -140,7 +144,9 @@ class SpmmPlan:
     sweep_t: tuple = ()
     wide: Optional["SpmmPlan"] = None             # work-item plan of the same adjacency for widths the sweep form lacks
     packed: tuple = ()                            # (epos, ecol, eval): the split rows' entries in launch order (mi_spmm_plan_pack_entries)
-    packed_of: tuple = ()                         # (val.data_ptr(), val._version) the packed values were copied from
+    sweep_src: Optional[Tensor] = None            # int32: position in a.val of every entry of sweep_t[1] (val_s), for a re-gather
+    values_of: tuple = ()                         # (source tensor, its _version, the adjacency's value generation) the
+                                                  # plan's value copies (packed[2], sweep_t[1]) were taken from: _sync_plan_values
     nnz_long: int = 0
     thin_rows: Optional[Tensor] = None            # int32: rows with chunk < degree <= thin_max, longest first (mi_spmm_ex.thin_rows)
     thin_max: int = 0
@@ -174,6 +180,23 @@ class DeviceCSR:
     perm: Optional[Tensor] = None
     plan: Optional[SpmmPlan] = None
     hot: Optional[Tuple[int, int]] = None   # (first row, rows) of X worth an LDS cache in dense launches: see spmm()
+
+    # Value generation: 0 for an adjacency whose `val` is the one it was built with, a process-wide fresh number after every
+    # later assignment of `val` and every invalidate_values().  With the identity and _version of the tensor itself it is
+    # what a plan's value copies are checked against (_sync_plan_values).
+    _val_gen = 0
+
+    def __setattr__(self, name, value):
+        if name == "val" and "val" in self.__dict__:
+            object.__setattr__(self, "_val_gen", next(_VAL_GEN))
+        object.__setattr__(self, name, value)
+
+    def invalidate_values(self) -> None:
+        """Tell the adjacency that the CONTENT of `val` was changed by a writer torch does not see: a kernel or a C-ABI
+        caller given val.data_ptr(), a write through another tensor that aliases its storage.  The next spmm(self, ...)
+        refreshes the value copies its plan holds.  Not needed after `self.val = tensor` or an in-place torch op on
+        `self.val` itself: those are seen."""
+        object.__setattr__(self, "_val_gen", next(_VAL_GEN))
 
     @property
     def nnz(self) -> int:
@@ -370,7 +393,8 @@ def build_sweep_plan(a: DeviceCSR, chunk: int = DEFAULT_CHUNK, band: int = SWEEP
     new_band = t.ones_like(band_key, dtype=t.bool)
     new_band[1:] = band_key[1:] != band_key[:-1]                                        # first entry of a band in its stream
     col_s = (((q_t[slot] << 28) | c)[order] | (new_band.to(t.int64) << 27)).to(t.int32).contiguous()
-    val_s = a.val[e][order].contiguous()
+    src = e[order].to(t.int32).contiguous()                                             # kept: a re-weighting is one gather
+    val_s = gather_f32(a.val, src)
     stream_ptr = t.searchsorted(stream_key, t.arange(8 * n_streams + 1, device=dev)).to(t.int32).contiguous()
     slot_of_t = t.tensor(slot_of, dtype=t.int32, device=dev)
     long_rows32 = long_rows.to(t.int32).contiguous()
@@ -385,7 +409,8 @@ def build_sweep_plan(a: DeviceCSR, chunk: int = DEFAULT_CHUNK, band: int = SWEEP
     # `epoch` carries the bands per XCD: read only by the MI_SWEEP_WG_SYNC experiment build of the kernel (profiles/r03_sweep.md)
     sw = SpmmSweepStruct(col_s.data_ptr(), val_s.data_ptr(), stream_ptr.data_ptr(), slot_of_t.data_ptr(), n_streams, n_slots,
                          None, int(n_t), max(SWEEP_PACE, 0))
-    return SpmmPlan(st, long_rows32, item_ptr, None, long_index, sweep=sw, sweep_t=(col_s, val_s, stream_ptr, slot_of_t))
+    return SpmmPlan(st, long_rows32, item_ptr, None, long_index, sweep=sw, sweep_t=(col_s, val_s, stream_ptr, slot_of_t),
+                    sweep_src=src, values_of=_values_key(a))
 
 
 def sweep_degree_threshold(a: DeviceCSR, chunk: int, n_streams: int = SWEEP_STREAMS, fill: float = 1.0) -> Optional[int]:
@@ -473,7 +498,8 @@ def build_hybrid_plan(a: DeviceCSR, chunk: int = DEFAULT_CHUNK, band: Optional[i
     st.n_items, st.n_launch = off + int(info.n_items), nlaunch
     st.long_rows, st.item_ptr, st.items, st.long_index = long_rows.data_ptr(), item_ptr.data_ptr(), items.data_ptr(), long_index.data_ptr()
     st.band, st.n_bands = int(info.band), int(info.n_bands)
-    return SpmmPlan(st, long_rows, item_ptr, items, long_index, sweep=sw.sweep, sweep_t=sw.sweep_t)
+    return SpmmPlan(st, long_rows, item_ptr, items, long_index, sweep=sw.sweep, sweep_t=sw.sweep_t,
+                    sweep_src=sw.sweep_src, values_of=sw.values_of)
 
 
 HYBRID_TAIL_BAND = int(_os_environ.get("LAPLACE_HYBRID_TAIL_BAND", 16384))  # columns per band of a hybrid plan's banded tail
@@ -533,6 +559,7 @@ def build_spmm_plan(a: DeviceCSR, chunk: int = DEFAULT_CHUNK, band: Optional[int
             plan.thin_rows = rows.to(t.int32).contiguous()
     if PACK_ENTRIES and nlaunch > 0 and plan.nnz_long > 0 and a.val is not None:
         _pack_plan_entries(a, plan, values_only=False)
+        plan.values_of = _values_key(a)
     return plan
 
 
@@ -548,7 +575,33 @@ def _pack_plan_entries(a: DeviceCSR, plan: SpmmPlan, values_only: bool) -> None:
     ws = _ws(L.mi_spmm_plan_pack_workspace_bytes(int(st.n_launch)), dev)
     check(L.mi_spmm_plan_pack_entries(ctypes.byref(st), plan.nnz_long, _ptr(a.col), _ptr(a.val), 1 if values_only else 0,
                                       ws.data_ptr(), ws.numel(), _stream()), "mi_spmm_plan_pack_entries")
-    plan.packed_of = (a.val.data_ptr(), a.val._version)
+
+
+def _values_key(a: DeviceCSR) -> tuple:
+    v = a.val
+    return (v, v._version, a._val_gen)
+
+
+def _sync_plan_values(a: DeviceCSR, plan: SpmmPlan) -> None:
+    """Every value COPY a plan holds — packed[2] of a banded / row-major plan, val_s of a sweep or hybrid plan — follows
+    a.val.  The plan remembers the tensor it copied from (a reference: its address cannot be handed to another tensor
+    meanwhile, and an alias of equal data_ptr() and _version is another object), that tensor's _version (in-place torch
+    ops) and the adjacency's value generation (DeviceCSR: assignment, invalidate_values()).  Unchanged = three
+    comparisons on the host, no device work.  Changed = one pack pass / one gather into the EXISTING storage (the
+    pointers inside the plan's structs stay), enqueued on the current stream ahead of the product."""
+    v = a.val
+    src, ver, gen = plan.values_of
+    if src is v and ver == v._version and gen == a._val_gen:
+        return
+    _need(v, t.float32, "val")
+    if v.numel() != a.nnz:
+        raise ValueError(f"val has {v.numel()} entries, the adjacency {a.nnz}")
+    if plan.packed:
+        _pack_plan_entries(a, plan, values_only=True)
+    if plan.sweep is not None:
+        val_s = plan.sweep_t[1]
+        check(_lib.lib().mi_gather_f32(val_s.numel(), _ptr(v), _ptr(plan.sweep_src), _ptr(val_s), _stream()), "mi_gather_f32")
+    plan.values_of = _values_key(a)
 
 
 def spmm(a: DeviceCSR, X: Tensor, *, Y: Optional[Tensor] = None, addend: Optional[Tensor] = None,
@@ -568,7 +621,11 @@ def spmm(a: DeviceCSR, X: Tensor, *, Y: Optional[Tensor] = None, addend: Optiona
     X[x_map[c]], negative = an all-zero row; addend_map int32[n_rows] — addend is compact; row_list
     int32[n] (+ n_list_dev, device int32[1]) — compute only these rows, Y/S/addend compact by list position.
     x_rare (with x_map): few columns are live (mi_spmm_ex.x_bits) — the split rows' work items test a bitmap of the map
-    first, gather only live entries and skip work items without any; bitwise the result without the hint."""
+    first, gather only live entries and skip work items without any; bitwise the result without the hint.
+
+    Re-weighting: a plan holds copies of the split rows' values.  `a.val = tensor` and in-place torch ops on `a.val` are
+    noticed by the next call (three integer / identity comparisons per call, _sync_plan_values); after a write torch cannot
+    see — a kernel or C-ABI caller given a.val.data_ptr(), a write through an aliasing tensor — call a.invalidate_values()."""
     if a.val is None:
         raise ValueError("spmm needs edge values (run gcn_norm or set val)")
     d = X.shape[1]
@@ -621,8 +678,8 @@ def spmm(a: DeviceCSR, X: Tensor, *, Y: Optional[Tensor] = None, addend: Optiona
             plan.wide = build_spmm_plan(a, chunk=int(plan.struct.chunk), sweep=False, thin_max=0)
         plan = plan.wide
     L = _lib.lib()
-    if plan is not None and plan.packed and plan.packed_of != (a.val.data_ptr(), a.val._version):
-        _pack_plan_entries(a, plan, values_only=True)     # the adjacency was re-weighted since the plan copied its values
+    if plan is not None and plan.values_of:
+        _sync_plan_values(a, plan)                        # the adjacency was re-weighted since the plan copied its values?
     ws_ptr, ws_bytes = None, 0
     if plan is not None and plan.n_items > 0:
         if d not in plan.partial:

@@ -239,11 +239,20 @@ class NativeRankerStep:
         others = []
         for key, name in ((Constants.node_user, "encoder_layer_norm_customer"), (Constants.node_item, "encoder_layer_norm_article")):
             bn = getattr(model, name)
-            if bn.track_running_stats:
+            if bn.track_running_stats:      # every buffer _build stores a pointer to, each replaceable on its own
                 others.append((lambda bn=bn: bn.running_mean, bn.running_mean.data_ptr()))
+                others.append((lambda bn=bn: bn.running_var, bn.running_var.data_ptr()))
+                others.append((lambda bn=bn: bn.num_batches_tracked, bn.num_batches_tracked.data_ptr()))
             tables = model.embedding_layers[key]
             for c in range(len(tables)):
                 others.append((lambda tables=tables, c=c: tables[c], tables[c].data_ptr()))
+        # weights the descriptor points to without the optimizer owning them (a frozen layer): parameter and gradient
+        owned = {id(p) for p in params}
+        for p in model.parameters():
+            if id(p) not in owned:
+                others.append((lambda p=p: p, p.data_ptr()))
+                if p.grad is not None:
+                    others.append((lambda p=p: p.grad if p.grad is not None else p, p.grad.data_ptr()))
         self._snapshot = (rows, others)
 
     # ------------------------------------------------------------------------------------------
@@ -317,8 +326,14 @@ class NativeRankerStep:
         dims = (n_c, n_a, int(by_c.nnz), n_lab, d.p_dropout > 0.0)
         sized = self._ws_dims      # (dims of the largest batch the counting pass has seen, its byte count)
         if self._ws is None or sized is None or dims[4] != sized[0][4] or any(x > y for x, y in zip(dims[:4], sized[0][:4])):
-            # the workspace is a sum of arrays proportional to these four counts, so a batch no larger in ANY of them than one the
-            # counting pass has sized needs no more than that one: the pass (a host walk of the whole iteration) is skipped for it
+            # The counting pass (a host walk of the whole iteration) is skipped for a batch no larger in ANY of these four counts
+            # than one it has sized.  That is a bet, not a bound: most of the workspace is arrays proportional to the counts, but
+            # the GEMMs' split-K partials are not monotone in them (mi_gemm_splits: an output of <= 8 tiles splits K from 512
+            # on, a ninth tile stops it — at a first-layer width of 512, (20000, 256, 1024, 300) is counted at MORE than
+            # (20000, 257, 4096, 300); no violation found at this suite's width of 64; tests/test_workspace_monotone_cpu.py).
+            # The count's own slack and the 25 % + 1 MiB of head-room below usually cover it; where they do not, the
+            # executor's validation pass answers MI_ERR_WORKSPACE before anything is
+            # enqueued and the pass is run after all (_recount_workspace: here under data parallelism, in step() otherwise).
             need = int(L.mi_ranker_step_workspace_bytes(ctypes.byref(d), ctypes.byref(b)))
             if self._ws is None or self._ws.numel() < need:
                 self._ws = t.empty(int(need * 1.25) + (1 << 20), dtype=t.uint8, device=xc.device)
@@ -327,11 +342,21 @@ class NativeRankerStep:
         if self._world() > 1:    # the validation pass on its own only where the ranks must agree BEFORE anything is enqueued;
             #                      a single process lets mi_ranker_step_f32 run it (the loop is host-bound: every call counts)
             rc = L.mi_ranker_step_check(ctypes.byref(d), ctypes.byref(b), self._ws.data_ptr(), self._ws.numel())
+            if rc == _lib.MI_ERR_WORKSPACE:    # the skipped counting pass after all, BEFORE the ranks vote
+                self._recount_workspace(d, b)
+                rc = L.mi_ranker_step_check(ctypes.byref(d), ctypes.byref(b), self._ws.data_ptr(), self._ws.numel())
             if rc == _lib.MI_ERR_UNSUPPORTED:
                 self.declined = "mi_ranker_step_f32: MI_ERR_UNSUPPORTED (shape outside the executor's)"
                 return None
             _lib.check(rc, "mi_ranker_step_check")
         return d, b, loss, steps, (xc, xa, row, col, labels, ones, by_c, by_a)
+
+    def _recount_workspace(self, d: RankerModel, b: RankerBatch) -> None:
+        """MI_ERR_WORKSPACE from the validation pass (nothing enqueued): this batch needs more than the larger one the
+        workspace was sized on.  Count it, allocate, and forget the remembered dims so that the next batch is counted too."""
+        need = int(_lib.lib().mi_ranker_step_workspace_bytes(ctypes.byref(d), ctypes.byref(b)))
+        self._ws = t.empty(int(need * 1.25) + (1 << 20), dtype=t.uint8, device=self._ws.device)
+        self._ws_dims = None
 
     def _world(self) -> int:
         import torch.distributed as dist
@@ -353,7 +378,12 @@ class NativeRankerStep:
         rank the decision is collective: every rank returns None when ANY rank's batch is declined, so all of them take the
         caller's fallback together (`declined` then names the local reason, or says that a peer declined)."""
         self.declined = None       # why the last call returned None (diagnostics)
-        prep = self._prepare(x_dict, edge_index_dict, edge_label_index, labels)
+        try:
+            prep = self._prepare(x_dict, edge_index_dict, edge_label_index, labels)
+        except BaseException:
+            if self._world() > 1:          # the peers are on their way into the vote: answer it, then fail here
+                self._all_ranks_take_it(False, next(self.model.parameters()).device)
+            raise
         if self._world() > 1:
             if not self._all_ranks_take_it(prep is not None, next(self.model.parameters()).device):
                 if prep is not None:
@@ -366,9 +396,7 @@ class NativeRankerStep:
         L = _lib.lib()
         rc = L.mi_ranker_step_f32(ctypes.byref(d), ctypes.byref(b), self._ws.data_ptr(), self._ws.numel(), _lib.current_stream())
         if rc == _lib.MI_ERR_WORKSPACE:        # (found by the validation pass: nothing enqueued) the skipped counting pass after all
-            need = int(L.mi_ranker_step_workspace_bytes(ctypes.byref(d), ctypes.byref(b)))
-            self._ws = t.empty(int(need * 1.25) + (1 << 20), dtype=t.uint8, device=self._ws.device)
-            self._ws_dims = None
+            self._recount_workspace(d, b)
             rc = L.mi_ranker_step_f32(ctypes.byref(d), ctypes.byref(b), self._ws.data_ptr(), self._ws.numel(), _lib.current_stream())
         if rc == _lib.MI_ERR_UNSUPPORTED:
             if self._world() > 1:              # cannot happen: mi_ranker_step_check took the same descriptors
