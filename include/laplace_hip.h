@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define MI_ABI_VERSION 10
+#define MI_ABI_VERSION 11
 
 #define MI_ERR_BAD_ARG      (-1)  /* null pointer, negative size, misaligned buffer   */
 #define MI_ERR_TOO_LARGE    (-2)  /* a size does not fit int32 indexing                */
@@ -394,6 +394,58 @@ int    mi_bpr_fwd_bwd_f32(int64_t batch, int64_t d, int64_t n_users,
                           float* reg_w,
                           const int32_t* node_map,
                           void* ws, size_t ws_bytes, mi_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
+ * Ranking objectives over M negatives per positive (SURVEY F9 behind a flag).
+ * A batch is users[B], pos[B], neg[B, n_neg] (int64, row-major), 1 <= n_neg <= 16; n_neg outside that range or
+ * an unknown objective returns MI_ERR_UNSUPPORTED before anything is enqueued.
+ *
+ * Sampler: n_neg structured negatives per slot, drawn independently (they may repeat), same rejection rules and
+ * quirk bits as the one-negative sampler.  Negative m of edge e, attempt t, takes the Philox counter
+ * (e, t | m << 16) of the negative stream: column 0 is bit-identical to the one-negative sampler's output.
+ *
+ * Node set: the unique nodes over the (2 + n_neg) * batch references; same slot order contract and workspace as
+ * the one-negative form; nodes int32[>= (2 + n_neg) * batch].
+ *
+ * Loss, with s+_b = <f_u, f_p>, s-_{b,m} = <f_u, f_{n_m}> on rows of final_emb and x_{b,m} = s+_b - s-_{b,m}:
+ *   MI_RANK_REFERENCE  -(1/(B M)) sum softplus(x)      (torch softplus, threshold 20: the reference's objective)
+ *   MI_RANK_BPR         (1/(B M)) sum softplus(-x)     = -mean log sigmoid(x)
+ *   MI_RANK_SOFTMAX     (1/B) sum_b [ logsumexp(s+_b, s-_{b,1..M}) - s+_b ]   (max subtracted, m ascending)
+ * plus lambda * sum_b (|u0|^2 + |p0|^2 + sum_m |n0_m|^2) on rows of e0.  reg_scale scales reg_w (the L2 term's
+ * GRADIENT) only: the L2 term of the loss VALUE carries lambda alone, exactly as mi_bpr_fwd_bwd_f32 writes it, which the
+ * bitwise identity at (MI_RANK_REFERENCE, n_neg = 1) needs for every reg_scale.
+ * g_final, reg_w, node_map, g_scale, reg_scale, loss_out and the workspace behave as in the one-negative
+ * entry: g_final[row] = g_scale * dL/dfinal[row] on zeroed input, reg_w[row] = occurrences * 2*lambda*reg_scale.
+ * No float atomics on the gradient: the (2 + M) B row references (role 0 user, 1 positive, 2 + m negative m) are
+ * stable-sorted by row and summed in 64-reference chunks in reference order, one writer per row — bitwise
+ * reproducible.  d <= 512.  With MI_RANK_REFERENCE and n_neg = 1 loss, g_final and reg_w carry the bits of
+ * the one-negative entry.
+ * ---------------------------------------------------------------------------------- */
+#define MI_RANK_REFERENCE 0
+#define MI_RANK_BPR       1
+#define MI_RANK_SOFTMAX   2
+int mi_sample_bpr_batch_ex(int64_t batch, int32_t n_neg, int64_t nnz,
+                           const int32_t* rowptr, const int32_t* col,
+                           const int32_t* row_of_edge,
+                           int64_t neg_range, int32_t quirk_user_rows, int32_t edges_in_order,
+                           uint64_t seed, uint64_t step,
+                           int64_t* users, int64_t* pos, int64_t* neg /* [batch, n_neg] */,
+                           mi_stream_t stream);
+int mi_batch_nodes_ex_i32(int64_t batch, int32_t n_neg, int64_t n_users, int64_t n_nodes,
+                          const int64_t* users, const int64_t* pos, const int64_t* neg,
+                          int32_t* gmap, int32_t* nodes, int32_t* count,
+                          void* ws, size_t ws_bytes, mi_stream_t stream);
+size_t mi_rank_loss_workspace_bytes(int64_t batch, int32_t n_neg);
+int    mi_rank_loss_fwd_bwd_f32(int64_t batch, int32_t n_neg, int32_t objective, int64_t d, int64_t n_users,
+                                const int64_t* users, const int64_t* pos, const int64_t* neg,
+                                const float* final_emb, int64_t ldf,
+                                const float* e0, int64_t lde,
+                                float lambda, float g_scale, float reg_scale,
+                                float* loss_out,
+                                float* g_final, int64_t ldg,
+                                float* reg_w,
+                                const int32_t* node_map,
+                                void* ws, size_t ws_bytes, mi_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
  * a9  dense Adam step (torch.optim.Adam semantics, no weight decay, no amsgrad).

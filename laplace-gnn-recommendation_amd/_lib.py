@@ -10,7 +10,7 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 # the package directory is never overwritten by an experiment.  It is still this library or nothing — no fallback.
 LIB_PATH = os.environ.get("LAPLACE_HIP_LIB") or os.path.join(PKG_DIR, "liblaplace_hip.so")
 
-MI_ABI_VERSION = 10
+MI_ABI_VERSION = 11
 MI_SPMM_GROUP = 32
 
 
@@ -54,6 +54,8 @@ MI_SPMM_SHORT_ROWS, MI_SPMM_SPLIT_ROWS = 1, 2
 MI_ERR_UNSUPPORTED = -4
 MI_ERR_WORKSPACE = -3
 MI_TOPK_ITEMS_PREPARED = 1
+MI_RANK_OBJECTIVES = {"reference": 0, "bpr": 1, "softmax": 2}
+MI_RANK_MAX_NEG = 16
 
 
 class GemmProblem(Structure):
@@ -207,6 +209,12 @@ _PROTOTYPES = {
     "mi_bpr_workspace_bytes": (c_size_t, [c_int64]),
     "mi_bpr_fwd_bwd_f32": (c_int32, [c_int64, c_int64, c_int64, P, P, P, P, c_int64, P, c_int64,
                                      c_float, c_float, c_float, P, P, c_int64, P, P, P, c_size_t, P]),
+    "mi_sample_bpr_batch_ex": (c_int32, [c_int64, c_int32, c_int64, P, P, P, c_int64, c_int32, c_int32, c_uint64, c_uint64,
+                                         P, P, P, P]),
+    "mi_batch_nodes_ex_i32": (c_int32, [c_int64, c_int32, c_int64, c_int64, P, P, P, P, P, P, P, c_size_t, P]),
+    "mi_rank_loss_workspace_bytes": (c_size_t, [c_int64, c_int32]),
+    "mi_rank_loss_fwd_bwd_f32": (c_int32, [c_int64, c_int32, c_int32, c_int64, c_int64, P, P, P, P, c_int64, P, c_int64,
+                                           c_float, c_float, c_float, P, P, c_int64, P, P, P, c_size_t, P]),
     "mi_gemm_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64]),
     "mi_gemm_f32": (c_int32, [c_int32, c_int32, c_int64, c_int64, c_int64, P, c_int64, P, c_int64, P, P, c_int64,
                               c_int32, c_int32, P, c_size_t, P]),

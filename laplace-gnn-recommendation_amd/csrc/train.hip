@@ -58,6 +58,38 @@ __global__ void sample_bpr_kernel(int64_t batch, int64_t nnz, const int32_t* __r
     neg[b] = cand;
 }
 
+// M negatives per slot (mi_sample_bpr_batch_ex): one thread per (slot, m).  Negative m of edge e, attempt t, takes the
+// counter (e, t | m << 16) of the NEG! stream (t < 4096 < 2^16), so column 0 is the one-negative sampler's draw.
+__global__ void sample_bpr_ex_kernel(int64_t batch, int n_neg, int64_t nnz, const int32_t* __restrict__ rowptr,
+                                     const int32_t* __restrict__ col, const int32_t* __restrict__ row_of_edge,
+                                     int64_t neg_range, int32_t quirk, int32_t edges_in_order, uint64_t seed,
+                                     uint64_t step, int64_t* __restrict__ users, int64_t* __restrict__ pos,
+                                     int64_t* __restrict__ neg) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= batch * n_neg) return;
+    const int64_t b = i / n_neg;
+    const uint32_t m = (uint32_t)(i - b * n_neg);
+    const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+    const uint32_t s0 = (uint32_t)step, s1 = (uint32_t)(step >> 32);
+    MiPhilox r = mi_philox4x32((uint32_t)b, (uint32_t)((uint64_t)b >> 32), s0, s1 ^ kTagEdge, k0, k1);
+    const uint64_t e = edges_in_order ? (uint64_t)b : (((uint64_t)r.c[0] << 32) | r.c[1]) % (uint64_t)nnz;
+    const int64_t u = row_of_edge[e];
+    int32_t cand = 0;
+    for (int t = 0; t < kMaxNegAttempts; ++t) {
+        MiPhilox q = mi_philox4x32((uint32_t)e, (uint32_t)t | (m << 16), s0, s1 ^ kTagNeg, k0, k1);
+        cand = (int32_t)((((uint64_t)q.c[0] << 32) | q.c[1]) % (uint64_t)neg_range);
+        bool hit = csr_contains(rowptr, col, u, cand);
+        if (!hit && (quirk & 1) && cand == 0 && u > 0) hit = csr_contains(rowptr, col, u - 1, (int32_t)neg_range);
+        if (!hit && (quirk & 2) && (int64_t)cand == u) hit = true;
+        if (!hit) break;
+    }
+    if (m == 0) {
+        users[b] = u;
+        pos[b] = col[e];
+    }
+    neg[i] = cand;
+}
+
 // ------------------------------------------------------------------ BPR ----------------
 __device__ __forceinline__ float softplus_ref(float x) {  // torch softplus, beta=1, threshold=20
     return x > 20.f ? x : log1pf(expf(x));
@@ -245,11 +277,10 @@ __global__ __launch_bounds__(kBlock) void bpr_chunk_kernel(
 // One wavefront per chunk whose trailing run starts in it and runs on: tail partial + the head partials of the following
 // chunks, in chunk order, added to the row.
 template <int VPT>
-__global__ __launch_bounds__(kBlock) void bpr_combine_kernel(int64_t batch, int d, const uint32_t* __restrict__ keys,
+__global__ __launch_bounds__(kBlock) void bpr_combine_kernel(int64_t n_ref, int d, const uint32_t* __restrict__ keys,
                                                              const float* __restrict__ part_head,
                                                              const float* __restrict__ part_tail,
                                                              float* __restrict__ g_final, int64_t ldg) {
-    const int64_t n_ref = 3 * batch;
     const int64_t chunk = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / MI_WAVE;
     const int64_t j0 = chunk * kRefChunk;
     if (j0 >= n_ref) return;
@@ -308,6 +339,260 @@ __global__ __launch_bounds__(1024) void bpr_finish_kernel(int64_t batch,
     if (t == 0) loss_out[0] = -sh_a[0] * inv_batch + lambda * sh_b[0];
 }
 
+// ------------------------------------------------------------------ ranking objectives, M negatives ------------
+// mi_rank_loss_fwd_bwd_f32: the same three passes as above over users[B], pos[B], neg[B, M].
+//   x_{b,m} = s+_b - s-_{b,m};  reference: -softplus(x) / (BM);  bpr: softplus(-x) / (BM);
+//   softmax: (logsumexp(s+_b, s-_{b,1..M}) - s+_b) / B
+// The slot pass leaves 1 + M coefficients per slot for the gradient pass, coef[b][0] = g_scale * dL/ds+_b and
+// coef[b][1 + m] = g_scale * dL/ds-_{b,m}.  At (reference, M = 1) every sum below runs in the order of the kernels above.
+constexpr int kRankReference = 0, kRankBpr = 1, kRankSoftmax = 2;
+constexpr int kMaxNeg = 16;
+
+__device__ __forceinline__ float softplus_stable(float x) { return fmaxf(x, 0.f) + log1pf(expf(-fabsf(x))); }
+__device__ __forceinline__ float sigmoid_stable(float x) {
+    const float z = expf(-fabsf(x));
+    return (x >= 0.f ? 1.f : z) / (1.f + z);
+}
+
+// One wavefront per batch slot; the user's final row stays in registers (VPT = ceil(d / 64) floats per lane) while the
+// positive and the M negatives stream past it.  Lane m keeps s-_{b,m}: scalars only, nothing indexed by m.
+template <int VPT>
+__global__ __launch_bounds__(kBlock) void rank_slot_kernel(
+    int64_t batch, int n_neg, int objective, int d, int64_t n_users, const int64_t* __restrict__ users,
+    const int64_t* __restrict__ pos, const int64_t* __restrict__ neg, const float* __restrict__ fin, int64_t ldf,
+    const float* __restrict__ e0, int64_t lde, float inv_count, float g_scale, float reg_coef,
+    float* __restrict__ term_out /* minus the slot's loss term, before the mean */, float* __restrict__ reg_out,
+    float* __restrict__ coef_out, float* __restrict__ reg_w /* only when no gradient pass follows */,
+    const int32_t* __restrict__ node_map) {
+    const int64_t b = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / MI_WAVE;
+    if (b >= batch) return;
+    const int lane = mi_lane();
+    const int64_t u = users[b], p = n_users + pos[b];
+    const float* uf_row = fin + (node_map ? (int64_t)node_map[u] : u) * ldf;
+    const float* pf_row = fin + (node_map ? (int64_t)node_map[p] : p) * ldf;
+    const float* u0 = e0 + u * lde;
+    const float* p0 = e0 + p * lde;
+    float uf[VPT];
+    float sp = 0.f, rg = 0.f;
+#pragma unroll
+    for (int v = 0; v < VPT; ++v) {
+        const int k = lane + v * MI_WAVE;
+        uf[v] = k < d ? uf_row[k] : 0.f;
+        sp = fmaf(uf[v], k < d ? pf_row[k] : 0.f, sp);
+    }
+    sp = mi_wave_sum(sp);
+    float my_sn = 0.f;
+    for (int m = 0; m < n_neg; ++m) {
+        const int64_t n = n_users + neg[b * n_neg + m];
+        const float* nf_row = fin + (node_map ? (int64_t)node_map[n] : n) * ldf;
+        const float* n0 = e0 + n * lde;
+        float sn = 0.f;
+#pragma unroll
+        for (int v = 0; v < VPT; ++v) {
+            const int k = lane + v * MI_WAVE;
+            const bool in = k < d;
+            sn = fmaf(uf[v], in ? nf_row[k] : 0.f, sn);
+            if (m == 0) {   // |u0|^2 and |p0|^2 once, interleaved with the first negative's as in bpr_slot_kernel
+                const float x0 = in ? u0[k] : 0.f, x1 = in ? p0[k] : 0.f;
+                rg = fmaf(x0, x0, rg);
+                rg = fmaf(x1, x1, rg);
+            }
+            const float x2 = in ? n0[k] : 0.f;
+            rg = fmaf(x2, x2, rg);
+        }
+        sn = mi_wave_sum(sn);
+        if (lane == m) my_sn = sn;
+    }
+    rg = mi_wave_sum(rg);
+    const bool mine = lane < n_neg;
+    float term, a, dm;   // term: wave-uniform; a = coef[b][0]: wave-uniform; dm = coef[b][1 + lane]
+    if (objective == kRankSoftmax) {
+        float mx = sp;
+        for (int m = 0; m < n_neg; ++m) mx = fmaxf(mx, __shfl(my_sn, m, MI_WAVE));
+        const float ep = expf(sp - mx);
+        const float en = mine ? expf(my_sn - mx) : 0.f;
+        float sum = ep;
+        for (int m = 0; m < n_neg; ++m) sum += __shfl(en, m, MI_WAVE);   // ascending m
+        term = -((mx + logf(sum)) - sp);
+        const float w = inv_count * g_scale;
+        a = (ep / sum - 1.f) * w;
+        dm = (en / sum) * w;
+    } else {
+        const float x = sp - my_sn;
+        float val, c;   // c = g_scale * dL/dx_{b,lane}
+        if (objective == kRankReference) {
+            val = softplus_ref(x);
+            c = -softplus_grad_ref(x) * inv_count * g_scale;
+        } else {
+            val = -softplus_stable(-x);
+            c = -sigmoid_stable(-x) * inv_count * g_scale;
+        }
+        term = __shfl(val, 0, MI_WAVE);
+        a = __shfl(c, 0, MI_WAVE);
+        for (int m = 1; m < n_neg; ++m) {   // ascending m
+            term += __shfl(val, m, MI_WAVE);
+            a += __shfl(c, m, MI_WAVE);
+        }
+        dm = -c;
+    }
+    if (lane == 0) {
+        term_out[b] = term;
+        reg_out[b] = rg;
+    }
+    if (coef_out) {
+        float* cb = coef_out + b * (1 + n_neg);
+        if (lane == 0) cb[0] = a;
+        if (mine) cb[1 + lane] = dm;
+    }
+    if (reg_w) {
+        const float w = 2.0f * reg_coef;
+        if (lane == 0) {
+            atomicAdd(reg_w + u, w);
+            atomicAdd(reg_w + p, w);
+        }
+        if (mine) atomicAdd(reg_w + n_users + neg[b * n_neg + lane], w);
+    }
+}
+
+__global__ void rank_refs_kernel(int64_t batch, int n_neg, int64_t n_users, const int64_t* __restrict__ users,
+                                 const int64_t* __restrict__ pos, const int64_t* __restrict__ neg,
+                                 const int32_t* __restrict__ node_map, uint32_t* __restrict__ keys,
+                                 uint32_t* __restrict__ refs) {
+    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;  // reference id = role * batch + b
+    if (r >= (2 + n_neg) * batch) return;
+    const int role = (int)(r / batch);   // 0 user, 1 positive, 2 + m negative m
+    const int64_t b = r - role * batch;
+    const int64_t node = role == 0 ? users[b] : n_users + (role == 1 ? pos[b] : neg[b * n_neg + (role - 2)]);
+    keys[r] = (uint32_t)(node_map ? node_map[node] : node);
+    refs[r] = (uint32_t)r;
+}
+
+// bpr_chunk_kernel for (2 + M) B references.  A user reference carries 1 + M (source row, weight) terms — the positive,
+// then the negatives in order — an item reference one.  The terms of a chunk are numbered through (wave prefix sum of the
+// per-reference counts) and taken in rounds of 64, lane L preparing term r0 + L; the in-order pass then keeps U source rows
+// in flight whatever the mix of roles.
+template <int VPT>
+__global__ __launch_bounds__(kBlock) void rank_chunk_kernel(
+    int64_t batch, int n_neg, int d, int64_t n_users, const int64_t* __restrict__ users,
+    const int64_t* __restrict__ pos, const int64_t* __restrict__ neg, const float* __restrict__ fin, int64_t ldf,
+    const float* __restrict__ coef, const uint32_t* __restrict__ keys, const uint32_t* __restrict__ refs,
+    const int32_t* __restrict__ node_map, float* __restrict__ g_final, int64_t ldg, float* __restrict__ part_head,
+    float* __restrict__ part_tail, float* __restrict__ reg_w, float reg_unit) {
+    const int64_t n_ref = (2 + n_neg) * batch;
+    const int64_t chunk = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / MI_WAVE;
+    const int64_t j0 = chunk * kRefChunk;
+    if (j0 >= n_ref) return;
+    const int lane = mi_lane();
+    const int n_here = (int)min((int64_t)kRefChunk, n_ref - j0);
+    uint32_t my_key = 0xFFFFFFFFu;
+    int my_role = 1, my_b = 0, my_terms = 0;
+    if (lane < n_here) {
+        my_key = keys[j0 + lane];
+        const uint32_t r = refs[j0 + lane];
+        my_role = (int)(r / batch);
+        my_b = (int)(r - (int64_t)my_role * batch);
+        my_terms = my_role == 0 ? 1 + n_neg : 1;
+        if (reg_w) {   // the reference that opens the node's run is the entry's only writer (see bpr_chunk_kernel)
+            const int64_t j = j0 + lane;
+            if (j == 0 || keys[j - 1] != my_key) {
+                int64_t lo = j + 1, hi = n_ref;
+                while (lo < hi) {
+                    const int64_t mid = (lo + hi) >> 1;
+                    if (keys[mid] == my_key) lo = mid + 1; else hi = mid;
+                }
+                const int64_t node = my_role == 0 ? users[my_b] : n_users + (my_role == 1 ? pos[my_b] : neg[(int64_t)my_b * n_neg + (my_role - 2)]);
+                reg_w[node] = (float)(lo - j) * reg_unit;
+            }
+        }
+    }
+    int incl = my_terms;   // inclusive prefix sum over the wavefront
+#pragma unroll
+    for (int off = 1; off < MI_WAVE; off <<= 1) {
+        const int below = __shfl_up(incl, off, MI_WAVE);
+        if (lane >= off) incl += below;
+    }
+    const int total = __shfl(incl, MI_WAVE - 1, MI_WAVE);
+    const int excl = incl - my_terms;
+    const bool head_open = j0 > 0 && keys[j0 - 1] == __shfl(my_key, 0, MI_WAVE);
+    const bool next_same = (j0 + n_here < n_ref) && keys[j0 + n_here] == __shfl(my_key, n_here - 1, MI_WAVE);
+    float acc[VPT];
+#pragma unroll
+    for (int v = 0; v < VPT; ++v) acc[v] = 0.f;
+    int run_start = 0;
+    constexpr int U = 8;  // terms whose source rows are in flight together
+    for (int r0 = 0; r0 < total; r0 += MI_WAVE) {
+        // a round of up to 64 terms, one per lane: owner by bisection over the prefix sums, then this lane's own chain of
+        // loads (ids -> slot -> weight), so that the in-order pass below only shuffles
+        const int n_round = min(MI_WAVE, total - r0);
+        const int j = min(r0 + lane, total - 1);
+        // owner of term j = the q with incl[q - 1] <= j < incl[q] (incl[-1] = 0): the smallest q with incl[q] > j.  It lies in
+        // [lo, hi] throughout — incl[n_here - 1] = total > j, so hi always satisfies the test — and each step halves that
+        // range of at most 64 references: 6 steps leave lo == hi.  Every lane runs all 6 (the shuffles need the whole wave).
+        int lo = 0, hi = n_here - 1;
+#pragma unroll
+        for (int it = 0; it < 6; ++it) {
+            const int mid = (lo + hi) >> 1;
+            if (__shfl(incl, mid, MI_WAVE) > j) hi = mid; else lo = mid + 1;
+        }
+        const int t_owner = hi;
+        const int role = __shfl(my_role, t_owner, MI_WAVE);
+        const int64_t b = __shfl(my_b, t_owner, MI_WAVE);
+        const int tt = j - __shfl(excl, t_owner, MI_WAVE);
+        const int t_closes = j + 1 == __shfl(incl, t_owner, MI_WAVE);
+        int64_t t_src;
+        int ci;
+        if (role == 0) {
+            t_src = n_users + (tt == 0 ? pos[b] : neg[b * n_neg + (tt - 1)]);
+            ci = tt;
+        } else {
+            t_src = users[b];
+            ci = role - 1;
+        }
+        if (node_map) t_src = node_map[t_src];
+        const float t_w = r0 + lane < total ? coef[b * (1 + n_neg) + ci] : 0.f;
+        for (int q0 = 0; q0 < n_round; q0 += U) {
+            float x[U][VPT], w[U];
+#pragma unroll
+            for (int i = 0; i < U; ++i) {
+                const int sl = min(q0 + i, n_round - 1);
+                const bool live = q0 + i < n_round;
+                w[i] = live ? __shfl(t_w, sl, MI_WAVE) : 0.f;
+                const float* row = fin + __shfl(t_src, sl, MI_WAVE) * ldf;
+#pragma unroll
+                for (int v = 0; v < VPT; ++v) {
+                    const int k = lane + v * MI_WAVE;
+                    x[i][v] = (live && k < d) ? row[k] : 0.f;
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < U; ++i) {
+                const int sl = q0 + i;
+                if (sl >= n_round) break;
+#pragma unroll
+                for (int v = 0; v < VPT; ++v) acc[v] = fmaf(w[i], x[i][v], acc[v]);
+                if (!__shfl(t_closes, sl, MI_WAVE)) continue;   // more terms of this reference follow
+                const int q = __shfl(t_owner, sl, MI_WAVE);
+                const uint32_t kq = __shfl(my_key, q, MI_WAVE);
+                const bool last_of_run = (q + 1 == n_here) || __shfl(my_key, q + 1, MI_WAVE) != kq;
+                if (!last_of_run) continue;
+                const bool from_prev = run_start == 0 && head_open;
+                const bool into_next = (q + 1 == n_here) && next_same;
+                float* dst;
+                if (from_prev) dst = part_head + chunk * d;
+                else if (into_next) dst = part_tail + chunk * d;
+                else dst = g_final + (int64_t)kq * ldg;
+#pragma unroll
+                for (int v = 0; v < VPT; ++v) {
+                    const int k = lane + v * MI_WAVE;
+                    if (k < d) dst[k] = acc[v];
+                    acc[v] = 0.f;
+                }
+                run_start = q + 1;
+            }
+        }
+    }
+}
+
 // ------------------------------------------------------------------ batch node set ------
 __global__ void mark_batch_nodes_kernel(int64_t batch, int64_t n_users, const int64_t* __restrict__ users,
                                         const int64_t* __restrict__ pos, const int64_t* __restrict__ neg,
@@ -317,6 +602,19 @@ __global__ void mark_batch_nodes_kernel(int64_t batch, int64_t n_users, const in
     flag[users[b]] = 1;  // same value from every writer: order does not matter
     flag[n_users + pos[b]] = 1;
     flag[n_users + neg[b]] = 1;
+}
+
+__global__ void mark_batch_nodes_ex_kernel(int64_t batch, int n_neg, int64_t n_users, const int64_t* __restrict__ users,
+                                           const int64_t* __restrict__ pos, const int64_t* __restrict__ neg,
+                                           int32_t* __restrict__ flag) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;   // (slot, m)
+    if (i >= batch * n_neg) return;
+    flag[n_users + neg[i]] = 1;
+    if (i % n_neg == 0) {
+        const int64_t b = i / n_neg;
+        flag[users[b]] = 1;
+        flag[n_users + pos[b]] = 1;
+    }
 }
 
 __global__ void finish_batch_nodes_kernel(int64_t n_nodes, int64_t n_users, const int32_t* __restrict__ flag,
@@ -415,14 +713,30 @@ int mi_sample_bpr_batch(int64_t batch, int64_t nnz, const int32_t* rowptr, const
     return mi_launch_status();
 }
 
+int mi_sample_bpr_batch_ex(int64_t batch, int32_t n_neg, int64_t nnz, const int32_t* rowptr, const int32_t* col,
+                           const int32_t* row_of_edge, int64_t neg_range, int32_t quirk_user_rows,
+                           int32_t edges_in_order, uint64_t seed, uint64_t step, int64_t* users, int64_t* pos,
+                           int64_t* neg, mi_stream_t stream) {
+    if (n_neg < 1 || n_neg > kMaxNeg) return MI_ERR_UNSUPPORTED;
+    MI_CHECK_ARG(batch >= 0 && (!edges_in_order || batch <= nnz));
+    if (batch == 0) return 0;
+    MI_CHECK_ARG(nnz > 0 && neg_range > 0 && rowptr && col && row_of_edge && users && pos && neg);
+    if (nnz >= INT32_MAX || neg_range >= INT32_MAX) return MI_ERR_TOO_LARGE;
+    dim3 g((unsigned)mi_ceil_div(batch * n_neg, kBlock));
+    hipLaunchKernelGGL(sample_bpr_ex_kernel, g, dim3(kBlock), 0, (hipStream_t)stream, batch, (int)n_neg, nnz, rowptr, col,
+                       row_of_edge, neg_range, quirk_user_rows, edges_in_order, seed, step, users, pos, neg);
+    return mi_launch_status();
+}
+
 size_t mi_batch_nodes_workspace_bytes(int64_t n_nodes) {
     const size_t n1 = (size_t)(n_nodes > 0 ? n_nodes : 0) + 1;
     return 2 * mi_align_up(n1 * sizeof(int32_t), 256) + ((size_t)16 << 20);
 }
 
-int mi_batch_nodes_i32(int64_t batch, int64_t n_users, int64_t n_nodes, const int64_t* users,
-                       const int64_t* pos, const int64_t* neg, int32_t* gmap, int32_t* nodes,
-                       int32_t* count, void* ws, size_t ws_bytes, mi_stream_t stream) {
+// n_neg == 0: the one-negative marking kernel of mi_batch_nodes_i32
+static int batch_nodes_run(int64_t batch, int n_neg, int64_t n_users, int64_t n_nodes, const int64_t* users,
+                           const int64_t* pos, const int64_t* neg, int32_t* gmap, int32_t* nodes,
+                           int32_t* count, void* ws, size_t ws_bytes, mi_stream_t stream) {
     MI_CHECK_ARG(batch > 0 && n_users >= 0 && n_nodes >= n_users && n_nodes > 0);
     MI_CHECK_ARG(users && pos && neg && gmap && nodes && count && ws);
     if (n_nodes >= INT32_MAX) return MI_ERR_TOO_LARGE;
@@ -433,8 +747,12 @@ int mi_batch_nodes_i32(int64_t batch, int64_t n_users, int64_t n_nodes, const in
     int32_t* slot = arena.take<int32_t>(n1);
     if (!flag || !slot) return MI_ERR_WORKSPACE;
     MI_HIP(hipMemsetAsync(flag, 0, (size_t)n1 * sizeof(int32_t), s));
-    hipLaunchKernelGGL(mark_batch_nodes_kernel, dim3((unsigned)mi_ceil_div(batch, kBlock)), dim3(kBlock), 0, s, batch,
-                       n_users, users, pos, neg, flag);
+    if (n_neg == 0)
+        hipLaunchKernelGGL(mark_batch_nodes_kernel, dim3((unsigned)mi_ceil_div(batch, kBlock)), dim3(kBlock), 0, s, batch,
+                           n_users, users, pos, neg, flag);
+    else
+        hipLaunchKernelGGL(mark_batch_nodes_ex_kernel, dim3((unsigned)mi_ceil_div(batch * n_neg, kBlock)), dim3(kBlock), 0,
+                           s, batch, n_neg, n_users, users, pos, neg, flag);
     size_t tmp_bytes = 0;
     MI_HIP(rocprim::exclusive_scan(nullptr, tmp_bytes, flag, slot, 0, (size_t)n1, rocprim::plus<int32_t>(), s));
     char* tmp = arena.take<char>(tmp_bytes ? tmp_bytes : 1);
@@ -443,6 +761,19 @@ int mi_batch_nodes_i32(int64_t batch, int64_t n_users, int64_t n_nodes, const in
     hipLaunchKernelGGL(finish_batch_nodes_kernel, dim3((unsigned)mi_ceil_div(n1, kBlock)), dim3(kBlock), 0, s, n_nodes,
                        n_users, flag, slot, gmap, nodes, count);
     return mi_launch_status();
+}
+
+int mi_batch_nodes_i32(int64_t batch, int64_t n_users, int64_t n_nodes, const int64_t* users,
+                       const int64_t* pos, const int64_t* neg, int32_t* gmap, int32_t* nodes,
+                       int32_t* count, void* ws, size_t ws_bytes, mi_stream_t stream) {
+    return batch_nodes_run(batch, 0, n_users, n_nodes, users, pos, neg, gmap, nodes, count, ws, ws_bytes, stream);
+}
+
+int mi_batch_nodes_ex_i32(int64_t batch, int32_t n_neg, int64_t n_users, int64_t n_nodes, const int64_t* users,
+                          const int64_t* pos, const int64_t* neg, int32_t* gmap, int32_t* nodes,
+                          int32_t* count, void* ws, size_t ws_bytes, mi_stream_t stream) {
+    if (n_neg < 1 || n_neg > kMaxNeg) return MI_ERR_UNSUPPORTED;
+    return batch_nodes_run(batch, n_neg, n_users, n_nodes, users, pos, neg, gmap, nodes, count, ws, ws_bytes, stream);
 }
 
 int mi_gather_rows_f32(int64_t n_max, const int32_t* n_dev, const int32_t* begin_dev, int64_t d,
@@ -474,14 +805,14 @@ int mi_scatter_rows_f32(int64_t n_max, const int32_t* n_dev, const int32_t* begi
     return mi_launch_status();
 }
 
-static size_t bpr_sort_tmp_bytes(int64_t batch) { return ((size_t)1 << 20) + mi_align_up((size_t)3 * batch * 2, 256); }
+static size_t bpr_sort_tmp_bytes(int64_t n_ref) { return ((size_t)1 << 20) + mi_align_up((size_t)n_ref * 2, 256); }
 
 size_t mi_bpr_workspace_bytes(int64_t batch) {
     const size_t b = (size_t)(batch > 0 ? batch : 1);
     const size_t chunks = (3 * b + 63) / 64;
     // softplus, reg, coef per sample; (key, reference) double buffers of the 3B row references; rocPRIM scratch;
     // head / tail partial rows per 64-reference chunk (d <= 512)
-    return 3 * mi_align_up(b * sizeof(float), 256) + 4 * mi_align_up(3 * b * sizeof(uint32_t), 256) + bpr_sort_tmp_bytes((int64_t)b) +
+    return 3 * mi_align_up(b * sizeof(float), 256) + 4 * mi_align_up(3 * b * sizeof(uint32_t), 256) + bpr_sort_tmp_bytes(3 * (int64_t)b) +
            2 * mi_align_up(chunks * 512 * sizeof(float), 256);
 }
 
@@ -505,7 +836,7 @@ int mi_bpr_fwd_bwd_f32(int64_t batch, int64_t d, int64_t n_users, const int64_t*
     uint32_t* k1 = arena.take<uint32_t>(n_ref);
     uint32_t* r0 = arena.take<uint32_t>(n_ref);
     uint32_t* r1 = arena.take<uint32_t>(n_ref);
-    const size_t tmp_cap = bpr_sort_tmp_bytes(batch);
+    const size_t tmp_cap = bpr_sort_tmp_bytes(n_ref);
     char* tmp = arena.take<char>(tmp_cap);
     float* part_head = arena.take<float>((size_t)n_chunks * 512);
     float* part_tail = arena.take<float>((size_t)n_chunks * 512);
@@ -536,7 +867,7 @@ int mi_bpr_fwd_bwd_f32(int64_t batch, int64_t d, int64_t n_users, const int64_t*
         hipLaunchKernelGGL(bpr_chunk_kernel<V>, gc, dim3(kBlock), 0, s, batch, (int)d, n_users, users, pos, neg, final_emb, \
                            ldf, coef, keys.current(), refs.current(), node_map, g_final, ldg, part_head, part_tail,        \
                            reg_w, 2.0f * (reg_scale * lambda));                                                             \
-        hipLaunchKernelGGL(bpr_combine_kernel<V>, gc, dim3(kBlock), 0, s, batch, (int)d, keys.current(), part_head,         \
+        hipLaunchKernelGGL(bpr_combine_kernel<V>, gc, dim3(kBlock), 0, s, n_ref, (int)d, keys.current(), part_head,         \
                            part_tail, g_final, ldg);                                                                        \
     } while (0)
         if (d <= 64) MI_BPR_GO(1);
@@ -546,6 +877,91 @@ int mi_bpr_fwd_bwd_f32(int64_t batch, int64_t d, int64_t n_users, const int64_t*
 #undef MI_BPR_GO
     }
     hipLaunchKernelGGL(bpr_finish_kernel, dim3(1), dim3(1024), 0, s, batch, spv, rgv, inv_b, lambda, loss_out);
+    return mi_launch_status();
+}
+
+size_t mi_rank_loss_workspace_bytes(int64_t batch, int32_t n_neg) {
+    const size_t b = (size_t)(batch > 0 ? batch : 1);
+    const size_t m = (size_t)(n_neg >= 1 && n_neg <= kMaxNeg ? n_neg : 1);
+    const size_t n_ref = (2 + m) * b, chunks = (n_ref + 63) / 64;
+    // loss term, reg per slot; 1 + M coefficients per slot; (key, reference) double buffers; rocPRIM scratch; head / tail
+    // partial rows per 64-reference chunk (d <= 512)
+    return 2 * mi_align_up(b * sizeof(float), 256) + mi_align_up((1 + m) * b * sizeof(float), 256) +
+           4 * mi_align_up(n_ref * sizeof(uint32_t), 256) + bpr_sort_tmp_bytes((int64_t)n_ref) +
+           2 * mi_align_up(chunks * 512 * sizeof(float), 256);
+}
+
+int mi_rank_loss_fwd_bwd_f32(int64_t batch, int32_t n_neg, int32_t objective, int64_t d, int64_t n_users,
+                             const int64_t* users, const int64_t* pos, const int64_t* neg, const float* final_emb,
+                             int64_t ldf, const float* e0, int64_t lde, float lambda, float g_scale, float reg_scale,
+                             float* loss_out, float* g_final, int64_t ldg, float* reg_w, const int32_t* node_map,
+                             void* ws, size_t ws_bytes, mi_stream_t stream) {
+    if (n_neg < 1 || n_neg > kMaxNeg) return MI_ERR_UNSUPPORTED;
+    if (objective != kRankReference && objective != kRankBpr && objective != kRankSoftmax) return MI_ERR_UNSUPPORTED;
+    MI_CHECK_ARG(batch > 0 && d > 0 && n_users >= 0);
+    MI_CHECK_ARG(users && pos && neg && final_emb && e0 && loss_out && ws);
+    MI_CHECK_ARG(ldf >= d && lde >= d && (!g_final || ldg >= d));
+    if ((2 + (int64_t)n_neg) * batch >= INT32_MAX) return MI_ERR_TOO_LARGE;
+    if (d > MI_WAVE * kMaxDPerLane) return MI_ERR_UNSUPPORTED;
+    if (ws_bytes < mi_rank_loss_workspace_bytes(batch, n_neg)) return MI_ERR_WORKSPACE;
+    const int64_t n_ref = (2 + (int64_t)n_neg) * batch, n_chunks = mi_ceil_div(n_ref, kRefChunk);
+    MiArena arena(ws, ws_bytes);
+    float* termv = arena.take<float>(batch);
+    float* rgv = arena.take<float>(batch);
+    float* coef = arena.take<float>((size_t)(1 + n_neg) * batch);
+    uint32_t* k0 = arena.take<uint32_t>(n_ref);
+    uint32_t* k1 = arena.take<uint32_t>(n_ref);
+    uint32_t* r0 = arena.take<uint32_t>(n_ref);
+    uint32_t* r1 = arena.take<uint32_t>(n_ref);
+    const size_t tmp_cap = bpr_sort_tmp_bytes(n_ref);
+    char* tmp = arena.take<char>(tmp_cap);
+    float* part_head = arena.take<float>((size_t)n_chunks * 512);
+    float* part_tail = arena.take<float>((size_t)n_chunks * 512);
+    if (!termv || !rgv || !coef || !k0 || !k1 || !r0 || !r1 || !tmp || !part_head || !part_tail) return MI_ERR_WORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    // the mean runs over the B*M pairs, or over the B slots for the softmax
+    const float inv_count = 1.0f / (float)(objective == kRankSoftmax ? batch : batch * n_neg);
+    const int vpt = d <= 64 ? 1 : (d <= 128 ? 2 : (d <= 256 ? 4 : 8));
+    dim3 g((unsigned)mi_ceil_div(batch * MI_WAVE, kBlock));
+#define MI_RANK_SLOT(V)                                                                                                    \
+    hipLaunchKernelGGL(rank_slot_kernel<V>, g, dim3(kBlock), 0, s, batch, (int)n_neg, (int)objective, (int)d, n_users,      \
+                       users, pos, neg, final_emb, ldf, e0, lde, inv_count, g_scale, reg_scale * lambda, termv, rgv,        \
+                       g_final ? coef : nullptr, g_final ? nullptr : reg_w, node_map)
+    if (vpt == 1) MI_RANK_SLOT(1);
+    else if (vpt == 2) MI_RANK_SLOT(2);
+    else if (vpt == 4) MI_RANK_SLOT(4);
+    else MI_RANK_SLOT(8);
+#undef MI_RANK_SLOT
+    if (g_final) {
+        hipLaunchKernelGGL(rank_refs_kernel, dim3((unsigned)mi_ceil_div(n_ref, 256)), dim3(256), 0, s, batch, (int)n_neg,
+                           n_users, users, pos, neg, node_map, k0, r0);
+        unsigned bits = 32;   // compact slots are < (2 + M) B; node ids need all 32 bits
+        if (node_map) {
+            bits = 1;
+            while (((int64_t)1 << bits) < n_ref) ++bits;
+        }
+        rocprim::double_buffer<uint32_t> keys(k0, k1), refs(r0, r1);
+        size_t need = 0;
+        MI_HIP(rocprim::radix_sort_pairs(nullptr, need, keys, refs, (size_t)n_ref, 0, bits, s));
+        if (need > tmp_cap) return MI_ERR_WORKSPACE;
+        MI_HIP(rocprim::radix_sort_pairs(tmp, need, keys, refs, (size_t)n_ref, 0, bits, s));
+        dim3 gc((unsigned)mi_ceil_div(n_chunks * MI_WAVE, kBlock));
+#define MI_RANK_GO(V)                                                                                                      \
+    do {                                                                                                                    \
+        hipLaunchKernelGGL(rank_chunk_kernel<V>, gc, dim3(kBlock), 0, s, batch, (int)n_neg, (int)d, n_users, users, pos,    \
+                           neg, final_emb, ldf, coef, keys.current(), refs.current(), node_map, g_final, ldg, part_head,    \
+                           part_tail, reg_w, 2.0f * (reg_scale * lambda));                                                  \
+        hipLaunchKernelGGL(bpr_combine_kernel<V>, gc, dim3(kBlock), 0, s, n_ref, (int)d, keys.current(), part_head,         \
+                           part_tail, g_final, ldg);                                                                        \
+    } while (0)
+        if (vpt == 1) MI_RANK_GO(1);
+        else if (vpt == 2) MI_RANK_GO(2);
+        else if (vpt == 4) MI_RANK_GO(4);
+        else MI_RANK_GO(8);
+#undef MI_RANK_GO
+    }
+    // the slot terms are stored negated, so every objective closes with loss = -sum(term) / count + lambda * sum(reg)
+    hipLaunchKernelGGL(bpr_finish_kernel, dim3(1), dim3(1024), 0, s, batch, termv, rgv, inv_count, lambda, loss_out);
     return mi_launch_status();
 }
 

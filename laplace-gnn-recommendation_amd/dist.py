@@ -43,12 +43,17 @@ class ShardedLightGCNTrainer:
     def __init__(self, model: LightGCN, train: Interactions, *, lr: float, Lambda: float, batch_size: int,
                  betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8, seed: int = 0,
                  neg_range: Optional[int] = None, group=None, ops_impl=None, sparse_batch: bool = True,
-                 reorder: Optional[bool] = None):
+                 reorder: Optional[bool] = None, objective: str = "reference", n_neg: int = 1):
         """model: LightGCN(num_users = this rank's users, num_items = all items).  `train` holds this
         rank's edges with LOCAL user ids.  ops_impl: the kernel provider (default: the HIP ops;
         the CPU gloo tests inject an oracle-backed one — the product never does).
         reorder (default: on from 1M edges per rank, decided on the all-reduced total): train under the locality order of trainer.LightGCNTrainer — the
-        replicated items are ranked by their GLOBAL degree, so every rank numbers them alike; users are local anyway."""
+        replicated items are ranked by their GLOBAL degree, so every rank numbers them alike; users are local anyway.
+        objective / n_neg: as trainer.LightGCNTrainer (the same on every rank); anything but the default needs a provider
+        with rank_loss_fwd_bwd, sample_bpr_batch(n_neg=) and batch_nodes over neg [B, M]."""
+        hip_ops.rank_objective_code(objective)   # ValueError for an unknown name
+        hip_ops.check_n_neg(n_neg)
+        self.objective, self.n_neg = objective, n_neg
         self.ops = ops_impl if ops_impl is not None else hip_ops
         self.group = group
         self.world = dist.get_world_size(group) if dist.is_initialized() else 1
@@ -118,7 +123,7 @@ class ShardedLightGCNTrainer:
         self.final = t.empty(n, d, device=dev)
         self.bufs = (t.empty(n, d, device=dev), t.empty(n, d, device=dev))
         if self.sparse_batch:  # compact per-batch tables (see trainer.py) + dense item-side exchange buffers
-            nb = 3 * self.batch_size
+            nb = (2 + self.n_neg) * self.batch_size
             self.gc = None
             self.gmap = t.empty(n, dtype=t.int32, device=dev)
             self.nodes = t.zeros(nb, dtype=t.int32, device=dev)
@@ -135,7 +140,9 @@ class ShardedLightGCNTrainer:
         self.m = t.zeros(n, d, device=dev)
         self.v = t.zeros(n, d, device=dev)
         self.loss = t.zeros(1, device=dev)
-        self.batch_idx = tuple(t.empty(self.batch_size, dtype=t.int64, device=dev) for _ in range(3))
+        self.batch_idx = (t.empty(self.batch_size, dtype=t.int64, device=dev),
+                          t.empty(self.batch_size, dtype=t.int64, device=dev),
+                          t.empty(self.batch_size if n_neg == 1 else (self.batch_size, n_neg), dtype=t.int64, device=dev))
         self.step_count = 0
         self._r = train.csr() if ops_impl is None else self.ops.coo_to_csr(u.contiguous(), i.contiguous(), U, I,
                                                                              want_perm=False)
@@ -155,9 +162,13 @@ class ShardedLightGCNTrainer:
     finish = to_original_order
 
     def _ids_to_training(self, batch):
-        if self.order is None or batch is None:
+        if batch is None:
             return batch
         users, pos, neg = batch
+        if self.n_neg > 1 and (neg.dim() != 2 or neg.shape[1] != self.n_neg):
+            raise ValueError(f"batch: neg [B, {self.n_neg}] expected, got {list(neg.shape)}")
+        if self.order is None:
+            return batch
         return self.order.user_new_of_old[users], self.order.item_new_of_old[pos], self.order.item_new_of_old[neg]
 
     # -- collectives ---------------------------------------------------------------------------
@@ -209,8 +220,18 @@ class ShardedLightGCNTrainer:
         return S
 
     def _sample(self):
+        more = {} if self.n_neg == 1 else {"n_neg": self.n_neg}
         return self.ops.sample_bpr_batch(self._r, self._row_of_edge, self.batch_size, self.neg_range, self.seed,
-                                         self.step_count, out=self.batch_idx)
+                                         self.step_count, out=self.batch_idx, **more)
+
+    def _loss(self, users, pos, neg, final, **kw) -> None:
+        """This rank's loss term and gradient; the default objective keeps the one-negative call of the provider."""
+        if self.objective == "reference" and self.n_neg == 1:
+            self.ops.bpr_fwd_bwd(users, pos, neg, final, self.table, self.U, self.Lambda, reg_w=self.reg_w,
+                                 loss_out=self.loss, **kw)
+        else:
+            self.ops.rank_loss_fwd_bwd(users, pos, neg, final, self.table, self.U, self.Lambda,
+                                       objective=self.objective, reg_w=self.reg_w, loss_out=self.loss, **kw)
 
     def sample(self):
         """(users, pos, neg) of the next step's batch, ORIGINAL (local) ids."""
@@ -234,8 +255,7 @@ class ShardedLightGCNTrainer:
         self.gc.zero_()
         self.reg_w.zero_()
         # global loss = mean over P*B slots => each rank's share of the softplus term carries 1/P
-        self.ops.bpr_fwd_bwd(users, pos, neg, self.final, self.table, U, self.Lambda, g_final=self.gc,
-                             reg_w=self.reg_w, g_scale=1.0 / ((K + 1) * P), loss_out=self.loss)
+        self._loss(users, pos, neg, self.final, g_final=self.gc, g_scale=1.0 / ((K + 1) * P))
         self._allreduce(self.gc[U:])
         self._allreduce(self.reg_w[U:])
         g = self.gc
@@ -289,8 +309,7 @@ class ShardedLightGCNTrainer:
         # ---- loss on the compact tables; softplus share of the global mean carries 1/P
         self.gc_c.zero_()
         self.reg_w.zero_()
-        ops.bpr_fwd_bwd(users, pos, neg, self.sum_c, tab, U, self.Lambda, g_final=self.gc_c, reg_w=self.reg_w,
-                        g_scale=c / P, loss_out=self.loss, node_map=gmap)
+        self._loss(users, pos, neg, self.sum_c, g_final=self.gc_c, g_scale=c / P, node_map=gmap)
         # ---- global item gradient: dense [I, D], summed over ranks; which item rows are non-zero anywhere
         self.items_g.zero_()
         ops.scatter_rows(self.items_g, self.gc_c, nodes, cnt, begin_dev=cnt_u, row_offset=U)

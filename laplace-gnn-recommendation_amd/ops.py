@@ -753,25 +753,51 @@ def expand_rows(a: DeviceCSR) -> Tensor:
     return out
 
 
+def check_n_neg(n_neg: int) -> int:
+    if not isinstance(n_neg, int) or isinstance(n_neg, bool) or not 1 <= n_neg <= _lib.MI_RANK_MAX_NEG:
+        raise ValueError(f"n_neg must be an integer in 1..{_lib.MI_RANK_MAX_NEG}, got {n_neg!r}")
+    return n_neg
+
+
+def rank_objective_code(objective: str) -> int:
+    """The C constant of a ranking objective name (ValueError for anything else)."""
+    if objective not in _lib.MI_RANK_OBJECTIVES:
+        raise ValueError(f"objective must be one of {sorted(_lib.MI_RANK_OBJECTIVES)}, got {objective!r}")
+    return _lib.MI_RANK_OBJECTIVES[objective]
+
+
 def sample_bpr_batch(r: DeviceCSR, row_of_edge: Tensor, batch: int, neg_range: int, seed: int, step: int,
                      quirk: bool = False, out: Optional[Tuple[Tensor, Tensor, Tensor]] = None,
-                     edges_in_order: bool = False, no_self_loops: bool = False) -> Tuple[Tensor, Tensor, Tensor]:
+                     edges_in_order: bool = False, no_self_loops: bool = False, n_neg: int = 1
+                     ) -> Tuple[Tensor, Tensor, Tensor]:
     """K9 — replaces sample_mini_batch (data/lightgcn_loader.py:95-112) on device.  quirk: the reference's key
-    collision; no_self_loops: structured_negative_sampling(contains_neg_self_loops=False) — never negative id == user id."""
+    collision; no_self_loops: structured_negative_sampling(contains_neg_self_loops=False) — never negative id == user id.
+    n_neg > 1: neg is [batch, n_neg], independent draws per slot whose column 0 is the n_neg = 1 result."""
+    check_n_neg(n_neg)
     if r.nnz == 0:
         raise ValueError("cannot sample from an empty edge set")
     if neg_range <= 0:
         raise ValueError("neg_range must be positive")
     dev = r.device
     if out is None:
-        out = tuple(t.empty(batch, dtype=t.int64, device=dev) for _ in range(3))
+        out = (t.empty(batch, dtype=t.int64, device=dev), t.empty(batch, dtype=t.int64, device=dev),
+               t.empty(batch if n_neg == 1 else (batch, n_neg), dtype=t.int64, device=dev))
     users, pos, neg = out
-    check(_lib.lib().mi_sample_bpr_batch(batch, r.nnz, _ptr(r.rowptr), _ptr(r.col), _ptr(row_of_edge),
-                                         int(neg_range), (1 if quirk else 0) | (2 if no_self_loops else 0),
-                                         1 if edges_in_order else 0,
-                                         int(seed) & (2**64 - 1),
-                                         int(step) & (2**64 - 1), _ptr(users), _ptr(pos), _ptr(neg),
-                                         _stream()), "mi_sample_bpr_batch")
+    quirks = (1 if quirk else 0) | (2 if no_self_loops else 0)
+    if n_neg == 1:
+        check(_lib.lib().mi_sample_bpr_batch(batch, r.nnz, _ptr(r.rowptr), _ptr(r.col), _ptr(row_of_edge),
+                                             int(neg_range), quirks,
+                                             1 if edges_in_order else 0,
+                                             int(seed) & (2**64 - 1),
+                                             int(step) & (2**64 - 1), _ptr(users), _ptr(pos), _ptr(neg),
+                                             _stream()), "mi_sample_bpr_batch")
+    else:
+        if neg.numel() != batch * n_neg:
+            raise ValueError("out: neg must hold batch * n_neg ids")
+        check(_lib.lib().mi_sample_bpr_batch_ex(batch, n_neg, r.nnz, _ptr(r.rowptr), _ptr(r.col), _ptr(row_of_edge),
+                                                int(neg_range), quirks, 1 if edges_in_order else 0,
+                                                int(seed) & (2**64 - 1), int(step) & (2**64 - 1), _ptr(users),
+                                                _ptr(pos), _ptr(neg), _stream()), "mi_sample_bpr_batch_ex")
     return users, pos, neg
 
 
@@ -798,6 +824,36 @@ def bpr_fwd_bwd(users: Tensor, pos: Tensor, neg: Tensor, final_emb: Tensor, e0: 
                                e0.data_ptr(), lde, float(lambda_val), float(g_scale), float(reg_scale),
                                loss_out.data_ptr(), _ptr(g_final), ldg, _ptr(reg_w), _ptr(node_map), ws.data_ptr(),
                                ws.numel(), _stream()), "mi_bpr_fwd_bwd_f32")
+    return loss_out
+
+
+def rank_loss_fwd_bwd(users: Tensor, pos: Tensor, neg: Tensor, final_emb: Tensor, e0: Tensor, n_users: int,
+                      lambda_val: float, *, objective: str = "reference", g_final: Optional[Tensor] = None,
+                      reg_w: Optional[Tensor] = None, g_scale: float = 1.0, reg_scale: float = 1.0,
+                      loss_out: Optional[Tensor] = None, node_map: Optional[Tensor] = None) -> Tensor:
+    """bpr_fwd_bwd with a choice of objective ("reference", "bpr", "softmax") and neg [B] or [B, M], M <= 16."""
+    code = rank_objective_code(objective)
+    batch = users.numel()
+    if pos.numel() != batch or neg.dim() not in (1, 2) or neg.shape[0] != batch:
+        raise ValueError("users [B], pos [B], neg [B] or [B, M] expected")
+    n_neg = check_n_neg(1 if neg.dim() == 1 else int(neg.shape[1]))
+    for n, x in (("users", users), ("pos", pos), ("neg", neg)):
+        _need(x, t.int64, n)
+    d = final_emb.shape[1]
+    ldf = _rows_ok(final_emb, "final_emb")
+    lde = _rows_ok(e0, "e0")
+    ldg = _rows_ok(g_final, "g_final") if g_final is not None else 0
+    if reg_w is not None:
+        _need(reg_w, t.float32, "reg_w")
+    dev = final_emb.device
+    if loss_out is None:
+        loss_out = t.empty(1, dtype=t.float32, device=dev)
+    L = _lib.lib()
+    ws = _ws(L.mi_rank_loss_workspace_bytes(batch, n_neg), dev)
+    check(L.mi_rank_loss_fwd_bwd_f32(batch, n_neg, code, d, n_users, _ptr(users), _ptr(pos), _ptr(neg),
+                                     final_emb.data_ptr(), ldf, e0.data_ptr(), lde, float(lambda_val), float(g_scale),
+                                     float(reg_scale), loss_out.data_ptr(), _ptr(g_final), ldg, _ptr(reg_w),
+                                     _ptr(node_map), ws.data_ptr(), ws.numel(), _stream()), "mi_rank_loss_fwd_bwd_f32")
     return loss_out
 
 
@@ -1238,18 +1294,28 @@ def linear1_bwd(dy: Tensor, weight: Tensor, x: Tensor, need_dx: bool = True):
 
 def batch_nodes(users: Tensor, pos: Tensor, neg: Tensor, n_users: int, n_nodes: int, *, gmap: Optional[Tensor] = None,
                 nodes: Optional[Tensor] = None, count: Optional[Tensor] = None, ws: Optional[Tensor] = None):
-    """Unique node set of a BPR batch: (gmap int32[n_nodes], nodes int32[3B], count int32[2] on device:
-    count[0] = unique nodes, count[1] = unique user nodes, whose slots come first)."""
+    """Unique node set of a BPR batch (neg [B] or [B, M]): (gmap int32[n_nodes], nodes int32[(2+M)B], count int32[2] on
+    device: count[0] = unique nodes, count[1] = unique user nodes, whose slots come first)."""
+    B, dev = users.numel(), users.device
+    n_neg = 1 if neg.dim() == 1 else check_n_neg(int(neg.shape[1]))
+    if neg.numel() != B * n_neg:
+        raise ValueError("neg must be [B] or [B, M]")
     for n, x in (("users", users), ("pos", pos), ("neg", neg)):
         _need(x, t.int64, n)
-    B, dev = users.numel(), users.device
     gmap = gmap if gmap is not None else t.empty(n_nodes, dtype=t.int32, device=dev)
-    nodes = nodes if nodes is not None else t.empty(3 * B, dtype=t.int32, device=dev)
+    nodes = nodes if nodes is not None else t.empty((2 + n_neg) * B, dtype=t.int32, device=dev)
+    if nodes.numel() < (2 + n_neg) * B:
+        raise ValueError("nodes must hold (2 + M) * B slots")
     count = count if count is not None else t.empty(2, dtype=t.int32, device=dev)
     L = _lib.lib()
     ws = ws if ws is not None else _ws(L.mi_batch_nodes_workspace_bytes(n_nodes), dev)
-    check(L.mi_batch_nodes_i32(B, n_users, n_nodes, _ptr(users), _ptr(pos), _ptr(neg), _ptr(gmap), _ptr(nodes),
-                               _ptr(count), ws.data_ptr(), ws.numel(), _stream()), "mi_batch_nodes_i32")
+    if neg.dim() == 1:
+        check(L.mi_batch_nodes_i32(B, n_users, n_nodes, _ptr(users), _ptr(pos), _ptr(neg), _ptr(gmap), _ptr(nodes),
+                                   _ptr(count), ws.data_ptr(), ws.numel(), _stream()), "mi_batch_nodes_i32")
+    else:
+        check(L.mi_batch_nodes_ex_i32(B, n_neg, n_users, n_nodes, _ptr(users), _ptr(pos), _ptr(neg), _ptr(gmap),
+                                      _ptr(nodes), _ptr(count), ws.data_ptr(), ws.numel(), _stream()),
+              "mi_batch_nodes_ex_i32")
     return gmap, nodes, count
 
 

@@ -23,11 +23,23 @@ from .trainer import LightGCNTrainer
 from .utils.metrics_lightgcn import get_metrics_lightgcn, topk_for_users
 
 
+PREDICTORS = ("layer0", "propagated")
+
+
+def propagated_embeddings(model: LightGCN, train_sparse: SparseTensor) -> Tuple[Tensor, Tensor]:
+    """(users, items) rows of mean_k(A^k E0) on the TRAINING adjacency: what the loss trains."""
+    with t.no_grad():
+        users_final, _, items_final, _ = model.forward(train_sparse)
+    return users_final.contiguous(), items_final.contiguous()
+
+
 def evaluation(model: LightGCN, edge_index: Tensor, sparse_edge_index: SparseTensor,
-               exclude_edge_indices: List[Tensor], k: int, lambda_val: float, seed: int = 0
+               exclude_edge_indices: List[Tensor], k: int, lambda_val: float, seed: int = 0, *,
+               objective: str = "reference", embeddings: Optional[Tuple[Tensor, Tensor]] = None
                ) -> Tuple[float, float, float, float]:
-    """bpr loss over every edge of the split (one structured negative each) on the split's own
-    adjacency, plus recall / precision / ndcg @ k (run_pipeline_lightgcn.py:20-73)."""
+    """loss over every edge of the split (one structured negative each) on the split's own
+    adjacency, plus recall / precision / ndcg @ k (run_pipeline_lightgcn.py:20-73).  objective: the loss's form
+    (default: the reference's); embeddings: the tables the ranking metrics score with (default: layer 0)."""
     with t.no_grad():
         users_final, users_0, items_final, items_0 = model.forward(sparse_edge_index)
         n_users, n_items = model.num_users, model.num_items
@@ -36,14 +48,22 @@ def evaluation(model: LightGCN, edge_index: Tensor, sparse_edge_index: SparseTen
         u, p, n = ops.sample_bpr_batch(inter.csr(), inter.row_of_edge(), inter.num_edges, neg_range, seed, 0,
                                        quirk=True, edges_in_order=True, no_self_loops=True)  # :40-44 contains_neg_self_loops=False
         final = t.cat([users_final, items_final])
-        loss = ops.bpr_fwd_bwd(u, p, n, final, model.table(), n_users, lambda_val)
-    recall, precision, ndcg = get_metrics_lightgcn(model, edge_index, exclude_edge_indices, k)
+        if objective == "reference":
+            loss = ops.bpr_fwd_bwd(u, p, n, final, model.table(), n_users, lambda_val)
+        else:
+            loss = ops.rank_loss_fwd_bwd(u, p, n, final, model.table(), n_users, lambda_val, objective=objective)
+    recall, precision, ndcg = get_metrics_lightgcn(model, edge_index, exclude_edge_indices, k, embeddings=embeddings)
     return float(loss), recall, precision, ndcg
 
 
 def train(config: LightGCNConfig = lightgcn_config, *, edge_index: Tensor, num_users: int, num_articles: int,
           compat: str = "reference", device: str = "cuda", seed: int = 0, save_dir: Optional[str] = None,
-          verbose: bool = True) -> Stats:
+          verbose: bool = True, objective: str = "reference", n_neg: int = 1, predictor: str = "layer0") -> Stats:
+    """objective / n_neg: the training loss (trainer.LightGCNTrainer).  predictor="propagated": evaluation,
+    the ranking metrics and the saved predictions score with mean_k(A^k E0) of the training adjacency — the scores the
+    loss trains — instead of the layer-0 tables."""
+    if predictor not in PREDICTORS:
+        raise ValueError(f"predictor must be one of {PREDICTORS}, got {predictor!r}")
     if verbose:
         config.print()
     (train_sparse, val_sparse, test_sparse, train_edges, val_edges, test_edges, all_edges, num_users,
@@ -57,7 +77,10 @@ def train(config: LightGCNConfig = lightgcn_config, *, edge_index: Tensor, num_u
     # reference sampler: negatives from [0, max train item id) with its key-collision quirk
     trainer = LightGCNTrainer(model, train_sparse, train_inter, lr=config.learning_rate, Lambda=config.Lambda,
                               batch_size=config.batch_size, seed=seed, neg_range=int(train_edges[1].max()),
-                              reference_sampler_quirks=(compat == "reference"))
+                              reference_sampler_quirks=(compat == "reference"), objective=objective, n_neg=n_neg)
+
+    def scoring_tables():
+        return propagated_embeddings(model, train_sparse) if predictor == "propagated" else None
     train_loss = t.zeros(1, device=device)
     recall = precision = 0.0
     try:   # the trainer permutes the model's rows in place: whatever happens, hand them back under their original ids
@@ -67,7 +90,8 @@ def train(config: LightGCNConfig = lightgcn_config, *, edge_index: Tensor, num_u
                 model.eval()
                 trainer.to_original_order()  # evaluation reads the model's tables by original id; step() re-enters the training order
                 val_loss, recall, precision, ndcg = evaluation(model, val_edges, val_sparse, [train_edges], config.k,
-                                                               config.Lambda, seed)
+                                                               config.Lambda, seed, objective=objective,
+                                                               embeddings=scoring_tables())
                 if verbose:
                     print(f"[Iter {it}/{config.epochs}] train_loss: {round(float(train_loss), 5)}, val_loss: "
                           f"{round(val_loss, 5)}, val_recall@{config.k}: {round(recall, 6)}, val_precision@{config.k}: "
@@ -80,27 +104,30 @@ def train(config: LightGCNConfig = lightgcn_config, *, edge_index: Tensor, num_u
 
     model.eval()
     test_loss, test_recall, test_precision, test_ndcg = evaluation(
-        model, test_edges, test_sparse, [train_edges, val_edges], config.k, config.Lambda, seed)
+        model, test_edges, test_sparse, [train_edges, val_edges], config.k, config.Lambda, seed, objective=objective,
+        embeddings=scoring_tables())
     if verbose:
         print(f"[test_loss: {round(test_loss, 5)}, test_recall@{config.k}: {round(test_recall, 5)}, "
               f"test_precision@{config.k}: {round(test_precision, 5)}, test_ndcg@{config.k}: {round(test_ndcg, 5)}")
 
-    # predictions for the matcher: top `num_recommendations` unseen items per user, layer-0 scores (F8)
-    top_items = save_predictions(model, all_edges, config.num_recommendations, save_dir)
+    # predictions for the matcher: top `num_recommendations` unseen items per user, layer-0 scores (F8) by default
+    top_items = save_predictions(model, all_edges, config.num_recommendations, save_dir, embeddings=scoring_tables())
     return Stats(loss=float(train_loss), recall_val=recall, recall_test=test_recall, precision_val=precision,
                  precision_test=test_precision)
 
 
 def save_predictions(model: LightGCN, all_edges: Tensor, num_recommendations: int,
-                     save_dir: Optional[str] = None) -> Tensor:
-    """[U, num_recommendations] item ids (run_pipeline_lightgcn.py:210-238)."""
+                     save_dir: Optional[str] = None, embeddings: Optional[Tuple[Tensor, Tensor]] = None) -> Tensor:
+    """[U, num_recommendations] item ids (run_pipeline_lightgcn.py:210-238); embeddings = (users, items) tables to
+    score and dump instead of the layer-0 ones."""
     k = min(num_recommendations, model.num_items)
     users = t.arange(model.num_users, dtype=t.int64, device=all_edges.device)
-    top = topk_for_users(model.users_emb.weight.detach(), model.items_emb.weight.detach(), users, all_edges, k)
+    ue, ie = embeddings if embeddings is not None else (model.users_emb.weight.detach(), model.items_emb.weight.detach())
+    top = topk_for_users(ue, ie, users, all_edges, k)
     if save_dir is not None:
         import os
         os.makedirs(save_dir, exist_ok=True)
         t.save(top.cpu(), os.path.join(save_dir, "lightgcn_output.pt"))
-        t.save(model.users_emb.weight.detach().cpu(), os.path.join(save_dir, "users_emb_final_lightgcn.pt"))
-        t.save(model.items_emb.weight.detach().cpu(), os.path.join(save_dir, "items_emb_final_lightgcn.pt"))
+        t.save(ue.cpu(), os.path.join(save_dir, "users_emb_final_lightgcn.pt"))
+        t.save(ie.cpu(), os.path.join(save_dir, "items_emb_final_lightgcn.pt"))
     return top

@@ -4,6 +4,7 @@ the GPU and no host round trip.
     forward   K fused SpMM launches (layer sum in the epilogue)      model/lightgcn.py:46-80
     sample    B edges + structured negatives on device               data/lightgcn_loader.py:95-112
     loss      gathers + BPR forward/backward in one kernel           run_pipeline_lightgcn.py:133-155
+              (objective="bpr" / "softmax" and n_neg = M <= 16 negatives per positive: opt-in)
     backward  K SpMM launches on A^T, G/(K+1) folded in as addend    (autograd of the forward)
     update    dense Adam over the whole table, L2 term folded in     run_pipeline_lightgcn.py:157-159
 
@@ -61,7 +62,11 @@ class LightGCNTrainer:
     def __init__(self, model: LightGCN, adj: SparseTensor, train: Interactions, *, lr: float, Lambda: float,
                  batch_size: int, betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8, seed: int = 0,
                  neg_range: Optional[int] = None, reference_sampler_quirks: bool = False,
-                 sparse_batch: bool = True, fuse_adam: bool = True, reorder: Optional[bool] = None):
+                 sparse_batch: bool = True, fuse_adam: bool = True, reorder: Optional[bool] = None,
+                 objective: str = "reference", n_neg: int = 1):
+        ops.rank_objective_code(objective)   # ValueError for an unknown name
+        ops.check_n_neg(n_neg)
+        self.objective, self.n_neg = objective, n_neg
         self.model = model
         self.table = model.table()
         if not self.table.is_cuda:
@@ -101,7 +106,7 @@ class LightGCNTrainer:
         self.final = t.empty(n, d, device=dev)
         self.buf_a = t.empty(n, d, device=dev)
         self.buf_b = t.empty(n, d, device=dev)
-        nb = 3 * self.batch_size
+        nb = (2 + self.n_neg) * self.batch_size
         if self.sparse_batch:  # compact per-batch tables instead of the dense gradient buffer
             self.gc = None
             self.gmap = t.empty(n, dtype=t.int32, device=dev)
@@ -117,7 +122,9 @@ class LightGCNTrainer:
         self.m = t.zeros(n, d, device=dev)
         self.v = t.zeros(n, d, device=dev)
         self.loss = t.zeros(1, device=dev)
-        self.batch_idx = tuple(t.empty(self.batch_size, dtype=t.int64, device=dev) for _ in range(3))
+        self.batch_idx = (t.empty(self.batch_size, dtype=t.int64, device=dev),
+                          t.empty(self.batch_size, dtype=t.int64, device=dev),
+                          t.empty(self.batch_size if n_neg == 1 else (self.batch_size, n_neg), dtype=t.int64, device=dev))
         self.step_count = 0
         self._r = train.csr()
         self._row_of_edge = train.row_of_edge()
@@ -138,9 +145,11 @@ class LightGCNTrainer:
     finish = to_original_order
 
     def _ids_to_training(self, batch):
+        users, pos, neg = batch
+        if self.n_neg > 1 and (neg.dim() != 2 or neg.shape[1] != self.n_neg):
+            raise ValueError(f"batch: neg [B, {self.n_neg}] expected, got {list(neg.shape)}")
         if self.order is None:
             return batch
-        users, pos, neg = batch
         return self.order.user_new_of_old[users], self.order.item_new_of_old[pos], self.order.item_new_of_old[neg]
 
     # -- pieces (also used one by one in tests) ------------------------------------------------
@@ -151,7 +160,16 @@ class LightGCNTrainer:
 
     def _sample(self) -> Tuple[Tensor, Tensor, Tensor]:
         return ops.sample_bpr_batch(self._r, self._row_of_edge, self.batch_size, self.neg_range, self.seed,
-                                    self.step_count, quirk=self.quirk, out=self.batch_idx)
+                                    self.step_count, quirk=self.quirk, out=self.batch_idx, n_neg=self.n_neg)
+
+    def _loss(self, users, pos, neg, final, **kw) -> None:
+        """Loss and its gradient on `final`; the default objective keeps the one-negative entry (same launches, same bits)."""
+        if self.objective == "reference" and self.n_neg == 1:
+            ops.bpr_fwd_bwd(users, pos, neg, final, self.table, self.model.num_users, self.Lambda, reg_w=self.reg_w,
+                            loss_out=self.loss, **kw)
+        else:
+            ops.rank_loss_fwd_bwd(users, pos, neg, final, self.table, self.model.num_users, self.Lambda,
+                                  objective=self.objective, reg_w=self.reg_w, loss_out=self.loss, **kw)
 
     def sample(self) -> Tuple[Tensor, Tensor, Tensor]:
         """(users, pos, neg) of the next step's batch, ORIGINAL ids."""
@@ -171,8 +189,7 @@ class LightGCNTrainer:
         users, pos, neg = batch if batch is not None else self._sample()
         self.gc.zero_()
         self.reg_w.zero_()
-        ops.bpr_fwd_bwd(users, pos, neg, self.final, self.table, self.model.num_users, self.Lambda,
-                        g_final=self.gc, reg_w=self.reg_w, g_scale=1.0 / (K + 1), loss_out=self.loss)
+        self._loss(users, pos, neg, self.final, g_final=self.gc, g_scale=1.0 / (K + 1))
         g0 = propagate_mean_backward(self.adj_bwd, self.gc, K, scratch=(self.buf_a, self.buf_b), pre_scaled=True)
         self.step_count += 1
         ops.adam_step(self.table, g0, self.m, self.v, step=self.step_count, lr=self.lr, beta1=self.betas[0],
@@ -205,8 +222,7 @@ class LightGCNTrainer:
         # ---- loss + its gradient on the compact tables
         self.gc_c.zero_()
         self.reg_w.zero_()
-        ops.bpr_fwd_bwd(users, pos, neg, final_c, tab, self.model.num_users, self.Lambda, g_final=self.gc_c,
-                        reg_w=self.reg_w, g_scale=c, loss_out=self.loss, node_map=gmap)
+        self._loss(users, pos, neg, final_c, g_final=self.gc_c, g_scale=c, node_map=gmap)
         # ---- backward: g_K = Gc (compact); g_k = Gc + A^T g_{k+1}
         if K == 0:
             g0 = self.buf_a

@@ -50,6 +50,54 @@ def bpr_loss(users_emb_final: Tensor, users_emb_0: Tensor, pos_items_emb_final: 
                             neg_items_emb_final, neg_items_emb_0, float(lambda_val))
 
 
+class _RankingLossFn(t.autograd.Function):
+    """ranking_loss over gathered blocks through mi_rank_loss_fwd_bwd_f32: the blocks become two (2 + M) B-row tables
+    (users | positives | negatives, slot-major) addressed by arange, as in _BprLossFn."""
+
+    @staticmethod
+    def forward(ctx, uf, u0, pf, p0, nf, n0, lambda_val: float, objective: str):
+        B, D = uf.shape
+        M = nf.shape[1]
+        final = t.cat([uf, pf, nf.reshape(B * M, D)]).contiguous()
+        e0 = t.cat([u0, p0, n0.reshape(B * M, D)]).contiguous()
+        dev = uf.device
+        users = t.arange(B, device=dev)
+        neg = t.arange(B, B + B * M, device=dev).reshape(B, M)   # item ids: the positives are items [0, B)
+        g_final = t.zeros_like(final)
+        reg_w = t.zeros((2 + M) * B, device=dev)
+        loss = ops.rank_loss_fwd_bwd(users, users, neg, final, e0, B, lambda_val, objective=objective, g_final=g_final,
+                                     reg_w=reg_w)
+        ctx.save_for_backward(g_final, reg_w, e0)
+        ctx.dims = (B, M, D)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        g_final, reg_w, e0 = ctx.saved_tensors
+        B, M, D = ctx.dims
+        gf = g_final * grad_out
+        g0 = (reg_w[:, None] * e0) * grad_out
+        return (gf[:B], g0[:B], gf[B:2 * B], g0[B:2 * B], gf[2 * B:].reshape(B, M, D), g0[2 * B:].reshape(B, M, D),
+                None, None)
+
+
+def ranking_loss(users_emb_final: Tensor, users_emb_0: Tensor, pos_items_emb_final: Tensor, pos_items_emb_0: Tensor,
+                 neg_items_emb_final: Tensor, neg_items_emb_0: Tensor, lambda_val: float,
+                 objective: str = "reference") -> Tensor:
+    """bpr_loss with a choice of objective and M negatives per positive (negatives [B, D] or [B, M, D], M <= 16):
+    "reference" -mean softplus(x) as the reference writes it, "bpr" -mean log sigmoid(x), "softmax" the sampled softmax
+    over (positive, negatives); x = <u, p> - <u, n>.  The L2 term is the reference's sum form over all 2 + M rows."""
+    ops.rank_objective_code(objective)
+    if neg_items_emb_final.dim() not in (2, 3) or neg_items_emb_0.shape != neg_items_emb_final.shape:
+        raise ValueError("negatives: [B, D] or [B, M, D], the same shape for both tables")
+    two_d = neg_items_emb_final.dim() == 2
+    nf = neg_items_emb_final[:, None, :] if two_d else neg_items_emb_final
+    n0 = neg_items_emb_0[:, None, :] if two_d else neg_items_emb_0
+    ops.check_n_neg(int(nf.shape[1]))
+    return _RankingLossFn.apply(users_emb_final, users_emb_0, pos_items_emb_final, pos_items_emb_0, nf, n0,
+                                float(lambda_val), objective)
+
+
 # ----------------------------------------------------------------------------------------------
 # evaluation: batched on device (reference: per-user Python loops on the CPU)
 # ----------------------------------------------------------------------------------------------
@@ -120,12 +168,16 @@ def rank_metrics(r: Tensor, gt_len: Tensor, k: int) -> Tuple[float, float, float
     return recall, precision, ndcg.mean().item()
 
 
-def get_metrics_lightgcn(model, edge_index: Tensor, exclude_edge_indices: List[Tensor], k: int
-                         ) -> Tuple[float, float, float]:
+def get_metrics_lightgcn(model, edge_index: Tensor, exclude_edge_indices: List[Tensor], k: int,
+                         embeddings: Optional[Tuple[Tensor, Tensor]] = None) -> Tuple[float, float, float]:
     """recall / precision / ndcg @ k of the layer-0 embeddings on the users of `edge_index`,
-    never recommending items in `exclude_edge_indices` (utils/metrics_lightgcn.py:79-122)."""
-    ue = model.users_emb.weight.detach()
-    ie = model.items_emb.weight.detach()
+    never recommending items in `exclude_edge_indices` (utils/metrics_lightgcn.py:79-122).
+    embeddings = (users [U, D], items [I, D]) scores with those tables instead (the propagated predictor)."""
+    if embeddings is not None:
+        ue, ie = embeddings[0].detach(), embeddings[1].detach()
+    else:
+        ue = model.users_emb.weight.detach()
+        ie = model.items_emb.weight.detach()
     dev = ie.device
     edge_index = edge_index.to(dev)
     n_items = ie.shape[0]
