@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define MI_ABI_VERSION 11
+#define MI_ABI_VERSION 12
 
 #define MI_ERR_BAD_ARG      (-1)  /* null pointer, negative size, misaligned buffer   */
 #define MI_ERR_TOO_LARGE    (-2)  /* a size does not fit int32 indexing                */
@@ -548,6 +548,37 @@ int    mi_topk_excl_ex_f32(int64_t n_q, int64_t n_items, int64_t d, int64_t k, c
                            const float* user_emb, int64_t ldu, const float* item_emb, int64_t ldi,
                            const int32_t* excl_ptr, const int32_t* excl_idx, int64_t* out_idx,
                            float* out_score, void* ws, size_t ws_bytes, uint32_t flags, mi_stream_t stream);
+
+/* Which of K10's five code paths a call with these arguments takes; host-only, enqueues nothing (the precedent is
+ * mi_gemm_group_supported).  The dispatcher of mi_topk_excl_ex_f32 asks the same function, so the answer is what runs.
+ * "fused-eligible": n_items >= 32 768, d <= 128, d % 4 == 0, ldu % 4 == 0, ldi % 4 == 0, both bases 16-byte aligned.
+ *
+ *   path                       chosen when                                               select step
+ *   M   materialised           n_items < 32 768                                          select_kernel, multi-pass
+ *   M1  materialised, one pass n_items >= 32 768 and not fused-eligible                  select_kernel, sampled threshold
+ *                                                                                        + one collect pass
+ *   G   fused, generic         fused-eligible, d neither 64 nor 128                      topk_scores_filter_kernel; sample
+ *                                                                                        scores from the plain GEMM
+ *   D   fused, LDS-DMA         fused-eligible, d 64 or 128, and the prefilter is off,    topk_scores_filter_dma_kernel
+ *                              k > 256, or the prefilter's LDS attribute is refused
+ *   P   bf16x3 prefilter       fused-eligible, d 64 or 128, k <= 256, prefilter on       topk_prefilter_launch
+ *                              and usable
+ *
+ * user_emb / item_emb are tested for alignment only, never read.  LAPLACE_TOPK_PREFILTER is read per call, as the
+ * dispatcher reads it; the build switches MI_TOPK_FUSED, MI_TOPK_ONE_PASS and MI_TOPK_DMA are honoured, so an A/B build
+ * reports what it runs.  Only a P answer touches the HIP runtime (the kernel's LDS attribute on the current device).
+ * Bad arguments: the negative codes of mi_topk_excl_ex_f32 (MI_ERR_BAD_ARG, MI_ERR_UNSUPPORTED for k > 1024,
+ * MI_ERR_TOO_LARGE).
+ * NON-FINITE inputs (NaN / inf embeddings) are outside K10's contract on every path: the order of such scores is
+ * unspecified. */
+#define MI_TOPK_PATH_MATERIALISED 0 /* M  */
+#define MI_TOPK_PATH_ONE_PASS     1 /* M1 */
+#define MI_TOPK_PATH_FUSED        2 /* G  */
+#define MI_TOPK_PATH_FUSED_DMA    3 /* D  */
+#define MI_TOPK_PATH_PREFILTER    4 /* P  */
+int mi_topk_path(int64_t n_items, int64_t d, int64_t k,
+                 const float* user_emb, int64_t ldu,
+                 const float* item_emb, int64_t ldi);
 
 /* Diagnostic of K10's bf16x3 prefilter (csrc/topk_prefilter.hpp), d = 64 / 128: scores[q, i] = the APPROXIMATE score the
  * prefilter compares with its thresholds, eps[q] = the bound it assumes, |scores[q, i] - exact fma chain| <= eps[q] for

@@ -10,7 +10,7 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 # the package directory is never overwritten by an experiment.  It is still this library or nothing — no fallback.
 LIB_PATH = os.environ.get("LAPLACE_HIP_LIB") or os.path.join(PKG_DIR, "liblaplace_hip.so")
 
-MI_ABI_VERSION = 11
+MI_ABI_VERSION = 12
 MI_SPMM_GROUP = 32
 
 
@@ -54,6 +54,7 @@ MI_SPMM_SHORT_ROWS, MI_SPMM_SPLIT_ROWS = 1, 2
 MI_ERR_UNSUPPORTED = -4
 MI_ERR_WORKSPACE = -3
 MI_TOPK_ITEMS_PREPARED = 1
+MI_TOPK_PATH_MATERIALISED, MI_TOPK_PATH_ONE_PASS, MI_TOPK_PATH_FUSED, MI_TOPK_PATH_FUSED_DMA, MI_TOPK_PATH_PREFILTER = range(5)
 MI_RANK_OBJECTIVES = {"reference": 0, "bpr": 1, "softmax": 2}
 MI_RANK_MAX_NEG = 16
 
@@ -225,6 +226,7 @@ _PROTOTYPES = {
                                    c_size_t, P]),
     "mi_topk_excl_ex_f32": (c_int32, [c_int64, c_int64, c_int64, c_int64, P, P, c_int64, P, c_int64, P, P, P, P, P,
                                       c_size_t, c_uint32, P]),
+    "mi_topk_path": (c_int32, [c_int64, c_int64, c_int64, P, c_int64, P, c_int64]),
     "mi_topk_prefilter_scores_workspace_bytes": (c_size_t, [c_int64, c_int64]),
     "mi_topk_prefilter_scores_f32": (c_int32, [c_int64, c_int64, c_int64, P, P, c_int64, P, c_int64, P, P, P, c_size_t, P]),
     "mi_segment_max_f32": (c_int32, [c_int64, c_int64, P, P, P, c_int64, P, c_int64, P, P]),

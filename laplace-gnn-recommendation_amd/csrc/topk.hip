@@ -1388,6 +1388,27 @@ static size_t topk_fused_extra_bytes(int64_t n_q, int64_t n_items) {
            topk_prefilter_bytes(n_q, n_items);
 }
 
+// The one decision of which path a call takes (include/laplace_hip.h: MI_TOPK_PATH_*): the dispatcher below and the
+// host-only query mi_topk_path both ask here.  The pointers are tested for alignment only.  The prefilter's LDS attribute
+// (topk_prefilter_usable: a HIP call) is asked last and only when everything else says P.
+static int topk_choose_path(int64_t n_items, int64_t d, int64_t k, const float* user_emb, int64_t ldu, const float* item_emb,
+                            int64_t ldi) {
+    const bool fused = MI_TOPK_FUSED && n_items >= 8 * kSample && d <= FKC && d % 4 == 0 && ldu % 4 == 0 && ldi % 4 == 0 &&
+                       mi_aligned16(user_emb) && mi_aligned16(item_emb);
+    if (!fused) return (MI_TOPK_ONE_PASS && n_items >= 8 * kSample) ? MI_TOPK_PATH_ONE_PASS : MI_TOPK_PATH_MATERIALISED;
+    if (d != 128 && d != 64) return MI_TOPK_PATH_FUSED;
+    if (topk_prefilter_on() && k <= kPreMaxK && topk_prefilter_usable(d)) return MI_TOPK_PATH_PREFILTER;
+    return MI_TOPK_DMA ? MI_TOPK_PATH_FUSED_DMA : MI_TOPK_PATH_FUSED;
+}
+
+int mi_topk_path(int64_t n_items, int64_t d, int64_t k, const float* user_emb, int64_t ldu, const float* item_emb, int64_t ldi) {
+    MI_CHECK_ARG(n_items >= 0 && d > 0 && k > 0);
+    if (k > kMaxK) return MI_ERR_UNSUPPORTED;
+    if (n_items >= INT32_MAX) return MI_ERR_TOO_LARGE;
+    MI_CHECK_ARG(user_emb && item_emb && ldu >= d && ldi >= d);
+    return topk_choose_path(n_items, d, k, user_emb, ldu, item_emb, ldi);
+}
+
 size_t mi_topk_workspace_bytes(int64_t n_q, int64_t n_items, int64_t k) {
     (void)k;
     if (n_q <= 0 || n_items <= 0) return 256;
@@ -1417,9 +1438,8 @@ int mi_topk_excl_ex_f32(int64_t n_q, int64_t n_items, int64_t d, int64_t k, cons
     float* scores = static_cast<float*>(ws);
     int kpow2 = 2;
     while (kpow2 < k) kpow2 <<= 1;
-    const bool fused = MI_TOPK_FUSED && n_items >= 8 * kSample && d <= FKC && d % 4 == 0 && ldu % 4 == 0 && ldi % 4 == 0 &&
-                       mi_aligned16(user_emb) && mi_aligned16(item_emb);
-    if (fused) {
+    const int path = topk_choose_path(n_items, d, k, user_emb, ldu, item_emb, ldi);
+    if (path >= MI_TOPK_PATH_FUSED) {
         MiArena ar(static_cast<char*>(ws) + mi_align_up((size_t)n_q * (size_t)n_items * sizeof(float), 256),
                    topk_fused_extra_bytes(n_q, n_items));
         const int64_t words = (n_items + 31) / 32;
@@ -1430,7 +1450,7 @@ int mi_topk_excl_ex_f32(int64_t n_q, int64_t n_items, int64_t d, int64_t k, cons
         int* cnt = ar.take<int>((size_t)n_q);
         unsigned long long* cand = ar.take<unsigned long long>((size_t)n_q * kCap);
         if (!Is || !sample_scores || !bitmap || !thr || !cnt || !cand) return MI_ERR_WORKSPACE;
-        const bool pre_path = topk_prefilter_on() && (d == 128 || d == 64) && k <= kPreMaxK && topk_prefilter_usable(d);
+        const bool pre_path = path == MI_TOPK_PATH_PREFILTER;
         // MI_TOPK_ITEMS_PREPARED: the item side of the prefilter (sample rows, the bf16 split of the item table and of the
         // sample, the largest |item|^2) is still in `ws` from the previous call: nothing of it is recomputed
         const bool items_ready = pre_path && (flags & MI_TOPK_ITEMS_PREPARED) != 0;
@@ -1451,7 +1471,7 @@ int mi_topk_excl_ex_f32(int64_t n_q, int64_t n_items, int64_t d, int64_t k, cons
         }
         const int64_t strips = mi_ceil_div(n_q, FM);
         const int64_t capacity = 2 * (int64_t)mi_cu_count();
-        if (MI_TOPK_DMA && (d == 128 || d == 64)) {
+        if (path == MI_TOPK_PATH_FUSED_DMA) {
             int64_t sl = 1, best = INT64_MAX;  // split of the 64 sample panels: rounds x (panels + prologue), as below
             for (int64_t l = 1; l <= kSample / FN; ++l) {
                 const int64_t cost = mi_ceil_div(strips * l, capacity) * (mi_ceil_div(kSample / FN, l) + 2);
@@ -1488,9 +1508,9 @@ int mi_topk_excl_ex_f32(int64_t n_q, int64_t n_items, int64_t d, int64_t k, cons
         }
         a.tiles_per_slice = mi_ceil_div(n_tiles, slices);
         slices = mi_ceil_div(n_tiles, a.tiles_per_slice);
-        if (MI_TOPK_DMA && d == 128)
+        if (path == MI_TOPK_PATH_FUSED_DMA && d == 128)
             hipLaunchKernelGGL(topk_scores_filter_dma_kernel<64>, dim3((unsigned)slices, (unsigned)strips), dim3(256), 0, s, a);
-        else if (MI_TOPK_DMA && d == 64)
+        else if (path == MI_TOPK_PATH_FUSED_DMA)
             hipLaunchKernelGGL(topk_scores_filter_dma_kernel<32>, dim3((unsigned)slices, (unsigned)strips), dim3(256), 0, s, a);
         else
             hipLaunchKernelGGL(topk_scores_filter_kernel, dim3((unsigned)slices, (unsigned)strips), dim3(256), 0, s, a);
@@ -1508,7 +1528,7 @@ int mi_topk_excl_ex_f32(int64_t n_q, int64_t n_items, int64_t d, int64_t k, cons
     if (excl_ptr)
         hipLaunchKernelGGL(exclude_kernel, dim3((unsigned)n_q), dim3(kBlock), 0, s, n_q, n_items, excl_ptr, excl_idx, scores);
     hipLaunchKernelGGL(select_kernel, dim3((unsigned)n_q), dim3(kBlock), 0, s, n_q, n_items, (int)k, kpow2, scores,
-                       out_idx, out_score, MI_TOPK_ONE_PASS);
+                       out_idx, out_score, path == MI_TOPK_PATH_ONE_PASS);
     return mi_launch_status();
 }
 

@@ -1042,6 +1042,20 @@ def topk_excl(uid: Tensor, user_emb: Tensor, item_emb: Tensor, k: int, excl: Opt
     return (out_idx, out_sc) if want_scores else out_idx
 
 
+def topk_path(user_emb: Tensor, item_emb: Tensor, k: int) -> int:
+    """Which code path of K10 topk_excl takes for these tables and this k (_lib.MI_TOPK_PATH_*: materialised, one pass, fused,
+    fused LDS-DMA, bf16 prefilter) — asked of the dispatcher's own decision function; host-only, nothing is enqueued.  The
+    choice does not depend on the number of queries, so it holds for every chunk of a chunked call."""
+    ldu = _rows_ok(user_emb, "user_emb")
+    ldi = _rows_ok(item_emb, "item_emb")
+    n_items, d = item_emb.shape
+    if user_emb.shape[1] != d:
+        raise ValueError("user and item embeddings differ in width")
+    rc = int(_lib.lib().mi_topk_path(n_items, d, k, user_emb.data_ptr(), ldu, item_emb.data_ptr(), ldi))
+    check(rc if rc < 0 else 0, "mi_topk_path")
+    return rc
+
+
 def topk_prefilter_scores(uid: Optional[Tensor], user_emb: Tensor, item_emb: Tensor) -> Tuple[Tensor, Tensor]:
     """Diagnostic of the bf16x3 prefilter behind topk_excl (csrc/topk_prefilter.hpp): the approximate scores [n_q, n_items]
     it compares with its thresholds and the per-query bound eps it assumes for |approximate - exact fma chain|."""

@@ -249,6 +249,19 @@ def main():
     assert L.mi_gemm_group_supported(None, 1) == 0 and L.mi_gemm_group_supported(probs, 9) == 0
     for nq, ni, k in ((1, 100, 12), (4096, 100_000, 256), (0, 0, 0), (16384, 105_542, 1024), (-1, 10, 3)):
         L.mi_topk_workspace_bytes(nq, ni, k); L.mi_topk_prefilter_scores_workspace_bytes(nq, ni)
+    # mi_topk_path: the dispatcher's choice from sizes and alignment alone; bad arguments are refused with the main entry's codes
+    os.environ["LAPLACE_TOPK_PREFILTER"] = "0"   # the prefilter's question to the device is then never asked: host-only
+    f = Fake()
+    ue, ie = f(1 << 20), f(1 << 20)
+    assert L.mi_topk_path(1000, 64, 12, ue, 64, ie, 64) == _lib.MI_TOPK_PATH_MATERIALISED
+    assert L.mi_topk_path(40_000, 200, 12, ue, 200, ie, 200) == _lib.MI_TOPK_PATH_ONE_PASS
+    assert L.mi_topk_path(40_000, 32, 12, ue, 32, ie, 32) == _lib.MI_TOPK_PATH_FUSED
+    assert L.mi_topk_path(40_000, 32, 12, ue, 32, ie + 4, 32) == _lib.MI_TOPK_PATH_ONE_PASS
+    assert L.mi_topk_path(40_000, 128, 12, ue, 128, ie, 128) == _lib.MI_TOPK_PATH_FUSED_DMA
+    assert L.mi_topk_path(-1, 64, 12, ue, 64, ie, 64) == BAD_ARG and L.mi_topk_path(100, 0, 12, ue, 64, ie, 64) == BAD_ARG
+    assert L.mi_topk_path(100, 64, 0, ue, 64, ie, 64) == BAD_ARG and L.mi_topk_path(100, 64, 12, None, 64, ie, 64) == BAD_ARG
+    assert L.mi_topk_path(100, 64, 12, ue, 64, None, 64) == BAD_ARG and L.mi_topk_path(100, 64, 12, ue, 63, ie, 64) == BAD_ARG
+    assert L.mi_topk_path(100, 64, 1025, ue, 64, ie, 64) == UNSUPPORTED and L.mi_topk_path(1 << 31, 64, 12, ue, 64, ie, 64) == -2
     for args in ((96, 2, 10), (384, 3, 10), (0, 1, 1), (-1, 2, 3)):
         L.mi_pinsage_neighbors_workspace_bytes(*args)
     assert L.mi_gather_cat_bwd_max_edges() > 0 and L.mi_error_string(-4) and L.mi_error_string(12345)

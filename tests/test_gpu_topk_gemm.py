@@ -56,7 +56,9 @@ def test_topk_matches_reference_golden(golden_dir):
     ue, ie, tr = g["users_emb"].to(DEV), g["items_emb"].to(DEV), g["train_edges"].to(DEV)
     U = ue.shape[0]
     users = t.arange(U, device=DEV)
+    from laplace_amd import _lib, ops
     for k, per_user in g["preds"].items():
+        assert ops.topk_path(ue, ie, k) == _lib.MI_TOPK_PATH_MATERIALISED      # a small catalogue: the multi-pass select
         top = topk_for_users(ue, ie, users, tr, k).cpu()
         for u in range(U):
             assert t.equal(top[u], per_user[u]), (k, u)
@@ -72,12 +74,15 @@ def test_topk_matches_reference_golden(golden_dir):
 
 
 @pytest.mark.parametrize("n_items,k", [(1000, 12), (5000, 256), (100_000, 256), (70, 100), (3000, 1),
-                                       # one-pass path (sample threshold + single collect pass): rows >= 32 768 items, also
-                                       # rows that are not 16-byte aligned, k = 1 and the largest k
+                                       # rows >= 32 768 items at these widths are fused: the bf16 prefilter (P) for k <= 256,
+                                       # the LDS-DMA kernel (D) for k = 1 024; item counts that are not multiples of 4 / 64,
+                                       # k = 1 and the largest k.  Below 32 768 items: the materialised multi-pass select (M).
+                                       # (The materialised ONE-PASS path, M1, takes none of these: tests/test_gpu_topk_paths.py.)
                                        (40_000, 1), (50_001, 12), (33_333, 256), (100_000, 1024)])
 @pytest.mark.parametrize("D", [64, 128])
-def test_topk_exact_vs_oracle(n_items, k, D):
-    from laplace_amd import ops
+def test_topk_exact_vs_oracle(n_items, k, D, monkeypatch):
+    from laplace_amd import _lib, ops
+    monkeypatch.setenv("LAPLACE_TOPK_PREFILTER", "1")
     g = t.Generator().manual_seed(n_items + k)
     U, n_q = 300, 41
     ue, ie = t.randn(U, D, generator=g) * 0.1, t.randn(n_items, D, generator=g) * 0.1
@@ -85,7 +90,11 @@ def test_topk_exact_vs_oracle(n_items, k, D):
     excl = [t.randperm(n_items, generator=g)[: int(t.randint(0, min(n_items, 400), (1,), generator=g))] for _ in range(n_q)]
     rows = t.cat([t.full((len(e),), i) for i, e in enumerate(excl)]).long()
     ex = ops.coo_to_csr(rows.to(DEV), t.cat(excl).to(DEV), n_q, n_items, want_perm=False)
-    ids, sc = ops.topk_excl(uid.to(DEV), ue.to(DEV), ie.to(DEV), k, ex, want_scores=True)
+    ue_d, ie_d = ue.to(DEV), ie.to(DEV)
+    path = (_lib.MI_TOPK_PATH_MATERIALISED if n_items < 32_768 else
+            _lib.MI_TOPK_PATH_PREFILTER if k <= 256 else _lib.MI_TOPK_PATH_FUSED_DMA)
+    assert ops.topk_path(ue_d, ie_d, k) == path
+    ids, sc = ops.topk_excl(uid.to(DEV), ue_d, ie_d, k, ex, want_scores=True)
     scores = R.scores_fma(ue[uid], ie)
     want = R.topk_excl_exact(scores, excl, k)
     assert t.equal(ids.cpu(), want)
@@ -102,6 +111,8 @@ def test_topk_ties_resolved_by_item_id():
     ie = base[t.randint(0, 40, (n_items,), generator=g)]  # only 40 distinct rows -> massive ties
     ue = t.randn(7, D, generator=g)
     uid = t.arange(7)
+    from laplace_amd import _lib
+    assert ops.topk_path(ue.to(DEV), ie.to(DEV), k) == _lib.MI_TOPK_PATH_MATERIALISED
     ids = ops.topk_excl(uid.to(DEV), ue.to(DEV), ie.to(DEV), k, None)
     want = R.topk_excl_exact(R.scores_fma(ue, ie), [t.empty(0, dtype=t.int64)] * 7, k)
     assert t.equal(ids.cpu(), want)
@@ -109,10 +120,19 @@ def test_topk_ties_resolved_by_item_id():
     assert t.equal(zeros.cpu(), t.arange(k).repeat(7, 1))
 
 
-@pytest.mark.parametrize("D", [32, 64, 128])  # 32: the generic fused kernel; 64 / 128: the LDS-DMA kernel and its overflow marks
-def test_topk_large_rows_with_massive_ties_and_exclusions_fall_back_exactly(D):
+@pytest.mark.parametrize("D", [32, 64, 128])  # 32: the generic fused kernel (G); 64 / 128: the bf16 prefilter (P) as shipped, then
+def test_topk_large_rows_with_massive_ties_and_exclusions_fall_back_exactly(D, monkeypatch):  # the LDS-DMA kernel (D), overflow marks
     """Rows where the sampled threshold cannot work — thousands of equal scores at the cut, all scores equal,
     almost everything excluded — take the multi-pass path and still return the exact lists."""
+    from laplace_amd import _lib, ops
+    for prefilter in (("1",) if D == 32 else ("1", "0")):
+        monkeypatch.setenv("LAPLACE_TOPK_PREFILTER", prefilter)
+        path = (_lib.MI_TOPK_PATH_FUSED if D == 32 else
+                _lib.MI_TOPK_PATH_PREFILTER if prefilter == "1" else _lib.MI_TOPK_PATH_FUSED_DMA)
+        _large_rows_with_massive_ties(D, path)
+
+
+def _large_rows_with_massive_ties(D, path):
     from laplace_amd import ops
     g = t.Generator().manual_seed(9)
     n_items, k = 50_000, 100
@@ -121,6 +141,7 @@ def test_topk_large_rows_with_massive_ties_and_exclusions_fall_back_exactly(D):
     ue = t.randn(5, D, generator=g)
     uid = t.arange(5)
     none = [t.empty(0, dtype=t.int64)] * 5
+    assert ops.topk_path(ue.to(DEV), ie.to(DEV), k) == path
     ids = ops.topk_excl(uid.to(DEV), ue.to(DEV), ie.to(DEV), k, None)
     assert t.equal(ids.cpu(), R.topk_excl_exact(R.scores_fma(ue, ie), none, k))
     zeros = ops.topk_excl(uid.to(DEV), t.zeros(5, D, device=DEV), ie.to(DEV), k, None)
@@ -172,9 +193,12 @@ def test_topk_bf16_prefilter_equals_the_f32_path(D, n_q, k, monkeypatch):
     rows = t.cat([t.full((len(e),), i) for i, e in enumerate(excl)]).long()
     ex = ops.coo_to_csr(rows.to(DEV), t.cat(excl).to(DEV), n_q, n_items, want_perm=False)
     args = (uid.to(DEV), ue.to(DEV), ie.to(DEV), k, ex)
+    from laplace_amd import _lib
     monkeypatch.setenv("LAPLACE_TOPK_PREFILTER", "1")
+    assert ops.topk_path(args[1], args[2], k) == _lib.MI_TOPK_PATH_PREFILTER
     ids_b, sc_b = ops.topk_excl(*args, want_scores=True)
     monkeypatch.setenv("LAPLACE_TOPK_PREFILTER", "0")
+    assert ops.topk_path(args[1], args[2], k) == _lib.MI_TOPK_PATH_FUSED_DMA
     ids_f, sc_f = ops.topk_excl(*args, want_scores=True)
     assert t.equal(ids_b, ids_f)
     assert t.equal(sc_b, sc_f)
@@ -296,6 +320,8 @@ def test_topk_against_the_torch_product_the_reference_calls():
     ie = t.randint(-64, 65, (I, D), generator=g).float() / 64.0
     ie[1000:1100] = ie[:100]                                   # exact ties between distinct ids
     uid = t.arange(U)
+    from laplace_amd import _lib
+    assert ops.topk_path(ue.to(DEV), ie.to(DEV), k) == _lib.MI_TOPK_PATH_MATERIALISED
     ids, sc = ops.topk_excl(uid.to(DEV), ue.to(DEV), ie.to(DEV), k, None, want_scores=True)
     ids, sc = ids.cpu(), sc.cpu()
     prod = ue @ ie.T                                           # the reference's call
@@ -322,6 +348,7 @@ def test_topk_against_the_torch_product_the_reference_calls():
     col = t.randint(0, D, (I2 // 2,), generator=g)
     ar = t.arange(I2 // 2)
     ie2[1::2][ar, col] = t.nextafter(ie2[0::2][ar, col], t.full((I2 // 2,), 1.0))
+    assert ops.topk_path(ue2.to(DEV), ie2.to(DEV), k) == _lib.MI_TOPK_PATH_MATERIALISED
     ids2 = ops.topk_excl(uid.to(DEV), ue2.to(DEV), ie2.to(DEV), k, None).cpu()
     prod2 = ue2 @ ie2.T
     ti2 = t.topk(prod2, k, dim=1).indices
