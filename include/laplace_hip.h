@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define MI_ABI_VERSION 12
+#define MI_ABI_VERSION 13
 
 #define MI_ERR_BAD_ARG      (-1)  /* null pointer, negative size, misaligned buffer   */
 #define MI_ERR_TOO_LARGE    (-2)  /* a size does not fit int32 indexing                */
@@ -829,6 +829,57 @@ int mi_match_same_location_i32(int64_t n_queries, const int64_t* query_users, co
                                const int32_t* loc_ptr, const int32_t* loc_idx,
                                const int32_t* users_ptr, const int32_t* users_idx,
                                int32_t k, int32_t* out, int32_t* out_count, mi_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
+ * N3b  candidate matcher: scored item co-occurrence (item-to-item co-purchase similarity).
+ * replaces: nothing.  The reference has no such matcher: its UsersWithCommonItemsMatcher keeps the
+ *           first k entries of the user -> item -> user -> item walk and never counts how often an
+ *           item is reached.  This is the scored form of that walk, in two stages.
+ * Inputs of both stages: the adjacency lists IN LIST ORDER as int32 CSR on device, as
+ * mi_match_common_items_i32 takes them; the two lists are transposes of one another and repeated
+ * purchases are repeated entries of both.
+ *
+ * Stage 1, mi_cooc_items_topt: the item neighbour table.  d_i = length of article i's list;
+ * c(i, j), i != j = number of walks i -> u -> j, one per position of u in i's list times every
+ * position of j in u's list (= (A^T A)[i, j] with A[u, i] the multiplicity).  Score s(i, j) = c
+ * (weighting MI_COOC_COUNT) or c / sqrt(d_i * d_j) in fp32 (MI_COOC_COSINE).  Row i of
+ * nbr_id / nbr_count int32[n_items, T] and nbr_score float[n_items, T] holds the T best j with c > 0
+ * by (s descending, j ascending), padded with id -1, count 0, score 0.  1 <= T <= 64.  Counts are
+ * exact (integer LDS atomics) and every output is bit-identical from call to call; a count is
+ * assumed to fit int32.  One workgroup per item row, heaviest rows first, the row's expansion
+ * re-walked once per band of 36 864 item ids; the workspace holds the row order only.
+ *
+ * Stage 2, mi_match_cooc_i32: r(u, j) = sum over the list positions p taken of nbr_score[L_u[p], t]
+ * over every t with nbr_id[L_u[p], t] == j, summed in (p, t) order.  Positions taken: all of L_u,
+ * or the last n_recent (n_recent <= 0 = all; list order is transaction order).  exclude_seen != 0
+ * drops every item anywhere in the user's whole list.  out int32[n, k]: the k best j with r > 0 by
+ * (r descending, j ascending), -1 padded; out_score float[n, k] (nullable): their r, 0 padded;
+ * out_count int32[n] (nullable): entries written.  query_users int64[n] (null = users 0..n-1; any
+ * order, repeats allowed).  max_list_len: an upper bound of the longest purchase list among the
+ * queried users; it sizes the workspace slabs in which users whose |L_u| * T terms do not fit LDS
+ * are sorted (exactly: nothing is truncated).  A queried user whose list is longer than
+ * max_list_len gets no candidates and out_count -1.
+ *
+ * The size queries run without a GPU and return 0 for arguments the calls refuse.  Null pointers,
+ * T outside 1..64, k <= 0, an unknown weighting and nnz >= 2^31 return MI_ERR_BAD_ARG before any
+ * launch; a short workspace returns MI_ERR_WORKSPACE.
+ * ---------------------------------------------------------------------------------- */
+#define MI_COOC_COUNT  0
+#define MI_COOC_COSINE 1
+size_t mi_cooc_items_workspace_bytes(int64_t n_items, int64_t nnz, int32_t T);
+int    mi_cooc_items_topt(int64_t n_users, int64_t n_items, int64_t nnz,
+                          const int32_t* users_ptr, const int32_t* users_idx,
+                          const int32_t* articles_ptr, const int32_t* articles_idx,
+                          int32_t T, int32_t weighting,
+                          int32_t* nbr_id, int32_t* nbr_count, float* nbr_score,
+                          void* ws, size_t ws_bytes, mi_stream_t stream);
+size_t mi_match_cooc_workspace_bytes(int64_t n_queries, int64_t max_list_len, int32_t T);
+int    mi_match_cooc_i32(int64_t n_queries, const int64_t* query_users,
+                         const int32_t* users_ptr, const int32_t* users_idx, int64_t max_list_len,
+                         int32_t T, const int32_t* nbr_id, const float* nbr_score,
+                         int32_t k, int32_t n_recent, int32_t exclude_seen,
+                         int32_t* out, float* out_score, int32_t* out_count,
+                         void* ws, size_t ws_bytes, mi_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
  * N1  on-device N-hop subgraph sampler for the ranker.

@@ -10,7 +10,7 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 # the package directory is never overwritten by an experiment.  It is still this library or nothing — no fallback.
 LIB_PATH = os.environ.get("LAPLACE_HIP_LIB") or os.path.join(PKG_DIR, "liblaplace_hip.so")
 
-MI_ABI_VERSION = 12
+MI_ABI_VERSION = 13
 MI_SPMM_GROUP = 32
 
 
@@ -57,6 +57,7 @@ MI_TOPK_ITEMS_PREPARED = 1
 MI_TOPK_PATH_MATERIALISED, MI_TOPK_PATH_ONE_PASS, MI_TOPK_PATH_FUSED, MI_TOPK_PATH_FUSED_DMA, MI_TOPK_PATH_PREFILTER = range(5)
 MI_RANK_OBJECTIVES = {"reference": 0, "bpr": 1, "softmax": 2}
 MI_RANK_MAX_NEG = 16
+MI_COOC_WEIGHTINGS = {"count": 0, "cosine": 1}
 
 
 class GemmProblem(Structure):
@@ -254,6 +255,10 @@ _PROTOTYPES = {
     "mi_ranker_step_check": (c_int32, [POINTER(RankerModel), POINTER(RankerBatch), P, c_size_t]),
     "mi_ranker_adam_f32": (c_int32, [POINTER(RankerModel), ctypes.c_float, P]),
     "mi_match_same_location_i32": (c_int32, [c_int64, P, P, P, P, P, P, c_int32, P, P, P]),
+    "mi_cooc_items_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int32]),
+    "mi_cooc_items_topt": (c_int32, [c_int64, c_int64, c_int64, P, P, P, P, c_int32, c_int32, P, P, P, P, c_size_t, P]),
+    "mi_match_cooc_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int32]),
+    "mi_match_cooc_i32": (c_int32, [c_int64, P, P, P, c_int64, c_int32, P, P, c_int32, c_int32, c_int32, P, P, P, P, c_size_t, P]),
     "mi_sampler_workspace_bytes": (c_size_t, [POINTER(SamplerDesc)]),
     "mi_sampler_count": (c_int32, [POINTER(SamplerDesc), P, c_uint64, c_uint64, P, c_size_t, POINTER(c_int64), P]),
     "mi_sampler_count_async": (c_int32, [POINTER(SamplerDesc), P, c_uint64, c_uint64, P, c_size_t, P, P]),

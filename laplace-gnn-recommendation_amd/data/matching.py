@@ -13,7 +13,15 @@ the reference materialises every article of every co-purchasing user and then ke
                                itself included), all their articles (data/matching/fashion/users_same_location.py:8-25;
                                commented out of the reference's get_matchers, kept here the same way)
 
-All four are pinned against the reference's own classes: tests/golden/matchers.pt (tests/make_golden.py runs them on
+  ItemCooccurrenceMatcher      NO reference counterpart — the scored form of the walk above: item-to-item co-purchase
+                               similarity c(i, j) = (A^T A)[i, j] (raw, or cosine c / sqrt(d_i d_j)), the T best
+                               neighbours kept per item; a user's candidates are the k best j by the sum of the neighbour
+                               scores over the items the user holds (all, or the last n_recent), optionally without the
+                               items the user already has.  Device: mi_cooc_items_topt + mi_match_cooc_i32
+                               (csrc/cooccurrence.hip); the host get_matches restates the definitions in NumPy and is the
+                               checker (tests/test_cooccurrence_cpu.py, tests/test_gpu_cooccurrence.py)
+
+The first four are pinned against the reference's own classes: tests/golden/matchers.pt (tests/make_golden.py runs them on
 small dict-of-list files) — host forms in tests/test_oracle_golden.py, device forms in tests/test_gpu_matching.py.
 
 Device forms: every matcher also answers for ALL users at once as a device tensor [U, k] (int64, -1 = no
@@ -165,6 +173,100 @@ class UsersSameLocationMatcher(Matcher):
                          to32(self.users.ptr), to32(self.users.idx))
         out, _ = ops.match_same_location(*self._dev, self.k, n_queries=num_users)
         return out.to(t.int64)
+
+
+class ItemCooccurrenceMatcher(Matcher):
+    """Scored item co-occurrence candidates (include/laplace_hip.h, N3b, states the contract).  Not in get_matchers: the
+    reference has no such matcher, callers add it to their list themselves."""
+
+    def __init__(self, users_adj, articles_adj, k: int, *, neighbors: int = 32, weighting: str = "cosine",
+                 n_recent=None, exclude_seen: bool = False):
+        self.users = users_adj if isinstance(users_adj, AdjList) else AdjList(users_adj)
+        self.articles = articles_adj if isinstance(articles_adj, AdjList) else AdjList(articles_adj)
+        if not 1 <= int(neighbors) <= 64:
+            raise ValueError(f"neighbors must be within 1..64, got {neighbors}")
+        if weighting not in ("count", "cosine"):
+            raise ValueError(f"weighting must be 'count' or 'cosine', got {weighting!r}")
+        if int(k) <= 0 or (n_recent is not None and int(n_recent) <= 0):
+            raise ValueError("k and n_recent must be positive")
+        self.k, self.neighbors, self.weighting = int(k), int(neighbors), weighting
+        self.n_recent = None if n_recent is None else int(n_recent)
+        self.exclude_seen = bool(exclude_seen)
+        self._deg = np.diff(self.articles.ptr)
+        self._rows = {}      # host neighbour rows, computed on demand
+        self._dev = None     # (users_ptr, users_idx, articles_ptr, articles_idx) on one device
+        self._table = None   # (nbr_id, nbr_count, nbr_score) on that device
+
+    # ---- host form: the checker, independent of the device path --------------------------------------------------------
+    def item_neighbors(self, item: int):
+        """(ids int64[<= T], counts int64, scores float32) of one item row, best first."""
+        item = int(item)
+        if item not in self._rows:
+            n_items = len(self.articles)
+            reached, _ = self.users.gather(self.articles[item])         # every position of u in i's list x u's whole list
+            c = np.bincount(reached, minlength=n_items)
+            c[item] = 0
+            ids = np.nonzero(c)[0]
+            cnt = c[ids]
+            if self.weighting == "cosine":
+                sc = cnt.astype(np.float32) / np.sqrt(np.float32(self._deg[item]) * self._deg[ids].astype(np.float32))
+            else:
+                sc = cnt.astype(np.float32)
+            key = cnt if self.weighting == "count" else sc            # raw counts order exactly, also beyond 2^24
+            keep = np.lexsort((ids, -key.astype(np.float64)))[: self.neighbors]
+            self._rows[item] = (ids[keep].astype(np.int64), cnt[keep].astype(np.int64), sc[keep].astype(np.float32))
+        return self._rows[item]
+
+    def scores_for(self, user_id: int):
+        """(ids int64, r float32) of every item with r(u, j) > 0, best first; sums run in (list position, neighbour) order."""
+        lst = self.users[user_id]
+        taken = lst if self.n_recent is None else lst[-self.n_recent:]
+        r = np.zeros(len(self.articles), dtype=np.float32)
+        for a in taken:
+            ids, _, sc = self.item_neighbors(int(a))
+            r[ids] += sc                                                 # ids of one row are distinct
+        if self.exclude_seen:
+            r[lst] = 0
+        ids = np.nonzero(r > 0)[0]
+        order = np.lexsort((ids, -r[ids].astype(np.float64)))
+        return ids[order].astype(np.int64), r[ids][order]
+
+    def get_matches(self, user_id: int) -> Tensor:
+        return t.from_numpy(self.scores_for(user_id)[0][: self.k].copy())
+
+    def matches_for_all(self, num_users: int):
+        out = np.full((num_users, self.k), -1, dtype=np.int64)
+        for u in range(num_users):
+            got = self.scores_for(u)[0][: self.k]
+            out[u, : got.shape[0]] = got
+        return out
+
+    # ---- device form ---------------------------------------------------------------------------------------------------
+    def _on(self, device):
+        from .. import ops
+        dev = t.device(device)
+        if dev.type == "cuda" and dev.index is None:       # "cuda" and "cuda:0" are the same place: compare normalised devices
+            dev = t.device("cuda", t.cuda.current_device())
+        if self._dev is None or self._dev[0].device != dev:
+            to32 = lambda a: t.from_numpy(np.ascontiguousarray(a.astype(np.int32))).to(dev)
+            self._dev = (to32(self.users.ptr), to32(self.users.idx), to32(self.articles.ptr), to32(self.articles.idx))
+            self._table = ops.cooc_item_neighbors(*self._dev, self.neighbors, self.weighting)
+        return self._dev, self._table
+
+    def item_neighbors_device(self, device):
+        """(nbr_id int32[I, T], nbr_count int32[I, T], nbr_score float32[I, T]) on `device`, built once per device."""
+        return self._on(device)[1]
+
+    def matches_for_all_device(self, num_users: int, device, query_users=None, with_scores: bool = False):
+        from .. import ops
+        if num_users > len(self.users):
+            raise IndexError(f"{num_users} query users but the purchase lists cover {len(self.users)}")
+        (uptr, uidx, _, _), (nbr_id, _, nbr_score) = self._on(device)
+        longest = int(np.diff(self.users.ptr).max()) if len(self.users) else 0
+        out, score, cnt = ops.match_cooccurrence(uptr, uidx, nbr_id, nbr_score, self.k, n_queries=num_users,
+                                                 query_users=query_users, n_recent=self.n_recent,
+                                                 exclude_seen=self.exclude_seen, max_list_len=longest)
+        return (out.to(t.int64), score, cnt) if with_scores else out.to(t.int64)
 
 
 def get_matchers(dataset_type: str, users_adj, articles_adj, candidate_pool_size: int) -> List[Matcher]:

@@ -1170,6 +1170,81 @@ def match_same_location(location_of_user: Tensor, loc_ptr: Tensor, loc_idx: Tens
     return out, cnt
 
 
+_COOC_WS = {}
+
+
+def _cooc_ws(which: str, nbytes: int, device) -> Tensor:
+    """One grow-only workspace per device and stage, sized by the library's own query."""
+    key = (t.device(device).index, which)
+    if key not in _COOC_WS or _COOC_WS[key].numel() < nbytes:
+        _COOC_WS[key] = _ws(nbytes, device)
+    return _COOC_WS[key]
+
+
+def cooc_item_neighbors(users_ptr: Tensor, users_idx: Tensor, articles_ptr: Tensor, articles_idx: Tensor, T: int,
+                        weighting: str = "cosine"):
+    """N3b stage 1 — the item neighbour table of the co-occurrence matcher: (ids int32[I, T] with -1 pads, counts int32[I, T],
+    scores float32[I, T]); row i = the T best j by c(i, j) = (A^T A)[i, j] ("count") or c / sqrt(d_i d_j) ("cosine")."""
+    for n, x in (("users_ptr", users_ptr), ("users_idx", users_idx), ("articles_ptr", articles_ptr), ("articles_idx", articles_idx)):
+        _need(x, t.int32, n)
+    if weighting not in _lib.MI_COOC_WEIGHTINGS:
+        raise ValueError(f"weighting: expected one of {sorted(_lib.MI_COOC_WEIGHTINGS)}, got {weighting!r}")
+    if users_idx.numel() != articles_idx.numel():
+        raise ValueError("users_idx and articles_idx must list the same edges")
+    T = int(T)
+    n_users, n_items, nnz, dev = users_ptr.numel() - 1, articles_ptr.numel() - 1, users_idx.numel(), users_ptr.device
+    L = _lib.lib()
+    need = L.mi_cooc_items_workspace_bytes(n_items, nnz, T)
+    if need == 0:
+        raise ValueError(f"cooc_item_neighbors: T = {T} outside 1..64, or sizes beyond int32 indexing")
+    ws = _cooc_ws("items", need, dev)
+    ids = t.empty(n_items, T, dtype=t.int32, device=dev)
+    counts = t.empty(n_items, T, dtype=t.int32, device=dev)
+    scores = t.empty(n_items, T, dtype=t.float32, device=dev)
+    check(L.mi_cooc_items_topt(n_users, n_items, nnz, users_ptr.data_ptr(), _ptr(users_idx), articles_ptr.data_ptr(),
+                               _ptr(articles_idx), T, _lib.MI_COOC_WEIGHTINGS[weighting], _ptr(ids), _ptr(counts), _ptr(scores),
+                               ws.data_ptr(), ws.numel(), _stream()), "mi_cooc_items_topt")
+    return ids, counts, scores
+
+
+def match_cooccurrence(users_ptr: Tensor, users_idx: Tensor, nbr_id: Tensor, nbr_score: Tensor, k: int,
+                       n_queries: Optional[int] = None, query_users: Optional[Tensor] = None, n_recent: Optional[int] = None,
+                       exclude_seen: bool = False, max_list_len: Optional[int] = None):
+    """N3b stage 2 — co-occurrence candidates for many users at once: (ids int32[n, k] with -1 pads, scores float32[n, k],
+    counts int32[n]).  max_list_len: the longest purchase list (sizes the workspace of the users whose terms do not fit
+    LDS); read back from users_ptr when not given."""
+    _need(users_ptr, t.int32, "users_ptr")
+    _need(users_idx, t.int32, "users_idx")
+    _need(nbr_id, t.int32, "nbr_id")
+    _need(nbr_score, t.float32, "nbr_score")
+    if nbr_id.dim() != 2 or nbr_id.shape != nbr_score.shape:
+        raise ValueError("nbr_id and nbr_score must be [n_items, T] tables of one shape")
+    if query_users is not None:
+        _need(query_users, t.int64, "query_users")
+        n_queries = query_users.numel()
+    elif n_queries is None:
+        n_queries = users_ptr.numel() - 1
+    if n_recent is not None and int(n_recent) <= 0:
+        raise ValueError("n_recent must be positive (None = the whole list)")
+    if max_list_len is None:
+        max_list_len = int((users_ptr[1:] - users_ptr[:-1]).max()) if users_ptr.numel() > 1 else 0
+    T, k, dev = int(nbr_id.shape[1]), int(k), users_ptr.device
+    L = _lib.lib()
+    need = L.mi_match_cooc_workspace_bytes(n_queries, int(max_list_len), T)
+    if need == 0 or k <= 0:
+        raise ValueError(f"match_cooccurrence: k = {k} must be positive and T = {T} within 1..64")
+    ws = _cooc_ws("match", need, dev)
+    out = t.empty(n_queries, k, dtype=t.int32, device=dev)
+    score = t.empty(n_queries, k, dtype=t.float32, device=dev)
+    cnt = t.empty(n_queries, dtype=t.int32, device=dev)
+    if n_queries and users_idx.numel() == 0:   # nobody holds anything: nothing to propose
+        return out.fill_(-1), score.zero_(), cnt.zero_()
+    check(L.mi_match_cooc_i32(n_queries, _ptr(query_users), users_ptr.data_ptr(), _ptr(users_idx), int(max_list_len), T,
+                              _ptr(nbr_id), _ptr(nbr_score), k, int(n_recent or 0), int(bool(exclude_seen)),
+                              _ptr(out), _ptr(score), _ptr(cnt), ws.data_ptr(), ws.numel(), _stream()), "mi_match_cooc_i32")
+    return out, score, cnt
+
+
 _BN_WS = {}
 
 
