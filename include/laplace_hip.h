@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define MI_ABI_VERSION 13
+#define MI_ABI_VERSION 14
 
 #define MI_ERR_BAD_ARG      (-1)  /* null pointer, negative size, misaligned buffer   */
 #define MI_ERR_TOO_LARGE    (-2)  /* a size does not fit int32 indexing                */
@@ -1109,6 +1109,63 @@ int    mi_pinsage_embed_items_f32(const mi_pinsage_model* model, const int32_t* 
                                   const int32_t* ui_ptr, const int32_t* ui_idx, int32_t walk_length, double restart_prob,
                                   int32_t num_walks, int32_t num_neighbors, uint64_t seed, uint64_t step, float* out,
                                   void* ws, size_t ws_bytes, mi_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
+ * N5  PinSAGE item feature projector (ABI 14).
+ * replaces: LinearProjector (pinsage/layers.py:14-46, 90-118): every node feature column is projected to `hidden` and
+ *           the results are summed — an embedding table per integer column, a Linear over the float columns, the item
+ *           id being one more integer column.  With it an item that has no interactions still gets a representation.
+ * Forward, for output row r (item i = ids ? ids[r] : r), ONE f32 addition chain in this order:
+ *     id_table[i]  (if id_table)  +  tables[0][x[i, 0]]  + ... +  tables[n_cols - 1][x[i, n_cols - 1]]
+ *     +  (dense[i, :] @ w^T + b)   (if n_dense > 0; the product is the k-ascending fma chain of mi_gemm_f32)
+ * The codes x[i, c] index tables[c] UNCHECKED: the caller guarantees 0 <= x[i, c] < table_rows[c] (and ids < n_items).
+ * Backward, given g = dL/d out [n, hidden]: every table row (id table included) that some r < n looks up is WRITTEN with
+ * the sum of those g[r] (rows nobody looks up are not touched: the caller keeps the buffers zero, as the executor does
+ * for g_proj); g_w = sum_r g[r]^T dense[i_r], g_b = sum_r g[r] are written whole.  The (column, code) references are
+ * radix-sorted (stable: ascending r within a code), summed in 64-reference chunks with several row loads in flight and
+ * the chunk partials of a run are combined in chunk order; g_b is a fixed-order column sum; g_w a trans_a product with
+ * the launcher's split-K rule.  No float atomics: both calls give the same bits on every run.
+ * hidden % 4 == 0, 4 <= hidden <= 128, n_cols <= 16 (MI_ERR_UNSUPPORTED otherwise); at least one of id_table, n_cols,
+ * n_dense; tables, out, g and the gradient buffers 16-byte aligned with ldo / ldg % 4 == 0.  Everything is validated before
+ * anything is enqueued.
+ * ---------------------------------------------------------------------------------- */
+#define MI_PROJECTOR_MAX_COLS 16
+typedef struct mi_item_projector {
+    int32_t hidden, n_cols;
+    int64_t n_items;
+    const int64_t* x;                               /* [n_items, n_cols] codes */
+    const float*   tables[MI_PROJECTOR_MAX_COLS];   /* tables[c]: [table_rows[c], hidden] */
+    int64_t        table_rows[MI_PROJECTOR_MAX_COLS];
+    const float*   id_table;                        /* nullable; [>= n_items, hidden] */
+    int64_t        n_dense;
+    const float*   dense; int64_t ld_dense;         /* [n_items, n_dense], leading dimension in floats */
+    const float*   w;                               /* [hidden, n_dense] */
+    const float*   b;                               /* [hidden] */
+} mi_item_projector;
+typedef struct mi_item_projector_grads {           /* each with the shape of its parameter */
+    float* g_tables[MI_PROJECTOR_MAX_COLS];
+    float* g_id_table;
+    float* g_w;
+    float* g_b;
+} mi_item_projector_grads;
+int64_t mi_pinsage_project_sizeof(int32_t which);   /* sizeof of: 0 projector, 1 grads (binding self-check); else -1 */
+size_t mi_pinsage_project_workspace_bytes(const mi_item_projector* p, int64_t n);
+int    mi_pinsage_project_f32(const mi_item_projector* p, int64_t n, const int64_t* ids /* null = 0 .. n-1 */, float* out,
+                              int64_t ldo, void* ws, size_t ws_bytes, mi_stream_t stream);
+size_t mi_pinsage_project_bwd_workspace_bytes(const mi_item_projector* p, int64_t n);
+int    mi_pinsage_project_bwd_f32(const mi_item_projector* p, const mi_item_projector_grads* grads, int64_t n,
+                                  const int64_t* ids, const float* g, int64_t ldg, void* ws, size_t ws_bytes,
+                                  mi_stream_t stream);
+/* Zeroes again the table rows (id table included) that mi_pinsage_project_bwd_f32 wrote for the same (n, ids): how a caller
+ * keeps the dense table gradients all-zero between iterations without clearing whole tables.  g_w / g_b are not touched. */
+int    mi_pinsage_project_clear_f32(const mi_item_projector* p, const mi_item_projector_grads* grads, int64_t n,
+                                    const int64_t* ids, mi_stream_t stream);
+/* torch.optim.Adam's dense update (the arithmetic of mi_adam_dense_f32, bit for bit) over a list of parameter tensors of any
+ * sizes — a featured model's tables, Linear, layers and scorer bias after the gradients above: tensors of 64 Ki elements or
+ * more that are float4-addressable take mi_adam_dense_f32's kernel, the others share one multi-tensor launch per
+ * MI_RANKER_MAX_PARAMS of them.  `step` counts from 1.  Every pointer is checked before anything is enqueued. */
+int    mi_adam_multi_f32(const mi_ranker_param* params, int32_t n_params, double lr, double beta1, double beta2, double eps,
+                         int64_t step, mi_stream_t stream);
 
 #ifdef __cplusplus
 }

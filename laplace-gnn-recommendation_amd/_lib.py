@@ -10,7 +10,7 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 # the package directory is never overwritten by an experiment.  It is still this library or nothing — no fallback.
 LIB_PATH = os.environ.get("LAPLACE_HIP_LIB") or os.path.join(PKG_DIR, "liblaplace_hip.so")
 
-MI_ABI_VERSION = 13
+MI_ABI_VERSION = 14
 MI_SPMM_GROUP = 32
 
 
@@ -52,6 +52,8 @@ class SpmmExStruct(Structure):
 
 MI_SPMM_SHORT_ROWS, MI_SPMM_SPLIT_ROWS = 1, 2
 MI_ERR_UNSUPPORTED = -4
+MI_ERR_BAD_ARG = -1
+MI_ERR_TOO_LARGE = -2
 MI_ERR_WORKSPACE = -3
 MI_TOPK_ITEMS_PREPARED = 1
 MI_TOPK_PATH_MATERIALISED, MI_TOPK_PATH_ONE_PASS, MI_TOPK_PATH_FUSED, MI_TOPK_PATH_FUSED_DMA, MI_TOPK_PATH_PREFILTER = range(5)
@@ -176,6 +178,20 @@ class PinsageGradList(Structure):
     _fields_ = [("n_rows", c_int64), ("n_seeds", c_int64), ("ids", c_void_p), ("rows", c_void_p), ("bias", c_void_p)]
 
 
+MI_PROJECTOR_MAX_COLS = 16
+
+
+class ItemProjector(Structure):
+    _fields_ = [("hidden", c_int32), ("n_cols", c_int32), ("n_items", c_int64), ("x", c_void_p),
+                ("tables", c_void_p * MI_PROJECTOR_MAX_COLS), ("table_rows", c_int64 * MI_PROJECTOR_MAX_COLS),
+                ("id_table", c_void_p), ("n_dense", c_int64), ("dense", c_void_p), ("ld_dense", c_int64),
+                ("w", c_void_p), ("b", c_void_p)]
+
+
+class ItemProjectorGrads(Structure):
+    _fields_ = [("g_tables", c_void_p * MI_PROJECTOR_MAX_COLS), ("g_id_table", c_void_p), ("g_w", c_void_p), ("g_b", c_void_p)]
+
+
 P = c_void_p
 _PROTOTYPES = {
     # name: (restype, [argtypes])
@@ -279,6 +295,14 @@ _PROTOTYPES = {
     "mi_pinsage_embed_items_workspace_bytes": (c_size_t, [c_int64, c_int32, c_int32]),
     "mi_pinsage_embed_items_f32": (c_int32, [POINTER(PinsageModel), P, P, P, P, c_int32, c_double, c_int32, c_int32, c_uint64,
                                              c_uint64, P, P, c_size_t, P]),
+    "mi_pinsage_project_sizeof": (c_int64, [c_int32]),
+    "mi_pinsage_project_workspace_bytes": (c_size_t, [POINTER(ItemProjector), c_int64]),
+    "mi_pinsage_project_f32": (c_int32, [POINTER(ItemProjector), c_int64, P, P, c_int64, P, c_size_t, P]),
+    "mi_pinsage_project_bwd_workspace_bytes": (c_size_t, [POINTER(ItemProjector), c_int64]),
+    "mi_pinsage_project_bwd_f32": (c_int32, [POINTER(ItemProjector), POINTER(ItemProjectorGrads), c_int64, P, P, c_int64, P,
+                                             c_size_t, P]),
+    "mi_pinsage_project_clear_f32": (c_int32, [POINTER(ItemProjector), POINTER(ItemProjectorGrads), c_int64, P, P]),
+    "mi_adam_multi_f32": (c_int32, [POINTER(RankerParam), c_int32, c_double, c_double, c_double, c_double, c_int64, P]),
     "mi_adam_dense_f32": (c_int32, [c_int64, c_int64, P, c_int64, P, c_int64, P, P, P,
                                     c_double, c_double, c_double, c_double, c_int64, P]),
 }

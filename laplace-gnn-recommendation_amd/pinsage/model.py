@@ -2,6 +2,10 @@
 pinsage/model.py:16-34 (PinSAGEModel.get_repr, hinge loss), with the trainable item-id feature the
 reference assigns (pinsage/model.py:52-53) as the projector input.
 
+With ItemFeatures the projector is the reference's LinearProjector over every feature column (pinsage/layers.py:14-46, 90-118:
+an embedding table per integer column, a Linear over the float columns, the id as one more column, summed) on
+mi_pinsage_project_f32 / mi_pinsage_project_bwd_f32 (csrc/pinsage_proj.hip): ItemFeatures, ItemProjector.
+
 Heavy ops on the HIP kernels: the Q / W products on mi_gemm_f32 (relu fused), the weighted
 neighbourhood sum on mi_spmm_csr_f32 over the block's destination-sorted CSR with values
 w_e / max(sum_e w_e, 1), the id-embedding lookup on mi_gather_rows_f32.  The row L2-normalisation,
@@ -9,13 +13,14 @@ the per-pair dot products and the hinge are torch ops on [batch]-sized tensors.
 """
 from __future__ import annotations
 
-from typing import List, Optional, Tuple
+import ctypes
+from typing import List, Optional, Sequence, Tuple
 
 import torch as t
 import torch.nn.functional as F
 from torch import Tensor, nn
 
-from .. import ops
+from .. import _lib, ops
 from ..model.layers import Linear
 
 
@@ -36,6 +41,195 @@ class _EmbedRowsFn(t.autograd.Function):
         gw = t.zeros(ctx.shape, device=g.device)
         gw.index_add_(0, ids, g.contiguous())
         return gw, None
+
+
+class ItemFeatures:
+    """The feature columns of every item — what the reference's LinearProjector projects beside the id (pinsage/layers.py:14-46,
+    90-118): `categorical` int64 [n_items, C] (0 <= C <= 16) codes, `dense` float32 [n_items, F]; at least one of them.
+    cardinalities[c] defaults to categorical[:, c].max() + 1 (one host read).  The kernels index the tables with these codes
+    unchecked, so they are checked once here: ValueError for a wrong dtype or rank, disagreeing item counts, a negative code
+    or a code >= its cardinality."""
+
+    def __init__(self, categorical: Optional[Tensor] = None, dense: Optional[Tensor] = None,
+                 cardinalities: Optional[Sequence[int]] = None):
+        if categorical is None and dense is None:
+            raise ValueError("ItemFeatures: give categorical, dense or both")
+        if categorical is not None and (not isinstance(categorical, Tensor) or categorical.dtype != t.int64 or categorical.dim() != 2):
+            raise ValueError("ItemFeatures: categorical must be an int64 [n_items, C] tensor")
+        if dense is not None and (not isinstance(dense, Tensor) or dense.dtype != t.float32 or dense.dim() != 2):
+            raise ValueError("ItemFeatures: dense must be a float32 [n_items, F] tensor")
+        if categorical is not None and dense is not None and categorical.shape[0] != dense.shape[0]:
+            raise ValueError(f"ItemFeatures: categorical has {categorical.shape[0]} items, dense {dense.shape[0]}")
+        if categorical is not None and dense is not None and categorical.device != dense.device:
+            raise ValueError("ItemFeatures: categorical and dense live on different devices")
+        n_cols = 0 if categorical is None else int(categorical.shape[1])
+        if n_cols > _lib.MI_PROJECTOR_MAX_COLS:
+            raise ValueError(f"ItemFeatures: at most {_lib.MI_PROJECTOR_MAX_COLS} categorical columns")
+        self.n_items = int((categorical if categorical is not None else dense).shape[0])
+        if self.n_items < 1:
+            raise ValueError("ItemFeatures: no items")
+        self.categorical = categorical.contiguous() if n_cols else None
+        self.dense = dense.contiguous() if dense is not None and dense.shape[1] > 0 else None
+        if self.categorical is None and self.dense is None:
+            raise ValueError("ItemFeatures: no feature column (C = 0 and F = 0)")
+        cards: List[int] = []
+        if n_cols:
+            lo, hi = self.categorical.min(0).values.cpu().tolist(), self.categorical.max(0).values.cpu().tolist()   # the one host read
+            if min(lo) < 0:
+                raise ValueError(f"ItemFeatures: negative code in column {lo.index(min(lo))}")
+            cards = [int(h) + 1 for h in hi] if cardinalities is None else [int(c) for c in cardinalities]
+            if len(cards) != n_cols:
+                raise ValueError(f"ItemFeatures: {len(cards)} cardinalities for {n_cols} columns")
+            for c, (h, card) in enumerate(zip(hi, cards)):
+                if h >= card:
+                    raise ValueError(f"ItemFeatures: code {h} in column {c} >= its cardinality {card}")
+        elif cardinalities is not None and len(cardinalities):
+            raise ValueError("ItemFeatures: cardinalities without categorical columns")
+        self.cardinalities: Tuple[int, ...] = tuple(cards)
+
+    @property
+    def n_cols(self) -> int:
+        return len(self.cardinalities)
+
+    @property
+    def n_dense(self) -> int:
+        return 0 if self.dense is None else int(self.dense.shape[1])
+
+
+class _ProjectFn(t.autograd.Function):
+    """ItemProjector.forward on mi_pinsage_project_f32; the backward on mi_pinsage_project_bwd_f32 into fresh zero buffers of
+    the parameters' shapes (dense table gradients, as _EmbedRowsFn's)."""
+
+    @staticmethod
+    def forward(ctx, projector: "ItemProjector", ids: Optional[Tensor], *params: Tensor):
+        ctx.projector, ctx.ids = projector, ids
+        ctx.shapes = [p.shape for p in params]
+        return projector.project(ids)
+
+    @staticmethod
+    def backward(ctx, g: Tensor):
+        projector = ctx.projector
+        grads = [t.zeros(s, dtype=t.float32, device=g.device) for s in ctx.shapes]
+        projector.project_backward(ctx.ids, g.contiguous(), grads)
+        return (None, None, *grads)
+
+
+class ItemProjector(nn.Module):
+    """projector(ids) = id row (if the model has an id table) + one table row per categorical column, in column order,
+    + dense[ids] @ W^T + b: one f32 addition chain in that order (mi_pinsage_project_f32).  Tables are [cardinality + 1,
+    hidden] (the reference's max + 2 rows; the last row is never looked up), xavier-uniform; Linear(F, hidden) with
+    xavier-uniform weight and zero bias.  The id table stays PinSAGEModel.proj (the same state_dict key as without features)."""
+
+    def __init__(self, features: ItemFeatures, hidden_dims: int, id_embedding: Optional[nn.Embedding]):
+        super().__init__()
+        self.hidden, self.n_items = int(hidden_dims), features.n_items
+        self.cardinalities = features.cardinalities
+        self.tables = nn.ParameterList([nn.Parameter(t.empty(card + 1, hidden_dims)) for card in features.cardinalities])
+        for tab in self.tables:
+            nn.init.xavier_uniform_(tab)
+        if features.n_dense:
+            self.weight = nn.Parameter(t.empty(hidden_dims, features.n_dense))
+            self.bias = nn.Parameter(t.zeros(hidden_dims))
+            nn.init.xavier_uniform_(self.weight)
+        else:
+            self.weight = self.bias = None
+        # buffers follow .to(device); not part of the state_dict (data, not weights)
+        self.register_buffer("x", features.categorical, persistent=False)
+        self.register_buffer("dense", features.dense, persistent=False)
+        self._id = [id_embedding] if id_embedding is not None else []    # a list: PinSAGEModel.proj stays its only registration
+        self._ws: Optional[Tensor] = None
+
+    @property
+    def id_weight(self) -> Optional[Tensor]:
+        return self._id[0].weight if self._id else None
+
+    def parameter_list(self) -> List[Tensor]:
+        """[id table?] + tables + [W, b]?: the order of forward's chain, of _ProjectFn's gradients and of descriptor()."""
+        out = [self.id_weight] if self._id else []
+        out += list(self.tables)
+        if self.weight is not None:
+            out += [self.weight, self.bias]
+        return out
+
+    def descriptor(self) -> "_lib.ItemProjector":
+        d = _lib.ItemProjector()
+        params = self.parameter_list()
+        if any(p.dtype != t.float32 or not p.is_cuda or not p.is_contiguous() for p in params):
+            raise _lib.MiError("ItemProjector: parameters must be contiguous float32 CUDA tensors (there is no CPU fallback)")
+        if any(b is not None and (not b.is_cuda or b.device != params[0].device) for b in (self.x, self.dense)):
+            raise _lib.MiError("ItemProjector: the feature tensors must live on the parameters' device")
+        d.hidden, d.n_cols, d.n_items = self.hidden, len(self.tables), self.n_items
+        d.x = self.x.data_ptr() if self.x is not None else None
+        for c, tab in enumerate(self.tables):
+            d.tables[c], d.table_rows[c] = tab.data_ptr(), int(tab.shape[0])
+        d.id_table = self.id_weight.data_ptr() if self._id else None
+        if self.weight is not None:
+            d.n_dense, d.dense, d.ld_dense = int(self.dense.shape[1]), self.dense.data_ptr(), int(self.dense.stride(0))
+            d.w, d.b = self.weight.data_ptr(), self.bias.data_ptr()
+        return d
+
+    def grads_descriptor(self, grads: Sequence[Tensor]) -> "_lib.ItemProjectorGrads":
+        """grads: one buffer per parameter_list() entry, each with its parameter's shape."""
+        gd = _lib.ItemProjectorGrads()
+        grads = list(grads)
+        if any(g.shape != p.shape or g.dtype != t.float32 or not g.is_contiguous() for g, p in zip(grads, self.parameter_list())):
+            raise ValueError("ItemProjector: gradient buffers must be contiguous float32 of their parameters' shapes")
+        if self._id:
+            gd.g_id_table = grads.pop(0).data_ptr()
+        for c in range(len(self.tables)):
+            gd.g_tables[c] = grads.pop(0).data_ptr()
+        if self.weight is not None:
+            gd.g_w, gd.g_b = grads[0].data_ptr(), grads[1].data_ptr()
+        return gd
+
+    def _workspace(self, nbytes: int, device) -> Tensor:
+        if self._ws is None or self._ws.numel() < nbytes or self._ws.device != device:
+            self._ws = t.empty(int(nbytes * 1.25) + 4096, dtype=t.uint8, device=device)
+        return self._ws
+
+    @staticmethod
+    def _ids(ids: Optional[Tensor]) -> Optional[Tensor]:
+        if ids is None:
+            return None
+        if ids.dtype != t.int64 or ids.dim() != 1 or not ids.is_cuda:
+            raise _lib.MiError("ItemProjector: ids must be a 1-d int64 CUDA tensor")
+        return ids.contiguous()
+
+    def project(self, ids: Optional[Tensor], out: Optional[Tensor] = None, n: Optional[int] = None) -> Tensor:
+        """The forward with no autograd: rows of `ids` (None: items 0 .. n - 1, n = n_items by default) into out [n, hidden]."""
+        ids = self._ids(ids)
+        n = (self.n_items if n is None else int(n)) if ids is None else int(ids.numel())
+        d, L = self.descriptor(), _lib.lib()
+        dev = self.parameter_list()[0].device
+        if out is None:
+            out = t.empty(n, self.hidden, dtype=t.float32, device=dev)
+        ws = self._workspace(int(L.mi_pinsage_project_workspace_bytes(ctypes.byref(d), n)), dev)
+        _lib.check(L.mi_pinsage_project_f32(ctypes.byref(d), n, ids.data_ptr() if ids is not None else None, out.data_ptr(),
+                                            int(out.stride(0)) if n else self.hidden, ws.data_ptr(), ws.numel(),
+                                            _lib.current_stream()), "mi_pinsage_project_f32")
+        return out
+
+    def project_backward(self, ids: Optional[Tensor], g: Tensor, grads: Sequence[Tensor]) -> None:
+        """g = dL/d project(ids) [n, hidden] into `grads` (parameter_list() order): looked-up table rows are written, others left."""
+        ids = self._ids(ids)
+        n = self.n_items if ids is None else int(ids.numel())
+        d, gd, L = self.descriptor(), self.grads_descriptor(grads), _lib.lib()
+        ws = self._workspace(int(L.mi_pinsage_project_bwd_workspace_bytes(ctypes.byref(d), n)), g.device)
+        _lib.check(L.mi_pinsage_project_bwd_f32(ctypes.byref(d), ctypes.byref(gd), n, ids.data_ptr() if ids is not None else None,
+                                                g.data_ptr(), int(g.stride(0)) if n else self.hidden, ws.data_ptr(), ws.numel(),
+                                                _lib.current_stream()), "mi_pinsage_project_bwd_f32")
+
+    def clear_rows(self, ids: Optional[Tensor], grads: Sequence[Tensor]) -> None:
+        """The table rows project_backward(ids, ...) wrote, back to zero (mi_pinsage_project_clear_f32)."""
+        ids = self._ids(ids)
+        n = self.n_items if ids is None else int(ids.numel())
+        d, gd = self.descriptor(), self.grads_descriptor(grads)
+        _lib.check(_lib.lib().mi_pinsage_project_clear_f32(ctypes.byref(d), ctypes.byref(gd), n,
+                                                           ids.data_ptr() if ids is not None else None, _lib.current_stream()),
+                   "mi_pinsage_project_clear_f32")
+
+    def forward(self, ids: Optional[Tensor] = None) -> Tensor:
+        return _ProjectFn.apply(self, ids, *self.parameter_list())
 
 
 class _WeightedSumFn(t.autograd.Function):
@@ -97,17 +291,39 @@ class WeightedSAGEConv(nn.Module):
 
 
 class PinSAGEModel(nn.Module):
-    def __init__(self, n_items: int, hidden_dims: int, n_layers: int):
+    def __init__(self, n_items: int, hidden_dims: int, n_layers: int, features: Optional[ItemFeatures] = None,
+                 use_id: bool = True):
+        """features=None, use_id=True: the id-only model (the id is the one feature the reference's dataset assigns).  With
+        `features` the LinearProjector sums the id row (if use_id) with every feature column's projection (ItemProjector):
+        an item without interactions, whose id row is never trained, is then placed by its features."""
         super().__init__()
-        self.proj = nn.Embedding(n_items + 1, hidden_dims)     # LinearProjector over the `id` feature
-        nn.init.xavier_uniform_(self.proj.weight)
+        if features is None and not use_id:
+            raise ValueError("PinSAGEModel: use_id=False needs features (nothing would be projected)")
+        if features is not None and features.n_items != n_items:
+            raise ValueError(f"PinSAGEModel: features describe {features.n_items} items, the model {n_items}")
+        self.n_items, self.hidden = int(n_items), int(hidden_dims)
+        if use_id:
+            self.proj = nn.Embedding(n_items + 1, hidden_dims)     # LinearProjector over the `id` feature
+            nn.init.xavier_uniform_(self.proj.weight)
         self.convs = nn.ModuleList([WeightedSAGEConv(hidden_dims, hidden_dims, hidden_dims) for _ in range(n_layers)])
         self.bias = nn.Parameter(t.zeros(n_items, 1))          # ItemToItemScorer
+        if features is not None:
+            self.projector = ItemProjector(features, hidden_dims, self.proj if use_id else None)
+
+    @property
+    def featured(self) -> bool:
+        return hasattr(self, "projector")
+
+    def project(self, ids: Tensor) -> Tensor:
+        """LinearProjector over the rows `ids`: the id table alone, or the feature projector."""
+        if self.featured:
+            return self.projector(ids)
+        return _EmbedRowsFn.apply(self.proj.weight, ids)
 
     def get_repr(self, blocks: List[dict]) -> Tensor:
-        h = _EmbedRowsFn.apply(self.proj.weight, blocks[0]["src_ids"])
+        h = self.project(blocks[0]["src_ids"])
         last = blocks[-1]
-        h_dst_final = _EmbedRowsFn.apply(self.proj.weight, last["src_ids"][: last["n_dst"]])
+        h_dst_final = self.project(last["src_ids"][: last["n_dst"]])
         for conv, block in zip(self.convs, blocks):
             h = conv(block, h, h[: block["n_dst"]])
         return h_dst_final + h
@@ -137,8 +353,7 @@ class PinSAGEModel(nn.Module):
     def batched_item_representations(self, sampler, step: int, batch_size: Optional[int] = None) -> Tensor:
         """get_repr over sample_blocks(batch, step) for consecutive batches of item ids (pinsage/sampler.py:181-185), as the
         reference evaluates; the caller sets eval mode and no_grad (item_representations does)."""
-        n_items = self.proj.weight.shape[0] - 1
-        ids = t.arange(n_items, device=self.proj.weight.device)
+        ids = t.arange(self.n_items, device=self.bias.device)
         return t.cat([self.get_repr(sampler.sample_blocks(b, step))
                       for b in ids.split(int(batch_size or sampler.batch_size))], 0)
 
@@ -172,6 +387,8 @@ def train_epoch(model: PinSAGEModel, optimizer: t.optim.Optimizer, sampler, batc
     if NativePinSAGEStep.supports(model, optimizer):
         if not multi:
             native = NativePinSAGEStep(model, optimizer)
+        elif model.featured:
+            native = None    # data-parallel native features are not built: the autograd iteration with its dense all-reduce, on every rank
         elif all(hasattr(sampler, a) for a in ("batch_size", "T", "n_layers")):
             native = NativePinSAGEStep(model, optimizer, data_parallel=True, group=group,
                                        seed=(t.initial_seed() + dist.get_rank(group)) & ((1 << 63) - 1))

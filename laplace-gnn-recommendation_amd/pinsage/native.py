@@ -8,6 +8,13 @@ tables and clears the rows again, so after a step those two `.grad`s read zero (
 and leaves them in place instead).  Batches must come from PinSAGESampler (its block layout: destination nodes first; the
 index-op path's blocks get their CSRs built here); a model / optimizer / batch outside the executor's shapes is declined
 and the caller takes the autograd path (pinsage.model.train_epoch does that by itself).
+
+A model with item features (PinSAGEModel(features=...)) runs the same executor between the projector's two calls: the rows of
+blocks[0].src_ids — distinct, and holding every block's destination nodes — are projected into a compact table
+(mi_pinsage_project_f32), the executor runs on it with apply_adam = 0 and hands the gradient of those rows back compactly
+(rows_out / bias_out), mi_pinsage_project_bwd_f32 turns it into the tables', the id table's and the Linear's gradients, and
+mi_adam_multi_f32 applies torch.optim.Adam's dense update to every tensor; the table rows written are cleared again
+(mi_pinsage_project_clear_f32), so the table gradients stay all-zero between iterations as the id table's does.
 """
 from __future__ import annotations
 
@@ -31,6 +38,9 @@ class NativePinSAGEStep:
         all-reduce of the dense 27 MB table gradient), all-reduce the dense layers' gradients (one flat buffer), and
         mi_pinsage_apply_f32 adds every rank's rows in rank order, applies Adam on the mean gradient and clears the rows:
         replicas stay bitwise identical.  Batches must keep the sampler's size bounds (they size the exchange buffer)."""
+        if data_parallel and getattr(model, "featured", False):
+            raise ValueError("NativePinSAGEStep: data_parallel with item features is not built (the compact row exchange carries "
+                             "id-table rows only); use the autograd iteration with its dense all-reduce")
         why = self.unsupported_reason(model, optimizer)
         if why:
             raise ValueError(f"NativePinSAGEStep: {why}")
@@ -48,6 +58,8 @@ class NativePinSAGEStep:
         self._ws: Optional[Tensor] = None
         self._adam_step = 0
         self.declined: Optional[str] = None
+        self._rows: Optional[Tensor] = None            # featured: projected rows / their gradient / bias_out, grown on demand
+        self._arange: Optional[Tensor] = None
 
     # ------------------------------------------------------------------------------------------
     @staticmethod
@@ -62,11 +74,13 @@ class NativePinSAGEStep:
         params = list(model.parameters())
         if len(g["params"]) != len(params) or any(a is not b for a, b in zip(g["params"], params)):
             return "the optimizer's parameter list is not model.parameters()"
-        hidden = model.proj.weight.shape[1]
+        hidden = model.hidden
         if hidden % 4 or hidden > 128 or not (1 <= len(model.convs) <= _lib.MI_PINSAGE_MAX_LAYERS):
             return "hidden size / layer count outside the executor's"
-        if len(params) - 1 > _lib.MI_PINSAGE_MAX_PARAMS:
+        if (4 * len(model.convs) if model.featured else len(params) - 1) > _lib.MI_PINSAGE_MAX_PARAMS:
             return "too many parameter tensors"
+        if model.featured and model.projector.n_items != model.n_items:
+            return "features and model disagree on the item count"
         for cv in model.convs:
             if tuple(cv.Q.weight.shape) != (hidden, hidden) or tuple(cv.W.weight.shape) != (hidden, 2 * hidden):
                 return "layer widths differ from the hidden size"
@@ -112,7 +126,10 @@ class NativePinSAGEStep:
                 st["exp_avg"] = t.zeros_like(p, memory_format=t.preserve_format)
                 st["exp_avg_sq"] = t.zeros_like(p, memory_format=t.preserve_format)
             keep += [p.grad, st["exp_avg"], st["exp_avg_sq"]]
-        proj, bias = model.proj.weight, model.bias
+        bias = model.bias
+        if model.featured:
+            return self._build_featured(d)
+        proj = model.proj.weight
         proj.grad.zero_()      # the two dense buffers the executor keeps all-zero between iterations
         bias.grad.zero_()
         d.n_layers, d.hidden, d.n_items = len(model.convs), int(proj.shape[1]), int(bias.shape[0])
@@ -138,9 +155,64 @@ class NativePinSAGEStep:
         self._adam_step = int(steps[0]) if steps else 0
         return d
 
+    def _build_featured(self, d: PinsageModel) -> PinsageModel:
+        """The executor's descriptor over a COMPACT projected table (set per batch, _prepare): its params are the layers' only,
+        it never applies Adam and never touches g_proj / m_proj / v_proj (rows_out mode).  Also the flat parameter list of
+        mi_adam_multi_f32: every tensor of the optimizer's group."""
+        model, opt = self.model, self.optimizer
+        group = opt.param_groups[0]
+        pr = model.projector
+        for p in pr.parameter_list()[: len(pr.parameter_list()) - (2 if pr.weight is not None else 0)]:
+            p.grad.zero_()     # the table gradients (id table included) stay all-zero between iterations
+        model.bias.grad.zero_()
+        d.n_layers, d.hidden, d.n_items = len(model.convs), model.hidden, model.n_items
+        d.bias, d.g_bias = model.bias.data_ptr(), model.bias.grad.data_ptr()
+        i = 0
+        for l, cv in enumerate(model.convs):
+            c = d.conv[l]
+            c.q_w, c.q_b, c.w_w, c.w_b = (x.data_ptr() for x in (cv.Q.weight, cv.Q.bias, cv.W.weight, cv.W.bias))
+            c.g_q_w, c.g_q_b, c.g_w_w, c.g_w_b = (x.grad.data_ptr() for x in (cv.Q.weight, cv.Q.bias, cv.W.weight, cv.W.bias))
+            for p in (cv.Q.weight, cv.Q.bias, cv.W.weight, cv.W.bias):
+                st = opt.state[p]
+                q = d.params[i]
+                q.p, q.g, q.m, q.v, q.n = p.data_ptr(), p.grad.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), p.numel()
+                i += 1
+        d.n_params = i
+        flat = (_lib.RankerParam * len(group["params"]))()
+        for q, p in zip(flat, group["params"]):
+            st = opt.state[p]
+            q.p, q.g, q.m, q.v, q.n = p.data_ptr(), p.grad.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), p.numel()
+        self._flat_params = flat
+        self._proj_grads = [p.grad for p in pr.parameter_list()]
+        self._pdesc, self._pgrads = pr.descriptor(), pr.grads_descriptor(self._proj_grads)
+        self._pws_rows = -1
+        steps = [opt.state[p]["step"] for p in group["params"]]
+        self._adam_step = int(steps[0]) if steps else 0
+        return d
+
+    def _proj_workspace(self, n: int, device) -> Tensor:
+        if n > getattr(self, "_pws_rows", -1):
+            L, pd = _lib.lib(), ctypes.byref(self._pdesc)
+            rows = max(1024, int(n * 1.25))
+            need = max(int(L.mi_pinsage_project_workspace_bytes(pd, rows)), int(L.mi_pinsage_project_bwd_workspace_bytes(pd, rows)))
+            self._pws, self._pws_rows = t.empty(need, dtype=t.uint8, device=device), rows
+        return self._pws
+
     def _current(self, d: PinsageModel) -> bool:
         """The descriptor holds raw pointers: rebuilt when a parameter, gradient or optimizer-state tensor was replaced."""
         group = self.optimizer.param_groups[0]
+        if self.model.featured:
+            flat = getattr(self, "_flat_params", None)
+            if flat is None or len(flat) != len(group["params"]):
+                return False
+            for q, p in zip(flat, group["params"]):
+                st = self.optimizer.state.get(p)
+                if p.grad is None or not st or (q.p, q.g, q.m, q.v) != (p.data_ptr(), p.grad.data_ptr(), st["exp_avg"].data_ptr(),
+                                                                        st["exp_avg_sq"].data_ptr()):
+                    return False
+            pr = self.model.projector
+            return (self._pdesc.x, self._pdesc.dense) == (pr.x.data_ptr() if pr.x is not None else None,
+                                                          pr.dense.data_ptr() if pr.dense is not None else None)
         proj = self.model.proj.weight
         i = 0
         for p in group["params"]:
@@ -184,14 +256,14 @@ class NativePinSAGEStep:
             return None
         if self._desc is None or not self._current(self._desc):
             self._desc = self._build()
-        elif self.keep_grads:      # the previous call left its rows in the two dense buffers
-            model.proj.weight.grad.zero_()
-            model.bias.grad.zero_()
+        elif self.keep_grads:      # the previous call left its rows in the dense buffers
+            for p in ([model.bias] + model.projector.parameter_list()) if model.featured else (model.proj.weight, model.bias):
+                p.grad.zero_()
         d = self._desc
         group = self.optimizer.param_groups[0]
         d.p_dropout = float(model.convs[0].dropout.p)
         d.lr, (d.beta1, d.beta2), d.eps = float(group["lr"]), (float(b) for b in group["betas"]), float(group["eps"])
-        d.apply_adam = 0 if (self.keep_grads or self.data_parallel) else 1
+        d.apply_adam = 0 if (self.keep_grads or self.data_parallel or model.featured) else 1
         d.step = self._adam_step + 1
         b = PinsageStepBatch()
         b.n_blocks = len(blocks)
@@ -217,6 +289,17 @@ class NativePinSAGEStep:
             send = self._exchange_buffer(b, blocks[0]["src_ids"], seeds)
             if send is None:
                 return None
+        if model.featured:
+            # the executor reads row r of a compact table for block 0's r-th source: its ids are 0 .. n0 - 1
+            n0, H = int(blocks[0]["src_ids"].numel()), model.hidden
+            if self._rows is None or self._rows.shape[1] < n0:
+                cap = max(1024, int(n0 * 1.25))
+                self._rows = t.empty(3, cap, H, dtype=t.float32, device=seeds.device)   # projected rows, their gradient, bias_out
+                self._arange = t.arange(cap, dtype=t.int64, device=seeds.device)
+            rows = self._rows
+            b.blocks[0].src_ids = self._arange.data_ptr()
+            d.proj = d.g_proj = d.m_proj = d.v_proj = rows[0].data_ptr()      # g / m / v: never touched in rows_out mode
+            b.rows_out, b.bias_out = rows[1].data_ptr(), rows[2].data_ptr()
         L = _lib.lib()
         need = int(L.mi_pinsage_step_workspace_bytes(ctypes.byref(d), ctypes.byref(b)))
         if self._ws is None or self._ws.numel() < need:
@@ -254,6 +337,14 @@ class NativePinSAGEStep:
         d, b, loss, _keep = prep
         group = self.optimizer.param_groups[0]
         L = _lib.lib()
+        featured = self.model.featured
+        if featured:
+            # the cached descriptors (rebuilt with the executor's, _current): no per-call ctypes fill on this path
+            ids0 = batch["blocks"][0]["src_ids"]
+            n0, H = int(ids0.numel()), self.model.hidden
+            pd, pg, pws = ctypes.byref(self._pdesc), ctypes.byref(self._pgrads), self._proj_workspace(n0, ids0.device)
+            _lib.check(L.mi_pinsage_project_f32(pd, n0, ids0.data_ptr(), self._rows[0].data_ptr(), H, pws.data_ptr(), pws.numel(),
+                                                _lib.current_stream()), "mi_pinsage_project_f32")
         rc = L.mi_pinsage_step_f32(ctypes.byref(d), ctypes.byref(b), self._ws.data_ptr(), self._ws.numel(), _lib.current_stream())
         if rc == _lib.MI_ERR_UNSUPPORTED:
             if world > 1:                      # cannot happen: mi_pinsage_step_check took the same descriptors
@@ -265,6 +356,19 @@ class NativePinSAGEStep:
         self.iteration += 1
         if self.data_parallel:
             self._exchange_and_apply(d)
+        if featured:
+            seeds = batch["seeds"]
+            _lib.check(L.mi_pinsage_project_bwd_f32(pd, pg, n0, ids0.data_ptr(), self._rows[1].data_ptr(), H, pws.data_ptr(),
+                                                    pws.numel(), _lib.current_stream()), "mi_pinsage_project_bwd_f32")
+            gb = self.model.bias.grad.view(-1)
+            gb.index_copy_(0, seeds, self._rows[2].view(-1)[: seeds.numel()])     # the seeds are distinct
+            if not self.keep_grads:
+                _lib.check(L.mi_adam_multi_f32(self._flat_params, len(self._flat_params), float(group["lr"]),
+                                               float(group["betas"][0]), float(group["betas"][1]), float(group["eps"]),
+                                               self._adam_step + 1, _lib.current_stream()), "mi_adam_multi_f32")
+                _lib.check(L.mi_pinsage_project_clear_f32(pd, pg, n0, ids0.data_ptr(), _lib.current_stream()),
+                           "mi_pinsage_project_clear_f32")
+                gb.index_fill_(0, seeds, 0.0)
         if not self.keep_grads:
             self._adam_step += 1
             steps = [self.optimizer.state[q]["step"] for q in group["params"]]
@@ -347,19 +451,22 @@ def embed_items(model: PinSAGEModel, sampler, step: int) -> Optional[Tensor]:
     (nothing has been enqueued then); the caller takes the batched path.  Eval semantics (no dropout); no autograd."""
     if not isinstance(model, PinSAGEModel) or not all(hasattr(sampler, a) for a in ("iu_ptr", "ui_ptr", "L", "p", "W", "T")):
         return None
-    proj = model.proj.weight
-    hidden, n_items = int(proj.shape[1]), int(proj.shape[0]) - 1
-    params = [proj] + [x for cv in model.convs for x in (cv.Q.weight, cv.Q.bias, cv.W.weight, cv.W.bias)]
+    hidden, n_items = model.hidden, model.n_items
+    dev = model.bias.device
+    params = ([] if model.featured else [model.proj.weight]) + [x for cv in model.convs for x in (cv.Q.weight, cv.Q.bias, cv.W.weight, cv.W.bias)]
     if (hidden % 4 or hidden > 128 or not (1 <= len(model.convs) <= _lib.MI_PINSAGE_MAX_LAYERS) or sampler.T > 16
             or n_items != sampler.num_items or len(model.convs) != sampler.n_layers):
         return None
-    if any(x is None or x.dtype != t.float32 or not x.is_cuda or not x.is_contiguous() or x.device != proj.device for x in params):
+    if any(x is None or x.dtype != t.float32 or not x.is_cuda or not x.is_contiguous() or x.device != dev for x in params):
         return None
     for cv in model.convs:
         if tuple(cv.Q.weight.shape) != (hidden, hidden) or tuple(cv.W.weight.shape) != (hidden, 2 * hidden):
             return None
-    if sampler.iu_ptr.device != proj.device:
+    if sampler.iu_ptr.device != dev:
         return None
+    # featured: the whole catalogue projected by one forward call (after every check: a decline enqueues nothing); the kernel
+    # reads rows 0 .. n_items - 1 of `proj`
+    proj = model.projector.project(None) if model.featured else model.proj.weight
     d = PinsageModel()
     d.n_layers, d.hidden, d.n_items = len(model.convs), hidden, n_items
     d.proj = proj.data_ptr()
