@@ -1167,6 +1167,53 @@ int    mi_pinsage_project_clear_f32(const mi_item_projector* p, const mi_item_pr
 int    mi_adam_multi_f32(const mi_ranker_param* params, int32_t n_params, double lr, double beta1, double beta2, double eps,
                          int64_t step, mi_stream_t stream);
 
+/* ------------------------------------------------------------------------------------
+ * N5  PinSAGE item feature projector: bag-of-words text columns (additive to ABI 14).
+ * replaces: BagOfWords / BagOfWordsPretrained (pinsage/layers.py:39-44, 49-87, 110-113): the mean of one embedding row per
+ *           token of an item's text.  The third input kind of the LinearProjector, beside mi_item_projector's two.
+ * A text column is a CSR over items: ptr[c] int64 [n_items + 1], tok[c] int32 [ptr[c][n_items]] with 0 <= token < vocab[c]
+ * (UNCHECKED here; pad tokens are not stored), tables[c] float [vocab[c], width].
+ * Forward, for output row r (item i = ids ? ids[r] : r) and column c in column order, len = ptr[c][i + 1] - ptr[c][i]:
+ *     bag_c = (( E_c[tok[p0]] + E_c[tok[p0 + 1]] ) + ... ) / (float)len      one f32 chain in ascending position, then a
+ *     correctly rounded division; len == 0: bag_c = 0.
+ *     accumulate = 1:  out[r] = (out[r] + bag_0) + bag_1 ...   (continues mi_pinsage_project_f32's chain, text last)
+ *     accumulate = 0:  out[r] =  bag_0 + bag_1 ...
+ * Backward, given g = dL/d out [n, width]: g_tables[c][v] is WRITTEN with the sum over every reference (r, position) whose
+ * token is v of g[r] / (float)len(i_r) (the division per reference, before the sum); rows of tokens nobody references are
+ * not touched (the caller keeps the buffers zero).  The scheme of mi_pinsage_project_bwd_f32: a stable radix sort of the
+ * (column, token) keys with the reference's row as payload (references in (column, r, position) order), 64-reference
+ * chunks summed in order with several row loads in flight, the chunk partials of a run combined in chunk order by one
+ * writer.  No float atomics: two calls give the same bits.
+ * The number of references of a call (the sum of the selected items' lengths over the columns) is data-dependent: it is
+ * computed on the device and the host never waits for it.  The caller passes an upper bound n_ref_max, which sizes the
+ * workspace (MI_ERR_WORKSPACE, nothing enqueued, if ws_bytes is below mi_pinsage_text_bwd_workspace_bytes(p, n, n_ref_max)).
+ * After the call the first int64 of ws holds the actual count; a count above n_ref_max means the bound was not one: the
+ * references beyond it were dropped (nothing is written out of bounds).
+ * mi_pinsage_text_clear_f32 zeroes again the rows the backward wrote for the same (n, ids).
+ * width % 4 == 0, 4 <= width <= 512 (wider than a model's hidden: the one-time pooling of pretrained word vectors is this
+ * forward at width = their dimension), 1 <= n_text <= MI_PROJECTOR_MAX_TEXT (MI_ERR_UNSUPPORTED otherwise); tables, out, g
+ * and the gradient buffers 16-byte aligned, ptr 8-byte, tok 4-byte, ldo / ldg % 4 == 0.  Everything is validated before
+ * anything is enqueued.
+ * ---------------------------------------------------------------------------------- */
+#define MI_PROJECTOR_MAX_TEXT 4
+typedef struct mi_text_columns {
+    int32_t width, n_text;
+    int64_t n_items;
+    const int64_t* ptr[MI_PROJECTOR_MAX_TEXT];
+    const int32_t* tok[MI_PROJECTOR_MAX_TEXT];
+    const float*   tables[MI_PROJECTOR_MAX_TEXT];    /* tables[c]: [vocab[c], width] */
+    int64_t        vocab[MI_PROJECTOR_MAX_TEXT];
+} mi_text_columns;
+int64_t mi_pinsage_text_sizeof(int32_t which);       /* sizeof of: 0 mi_text_columns (binding self-check); else -1 */
+int    mi_pinsage_text_f32(const mi_text_columns* p, int64_t n, const int64_t* ids /* null = 0 .. n-1 */, float* out,
+                           int64_t ldo, int32_t accumulate, mi_stream_t stream);
+size_t mi_pinsage_text_bwd_workspace_bytes(const mi_text_columns* p, int64_t n, int64_t n_ref_max);
+int    mi_pinsage_text_bwd_f32(const mi_text_columns* p, float* const g_tables[], int64_t n, const int64_t* ids,
+                               const float* g, int64_t ldg, int64_t n_ref_max, void* ws, size_t ws_bytes,
+                               mi_stream_t stream);
+int    mi_pinsage_text_clear_f32(const mi_text_columns* p, float* const g_tables[], int64_t n, const int64_t* ids,
+                                 mi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

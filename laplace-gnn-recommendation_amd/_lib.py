@@ -192,6 +192,17 @@ class ItemProjectorGrads(Structure):
     _fields_ = [("g_tables", c_void_p * MI_PROJECTOR_MAX_COLS), ("g_id_table", c_void_p), ("g_w", c_void_p), ("g_b", c_void_p)]
 
 
+MI_PROJECTOR_MAX_TEXT = 4
+
+
+class TextColumns(Structure):
+    _fields_ = [("width", c_int32), ("n_text", c_int32), ("n_items", c_int64),
+                ("ptr", c_void_p * MI_PROJECTOR_MAX_TEXT), ("tok", c_void_p * MI_PROJECTOR_MAX_TEXT),
+                ("tables", c_void_p * MI_PROJECTOR_MAX_TEXT), ("vocab", c_int64 * MI_PROJECTOR_MAX_TEXT)]
+
+
+TextGradTables = c_void_p * MI_PROJECTOR_MAX_TEXT      # the g_tables argument: one buffer per text column
+
 P = c_void_p
 _PROTOTYPES = {
     # name: (restype, [argtypes])
@@ -303,6 +314,11 @@ _PROTOTYPES = {
                                              c_size_t, P]),
     "mi_pinsage_project_clear_f32": (c_int32, [POINTER(ItemProjector), POINTER(ItemProjectorGrads), c_int64, P, P]),
     "mi_adam_multi_f32": (c_int32, [POINTER(RankerParam), c_int32, c_double, c_double, c_double, c_double, c_int64, P]),
+    "mi_pinsage_text_sizeof": (c_int64, [c_int32]),
+    "mi_pinsage_text_f32": (c_int32, [POINTER(TextColumns), c_int64, P, P, c_int64, c_int32, P]),
+    "mi_pinsage_text_bwd_workspace_bytes": (c_size_t, [POINTER(TextColumns), c_int64, c_int64]),
+    "mi_pinsage_text_bwd_f32": (c_int32, [POINTER(TextColumns), POINTER(c_void_p), c_int64, P, P, c_int64, c_int64, P, c_size_t, P]),
+    "mi_pinsage_text_clear_f32": (c_int32, [POINTER(TextColumns), POINTER(c_void_p), c_int64, P, P]),
     "mi_adam_dense_f32": (c_int32, [c_int64, c_int64, P, c_int64, P, c_int64, P, P, P,
                                     c_double, c_double, c_double, c_double, c_int64, P]),
 }

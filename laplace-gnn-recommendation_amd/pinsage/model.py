@@ -43,15 +43,118 @@ class _EmbedRowsFn(t.autograd.Function):
         return gw, None
 
 
+class TextColumn:
+    """One text column of every item as a bag of words — the input of the reference's BagOfWords (pinsage/layers.py:49-87).
+    `tokens` int64 [n_items, L], padded on the right as torchtext pads; `lengths` int64 [n_items]: the first lengths[i]
+    entries of row i are item i's bag, whatever stands behind them (pad_id, if given, is only recorded) is never read.
+    Validated once here, because the kernels index the tables with the tokens unchecked, and converted to the CSR that
+    mi_pinsage_text_f32 reads: `ptr` int64 [n_items + 1], `tok` int32 [sum of lengths] (one unused entry when every bag is
+    empty, so that the pointer is never null).  ValueError for a wrong dtype or rank, a length outside [0, L], a token outside
+    [0, vocab_size) among the first lengths[i].  One host read."""
+
+    def __init__(self, tokens: Tensor, lengths: Tensor, vocab_size: int, pad_id: Optional[int] = None):
+        if not isinstance(tokens, Tensor) or tokens.dtype != t.int64 or tokens.dim() != 2:
+            raise ValueError("TextColumn: tokens must be an int64 [n_items, L] tensor")
+        if not isinstance(lengths, Tensor) or lengths.dtype != t.int64 or lengths.dim() != 1:
+            raise ValueError("TextColumn: lengths must be an int64 [n_items] tensor")
+        if lengths.shape[0] != tokens.shape[0]:
+            raise ValueError(f"TextColumn: tokens has {tokens.shape[0]} items, lengths {lengths.shape[0]}")
+        if tokens.device != lengths.device:
+            raise ValueError("TextColumn: tokens and lengths live on different devices")
+        if tokens.shape[0] < 1:
+            raise ValueError("TextColumn: no items")
+        self.vocab_size = int(vocab_size)
+        if self.vocab_size < 1 or self.vocab_size > 2 ** 31 - 1:
+            raise ValueError("TextColumn: vocab_size must lie in [1, 2^31)")
+        self.pad_id = None if pad_id is None else int(pad_id)
+        L = int(tokens.shape[1])
+        live = t.arange(L, device=tokens.device)[None, :] < lengths[:, None]
+        tok = tokens[live]                                           # row-major: item by item, ascending position
+        stats = t.stack([lengths.min(), lengths.max(), tok.min() if tok.numel() else lengths.new_zeros(()),
+                         tok.max() if tok.numel() else lengths.new_zeros(())]).cpu().tolist()      # the one host read
+        if stats[0] < 0 or stats[1] > L:
+            raise ValueError(f"TextColumn: a length outside [0, {L}]")
+        if stats[2] < 0 or stats[3] >= self.vocab_size:
+            raise ValueError(f"TextColumn: a token outside [0, {self.vocab_size}) within its bag")
+        self.n_items, self.max_len, self.nnz = int(tokens.shape[0]), int(stats[1]), int(tok.numel())
+        ptr = t.zeros(self.n_items + 1, dtype=t.int64, device=tokens.device)
+        t.cumsum(lengths, 0, out=ptr[1:])
+        self.ptr = ptr
+        self.tok = tok.to(t.int32).contiguous() if tok.numel() else t.zeros(1, dtype=t.int32, device=tokens.device)
+
+    @property
+    def device(self):
+        return self.ptr.device
+
+    def to(self, device) -> "TextColumn":
+        out = object.__new__(TextColumn)
+        out.__dict__.update(self.__dict__)
+        out.ptr, out.tok = self.ptr.to(device), self.tok.to(device)
+        return out
+
+    @classmethod
+    def from_strings(cls, texts: Sequence[str], min_freq: int = 1) -> Tuple["TextColumn", List[str]]:
+        """Lower-case, split on whitespace, build the vocabulary — what the reference's Field(lower=True) + build_vocab do
+        (pinsage/layers.py:39-44): itos = ["<unk>", "<pad>"] + the words seen at least min_freq times, most frequent first
+        (ties alphabetically); rarer words map to <unk>.  Returns (column on the CPU, itos)."""
+        from collections import Counter
+        docs = [str(s).lower().split() for s in texts]
+        if not docs:
+            raise ValueError("TextColumn.from_strings: no texts")
+        freq = Counter(w for d in docs for w in d)
+        itos = ["<unk>", "<pad>"] + [w for w, c in sorted(freq.items(), key=lambda kv: (-kv[1], kv[0])) if c >= int(min_freq)]
+        stoi = {w: i for i, w in enumerate(itos)}
+        L = max(1, max(len(d) for d in docs))
+        tokens = t.full((len(docs), L), 1, dtype=t.int64)
+        for i, d in enumerate(docs):
+            if d:
+                tokens[i, : len(d)] = t.tensor([stoi.get(w, 0) for w in d], dtype=t.int64)
+        return cls(tokens, t.tensor([len(d) for d in docs], dtype=t.int64), len(itos), pad_id=1), itos
+
+
+def _pool_text(column: "TextColumn", table: Tensor) -> Tensor:
+    """The mean of table's rows over every item's bag, [n_items, table.shape[1]]: mi_pinsage_text_f32 over the catalogue."""
+    if not table.is_cuda or table.dtype != t.float32 or not table.is_contiguous() or column.device != table.device:
+        raise _lib.MiError("text pooling: the table must be a contiguous float32 CUDA tensor on the column's device "
+                           "(there is no CPU fallback)")
+    d = _lib.TextColumns()
+    d.width, d.n_text, d.n_items = int(table.shape[1]), 1, column.n_items
+    d.ptr[0], d.tok[0], d.tables[0], d.vocab[0] = column.ptr.data_ptr(), column.tok.data_ptr(), table.data_ptr(), column.vocab_size
+    out = t.empty(column.n_items, int(table.shape[1]), dtype=t.float32, device=table.device)
+    _lib.check(_lib.lib().mi_pinsage_text_f32(ctypes.byref(d), column.n_items, None, out.data_ptr(), int(out.stride(0)), 0,
+                                              _lib.current_stream()), "mi_pinsage_text_f32")
+    return out
+
+
 class ItemFeatures:
     """The feature columns of every item — what the reference's LinearProjector projects beside the id (pinsage/layers.py:14-46,
-    90-118): `categorical` int64 [n_items, C] (0 <= C <= 16) codes, `dense` float32 [n_items, F]; at least one of them.
+    90-118): `categorical` int64 [n_items, C] (0 <= C <= 16) codes, `dense` float32 [n_items, F], `text` up to 4 TextColumns
+    (bags of words, keyword-only); at least one of them.
     cardinalities[c] defaults to categorical[:, c].max() + 1 (one host read).  The kernels index the tables with these codes
     unchecked, so they are checked once here: ValueError for a wrong dtype or rank, disagreeing item counts, a negative code
     or a code >= its cardinality."""
 
     def __init__(self, categorical: Optional[Tensor] = None, dense: Optional[Tensor] = None,
-                 cardinalities: Optional[Sequence[int]] = None):
+                 cardinalities: Optional[Sequence[int]] = None, *, text: Optional[Sequence[TextColumn]] = None):
+        text = tuple(text) if text is not None else ()
+        if any(not isinstance(c, TextColumn) for c in text):
+            raise ValueError("ItemFeatures: text must be a sequence of TextColumn")
+        if len(text) > _lib.MI_PROJECTOR_MAX_TEXT:
+            raise ValueError(f"ItemFeatures: at most {_lib.MI_PROJECTOR_MAX_TEXT} text columns")
+        self.text: Tuple[TextColumn, ...] = text
+        if text:
+            others = [x for x in (categorical, dense) if isinstance(x, Tensor)]
+            if any(c.n_items != text[0].n_items for c in text) or any(x.dim() == 2 and x.shape[0] != text[0].n_items for x in others):
+                raise ValueError("ItemFeatures: the text columns and the other features disagree on the number of items")
+            if any(c.device != text[0].device for c in text) or any(x.device != text[0].device for x in others):
+                raise ValueError("ItemFeatures: the text columns and the other features live on different devices")
+        if categorical is None and dense is None and text:
+            self.n_items = text[0].n_items
+            self.categorical = self.dense = None
+            if cardinalities is not None and len(cardinalities):
+                raise ValueError("ItemFeatures: cardinalities without categorical columns")
+            self.cardinalities: Tuple[int, ...] = ()
+            return
         if categorical is None and dense is None:
             raise ValueError("ItemFeatures: give categorical, dense or both")
         if categorical is not None and (not isinstance(categorical, Tensor) or categorical.dtype != t.int64 or categorical.dim() != 2):
@@ -70,7 +173,7 @@ class ItemFeatures:
             raise ValueError("ItemFeatures: no items")
         self.categorical = categorical.contiguous() if n_cols else None
         self.dense = dense.contiguous() if dense is not None and dense.shape[1] > 0 else None
-        if self.categorical is None and self.dense is None:
+        if self.categorical is None and self.dense is None and not text:
             raise ValueError("ItemFeatures: no feature column (C = 0 and F = 0)")
         cards: List[int] = []
         if n_cols:
@@ -95,6 +198,30 @@ class ItemFeatures:
     def n_dense(self) -> int:
         return 0 if self.dense is None else int(self.dense.shape[1])
 
+    @property
+    def n_text(self) -> int:
+        return len(self.text)
+
+    def with_pooled_text(self, column: TextColumn, vectors: Tensor) -> "ItemFeatures":
+        """The reference's BagOfWordsPretrained (pinsage/layers.py:49-87): the mean of FROZEN word vectors, then a Linear.  The
+        pooled vector of an item never changes, so it is computed once here — mi_pinsage_text_f32 over the catalogue at
+        width = P — and appended to `dense`: a new ItemFeatures whose dense is [dense | pooled], everything else shared.
+        `vectors` float32 [column.vocab_size, P] with P % 4 == 0 and 4 <= P <= 512 on the column's (CUDA) device; ValueError
+        otherwise.  One Linear over [dense | pooled] equals the reference's sum of one Linear per input; only the
+        xavier-uniform fan-in of its initial weights differs (F + P inputs instead of F and P apart)."""
+        if not isinstance(column, TextColumn) or column.n_items != self.n_items:
+            raise ValueError("ItemFeatures.with_pooled_text: a TextColumn over the same items expected")
+        if not isinstance(vectors, Tensor) or vectors.dtype != t.float32 or vectors.dim() != 2 or vectors.shape[0] != column.vocab_size:
+            raise ValueError("ItemFeatures.with_pooled_text: vectors must be float32 [vocab_size, P]")
+        P = int(vectors.shape[1])
+        if P % 4 or not (4 <= P <= 512):
+            raise ValueError("ItemFeatures.with_pooled_text: P % 4 == 0 and 4 <= P <= 512 expected")
+        pooled = _pool_text(column, vectors.contiguous())
+        if self.dense is not None and self.dense.device != pooled.device:
+            raise ValueError("ItemFeatures.with_pooled_text: dense and the pooled vectors live on different devices")
+        dense = pooled if self.dense is None else t.cat([self.dense, pooled], 1)
+        return ItemFeatures(self.categorical, dense, self.cardinalities if self.cardinalities else None, text=self.text)
+
 
 class _ProjectFn(t.autograd.Function):
     """ItemProjector.forward on mi_pinsage_project_f32; the backward on mi_pinsage_project_bwd_f32 into fresh zero buffers of
@@ -118,7 +245,9 @@ class ItemProjector(nn.Module):
     """projector(ids) = id row (if the model has an id table) + one table row per categorical column, in column order,
     + dense[ids] @ W^T + b: one f32 addition chain in that order (mi_pinsage_project_f32).  Tables are [cardinality + 1,
     hidden] (the reference's max + 2 rows; the last row is never looked up), xavier-uniform; Linear(F, hidden) with
-    xavier-uniform weight and zero bias.  The id table stays PinSAGEModel.proj (the same state_dict key as without features)."""
+    xavier-uniform weight and zero bias.  The id table stays PinSAGEModel.proj (the same state_dict key as without features).
+    Text columns come last in the chain: + the mean of text_tables[c]'s rows over the item's bag, in column order
+    (mi_pinsage_text_f32; [vocab_size, hidden] xavier-uniform tables, drawn after every other parameter)."""
 
     def __init__(self, features: ItemFeatures, hidden_dims: int, id_embedding: Optional[nn.Embedding]):
         super().__init__()
@@ -138,18 +267,62 @@ class ItemProjector(nn.Module):
         self.register_buffer("dense", features.dense, persistent=False)
         self._id = [id_embedding] if id_embedding is not None else []    # a list: PinSAGEModel.proj stays its only registration
         self._ws: Optional[Tensor] = None
+        self.n_text = len(features.text)
+        if self.n_text:
+            self.text_tables = nn.ParameterList([nn.Parameter(t.empty(c.vocab_size, hidden_dims)) for c in features.text])
+            for tab in self.text_tables:
+                nn.init.xavier_uniform_(tab)
+            for c, col in enumerate(features.text):
+                self.register_buffer(f"text_ptr_{c}", col.ptr, persistent=False)
+                self.register_buffer(f"text_tok_{c}", col.tok, persistent=False)
+        self.text_vocab = tuple(c.vocab_size for c in features.text)
+        self.text_max_len = tuple(c.max_len for c in features.text)
+        self.text_nnz = tuple(c.nnz for c in features.text)
+        self._tws: Optional[Tensor] = None
 
     @property
     def id_weight(self) -> Optional[Tensor]:
         return self._id[0].weight if self._id else None
 
     def parameter_list(self) -> List[Tensor]:
-        """[id table?] + tables + [W, b]?: the order of forward's chain, of _ProjectFn's gradients and of descriptor()."""
+        """[id table?] + tables + [W, b]? + text tables: the order of forward's chain, of _ProjectFn's gradients and of
+        descriptor() / text_descriptor()."""
         out = [self.id_weight] if self._id else []
         out += list(self.tables)
         if self.weight is not None:
             out += [self.weight, self.bias]
+        if self.n_text:
+            out += list(self.text_tables)
         return out
+
+    @property
+    def has_base(self) -> bool:
+        """Anything for mi_pinsage_project_f32 (a text-only projector never calls it)."""
+        return bool(self._id) or len(self.tables) > 0 or self.weight is not None
+
+    def text_descriptor(self) -> "_lib.TextColumns":
+        d = _lib.TextColumns()
+        d.width, d.n_text, d.n_items = self.hidden, self.n_text, self.n_items
+        for c, tab in enumerate(self.text_tables):
+            ptr, tok = getattr(self, f"text_ptr_{c}"), getattr(self, f"text_tok_{c}")
+            if tab.dtype != t.float32 or not tab.is_cuda or not tab.is_contiguous() or ptr.device != tab.device or tok.device != tab.device:
+                raise _lib.MiError("ItemProjector: text tables must be contiguous float32 CUDA tensors on the text columns' device "
+                                   "(there is no CPU fallback)")
+            d.ptr[c], d.tok[c], d.tables[c], d.vocab[c] = ptr.data_ptr(), tok.data_ptr(), tab.data_ptr(), int(tab.shape[0])
+        return d
+
+    def text_grads(self, grads: Sequence[Tensor]) -> "_lib.TextGradTables":
+        """The g_tables argument of the text entries from `grads` (parameter_list() order: the text tables are its tail)."""
+        arr = _lib.TextGradTables()
+        for c, g in enumerate(list(grads)[len(grads) - self.n_text:]):
+            arr[c] = g.data_ptr()
+        return arr
+
+    def text_ref_bound(self, n: int, with_ids: bool) -> int:
+        """An upper bound of the references of a call over n rows: n times the longest bags; without ids (rows 0 .. n - 1,
+        each once) also the columns' token counts."""
+        bound = n * sum(self.text_max_len)
+        return bound if with_ids else min(bound, sum(self.text_nnz))
 
     def descriptor(self) -> "_lib.ItemProjector":
         d = _lib.ItemProjector()
@@ -172,7 +345,8 @@ class ItemProjector(nn.Module):
         """grads: one buffer per parameter_list() entry, each with its parameter's shape."""
         gd = _lib.ItemProjectorGrads()
         grads = list(grads)
-        if any(g.shape != p.shape or g.dtype != t.float32 or not g.is_contiguous() for g, p in zip(grads, self.parameter_list())):
+        if len(grads) != len(self.parameter_list()) or any(
+                g.shape != p.shape or g.dtype != t.float32 or not g.is_contiguous() for g, p in zip(grads, self.parameter_list())):
             raise ValueError("ItemProjector: gradient buffers must be contiguous float32 of their parameters' shapes")
         if self._id:
             gd.g_id_table = grads.pop(0).data_ptr()
@@ -203,10 +377,16 @@ class ItemProjector(nn.Module):
         dev = self.parameter_list()[0].device
         if out is None:
             out = t.empty(n, self.hidden, dtype=t.float32, device=dev)
-        ws = self._workspace(int(L.mi_pinsage_project_workspace_bytes(ctypes.byref(d), n)), dev)
-        _lib.check(L.mi_pinsage_project_f32(ctypes.byref(d), n, ids.data_ptr() if ids is not None else None, out.data_ptr(),
-                                            int(out.stride(0)) if n else self.hidden, ws.data_ptr(), ws.numel(),
-                                            _lib.current_stream()), "mi_pinsage_project_f32")
+        if self.has_base:
+            ws = self._workspace(int(L.mi_pinsage_project_workspace_bytes(ctypes.byref(d), n)), dev)
+            _lib.check(L.mi_pinsage_project_f32(ctypes.byref(d), n, ids.data_ptr() if ids is not None else None, out.data_ptr(),
+                                                int(out.stride(0)) if n else self.hidden, ws.data_ptr(), ws.numel(),
+                                                _lib.current_stream()), "mi_pinsage_project_f32")
+        if self.n_text:
+            td = self.text_descriptor()
+            _lib.check(L.mi_pinsage_text_f32(ctypes.byref(td), n, ids.data_ptr() if ids is not None else None, out.data_ptr(),
+                                             int(out.stride(0)) if n else self.hidden, 1 if self.has_base else 0,
+                                             _lib.current_stream()), "mi_pinsage_text_f32")
         return out
 
     def project_backward(self, ids: Optional[Tensor], g: Tensor, grads: Sequence[Tensor]) -> None:
@@ -214,19 +394,34 @@ class ItemProjector(nn.Module):
         ids = self._ids(ids)
         n = self.n_items if ids is None else int(ids.numel())
         d, gd, L = self.descriptor(), self.grads_descriptor(grads), _lib.lib()
-        ws = self._workspace(int(L.mi_pinsage_project_bwd_workspace_bytes(ctypes.byref(d), n)), g.device)
-        _lib.check(L.mi_pinsage_project_bwd_f32(ctypes.byref(d), ctypes.byref(gd), n, ids.data_ptr() if ids is not None else None,
-                                                g.data_ptr(), int(g.stride(0)) if n else self.hidden, ws.data_ptr(), ws.numel(),
-                                                _lib.current_stream()), "mi_pinsage_project_bwd_f32")
+        if self.has_base:
+            ws = self._workspace(int(L.mi_pinsage_project_bwd_workspace_bytes(ctypes.byref(d), n)), g.device)
+            _lib.check(L.mi_pinsage_project_bwd_f32(ctypes.byref(d), ctypes.byref(gd), n, ids.data_ptr() if ids is not None else None,
+                                                    g.data_ptr(), int(g.stride(0)) if n else self.hidden, ws.data_ptr(), ws.numel(),
+                                                    _lib.current_stream()), "mi_pinsage_project_bwd_f32")
+        if self.n_text:
+            td, tg, bound = self.text_descriptor(), self.text_grads(grads), self.text_ref_bound(n, ids is not None)
+            need = int(L.mi_pinsage_text_bwd_workspace_bytes(ctypes.byref(td), n, bound))
+            if self._tws is None or self._tws.numel() < need or self._tws.device != g.device:
+                self._tws = t.empty(int(need * 1.25) + 4096, dtype=t.uint8, device=g.device)
+            _lib.check(L.mi_pinsage_text_bwd_f32(ctypes.byref(td), tg, n, ids.data_ptr() if ids is not None else None, g.data_ptr(),
+                                                 int(g.stride(0)) if n else self.hidden, bound, self._tws.data_ptr(),
+                                                 self._tws.numel(), _lib.current_stream()), "mi_pinsage_text_bwd_f32")
 
     def clear_rows(self, ids: Optional[Tensor], grads: Sequence[Tensor]) -> None:
         """The table rows project_backward(ids, ...) wrote, back to zero (mi_pinsage_project_clear_f32)."""
         ids = self._ids(ids)
         n = self.n_items if ids is None else int(ids.numel())
         d, gd = self.descriptor(), self.grads_descriptor(grads)
-        _lib.check(_lib.lib().mi_pinsage_project_clear_f32(ctypes.byref(d), ctypes.byref(gd), n,
-                                                           ids.data_ptr() if ids is not None else None, _lib.current_stream()),
-                   "mi_pinsage_project_clear_f32")
+        if self.has_base:
+            _lib.check(_lib.lib().mi_pinsage_project_clear_f32(ctypes.byref(d), ctypes.byref(gd), n,
+                                                               ids.data_ptr() if ids is not None else None, _lib.current_stream()),
+                       "mi_pinsage_project_clear_f32")
+        if self.n_text:
+            td = self.text_descriptor()
+            _lib.check(_lib.lib().mi_pinsage_text_clear_f32(ctypes.byref(td), self.text_grads(grads), n,
+                                                            ids.data_ptr() if ids is not None else None, _lib.current_stream()),
+                       "mi_pinsage_text_clear_f32")
 
     def forward(self, ids: Optional[Tensor] = None) -> Tensor:
         return _ProjectFn.apply(self, ids, *self.parameter_list())

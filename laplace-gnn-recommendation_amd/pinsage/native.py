@@ -14,7 +14,10 @@ blocks[0].src_ids — distinct, and holding every block's destination nodes — 
 (mi_pinsage_project_f32), the executor runs on it with apply_adam = 0 and hands the gradient of those rows back compactly
 (rows_out / bias_out), mi_pinsage_project_bwd_f32 turns it into the tables', the id table's and the Linear's gradients, and
 mi_adam_multi_f32 applies torch.optim.Adam's dense update to every tensor; the table rows written are cleared again
-(mi_pinsage_project_clear_f32), so the table gradients stay all-zero between iterations as the id table's does.
+(mi_pinsage_project_clear_f32), so the table gradients stay all-zero between iterations as the id table's does.  Text columns
+(ItemFeatures(text=...)) are one more pair of calls beside those: mi_pinsage_text_f32 after the projector's forward (accumulating
+into its rows; alone for a text-only model), mi_pinsage_text_bwd_f32 after its backward, mi_pinsage_text_clear_f32 after its
+clear; the text tables are ordinary entries of mi_adam_multi_f32's list.
 """
 from __future__ import annotations
 
@@ -162,8 +165,9 @@ class NativePinSAGEStep:
         model, opt = self.model, self.optimizer
         group = opt.param_groups[0]
         pr = model.projector
-        for p in pr.parameter_list()[: len(pr.parameter_list()) - (2 if pr.weight is not None else 0)]:
-            p.grad.zero_()     # the table gradients (id table included) stay all-zero between iterations
+        for p in pr.parameter_list():
+            if p is not pr.weight and p is not pr.bias:
+                p.grad.zero_()     # the table gradients (id and text tables included) stay all-zero between iterations
         model.bias.grad.zero_()
         d.n_layers, d.hidden, d.n_items = len(model.convs), model.hidden, model.n_items
         d.bias, d.g_bias = model.bias.data_ptr(), model.bias.grad.data_ptr()
@@ -186,6 +190,9 @@ class NativePinSAGEStep:
         self._proj_grads = [p.grad for p in pr.parameter_list()]
         self._pdesc, self._pgrads = pr.descriptor(), pr.grads_descriptor(self._proj_grads)
         self._pws_rows = -1
+        if pr.n_text:
+            self._tdesc, self._tgrads = pr.text_descriptor(), pr.text_grads(self._proj_grads)
+            self._tws_rows = -1
         steps = [opt.state[p]["step"] for p in group["params"]]
         self._adam_step = int(steps[0]) if steps else 0
         return d
@@ -197,6 +204,16 @@ class NativePinSAGEStep:
             need = max(int(L.mi_pinsage_project_workspace_bytes(pd, rows)), int(L.mi_pinsage_project_bwd_workspace_bytes(pd, rows)))
             self._pws, self._pws_rows = t.empty(need, dtype=t.uint8, device=device), rows
         return self._pws
+
+    def _text_workspace(self, n: int, device):
+        """(workspace, reference bound) for a block of n rows: the bound is the row capacity times the longest bags, grown on
+        demand as _rows grows."""
+        if n > getattr(self, "_tws_rows", -1):
+            rows = max(1024, int(n * 1.25))
+            self._tref_max = self.model.projector.text_ref_bound(rows, True)
+            need = int(_lib.lib().mi_pinsage_text_bwd_workspace_bytes(ctypes.byref(self._tdesc), rows, self._tref_max))
+            self._tws, self._tws_rows = t.empty(need, dtype=t.uint8, device=device), rows
+        return self._tws, self._tref_max
 
     def _current(self, d: PinsageModel) -> bool:
         """The descriptor holds raw pointers: rebuilt when a parameter, gradient or optimizer-state tensor was replaced."""
@@ -211,8 +228,14 @@ class NativePinSAGEStep:
                                                                         st["exp_avg_sq"].data_ptr()):
                     return False
             pr = self.model.projector
-            return (self._pdesc.x, self._pdesc.dense) == (pr.x.data_ptr() if pr.x is not None else None,
-                                                          pr.dense.data_ptr() if pr.dense is not None else None)
+            if (self._pdesc.x, self._pdesc.dense) != (pr.x.data_ptr() if pr.x is not None else None,
+                                                      pr.dense.data_ptr() if pr.dense is not None else None):
+                return False
+            for c in range(pr.n_text):
+                if (self._tdesc.ptr[c], self._tdesc.tok[c]) != (getattr(pr, f"text_ptr_{c}").data_ptr(),
+                                                                getattr(pr, f"text_tok_{c}").data_ptr()):
+                    return False
+            return True
         proj = self.model.proj.weight
         i = 0
         for p in group["params"]:
@@ -342,9 +365,16 @@ class NativePinSAGEStep:
             # the cached descriptors (rebuilt with the executor's, _current): no per-call ctypes fill on this path
             ids0 = batch["blocks"][0]["src_ids"]
             n0, H = int(ids0.numel()), self.model.hidden
-            pd, pg, pws = ctypes.byref(self._pdesc), ctypes.byref(self._pgrads), self._proj_workspace(n0, ids0.device)
-            _lib.check(L.mi_pinsage_project_f32(pd, n0, ids0.data_ptr(), self._rows[0].data_ptr(), H, pws.data_ptr(), pws.numel(),
-                                                _lib.current_stream()), "mi_pinsage_project_f32")
+            pr = self.model.projector
+            base, text = pr.has_base, pr.n_text > 0
+            if base:
+                pd, pg, pws = ctypes.byref(self._pdesc), ctypes.byref(self._pgrads), self._proj_workspace(n0, ids0.device)
+                _lib.check(L.mi_pinsage_project_f32(pd, n0, ids0.data_ptr(), self._rows[0].data_ptr(), H, pws.data_ptr(), pws.numel(),
+                                                    _lib.current_stream()), "mi_pinsage_project_f32")
+            if text:
+                td, (tws, tref_max) = ctypes.byref(self._tdesc), self._text_workspace(n0, ids0.device)
+                _lib.check(L.mi_pinsage_text_f32(td, n0, ids0.data_ptr(), self._rows[0].data_ptr(), H, 1 if base else 0,
+                                                 _lib.current_stream()), "mi_pinsage_text_f32")
         rc = L.mi_pinsage_step_f32(ctypes.byref(d), ctypes.byref(b), self._ws.data_ptr(), self._ws.numel(), _lib.current_stream())
         if rc == _lib.MI_ERR_UNSUPPORTED:
             if world > 1:                      # cannot happen: mi_pinsage_step_check took the same descriptors
@@ -358,16 +388,24 @@ class NativePinSAGEStep:
             self._exchange_and_apply(d)
         if featured:
             seeds = batch["seeds"]
-            _lib.check(L.mi_pinsage_project_bwd_f32(pd, pg, n0, ids0.data_ptr(), self._rows[1].data_ptr(), H, pws.data_ptr(),
-                                                    pws.numel(), _lib.current_stream()), "mi_pinsage_project_bwd_f32")
+            if base:
+                _lib.check(L.mi_pinsage_project_bwd_f32(pd, pg, n0, ids0.data_ptr(), self._rows[1].data_ptr(), H, pws.data_ptr(),
+                                                        pws.numel(), _lib.current_stream()), "mi_pinsage_project_bwd_f32")
+            if text:
+                _lib.check(L.mi_pinsage_text_bwd_f32(td, self._tgrads, n0, ids0.data_ptr(), self._rows[1].data_ptr(), H, tref_max,
+                                                     tws.data_ptr(), tws.numel(), _lib.current_stream()), "mi_pinsage_text_bwd_f32")
             gb = self.model.bias.grad.view(-1)
             gb.index_copy_(0, seeds, self._rows[2].view(-1)[: seeds.numel()])     # the seeds are distinct
             if not self.keep_grads:
                 _lib.check(L.mi_adam_multi_f32(self._flat_params, len(self._flat_params), float(group["lr"]),
                                                float(group["betas"][0]), float(group["betas"][1]), float(group["eps"]),
                                                self._adam_step + 1, _lib.current_stream()), "mi_adam_multi_f32")
-                _lib.check(L.mi_pinsage_project_clear_f32(pd, pg, n0, ids0.data_ptr(), _lib.current_stream()),
-                           "mi_pinsage_project_clear_f32")
+                if base:
+                    _lib.check(L.mi_pinsage_project_clear_f32(pd, pg, n0, ids0.data_ptr(), _lib.current_stream()),
+                               "mi_pinsage_project_clear_f32")
+                if text:
+                    _lib.check(L.mi_pinsage_text_clear_f32(td, self._tgrads, n0, ids0.data_ptr(), _lib.current_stream()),
+                               "mi_pinsage_text_clear_f32")
                 gb.index_fill_(0, seeds, 0.0)
         if not self.keep_grads:
             self._adam_step += 1

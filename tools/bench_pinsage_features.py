@@ -4,7 +4,8 @@ pass for the three model kinds — id only, features only, id + features — at 
 settings are tools/bench_pinsage.py's (synthetic.C3's 1.37 M users x 105 542 items, 31.8 M edges; batch 32, 10 walks of length
 2, restart 0.5, T = 3, 2 layers); the item features are synthetic.generate_hetero's article columns (HM_ARTICLE_CARDS =
 47 224 / 132 / 30 / 50 values, drawn the same way).  Prints one JSON line.  --kinds / --hiddens narrow the run (a profiling
-run of one kind); --time-limit ends the process by itself after that many seconds."""
+run of one kind); --time-limit ends the process by itself after that many seconds.  --text N adds N bag-of-words text columns
+(TextColumn: vocabulary --text-vocab, lengths uniform over 0 .. 2 x --text-len, so --text-len is the mean) to the feature sets."""
 import argparse
 import json
 import os
@@ -32,6 +33,9 @@ def parse_args(argv=None):
     ap.add_argument("--hiddens", default="16,128")
     ap.add_argument("--kinds", default=",".join(KINDS))
     ap.add_argument("--dense", type=int, default=0, help="float feature columns beside the four categorical ones")
+    ap.add_argument("--text", type=int, default=0, help="bag-of-words text columns beside the other features (at most 4)")
+    ap.add_argument("--text-len", type=int, default=8, help="mean bag length (lengths are uniform over 0 .. 2 x this)")
+    ap.add_argument("--text-vocab", type=int, default=20000)
     ap.add_argument("--iters", type=int, default=300)
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--time-limit", type=int, default=540)
@@ -45,7 +49,7 @@ def main():
     import torch as t
     from laplace_amd import synthetic as S
     from laplace_amd.data.dataset import AdjList
-    from laplace_amd.pinsage.model import ItemFeatures, PinSAGEModel
+    from laplace_amd.pinsage.model import ItemFeatures, PinSAGEModel, TextColumn
     from laplace_amd.pinsage.native import NativePinSAGEStep
     from laplace_amd.pinsage.sampler import PinSAGESampler
 
@@ -57,10 +61,16 @@ def main():
     cards = S.HM_ARTICLE_CARDS
     ax = np.stack([rng.integers(0, min(c, args.items) if c > 1000 else c, size=args.items) for c in cards], 1)
     dense = t.from_numpy(rng.standard_normal((args.items, args.dense)).astype(np.float32)).to(dev) if args.dense else None
-    feats = ItemFeatures(t.from_numpy(ax.astype(np.int64)).to(dev), dense, cardinalities=cards)
+    text = []
+    for _ in range(args.text):
+        lens = rng.integers(0, 2 * args.text_len + 1, size=args.items)
+        toks = rng.integers(0, args.text_vocab, size=(args.items, max(1, 2 * args.text_len)))
+        text.append(TextColumn(t.from_numpy(toks), t.from_numpy(lens), args.text_vocab).to(dev))
+    feats = ItemFeatures(t.from_numpy(ax.astype(np.int64)).to(dev), dense, cardinalities=cards, text=text)
     out = {"workload": f"PinSAGE with item features, H&M-shaped synthetic {args.users}x{args.items}, {args.edges} edges; batch "
                        f"{args.batch} pairs, walks {args.walks} x length {args.walk_length}, restart {args.restart}, "
-                       f"T={args.neighbors}, {args.layers} layers; categorical columns {cards}, {args.dense} float columns",
+                       f"T={args.neighbors}, {args.layers} layers; categorical columns {cards}, {args.dense} float columns, "
+                       f"{args.text} text columns (mean length {args.text_len}, vocabulary {args.text_vocab})",
            "results": []}
     t.autograd.set_multithreading_enabled(False)
     for hidden in (int(h) for h in args.hiddens.split(",")):
