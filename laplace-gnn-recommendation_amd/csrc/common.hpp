@@ -29,6 +29,12 @@ static inline bool mi_aligned16(const void* p) { return (reinterpret_cast<uintpt
 
 static inline int64_t mi_ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+static inline unsigned mi_bits_for(int64_t n) {   // bits that hold every value of [0, n): the width of a sort key's field; >= 1
+    unsigned b = 1;
+    while (b < 62 && ((int64_t)1 << b) < n) ++b;
+    return b;
+}
+
 // Bump allocator over a caller-provided workspace (256-byte granules).
 struct MiArena {
     char*  base;

@@ -116,12 +116,6 @@ __global__ void gcn_scale_kernel(int64_t n, int64_t nnz, const int32_t* __restri
     val_out[i] = v;
 }
 
-inline unsigned bits_for(int64_t n) {  // bits needed to represent values in [0, n)
-    unsigned b = 0;
-    while (b < 32 && ((int64_t)1 << b) < n) ++b;
-    return b == 0 ? 1 : b;
-}
-
 inline dim3 grid_for(int64_t n) { return dim3((unsigned)mi_ceil_div(n > 0 ? n : 1, kBlock)); }
 
 // sort (keys, vals) ascending on the low `end_bit` bits; result pointers returned.
@@ -171,10 +165,10 @@ int mi_coo_to_csr_i32(int64_t n_rows, int64_t n_cols, int64_t nnz, const int64_t
     int32_t* v0 = arena.take<int32_t>(nnz);
     int32_t* v1 = arena.take<int32_t>(nnz);
     if (!k0 || !k1 || !v0 || !v1) return MI_ERR_WORKSPACE;
-    const unsigned cb = bits_for(n_cols);
+    const unsigned cb = mi_bits_for(n_cols);
     hipLaunchKernelGGL(make_keys_coo, grid_for(nnz), dim3(kBlock), 0, s, nnz, row, col, cb, k0, v0);
     uint64_t* ks; int32_t* vs;
-    int rc = sort_pairs(k0, k1, v0, v1, nnz, cb + bits_for(n_rows), arena, s, &ks, &vs);
+    int rc = sort_pairs(k0, k1, v0, v1, nnz, cb + mi_bits_for(n_rows), arena, s, &ks, &vs);
     if (rc) return rc;
     hipLaunchKernelGGL(rowptr_from_keys, grid_for(n_rows + 1), dim3(kBlock), 0, s, n_rows, nnz, cb, ks, rowptr);
     hipLaunchKernelGGL(decode_keys, grid_for(nnz), dim3(kBlock), 0, s, nnz, cb, ks, vs, col_out, perm);
@@ -203,10 +197,10 @@ int mi_csr_transpose_i32(int64_t n_rows, int64_t n_cols, int64_t nnz, const int3
     int32_t* v0 = arena.take<int32_t>(nnz);
     int32_t* v1 = arena.take<int32_t>(nnz);
     if (!k0 || !k1 || !v0 || !v1) return MI_ERR_WORKSPACE;
-    const unsigned cb = bits_for(n_rows);  // transposed: the old row is the minor key
+    const unsigned cb = mi_bits_for(n_rows);  // transposed: the old row is the minor key
     hipLaunchKernelGGL(make_keys_transpose, grid_for(nnz), dim3(kBlock), 0, s, n_rows, nnz, rowptr, col, cb, k0, v0);
     uint64_t* ks; int32_t* vs;
-    int rc = sort_pairs(k0, k1, v0, v1, nnz, cb + bits_for(n_cols), arena, s, &ks, &vs);
+    int rc = sort_pairs(k0, k1, v0, v1, nnz, cb + mi_bits_for(n_cols), arena, s, &ks, &vs);
     if (rc) return rc;
     hipLaunchKernelGGL(rowptr_from_keys, grid_for(n_cols + 1), dim3(kBlock), 0, s, n_cols, nnz, cb, ks, rowptr_t);
     hipLaunchKernelGGL(decode_keys, grid_for(nnz), dim3(kBlock), 0, s, nnz, cb, ks, vs, col_t, perm_t);

@@ -590,3 +590,45 @@ extern "C" int mi_pinsage_apply_f32(const mi_pinsage_model* model, const mi_pins
     }
     return mi_launch_status();
 }
+
+// torch.optim.Adam's dense update over a list of tensors: the small ones in launches of adam_multi_kernel, a big aligned one on
+// mi_adam_dense_f32.
+extern "C" int mi_adam_multi_f32(const mi_ranker_param* params, int32_t n_params, double lr, double beta1, double beta2, double eps,
+                                 int64_t step, mi_stream_t stream) {
+    MI_CHECK_ARG(n_params >= 0 && (n_params == 0 || params) && step >= 1);
+    for (int i = 0; i < n_params; ++i) {
+        const mi_ranker_param& q = params[i];
+        MI_CHECK_ARG(q.n >= 0 && (q.n == 0 || (q.p && q.g && q.m && q.v)));
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const MiAdamConsts c = mi_adam_consts(lr, beta1, beta2, eps, step);
+    AdamTable tb;
+    memset(&tb, 0, sizeof(tb));
+    int64_t longest = 1;
+    auto flush = [&]() -> int {
+        if (tb.n == 0) return 0;
+        const unsigned gx = (unsigned)std::min<int64_t>(mi_ceil_div(longest, kBlock), 64);
+        hipLaunchKernelGGL(adam_multi_kernel, dim3(gx, (unsigned)tb.n), dim3(kBlock), 0, s, tb, c, 1, (int64_t*)nullptr,
+                           (int64_t*)nullptr, 1.f);
+        memset(&tb, 0, sizeof(tb));
+        longest = 1;
+        return mi_launch_status();
+    };
+    for (int i = 0; i < n_params; ++i) {
+        const mi_ranker_param& q = params[i];
+        if (q.n == 0) continue;
+        if (q.n >= 65536 && q.n % 4 == 0 && mi_aligned16(q.p) && mi_aligned16(q.g) && mi_aligned16(q.m) && mi_aligned16(q.v)) {
+            const int rc = mi_adam_dense_f32(q.n / 4, 4, q.p, 4, q.g, 4, q.m, q.v, nullptr, lr, beta1, beta2, eps, step, stream);
+            if (rc) return rc;
+            continue;
+        }
+        tb.p[tb.n] = q;
+        tb.g_stride[tb.n] = 1;
+        longest = std::max(longest, q.n);
+        if (++tb.n == MI_RANKER_MAX_PARAMS) {
+            const int rc = flush();
+            if (rc) return rc;
+        }
+    }
+    return flush();
+}

@@ -8,42 +8,24 @@
 //
 // Backward.  A categorical column has tens of values, so at the executor's largest block one code is looked up by
 // thousands of rows, from every workgroup of any row-parallel grid: the table gradient is a segmented sum with very long
-// segments.  The (column, code) references are radix-sorted with the reference index as payload (reference = slot * n + r, a
-// stable sort: ascending r within a code; the payload carried is r), the sorted list is cut into chunks of 64 references, one lane group per chunk:
-// a run of equal keys inside a chunk is summed in order (16 row loads in flight) and stored by that group alone; a run that
-// crosses chunk borders leaves one partial row per chunk and the group of the chunk where the run starts adds them in chunk
-// order (the scheme of bpr_chunk_kernel / bpr_combine_kernel, csrc/train.hip).  One writer per row, a fixed association
-// that does not depend on scheduling, no float atomics.  g_b is a fixed-order column sum (128-row slabs, then the slabs in
-// order); g_w = g^T @ dense[ids] is a trans_a product on the launcher (split-K under its rule) over the gathered rows.
+// segments.  proj_refs_kernel writes one reference per (slot, r) — key (slot, code), the columns then the id, payload r — in
+// slot-major order, then ascending r, and segsum.hpp sums the rows of g by key in that order (stable sort, chunks of 64,
+// segsum::chunk_kernel / segsum::combine_kernel): one writer per row, a fixed association, no float atomics.  g_b is a
+// fixed-order column sum (128-row slabs, then the slabs in order); g_w = g^T @ dense[ids] is a trans_a product on the
+// launcher (split-K under its rule) over the gathered rows.
 #include "gemm.hpp"
-#include <rocprim/rocprim.hpp>
-#include <algorithm>
+#include "segsum.hpp"
 
 namespace {
 
 constexpr int kBlock = 256;
-constexpr int kChunk = 64;       // references per chunk
-constexpr int kInFlight = 16;    // rows of g a lane group keeps in flight
 constexpr int kSlab = 128;       // rows per partial of the g_b column sum
 constexpr int kMaxSlots = MI_PROJECTOR_MAX_COLS + 1;   // the columns, then the id
 
-#include "exec_common.hpp"   // adam_multi_kernel
-
 inline unsigned grid_for(int64_t n) { return (unsigned)mi_ceil_div(n > 0 ? n : 1, kBlock); }
 
-struct ProjTables {   // by value in the kernel arguments
-    const float4* t[kMaxSlots];
-};
-struct ProjGradTables {
-    float4* t[kMaxSlots];
-};
-
-__device__ __forceinline__ float4* slot_ptr(const ProjGradTables& gt, int slot) {   // selects, no dynamically indexed copy of gt
-    float4* p = gt.t[0];
-#pragma unroll
-    for (int s = 1; s < kMaxSlots; ++s) p = (s == slot) ? gt.t[s] : p;
-    return p;
-}
+using ProjTables = segsum::Ptrs<const float4, kMaxSlots>;   // by value in the kernel arguments
+using ProjGradTables = segsum::Ptrs<float4, kMaxSlots>;
 
 // ---- forward ---------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kBlock) void proj_gather_kernel(int64_t n, int h4, int n_cols, const int64_t* __restrict__ ids,
@@ -90,95 +72,7 @@ __global__ __launch_bounds__(kBlock) void proj_refs_kernel(int64_t n, int64_t n_
     refs[j] = (uint32_t)r;   // the payload is the row of g to add; the initial order (slot, then r) is what the stable sort keeps
 }
 
-// One group of `lpr` lanes (a power of two >= hidden / 4) per chunk of 64 sorted references.
-__global__ __launch_bounds__(kBlock) void proj_chunk_kernel(int64_t n, int64_t n_ref, int h4, int lpr, unsigned shift,
-                                                            const uint64_t* __restrict__ keys, const uint32_t* __restrict__ refs,
-                                                            const float4* __restrict__ g, int64_t ldg4, ProjGradTables gt,
-                                                            float4* __restrict__ part_head, float4* __restrict__ part_tail) {
-    // A small launch is a handful of wavefronts walking 64 references each, one after the other: its time is the
-    // instruction count per reference.  The table base comes from LDS (one read) instead of a 17-way select.
-    __shared__ float4* tab[kMaxSlots];
-    if (threadIdx.x < kMaxSlots) tab[threadIdx.x] = slot_ptr(gt, (int)threadIdx.x);
-    __syncthreads();
-    const int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    const int64_t chunk = t / lpr;
-    const int e = (int)(t - chunk * lpr);
-    const int64_t j0 = chunk * kChunk;
-    if (j0 >= n_ref || e >= h4) return;
-    const int n_here = (int)min((int64_t)kChunk, n_ref - j0);
-    const bool head_open = j0 > 0 && keys[j0 - 1] == keys[j0];
-    const bool next_same = (j0 + n_here < n_ref) && keys[j0 + n_here] == keys[j0 + n_here - 1];
-    const uint64_t mask = ((uint64_t)1 << shift) - 1;
-    float4 acc = mi_f4_zero();
-    int run_start = 0;
-    // Two dependent loads per reference (its index, then its row of g): the indices and keys of step s + 1 are fetched while
-    // the rows of step s are in flight, so a chunk costs one memory latency per step, not two.
-    uint64_t kn[kInFlight + 1];
-    uint32_t rn[kInFlight];
-#pragma unroll
-    for (int u = 0; u <= kInFlight; ++u) kn[u] = keys[j0 + min(u, n_here - 1)];
-#pragma unroll
-    for (int u = 0; u < kInFlight; ++u) rn[u] = refs[j0 + min(u, n_here - 1)];
-    for (int q0 = 0; q0 < n_here; q0 += kInFlight) {
-        uint64_t kq[kInFlight + 1];
-        float4 rows[kInFlight];
-#pragma unroll
-        for (int u = 0; u <= kInFlight; ++u) kq[u] = kn[u];
-#pragma unroll
-        for (int u = 0; u < kInFlight; ++u) rows[u] = g[(int64_t)rn[u] * ldg4 + e];
-        const int q1 = q0 + kInFlight;
-        if (q1 < n_here) {
-#pragma unroll
-            for (int u = 0; u <= kInFlight; ++u) kn[u] = keys[j0 + min(q1 + u, n_here - 1)];
-#pragma unroll
-            for (int u = 0; u < kInFlight; ++u) rn[u] = refs[j0 + min(q1 + u, n_here - 1)];
-        }
-#pragma unroll
-        for (int u = 0; u < kInFlight; ++u) {
-            const int q = q0 + u;
-            if (q >= n_here) break;
-            acc = mi_f4_add(acc, rows[u]);
-            const bool last_of_run = (q + 1 == n_here) || kq[u + 1] != kq[u];
-            if (!last_of_run) continue;
-            const bool from_prev = run_start == 0 && head_open;
-            const bool into_next = (q + 1 == n_here) && next_same;
-            float4* dst;
-            if (from_prev) dst = part_head + chunk * h4;          // finished by the chunk where the run starts
-            else if (into_next) dst = part_tail + chunk * h4;     // this chunk starts the run; proj_combine_kernel finishes it
-            else dst = tab[kq[u] >> shift] + (int64_t)(kq[u] & mask) * h4;   // the row's only writer
-            dst[e] = acc;
-            acc = mi_f4_zero();
-            run_start = q + 1;
-        }
-    }
-}
-
-// One lane group per chunk whose trailing run starts in it and runs on: tail partial + the head partials of the following
-// chunks, in chunk order.
-__global__ __launch_bounds__(kBlock) void proj_combine_kernel(int64_t n_ref, int h4, int lpr, unsigned shift,
-                                                              const uint64_t* __restrict__ keys, ProjGradTables gt,
-                                                              const float4* __restrict__ part_head,
-                                                              const float4* __restrict__ part_tail) {
-    const int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    const int64_t chunk = t / lpr;
-    const int e = (int)(t - chunk * lpr);
-    const int64_t j0 = chunk * kChunk;
-    if (j0 >= n_ref || e >= h4) return;
-    const int64_t j_last = min(j0 + kChunk, n_ref) - 1;
-    if (j_last + 1 >= n_ref) return;                        // nothing after this chunk
-    const uint64_t key = keys[j_last];
-    if (keys[j_last + 1] != key) return;                    // the trailing run ends here
-    if (keys[j0] == key && j0 > 0 && keys[j0 - 1] == key) return;   // the run started in an earlier chunk: not the owner
-    float4 acc = part_tail[chunk * h4 + e];
-    for (int64_t nb = chunk + 1; nb * kChunk < n_ref && keys[nb * kChunk] == key; ++nb) {
-        acc = mi_f4_add(acc, part_head[nb * h4 + e]);
-        if (keys[min((nb + 1) * kChunk, n_ref) - 1] != key) break;   // the run ends inside chunk nb
-    }
-    const uint64_t mask = ((uint64_t)1 << shift) - 1;
-    slot_ptr(gt, (int)(key >> shift))[(int64_t)(key & mask) * h4 + e] = acc;
-}
-
-// The rows proj_chunk / proj_combine wrote, back to zero (every writer stores the same zeros).
+// The rows the backward wrote, back to zero (every writer stores the same zeros).
 __global__ __launch_bounds__(kBlock) void proj_clear_kernel(int64_t n, int64_t n_ref, int h4, int n_cols,
                                                             const int64_t* __restrict__ ids, const int64_t* __restrict__ x,
                                                             ProjGradTables gt) {
@@ -189,7 +83,7 @@ __global__ __launch_bounds__(kBlock) void proj_clear_kernel(int64_t n, int64_t n
     const int64_t slot = j / n, r = j - slot * n;
     const int64_t item = ids ? ids[r] : r;
     const int64_t code = slot < n_cols ? x[item * n_cols + slot] : item;
-    slot_ptr(gt, (int)slot)[code * h4 + e] = mi_f4_zero();
+    gt.at((int)slot)[code * h4 + e] = mi_f4_zero();
 }
 
 // ---- backward: g_b, a fixed-order column sum -------------------------------------------------------------------------------
@@ -224,12 +118,6 @@ __global__ __launch_bounds__(kBlock) void proj_gather_dense_kernel(int64_t n, in
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------------
-inline unsigned bits_for(int64_t n) {   // bits that hold every value of [0, n)
-    unsigned b = 1;
-    while (b < 62 && ((int64_t)1 << b) < n) ++b;
-    return b;
-}
-
 inline int n_slots(const mi_item_projector& p) { return p.n_cols + (p.id_table ? 1 : 0); }
 
 // Everything about the descriptor that does not depend on the call's buffers.  0, or the code to return.
@@ -273,22 +161,18 @@ size_t fwd_ws_bytes(const mi_item_projector& p, int64_t n) {
 }
 
 struct BwdSizes {
-    int64_t n_ref, n_chunks, n_slabs, ldd;
+    int64_t n_ref, n_slabs, ldd;
 };
 BwdSizes bwd_sizes(const mi_item_projector& p, int64_t n) {
     BwdSizes z;
     z.n_ref = n * n_slots(p);
-    z.n_chunks = mi_ceil_div(z.n_ref, kChunk);
     z.n_slabs = mi_ceil_div(n, kSlab);
     z.ldd = (p.n_dense + 3) / 4 * 4;
     return z;
 }
 size_t bwd_ws_bytes(const mi_item_projector& p, int64_t n) {
     const BwdSizes z = bwd_sizes(p, n);
-    const size_t nr = (size_t)std::max<int64_t>(z.n_ref, 1), nc = (size_t)std::max<int64_t>(z.n_chunks, 1);
-    size_t total = 256;
-    total += 2 * mi_align_up(nr * sizeof(uint64_t), 256) + 2 * mi_align_up(nr * sizeof(uint32_t), 256) + mi_align_up(sort_tmp_cap(z.n_ref), 256);
-    total += 2 * mi_align_up(nc * p.hidden * sizeof(float), 256);
+    size_t total = 256 + segsum::workspace_bytes(z.n_ref, p.hidden, sort_tmp_cap(z.n_ref));
     if (p.n_dense > 0) {
         total += mi_align_up((size_t)std::max<int64_t>(z.n_slabs, 1) * p.hidden * sizeof(float), 256);
         total += mi_align_up((size_t)std::max<int64_t>(n, 1) * z.ldd * sizeof(float), 256);
@@ -312,12 +196,6 @@ int check_grads(const mi_item_projector& p, const mi_item_projector_grads* gr, b
     if (p.id_table && (!gr->g_id_table || !mi_aligned16(gr->g_id_table))) return MI_ERR_BAD_ARG;
     if (dense_too && p.n_dense > 0 && (!gr->g_w || !gr->g_b)) return MI_ERR_BAD_ARG;
     return 0;
-}
-
-inline int lanes_per_row(int h4) {
-    int l = 4;
-    while (l < h4) l *= 2;
-    return l;
 }
 
 }  // namespace
@@ -384,17 +262,10 @@ int mi_pinsage_project_bwd_f32(const mi_item_projector* pp, const mi_item_projec
     MI_CHECK_ARG(n == 0 || (g && mi_aligned16(g) && ldg >= p.hidden && ldg % 4 == 0));
     if (!ws || ws_bytes < bwd_ws_bytes(p, n)) return MI_ERR_WORKSPACE;
     const BwdSizes z = bwd_sizes(p, n);
-    const int H = p.hidden, h4 = H / 4;
+    const int H = p.hidden;
     hipStream_t s = (hipStream_t)stream;
     MiArena arena(ws, ws_bytes);
-    uint64_t* k0 = arena.take<uint64_t>(std::max<int64_t>(z.n_ref, 1));
-    uint64_t* k1 = arena.take<uint64_t>(std::max<int64_t>(z.n_ref, 1));
-    uint32_t* r0 = arena.take<uint32_t>(std::max<int64_t>(z.n_ref, 1));
-    uint32_t* r1 = arena.take<uint32_t>(std::max<int64_t>(z.n_ref, 1));
-    const size_t tmp_cap = sort_tmp_cap(z.n_ref);
-    char* tmp = arena.take<char>(tmp_cap);
-    float* part_head = arena.take<float>((size_t)std::max<int64_t>(z.n_chunks, 1) * H);
-    float* part_tail = arena.take<float>((size_t)std::max<int64_t>(z.n_chunks, 1) * H);
+    const segsum::Buffers sb = segsum::take(arena, z.n_ref, H, sort_tmp_cap(z.n_ref));
     float *slabs = nullptr, *dense_rows = nullptr;
     char* gemm_ws = nullptr;
     size_t gemm_ws_bytes = 0;
@@ -405,32 +276,19 @@ int mi_pinsage_project_bwd_f32(const mi_item_projector* pp, const mi_item_projec
         gemm_ws = arena.take<char>(gemm_ws_bytes ? gemm_ws_bytes : 1);
         if (!slabs || !dense_rows || !gemm_ws) return MI_ERR_WORKSPACE;
     }
-    if (!k0 || !k1 || !r0 || !r1 || !tmp || !part_head || !part_tail) return MI_ERR_WORKSPACE;
-    // the key: slot above `shift` bits of code (a column's code, or the item id in the last slot)
-    int64_t widest = p.id_table ? p.n_items : 1;
-    for (int c = 0; c < p.n_cols; ++c) widest = std::max(widest, p.table_rows[c]);
-    const unsigned shift = bits_for(widest), bits = shift + bits_for(kMaxSlots);
-    rocprim::double_buffer<uint64_t> keys(k0, k1);
-    rocprim::double_buffer<uint32_t> refs(r0, r1);
-    size_t need = 0;
-    if (z.n_ref > 0) {   // the size query enqueues nothing
-        MI_HIP(rocprim::radix_sort_pairs(nullptr, need, keys, refs, (size_t)z.n_ref, 0u, bits, s));
-        if (need > tmp_cap) return MI_ERR_WORKSPACE;
-    }
-    // ---- nothing has been enqueued up to here ----
+    if (!sb.ok()) return MI_ERR_WORKSPACE;
     if (z.n_ref > 0) {
-        const ProjGradTables gt = grad_tables(p, *grads);
-        const int lpr = lanes_per_row(h4);
-        hipLaunchKernelGGL(proj_refs_kernel, dim3(grid_for(z.n_ref)), dim3(kBlock), 0, s, n, z.n_ref, (int)p.n_cols, ids, p.x, shift,
-                           k0, r0);
-        MI_HIP(rocprim::radix_sort_pairs(tmp, need, keys, refs, (size_t)z.n_ref, 0u, bits, s));
-        const dim3 gc(grid_for(z.n_chunks * lpr));
-        hipLaunchKernelGGL(proj_chunk_kernel, gc, dim3(kBlock), 0, s, n, z.n_ref, h4, lpr, shift, keys.current(), refs.current(),
-                           reinterpret_cast<const float4*>(g), ldg / 4, gt, reinterpret_cast<float4*>(part_head),
-                           reinterpret_cast<float4*>(part_tail));
-        hipLaunchKernelGGL(proj_combine_kernel, gc, dim3(kBlock), 0, s, z.n_ref, h4, lpr, shift, keys.current(), gt,
-                           reinterpret_cast<const float4*>(part_head), reinterpret_cast<const float4*>(part_tail));
-        const int rc = mi_launch_status();
+        // the key: slot above `shift` bits of code (a column's code, or the item id in the last slot)
+        int64_t widest = p.id_table ? p.n_items : 1;
+        for (int c = 0; c < p.n_cols; ++c) widest = std::max(widest, p.table_rows[c]);
+        const unsigned shift = mi_bits_for(widest), bits = shift + mi_bits_for(kMaxSlots);
+        auto refs = [&]() -> int {
+            hipLaunchKernelGGL(proj_refs_kernel, dim3(grid_for(z.n_ref)), dim3(kBlock), 0, s, n, z.n_ref, (int)p.n_cols, ids, p.x,
+                               shift, sb.k0, sb.r0);
+            return 0;
+        };
+        const int rc = segsum::run<false>(sb, z.n_ref, nullptr, shift, bits, 0, refs, g, ldg, H, segsum::Plain(),
+                                          grad_tables(p, *grads), s);
         if (rc) return rc;
     }
     if (p.n_dense > 0) {
@@ -471,46 +329,6 @@ int mi_pinsage_project_clear_f32(const mi_item_projector* pp, const mi_item_proj
     hipLaunchKernelGGL(proj_clear_kernel, dim3(grid_for(n_ref * h4)), dim3(kBlock), 0, (hipStream_t)stream, n, n_ref, h4,
                        (int)p.n_cols, ids, p.x, grad_tables(p, *grads));
     return mi_launch_status();
-}
-
-int mi_adam_multi_f32(const mi_ranker_param* params, int32_t n_params, double lr, double beta1, double beta2, double eps,
-                      int64_t step, mi_stream_t stream) {
-    MI_CHECK_ARG(n_params >= 0 && (n_params == 0 || params) && step >= 1);
-    for (int i = 0; i < n_params; ++i) {
-        const mi_ranker_param& q = params[i];
-        MI_CHECK_ARG(q.n >= 0 && (q.n == 0 || (q.p && q.g && q.m && q.v)));
-    }
-    hipStream_t s = (hipStream_t)stream;
-    const MiAdamConsts c = mi_adam_consts(lr, beta1, beta2, eps, step);
-    AdamTable tb;
-    memset(&tb, 0, sizeof(tb));
-    int64_t longest = 1;
-    auto flush = [&]() -> int {
-        if (tb.n == 0) return 0;
-        const unsigned gx = (unsigned)std::min<int64_t>(mi_ceil_div(longest, kBlock), 64);
-        hipLaunchKernelGGL(adam_multi_kernel, dim3(gx, (unsigned)tb.n), dim3(kBlock), 0, s, tb, c, 1, (int64_t*)nullptr,
-                           (int64_t*)nullptr, 1.f);
-        memset(&tb, 0, sizeof(tb));
-        longest = 1;
-        return mi_launch_status();
-    };
-    for (int i = 0; i < n_params; ++i) {
-        const mi_ranker_param& q = params[i];
-        if (q.n == 0) continue;
-        if (q.n >= 65536 && q.n % 4 == 0 && mi_aligned16(q.p) && mi_aligned16(q.g) && mi_aligned16(q.m) && mi_aligned16(q.v)) {
-            const int rc = mi_adam_dense_f32(q.n / 4, 4, q.p, 4, q.g, 4, q.m, q.v, nullptr, lr, beta1, beta2, eps, step, stream);
-            if (rc) return rc;
-            continue;
-        }
-        tb.p[tb.n] = q;
-        tb.g_stride[tb.n] = 1;
-        longest = std::max(longest, q.n);
-        if (++tb.n == MI_RANKER_MAX_PARAMS) {
-            const int rc = flush();
-            if (rc) return rc;
-        }
-    }
-    return flush();
 }
 
 }  // extern "C"

@@ -135,6 +135,39 @@ def test_backward_whole_catalogue_without_ids():
     _check_backward(700, 128, (5, 30), 0, True, 700, 17, all_items=True)
 
 
+# n = 200, cardinalities (1, 3, 50), ids drawn from 40 items: with the id table 4 slots and 800 references in 13 pieces of 64.
+# The one-valued column is one run of 200 over 4 pieces (the two middle ones wholly inside it); the slot borders (200, 400,
+# 600) fall inside pieces.  hidden 20: 5 float4 lanes of a group of 8; hidden 128: groups of 32.  n = 65 with one one-valued
+# column: exactly one border.
+BITS_CASES = [(200, (1, 3, 50), True, 16), (200, (1, 3, 50), False, 16), (200, (1, 3, 50), True, 20), (200, (1, 3, 50), False, 20),
+              (200, (1, 3, 50), True, 128), (200, (1, 3, 50), False, 128), (65, (1,), False, 16), (1, (1, 3, 50), True, 16)]
+
+
+@pytest.mark.parametrize("n,cards,use_id,hidden", BITS_CASES,
+                         ids=[f"n{n}c{len(c)}{'id' if u else ''}h{h}" for n, c, u, h in BITS_CASES])
+def test_backward_bits_are_the_documented_association(n, cards, use_id, hidden):
+    """torch.equal with tests/segsum_emulation.py on every table row; rows nobody looks up keep the sentinel."""
+    import segsum_emulation as E
+    from laplace_amd.pinsage.model import PinSAGEModel
+    I, SENTINEL = 300, 7.0
+    t.manual_seed(n + hidden)
+    model = PinSAGEModel(I, hidden, 1, features=_features(I, cards, 0, 3), use_id=use_id).to(DEV)
+    pr = model.projector
+    g = t.Generator().manual_seed(n + 1)
+    ids = t.randint(0, 40, (n,), generator=g)                              # repeats: runs in the id slot
+    gout = t.randn(n, hidden, generator=g)
+    bufs = [t.full_like(p, SENTINEL) for p in pr.parameter_list()]
+    pr.project_backward(ids.to(DEV), gout.to(DEV), bufs)
+    x = pr.x.cpu()
+    slots = [x[ids, c].numpy() for c in range(len(cards))] + ([ids.numpy()] if use_id else [])   # the columns, then the id
+    sums = E.segmented_sum(*E.projector_references(slots, gout.numpy()))
+    assert len(sums) == sum(len(np.unique(s)) for s in slots)
+    tables = bufs[1:] + bufs[:1] if use_id else bufs                      # parameter_list() has the id table first
+    for slot, buf in enumerate(tables):
+        want = t.from_numpy(E.expected_tables(sums, slot, buf, SENTINEL))
+        assert t.equal(buf.cpu(), want), (slot, float((buf.cpu() - want).abs().max()))
+
+
 # ---- 3. the model's two iterations against PinSAGERef + twin ---------------------------------------------------------------------
 def _pin_graph(seed, U, I, E):
     from laplace_amd import synthetic as S

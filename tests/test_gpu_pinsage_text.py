@@ -213,6 +213,40 @@ def test_backward_one_item_of_65_equal_tokens_crosses_exactly_one_border():
     assert longest == 65
 
 
+@pytest.mark.parametrize("case", ["n150h16", "n150h20", "one_item_of_65_equal_tokens"])
+def test_backward_bits_are_the_documented_association(case):
+    """torch.equal with tests/segsum_emulation.py on every table row; rows nobody references keep the sentinel.  n = 150 rows
+    over vocabularies (2, 50) with lengths 0 .. 5: the two tokens of the first column are runs over several pieces of 64, some
+    bags are empty, and the bound passed (n x the longest bags) exceeds the actual count, so the sort sees padding keys."""
+    import segsum_emulation as E
+    from laplace_amd.pinsage.model import PinSAGEModel, TextColumn
+    if case == "one_item_of_65_equal_tokens":
+        I, hidden, ids = 3, 16, t.tensor([0])
+        tokens = t.full((3, 65), 1, dtype=t.int64)
+        tokens[1, :] = 2
+        text = [TextColumn(tokens, t.tensor([65, 3, 0]), 4)]
+    else:
+        I, hidden = 300, int(case[-2:])
+        ids = t.randint(0, I // 2, (150,), generator=t.Generator().manual_seed(29))
+        text = _text(I, (2, 50), 31, tuple(range(6)))
+    t.manual_seed(hidden)
+    model = PinSAGEModel(I, hidden, 1, features=_features(I, (), 0, text, 5), use_id=False).to(DEV)
+    pr = model.projector
+    gout = t.randn(len(ids), hidden, generator=t.Generator().manual_seed(37))
+    bufs = [t.full_like(p, SENTINEL) for p in pr.parameter_list()]
+    pr.project_backward(ids.to(DEV), gout.to(DEV), bufs)
+    columns = [(getattr(pr, f"text_ptr_{c}").cpu().numpy(), getattr(pr, f"text_tok_{c}").cpu().numpy()) for c in range(pr.n_text)]
+    keys, values = E.text_references(columns, ids.numpy(), gout.numpy())
+    if case != "one_item_of_65_equal_tokens":
+        lens = [ptr[ids.numpy() + 1] - ptr[ids.numpy()] for ptr, _ in columns]
+        assert len(keys) < pr.text_ref_bound(len(ids), True) and any((ln == 0).any() for ln in lens)
+        assert (keys == 0).sum() > 2 * E.PIECE and (keys == 1).sum() > 2 * E.PIECE
+    sums = E.segmented_sum(keys, values)
+    for c, buf in enumerate(bufs):
+        want = t.from_numpy(E.expected_tables(sums, c, buf, SENTINEL))
+        assert t.equal(buf.cpu(), want), (c, float((buf.cpu() - want).abs().max()))
+
+
 @pytest.mark.parametrize("case", ["n0", "all_empty", "n1"])
 def test_backward_small(case):
     from laplace_amd.pinsage.model import TextColumn

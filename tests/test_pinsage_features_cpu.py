@@ -86,6 +86,24 @@ def test_twin_on_a_hand_written_example():
     assert t.equal(tw.tables[0].grad[1], t.tensor([3., 3.]))     # items 1, 2, 1
 
 
+def test_segmented_sum_emulation_on_a_hand_written_example():
+    """The association the GPU tests pin (tests/segsum_emulation.py), on values where the order shows: 2^24 + 1 rounds back
+    to 2^24 in float32.  Key 5 comes first in the sorted list: 66 references = all of piece 0 and two of piece 1."""
+    import numpy as np
+    import segsum_emulation as E
+    big, one = np.float32(2.0 ** 24), np.float32(1.0)
+    keys = [9, 5, 9, 9] + [5] * 65
+    vals = [big, big, one, one] + [one] * 65
+    sums = E.segmented_sum(np.array(keys), np.array(vals, dtype=np.float32)[:, None])
+    assert sorted(sums) == [5, 9]
+    assert sums[9][0] == big               # ((0 + big) + 1) + 1 in list order (the stable sort keeps it); 1 + 1 first: big + 2
+    assert sums[5][0] == big + np.float32(2.0)   # piece 0: big + 63 ones = big; piece 1: 1 + 1; one chain over all 66: big
+    k, v = E.projector_references([np.array([0, 0, 1]), np.array([7, 8, 7])], np.arange(6, dtype=np.float32).reshape(3, 2))
+    assert k.tolist() == [0, 0, 1, E.SLOT + 7, E.SLOT + 8, E.SLOT + 7] and v[:, 0].tolist() == [0, 2, 4, 0, 2, 4]
+    k, v = E.text_references([(np.array([0, 3, 3]), np.array([4, 4, 6]))], np.array([1, 0, 0]), np.array([[3.0], [1.0], [6.0]]))
+    assert k.tolist() == [4, 4, 6, 4, 4, 6] and v[:, 0].tolist() == [np.float32(1.0) / np.float32(3.0)] * 3 + [2.0] * 3
+
+
 # ---- C ABI -------------------------------------------------------------------------------------------------------------
 NEW = ["mi_pinsage_project_sizeof", "mi_pinsage_project_workspace_bytes", "mi_pinsage_project_f32",
        "mi_pinsage_project_bwd_workspace_bytes", "mi_pinsage_project_bwd_f32", "mi_pinsage_project_clear_f32", "mi_adam_multi_f32"]
