@@ -4,7 +4,10 @@ reference assigns (pinsage/model.py:52-53) as the projector input.
 
 With ItemFeatures the projector is the reference's LinearProjector over every feature column (pinsage/layers.py:14-46, 90-118:
 an embedding table per integer column, a Linear over the float columns, the id as one more column, summed) on
-mi_pinsage_project_f32 / mi_pinsage_project_bwd_f32 (csrc/pinsage_proj.hip): ItemFeatures, ItemProjector.
+mi_pinsage_project_f32 / mi_pinsage_project_bwd_f32 (csrc/pinsage_proj.hip): ItemFeatures, ItemProjector.  ItemProjector's
+project / project_backward / clear_rows are the one place that issues the projector's C calls (the base part, the text part, their
+workspaces), for the autograd path and for the native iteration (pinsage/native.py) alike; its descriptors are cached and follow a
+replaced parameter or buffer (native_binding.PointerSnapshot).
 
 Heavy ops on the HIP kernels: the Q / W products on mi_gemm_f32 (relu fused), the weighted
 neighbourhood sum on mi_spmm_csr_f32 over the block's destination-sorted CSR with values
@@ -22,6 +25,7 @@ from torch import Tensor, nn
 
 from .. import _lib, ops
 from ..model.layers import Linear
+from ..native_binding import PointerSnapshot
 
 
 class _EmbedRowsFn(t.autograd.Function):
@@ -241,6 +245,18 @@ class _ProjectFn(t.autograd.Function):
         return (None, None, *grads)
 
 
+class _Bound:
+    """What ItemProjector.bind() keeps: the two descriptors, the snapshot of the tensors they point into, the gradient descriptors
+    of the last gradient buffers seen, and the workspaces with the row capacities they were sized for."""
+
+    def __init__(self, projector: "ItemProjector"):
+        self.base = projector.descriptor()
+        self.text = projector.text_descriptor() if projector.n_text else None
+        self.grads_of = self.grads_key = self.g_base = self.g_text = None
+        self.ws, self.rows, self.text_ws = None, -1, {}      # text_ws: with_ids -> (row capacity, workspace, reference bound)
+        self.snap = PointerSnapshot([projector.parameter_list, projector.feature_buffers])
+
+
 class ItemProjector(nn.Module):
     """projector(ids) = id row (if the model has an id table) + one table row per categorical column, in column order,
     + dense[ids] @ W^T + b: one f32 addition chain in that order (mi_pinsage_project_f32).  Tables are [cardinality + 1,
@@ -266,7 +282,7 @@ class ItemProjector(nn.Module):
         self.register_buffer("x", features.categorical, persistent=False)
         self.register_buffer("dense", features.dense, persistent=False)
         self._id = [id_embedding] if id_embedding is not None else []    # a list: PinSAGEModel.proj stays its only registration
-        self._ws: Optional[Tensor] = None
+        self._bound: Optional["_Bound"] = None     # descriptors, workspaces and the pointers they were built from (bind)
         self.n_text = len(features.text)
         if self.n_text:
             self.text_tables = nn.ParameterList([nn.Parameter(t.empty(c.vocab_size, hidden_dims)) for c in features.text])
@@ -275,10 +291,10 @@ class ItemProjector(nn.Module):
             for c, col in enumerate(features.text):
                 self.register_buffer(f"text_ptr_{c}", col.ptr, persistent=False)
                 self.register_buffer(f"text_tok_{c}", col.tok, persistent=False)
+        self._text_buffers = tuple(f"text_{k}_{c}" for c in range(self.n_text) for k in ("ptr", "tok"))
         self.text_vocab = tuple(c.vocab_size for c in features.text)
         self.text_max_len = tuple(c.max_len for c in features.text)
         self.text_nnz = tuple(c.nnz for c in features.text)
-        self._tws: Optional[Tensor] = None
 
     @property
     def id_weight(self) -> Optional[Tensor]:
@@ -356,72 +372,108 @@ class ItemProjector(nn.Module):
             gd.g_w, gd.g_b = grads[0].data_ptr(), grads[1].data_ptr()
         return gd
 
-    def _workspace(self, nbytes: int, device) -> Tensor:
-        if self._ws is None or self._ws.numel() < nbytes or self._ws.device != device:
-            self._ws = t.empty(int(nbytes * 1.25) + 4096, dtype=t.uint8, device=device)
-        return self._ws
+    # ---- the C calls.  This is the one place that knows the base / text branching, the two workspaces and the reference bound:
+    # the autograd path (forward / _ProjectFn.backward) and pinsage.native.NativePinSAGEStep both come through here. ----------------
+    def feature_buffers(self) -> tuple:
+        """The data the descriptors point to beside the parameters, each replaceable on its own."""
+        return (self.x, self.dense) + tuple(getattr(self, name) for name in self._text_buffers)
 
-    @staticmethod
-    def _ids(ids: Optional[Tensor]) -> Optional[Tensor]:
+    def __getstate__(self):    # a copy or a pickle starts without the cache: raw pointers into THIS module's tensors
+        return {**self.__dict__, "_bound": None}
+
+    def bind(self) -> "_Bound":
+        """The descriptors, built once and again when a parameter or a buffer was replaced (.to(device), a new code matrix);
+        the gradient descriptors and the workspaces are dropped with them.  A caller that knows by itself when that happens
+        (the native step: its own snapshot covers the same tensors) binds once and hands the result to the three calls below
+        as `bound`, which then check nothing."""
+        b = self._bound
+        if b is None or not b.snap.current():
+            b = self._bound = _Bound(self)
+        return b
+
+    def _grads(self, b: "_Bound", grads: Sequence[Tensor]):
+        """(mi_item_projector_grads, the text entries' g_tables) over `grads`, kept for as long as the same buffers come.  The
+        same TUPLE again (the native step's, made when its descriptor is built) is taken by identity; any other sequence by
+        its addresses (the autograd path brings fresh buffers with every backward)."""
+        if type(grads) is not tuple or grads is not b.grads_of:
+            key = tuple(g.data_ptr() for g in grads)
+            if key != b.grads_key:
+                b.grads_key, b.g_base, b.g_text = key, self.grads_descriptor(grads), self.text_grads(grads) if self.n_text else None
+            b.grads_of = grads
+        return b.g_base, b.g_text
+
+    def _workspace(self, b: "_Bound", n: int) -> Tensor:
+        """Of mi_pinsage_project_f32 and its backward, sized for a row capacity: the C size queries run when n exceeds it."""
+        if n > b.rows:
+            L, pd, rows = _lib.lib(), ctypes.byref(b.base), max(1024, int(n * 1.25))
+            need = max(int(L.mi_pinsage_project_workspace_bytes(pd, rows)), int(L.mi_pinsage_project_bwd_workspace_bytes(pd, rows)))
+            b.ws, b.rows = t.empty(need, dtype=t.uint8, device=self.parameter_list()[0].device), rows
+        return b.ws
+
+    def _text_workspace(self, b: "_Bound", n: int, with_ids: bool) -> Tuple[Tensor, int]:
+        """(workspace, reference bound) of mi_pinsage_text_bwd_f32: the bound is text_ref_bound of the row capacity, one capacity
+        for calls with ids and one for calls without."""
+        have = b.text_ws.get(with_ids)
+        if have is None or n > have[0]:
+            rows = max(1024, int(n * 1.25))
+            ref_max = self.text_ref_bound(rows, with_ids)
+            need = int(_lib.lib().mi_pinsage_text_bwd_workspace_bytes(ctypes.byref(b.text), rows, ref_max))
+            have = b.text_ws[with_ids] = (rows, t.empty(need, dtype=t.uint8, device=self.parameter_list()[0].device), ref_max)
+        return have[1], have[2]
+
+    def _rows_of(self, ids: Optional[Tensor], n: Optional[int] = None):
+        """(the ids, contiguous; their count; their address): rows `ids`, or None for items 0 .. n - 1 (n = n_items by default)."""
         if ids is None:
-            return None
+            return None, (self.n_items if n is None else int(n)), None
         if ids.dtype != t.int64 or ids.dim() != 1 or not ids.is_cuda:
             raise _lib.MiError("ItemProjector: ids must be a 1-d int64 CUDA tensor")
-        return ids.contiguous()
+        ids = ids.contiguous()
+        return ids, int(ids.numel()), ids.data_ptr()
 
-    def project(self, ids: Optional[Tensor], out: Optional[Tensor] = None, n: Optional[int] = None) -> Tensor:
-        """The forward with no autograd: rows of `ids` (None: items 0 .. n - 1, n = n_items by default) into out [n, hidden]."""
-        ids = self._ids(ids)
-        n = (self.n_items if n is None else int(n)) if ids is None else int(ids.numel())
-        d, L = self.descriptor(), _lib.lib()
-        dev = self.parameter_list()[0].device
+    def project(self, ids: Optional[Tensor], out: Optional[Tensor] = None, n: Optional[int] = None,
+                bound: Optional["_Bound"] = None) -> Tensor:
+        """The forward with no autograd: rows of `ids` (None: items 0 .. n - 1, n = n_items by default) into the first n rows of
+        out [>= n, hidden]."""
+        ids, n, idp = self._rows_of(ids, n)
+        b, L, stream = bound or self.bind(), _lib.lib(), _lib.current_stream()
         if out is None:
-            out = t.empty(n, self.hidden, dtype=t.float32, device=dev)
+            out = t.empty(n, self.hidden, dtype=t.float32, device=self.parameter_list()[0].device)
+        ldo = int(out.stride(0)) if n else self.hidden
         if self.has_base:
-            ws = self._workspace(int(L.mi_pinsage_project_workspace_bytes(ctypes.byref(d), n)), dev)
-            _lib.check(L.mi_pinsage_project_f32(ctypes.byref(d), n, ids.data_ptr() if ids is not None else None, out.data_ptr(),
-                                                int(out.stride(0)) if n else self.hidden, ws.data_ptr(), ws.numel(),
-                                                _lib.current_stream()), "mi_pinsage_project_f32")
+            ws = self._workspace(b, n)
+            _lib.check(L.mi_pinsage_project_f32(ctypes.byref(b.base), n, idp, out.data_ptr(), ldo, ws.data_ptr(), ws.numel(), stream),
+                       "mi_pinsage_project_f32")
         if self.n_text:
-            td = self.text_descriptor()
-            _lib.check(L.mi_pinsage_text_f32(ctypes.byref(td), n, ids.data_ptr() if ids is not None else None, out.data_ptr(),
-                                             int(out.stride(0)) if n else self.hidden, 1 if self.has_base else 0,
-                                             _lib.current_stream()), "mi_pinsage_text_f32")
+            _lib.check(L.mi_pinsage_text_f32(ctypes.byref(b.text), n, idp, out.data_ptr(), ldo, 1 if self.has_base else 0, stream),
+                       "mi_pinsage_text_f32")
         return out
 
-    def project_backward(self, ids: Optional[Tensor], g: Tensor, grads: Sequence[Tensor]) -> None:
-        """g = dL/d project(ids) [n, hidden] into `grads` (parameter_list() order): looked-up table rows are written, others left."""
-        ids = self._ids(ids)
-        n = self.n_items if ids is None else int(ids.numel())
-        d, gd, L = self.descriptor(), self.grads_descriptor(grads), _lib.lib()
+    def project_backward(self, ids: Optional[Tensor], g: Tensor, grads: Sequence[Tensor], bound: Optional["_Bound"] = None) -> None:
+        """g = dL/d project(ids), the first n rows of [>= n, hidden], into `grads` (parameter_list() order): looked-up table rows
+        are written, others left."""
+        ids, n, idp = self._rows_of(ids)
+        b, L, stream = bound or self.bind(), _lib.lib(), _lib.current_stream()
+        gd, tg = self._grads(b, grads)
+        ldg = int(g.stride(0)) if n else self.hidden
         if self.has_base:
-            ws = self._workspace(int(L.mi_pinsage_project_bwd_workspace_bytes(ctypes.byref(d), n)), g.device)
-            _lib.check(L.mi_pinsage_project_bwd_f32(ctypes.byref(d), ctypes.byref(gd), n, ids.data_ptr() if ids is not None else None,
-                                                    g.data_ptr(), int(g.stride(0)) if n else self.hidden, ws.data_ptr(), ws.numel(),
-                                                    _lib.current_stream()), "mi_pinsage_project_bwd_f32")
+            ws = self._workspace(b, n)
+            _lib.check(L.mi_pinsage_project_bwd_f32(ctypes.byref(b.base), ctypes.byref(gd), n, idp, g.data_ptr(), ldg, ws.data_ptr(),
+                                                    ws.numel(), stream), "mi_pinsage_project_bwd_f32")
         if self.n_text:
-            td, tg, bound = self.text_descriptor(), self.text_grads(grads), self.text_ref_bound(n, ids is not None)
-            need = int(L.mi_pinsage_text_bwd_workspace_bytes(ctypes.byref(td), n, bound))
-            if self._tws is None or self._tws.numel() < need or self._tws.device != g.device:
-                self._tws = t.empty(int(need * 1.25) + 4096, dtype=t.uint8, device=g.device)
-            _lib.check(L.mi_pinsage_text_bwd_f32(ctypes.byref(td), tg, n, ids.data_ptr() if ids is not None else None, g.data_ptr(),
-                                                 int(g.stride(0)) if n else self.hidden, bound, self._tws.data_ptr(),
-                                                 self._tws.numel(), _lib.current_stream()), "mi_pinsage_text_bwd_f32")
+            ws, ref_max = self._text_workspace(b, n, ids is not None)
+            _lib.check(L.mi_pinsage_text_bwd_f32(ctypes.byref(b.text), tg, n, idp, g.data_ptr(), ldg, ref_max, ws.data_ptr(), ws.numel(),
+                                                 stream), "mi_pinsage_text_bwd_f32")
 
-    def clear_rows(self, ids: Optional[Tensor], grads: Sequence[Tensor]) -> None:
+    def clear_rows(self, ids: Optional[Tensor], grads: Sequence[Tensor], bound: Optional["_Bound"] = None) -> None:
         """The table rows project_backward(ids, ...) wrote, back to zero (mi_pinsage_project_clear_f32)."""
-        ids = self._ids(ids)
-        n = self.n_items if ids is None else int(ids.numel())
-        d, gd = self.descriptor(), self.grads_descriptor(grads)
+        ids, n, idp = self._rows_of(ids)
+        b, L, stream = bound or self.bind(), _lib.lib(), _lib.current_stream()
+        gd, tg = self._grads(b, grads)
         if self.has_base:
-            _lib.check(_lib.lib().mi_pinsage_project_clear_f32(ctypes.byref(d), ctypes.byref(gd), n,
-                                                               ids.data_ptr() if ids is not None else None, _lib.current_stream()),
+            _lib.check(L.mi_pinsage_project_clear_f32(ctypes.byref(b.base), ctypes.byref(gd), n, idp, stream),
                        "mi_pinsage_project_clear_f32")
         if self.n_text:
-            td = self.text_descriptor()
-            _lib.check(_lib.lib().mi_pinsage_text_clear_f32(ctypes.byref(td), self.text_grads(grads), n,
-                                                            ids.data_ptr() if ids is not None else None, _lib.current_stream()),
-                       "mi_pinsage_text_clear_f32")
+            _lib.check(L.mi_pinsage_text_clear_f32(ctypes.byref(b.text), tg, n, idp, stream), "mi_pinsage_text_clear_f32")
 
     def forward(self, ids: Optional[Tensor] = None) -> Tensor:
         return _ProjectFn.apply(self, ids, *self.parameter_list())

@@ -17,7 +17,11 @@ mi_adam_multi_f32 applies torch.optim.Adam's dense update to every tensor; the t
 (mi_pinsage_project_clear_f32), so the table gradients stay all-zero between iterations as the id table's does.  Text columns
 (ItemFeatures(text=...)) are one more pair of calls beside those: mi_pinsage_text_f32 after the projector's forward (accumulating
 into its rows; alone for a text-only model), mi_pinsage_text_bwd_f32 after its backward, mi_pinsage_text_clear_f32 after its
-clear; the text tables are ordinary entries of mi_adam_multi_f32's list.
+clear; the text tables are ordinary entries of mi_adam_multi_f32's list.  All of those calls are ItemProjector's own methods
+(project / project_backward / clear_rows, pinsage/model.py) over its cached descriptors and workspaces: the step only says when.
+
+The host side shared with the ranker's executor — Adam's state, the flat gradient buffer, the stale-descriptor test, the
+collective decline — is native_binding.py.
 """
 from __future__ import annotations
 
@@ -30,7 +34,21 @@ from torch import Tensor
 from .. import _lib
 from .._lib import PinsageModel, PinsageStepBatch
 from ..model.layers import _ones4
+from ..native_binding import (PEER_DECLINED, PointerSnapshot, adam_unsupported_reason, all_ranks_take_it, bind_param,
+                              bump_adam_steps, collective_prepare, ensure_adam_state, flat_grad_views)
 from .model import PinSAGEModel
+
+
+def _conv_params(cv):
+    return cv.Q.weight, cv.Q.bias, cv.W.weight, cv.W.bias
+
+
+def _fill_convs(d: PinsageModel, model: PinSAGEModel, with_grads: bool) -> None:
+    for l, cv in enumerate(model.convs):
+        c = d.conv[l]
+        c.q_w, c.q_b, c.w_w, c.w_b = (x.data_ptr() for x in _conv_params(cv))
+        if with_grads:
+            c.g_q_w, c.g_q_b, c.g_w_w, c.g_w_b = (x.grad.data_ptr() for x in _conv_params(cv))
 
 
 class NativePinSAGEStep:
@@ -57,6 +75,7 @@ class NativePinSAGEStep:
         self.seed = int(t.initial_seed() if seed is None else seed) & ((1 << 64) - 1)
         self.iteration = 0
         self._desc: Optional[PinsageModel] = None
+        self._snapshot = None      # native_binding.PointerSnapshot of what _desc was built from
         self._keep: list = []
         self._ws: Optional[Tensor] = None
         self._adam_step = 0
@@ -69,11 +88,10 @@ class NativePinSAGEStep:
     def unsupported_reason(model, optimizer) -> Optional[str]:
         if not isinstance(model, PinSAGEModel):
             return "not a PinSAGEModel"
-        if type(optimizer) is not t.optim.Adam or len(optimizer.param_groups) != 1:
-            return "optimizer is not a single-group torch.optim.Adam"
+        why = adam_unsupported_reason(optimizer)
+        if why:
+            return why
         g = optimizer.param_groups[0]
-        if g.get("amsgrad") or g.get("weight_decay", 0) or g.get("maximize") or g.get("capturable") or g.get("differentiable"):
-            return "Adam options (amsgrad / weight_decay / maximize / capturable)"
         params = list(model.parameters())
         if len(g["params"]) != len(params) or any(a is not b for a, b in zip(g["params"], params)):
             return "the optimizer's parameter list is not model.parameters()"
@@ -101,157 +119,57 @@ class NativePinSAGEStep:
 
     # ------------------------------------------------------------------------------------------
     def _build(self) -> PinsageModel:
+        """The executor's descriptor.  Id-only: the id table with its gradient and moments apart (proj / g_proj / m_proj / v_proj),
+        every other tensor in `params`.  Featured: over a COMPACT projected table (set per batch, _prepare) — its params are the
+        layers' only, it never applies Adam and never touches g_proj / m_proj / v_proj (rows_out mode); every tensor of the
+        optimizer's group is in mi_adam_multi_f32's flat list instead."""
         model, opt = self.model, self.optimizer
         d = PinsageModel()
         keep = self._keep = []
         group = opt.param_groups[0]
+        params = group["params"]
         if self.data_parallel:   # every gradient except the two dense tables': views of one flat buffer (one all-reduce)
-            small = [p for p in group["params"] if p is not model.proj.weight and p is not model.bias]
-            offs, total = [], 0
-            for p in small:
-                offs.append(total)
-                total += (p.numel() + 3) // 4 * 4
-            flat = self._flat_small
-            if flat is None or flat.numel() != total or any(
-                    p.grad is None or p.grad.data_ptr() != flat.data_ptr() + 4 * o for p, o in zip(small, offs)):
-                flat = t.zeros(total, dtype=t.float32, device=model.proj.weight.device)
-                for p, o in zip(small, offs):
-                    p.grad = flat[o: o + p.numel()].view(p.shape)
-                self._flat_small = flat
-            keep.append(flat)
-        for p in group["params"]:
+            small = [p for p in params if p is not model.proj.weight and p is not model.bias]
+            self._flat_small = flat_grad_views(small, self._flat_small, keep_values=False)
+            keep.append(self._flat_small)
+        for p in params:
             if p.grad is None or p.grad.shape != p.shape or not p.grad.is_contiguous():
                 p.grad = t.zeros_like(p)
-            st = opt.state[p]
-            if len(st) == 0:   # created the way torch.optim.Adam creates it on its first step
-                on_device = bool(group.get("fused") or group.get("capturable"))
-                st["step"] = t.zeros((), dtype=t.float32, device=p.device) if on_device else t.tensor(0.0, dtype=t.float32)
-                st["exp_avg"] = t.zeros_like(p, memory_format=t.preserve_format)
-                st["exp_avg_sq"] = t.zeros_like(p, memory_format=t.preserve_format)
+            st = ensure_adam_state(opt, group, p)
             keep += [p.grad, st["exp_avg"], st["exp_avg_sq"]]
-        bias = model.bias
-        if model.featured:
-            return self._build_featured(d)
-        proj = model.proj.weight
-        proj.grad.zero_()      # the two dense buffers the executor keeps all-zero between iterations
-        bias.grad.zero_()
-        d.n_layers, d.hidden, d.n_items = len(model.convs), int(proj.shape[1]), int(bias.shape[0])
-        if proj.shape[0] != d.n_items + 1:
-            raise ValueError("NativePinSAGEStep: projector table and scorer bias disagree on the item count")
-        sp = opt.state[proj]
-        d.proj, d.g_proj, d.m_proj, d.v_proj = proj.data_ptr(), proj.grad.data_ptr(), sp["exp_avg"].data_ptr(), sp["exp_avg_sq"].data_ptr()
-        d.bias, d.g_bias = bias.data_ptr(), bias.grad.data_ptr()
-        for l, cv in enumerate(model.convs):
-            c = d.conv[l]
-            c.q_w, c.q_b, c.w_w, c.w_b = (x.data_ptr() for x in (cv.Q.weight, cv.Q.bias, cv.W.weight, cv.W.bias))
-            c.g_q_w, c.g_q_b, c.g_w_w, c.g_w_b = (x.grad.data_ptr() for x in (cv.Q.weight, cv.Q.bias, cv.W.weight, cv.W.bias))
-        i = 0
-        for p in group["params"]:
-            if p is proj:
-                continue
-            st = opt.state[p]
-            q = d.params[i]
-            q.p, q.g, q.m, q.v, q.n = p.data_ptr(), p.grad.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), p.numel()
-            i += 1
-        d.n_params = i
-        steps = [opt.state[p]["step"] for p in group["params"]]
-        self._adam_step = int(steps[0]) if steps else 0
-        return d
-
-    def _build_featured(self, d: PinsageModel) -> PinsageModel:
-        """The executor's descriptor over a COMPACT projected table (set per batch, _prepare): its params are the layers' only,
-        it never applies Adam and never touches g_proj / m_proj / v_proj (rows_out mode).  Also the flat parameter list of
-        mi_adam_multi_f32: every tensor of the optimizer's group."""
-        model, opt = self.model, self.optimizer
-        group = opt.param_groups[0]
-        pr = model.projector
-        for p in pr.parameter_list():
-            if p is not pr.weight and p is not pr.bias:
-                p.grad.zero_()     # the table gradients (id and text tables included) stay all-zero between iterations
-        model.bias.grad.zero_()
+        bias, pr = model.bias, (model.projector if model.featured else None)
+        # the dense buffers kept all-zero between iterations: the scorer bias's and every table's (id and text tables included)
+        tables = [model.proj.weight] if pr is None else [p for p in pr.parameter_list() if p is not pr.weight and p is not pr.bias]
+        for p in tables + [bias]:
+            p.grad.zero_()
         d.n_layers, d.hidden, d.n_items = len(model.convs), model.hidden, model.n_items
-        d.bias, d.g_bias = model.bias.data_ptr(), model.bias.grad.data_ptr()
-        i = 0
-        for l, cv in enumerate(model.convs):
-            c = d.conv[l]
-            c.q_w, c.q_b, c.w_w, c.w_b = (x.data_ptr() for x in (cv.Q.weight, cv.Q.bias, cv.W.weight, cv.W.bias))
-            c.g_q_w, c.g_q_b, c.g_w_w, c.g_w_b = (x.grad.data_ptr() for x in (cv.Q.weight, cv.Q.bias, cv.W.weight, cv.W.bias))
-            for p in (cv.Q.weight, cv.Q.bias, cv.W.weight, cv.W.bias):
-                st = opt.state[p]
-                q = d.params[i]
-                q.p, q.g, q.m, q.v, q.n = p.data_ptr(), p.grad.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), p.numel()
-                i += 1
-        d.n_params = i
-        flat = (_lib.RankerParam * len(group["params"]))()
-        for q, p in zip(flat, group["params"]):
-            st = opt.state[p]
-            q.p, q.g, q.m, q.v, q.n = p.data_ptr(), p.grad.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), p.numel()
-        self._flat_params = flat
-        self._proj_grads = [p.grad for p in pr.parameter_list()]
-        self._pdesc, self._pgrads = pr.descriptor(), pr.grads_descriptor(self._proj_grads)
-        self._pws_rows = -1
-        if pr.n_text:
-            self._tdesc, self._tgrads = pr.text_descriptor(), pr.text_grads(self._proj_grads)
-            self._tws_rows = -1
-        steps = [opt.state[p]["step"] for p in group["params"]]
-        self._adam_step = int(steps[0]) if steps else 0
+        d.bias, d.g_bias = bias.data_ptr(), bias.grad.data_ptr()
+        _fill_convs(d, model, with_grads=True)
+        if pr is None:
+            proj = model.proj.weight
+            d.hidden, d.n_items = int(proj.shape[1]), int(bias.shape[0])
+            if proj.shape[0] != d.n_items + 1:
+                raise ValueError("NativePinSAGEStep: projector table and scorer bias disagree on the item count")
+            sp = opt.state[proj]
+            d.proj, d.g_proj, d.m_proj, d.v_proj = proj.data_ptr(), proj.grad.data_ptr(), sp["exp_avg"].data_ptr(), sp["exp_avg_sq"].data_ptr()
+            mine = [p for p in params if p is not proj]
+        else:
+            mine = [p for cv in model.convs for p in _conv_params(cv)]
+            self._flat_params = (_lib.RankerParam * len(params))()
+            for q, p in zip(self._flat_params, params):
+                bind_param(q, p, p.grad, opt.state[p])
+            # the projector's descriptors, checked here and not again until this descriptor is rebuilt (_snapshot_now covers the
+            # same tensors); the gradient buffers as one tuple, which the projector recognises by identity
+            self._proj_bound, self._proj_grads = pr.bind(), tuple(p.grad for p in pr.parameter_list())
+        for q, p in zip(d.params, mine):
+            bind_param(q, p, p.grad, opt.state[p])
+        d.n_params = len(mine)
+        self._adam_step = int(opt.state[params[0]]["step"]) if params else 0
         return d
 
-    def _proj_workspace(self, n: int, device) -> Tensor:
-        if n > getattr(self, "_pws_rows", -1):
-            L, pd = _lib.lib(), ctypes.byref(self._pdesc)
-            rows = max(1024, int(n * 1.25))
-            need = max(int(L.mi_pinsage_project_workspace_bytes(pd, rows)), int(L.mi_pinsage_project_bwd_workspace_bytes(pd, rows)))
-            self._pws, self._pws_rows = t.empty(need, dtype=t.uint8, device=device), rows
-        return self._pws
-
-    def _text_workspace(self, n: int, device):
-        """(workspace, reference bound) for a block of n rows: the bound is the row capacity times the longest bags, grown on
-        demand as _rows grows."""
-        if n > getattr(self, "_tws_rows", -1):
-            rows = max(1024, int(n * 1.25))
-            self._tref_max = self.model.projector.text_ref_bound(rows, True)
-            need = int(_lib.lib().mi_pinsage_text_bwd_workspace_bytes(ctypes.byref(self._tdesc), rows, self._tref_max))
-            self._tws, self._tws_rows = t.empty(need, dtype=t.uint8, device=device), rows
-        return self._tws, self._tref_max
-
-    def _current(self, d: PinsageModel) -> bool:
-        """The descriptor holds raw pointers: rebuilt when a parameter, gradient or optimizer-state tensor was replaced."""
-        group = self.optimizer.param_groups[0]
-        if self.model.featured:
-            flat = getattr(self, "_flat_params", None)
-            if flat is None or len(flat) != len(group["params"]):
-                return False
-            for q, p in zip(flat, group["params"]):
-                st = self.optimizer.state.get(p)
-                if p.grad is None or not st or (q.p, q.g, q.m, q.v) != (p.data_ptr(), p.grad.data_ptr(), st["exp_avg"].data_ptr(),
-                                                                        st["exp_avg_sq"].data_ptr()):
-                    return False
-            pr = self.model.projector
-            if (self._pdesc.x, self._pdesc.dense) != (pr.x.data_ptr() if pr.x is not None else None,
-                                                      pr.dense.data_ptr() if pr.dense is not None else None):
-                return False
-            for c in range(pr.n_text):
-                if (self._tdesc.ptr[c], self._tdesc.tok[c]) != (getattr(pr, f"text_ptr_{c}").data_ptr(),
-                                                                getattr(pr, f"text_tok_{c}").data_ptr()):
-                    return False
-            return True
-        proj = self.model.proj.weight
-        i = 0
-        for p in group["params"]:
-            st = self.optimizer.state.get(p)
-            if p.grad is None or not st:
-                return False
-            if p is proj:
-                if (d.proj, d.g_proj, d.m_proj, d.v_proj) != (p.data_ptr(), p.grad.data_ptr(), st["exp_avg"].data_ptr(),
-                                                              st["exp_avg_sq"].data_ptr()):
-                    return False
-                continue
-            q = d.params[i]
-            if (q.p, q.g, q.m, q.v) != (p.data_ptr(), p.grad.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr()):
-                return False
-            i += 1
-        return i == d.n_params
+    def _snapshot_now(self) -> PointerSnapshot:
+        """Every tensor of the optimizer's group with its gradient and moments; featured: the projector's data buffers too."""
+        return PointerSnapshot([self.model.projector.feature_buffers] if self.model.featured else [], optimizer=self.optimizer)
 
     # ------------------------------------------------------------------------------------------
     def _prepare(self, batch: dict):
@@ -277,8 +195,9 @@ class NativePinSAGEStep:
         if pu.numel() == 0 or nu.data_ptr() != pu.data_ptr():
             self.declined = "no pairs / negative pairs with their own heads"
             return None
-        if self._desc is None or not self._current(self._desc):
+        if self._desc is None or not self._snapshot.current():
             self._desc = self._build()
+            self._snapshot = self._snapshot_now()
         elif self.keep_grads:      # the previous call left its rows in the dense buffers
             for p in ([model.bias] + model.projector.parameter_list()) if model.featured else (model.proj.weight, model.bias):
                 p.grad.zero_()
@@ -327,9 +246,7 @@ class NativePinSAGEStep:
         need = int(L.mi_pinsage_step_workspace_bytes(ctypes.byref(d), ctypes.byref(b)))
         if self._ws is None or self._ws.numel() < need:
             self._ws = t.empty(int(need * 1.25) + (1 << 20), dtype=t.uint8, device=seeds.device)
-        import torch.distributed as dist
-        if self.data_parallel and dist.is_initialized() and dist.get_world_size(self.group) > 1:
-            # the validation pass on its own only where the ranks must agree before anything is enqueued
+        if self._world() > 1:      # the validation pass on its own only where the ranks must agree before anything is enqueued
             rc = L.mi_pinsage_step_check(ctypes.byref(d), ctypes.byref(b), self._ws.data_ptr(), self._ws.numel())
             if rc == _lib.MI_ERR_UNSUPPORTED:
                 self.declined = "mi_pinsage_step_f32: MI_ERR_UNSUPPORTED (shape outside the executor's)"
@@ -338,43 +255,34 @@ class NativePinSAGEStep:
             _lib.check(rc, "mi_pinsage_step_check")
         return d, b, loss, (keep, ones, seeds, pu, pv, nv)
 
+    def _world(self) -> int:
+        import torch.distributed as dist
+        return dist.get_world_size(self.group) if (self.data_parallel and dist.is_initialized()) else 1
+
+    def _all_ranks_take_it(self, mine: bool, device) -> bool:
+        return all_ranks_take_it(mine, device, self.group)
+
     def step(self, batch: dict) -> Optional[Tensor]:
         """One iteration on a PinSAGESampler batch; the loss as a 1-element device tensor, or None when declined (nothing
-        has been enqueued then).  Data-parallel with more than one rank: the decline is COLLECTIVE — one all-reduce(MIN) of
-        a 1-int flag before anything is enqueued, so that a rank whose batch lies outside the executor's shapes does not
-        leave its peers waiting in the row exchange; every rank returns None together."""
-        import torch.distributed as dist
+        has been enqueued then).  Data-parallel with more than one rank: the decline is COLLECTIVE (native_binding), so that a rank
+        whose batch lies outside the executor's shapes, or whose _prepare raises, does not leave its peers waiting in the row
+        exchange; every rank returns None together."""
         self.declined = None
-        prep = self._prepare(batch)
-        world = dist.get_world_size(self.group) if (self.data_parallel and dist.is_initialized()) else 1
-        if world > 1:
-            flag = t.tensor([1 if prep is not None else 0], dtype=t.int32, device=self.model.proj.weight.device)
-            dist.all_reduce(flag, op=dist.ReduceOp.MIN, group=self.group)
-            if not int(flag.item()):
-                if prep is not None:
-                    self.declined = "a peer rank declined its batch (collective decision: every rank takes the fallback)"
-                    self._desc = None
-                return None
-        elif prep is None:
+        world = self._world()
+        prep, go = collective_prepare(world, lambda mine: self._all_ranks_take_it(mine, self.model.bias.device),
+                                      lambda: self._prepare(batch))
+        if not go:
+            if prep is not None:
+                self.declined = PEER_DECLINED
+                self._desc = None
             return None
         d, b, loss, _keep = prep
         group = self.optimizer.param_groups[0]
         L = _lib.lib()
-        featured = self.model.featured
-        if featured:
-            # the cached descriptors (rebuilt with the executor's, _current): no per-call ctypes fill on this path
-            ids0 = batch["blocks"][0]["src_ids"]
-            n0, H = int(ids0.numel()), self.model.hidden
-            pr = self.model.projector
-            base, text = pr.has_base, pr.n_text > 0
-            if base:
-                pd, pg, pws = ctypes.byref(self._pdesc), ctypes.byref(self._pgrads), self._proj_workspace(n0, ids0.device)
-                _lib.check(L.mi_pinsage_project_f32(pd, n0, ids0.data_ptr(), self._rows[0].data_ptr(), H, pws.data_ptr(), pws.numel(),
-                                                    _lib.current_stream()), "mi_pinsage_project_f32")
-            if text:
-                td, (tws, tref_max) = ctypes.byref(self._tdesc), self._text_workspace(n0, ids0.device)
-                _lib.check(L.mi_pinsage_text_f32(td, n0, ids0.data_ptr(), self._rows[0].data_ptr(), H, 1 if base else 0,
-                                                 _lib.current_stream()), "mi_pinsage_text_f32")
+        pr = self.model.projector if self.model.featured else None
+        if pr is not None:
+            ids0, rows, bound = batch["blocks"][0]["src_ids"], self._rows, self._proj_bound
+            pr.project(ids0, out=rows[0], bound=bound)
         rc = L.mi_pinsage_step_f32(ctypes.byref(d), ctypes.byref(b), self._ws.data_ptr(), self._ws.numel(), _lib.current_stream())
         if rc == _lib.MI_ERR_UNSUPPORTED:
             if world > 1:                      # cannot happen: mi_pinsage_step_check took the same descriptors
@@ -386,35 +294,20 @@ class NativePinSAGEStep:
         self.iteration += 1
         if self.data_parallel:
             self._exchange_and_apply(d)
-        if featured:
+        if pr is not None:
             seeds = batch["seeds"]
-            if base:
-                _lib.check(L.mi_pinsage_project_bwd_f32(pd, pg, n0, ids0.data_ptr(), self._rows[1].data_ptr(), H, pws.data_ptr(),
-                                                        pws.numel(), _lib.current_stream()), "mi_pinsage_project_bwd_f32")
-            if text:
-                _lib.check(L.mi_pinsage_text_bwd_f32(td, self._tgrads, n0, ids0.data_ptr(), self._rows[1].data_ptr(), H, tref_max,
-                                                     tws.data_ptr(), tws.numel(), _lib.current_stream()), "mi_pinsage_text_bwd_f32")
+            pr.project_backward(ids0, rows[1], self._proj_grads, bound=bound)
             gb = self.model.bias.grad.view(-1)
-            gb.index_copy_(0, seeds, self._rows[2].view(-1)[: seeds.numel()])     # the seeds are distinct
+            gb.index_copy_(0, seeds, rows[2].view(-1)[: seeds.numel()])     # the seeds are distinct
             if not self.keep_grads:
                 _lib.check(L.mi_adam_multi_f32(self._flat_params, len(self._flat_params), float(group["lr"]),
                                                float(group["betas"][0]), float(group["betas"][1]), float(group["eps"]),
                                                self._adam_step + 1, _lib.current_stream()), "mi_adam_multi_f32")
-                if base:
-                    _lib.check(L.mi_pinsage_project_clear_f32(pd, pg, n0, ids0.data_ptr(), _lib.current_stream()),
-                               "mi_pinsage_project_clear_f32")
-                if text:
-                    _lib.check(L.mi_pinsage_text_clear_f32(td, self._tgrads, n0, ids0.data_ptr(), _lib.current_stream()),
-                               "mi_pinsage_text_clear_f32")
+                pr.clear_rows(ids0, self._proj_grads, bound=bound)
                 gb.index_fill_(0, seeds, 0.0)
         if not self.keep_grads:
             self._adam_step += 1
-            steps = [self.optimizer.state[q]["step"] for q in group["params"]]
-            if steps and steps[0].is_cuda:
-                t._foreach_add_(steps, 1)
-            else:
-                for s in steps:
-                    s += 1
+            bump_adam_steps([self.optimizer.state[q]["step"] for q in group["params"]])
         return loss
 
     # ------------------------------------------------------------------------------------------
@@ -491,7 +384,7 @@ def embed_items(model: PinSAGEModel, sampler, step: int) -> Optional[Tensor]:
         return None
     hidden, n_items = model.hidden, model.n_items
     dev = model.bias.device
-    params = ([] if model.featured else [model.proj.weight]) + [x for cv in model.convs for x in (cv.Q.weight, cv.Q.bias, cv.W.weight, cv.W.bias)]
+    params = ([] if model.featured else [model.proj.weight]) + [x for cv in model.convs for x in _conv_params(cv)]
     if (hidden % 4 or hidden > 128 or not (1 <= len(model.convs) <= _lib.MI_PINSAGE_MAX_LAYERS) or sampler.T > 16
             or n_items != sampler.num_items or len(model.convs) != sampler.n_layers):
         return None
@@ -508,9 +401,7 @@ def embed_items(model: PinSAGEModel, sampler, step: int) -> Optional[Tensor]:
     d = PinsageModel()
     d.n_layers, d.hidden, d.n_items = len(model.convs), hidden, n_items
     d.proj = proj.data_ptr()
-    for l, cv in enumerate(model.convs):
-        c = d.conv[l]
-        c.q_w, c.q_b, c.w_w, c.w_b = (x.data_ptr() for x in (cv.Q.weight, cv.Q.bias, cv.W.weight, cv.W.bias))
+    _fill_convs(d, model, with_grads=False)
     L = _lib.lib()
     out = t.empty(n_items, hidden, dtype=t.float32, device=proj.device)
     ws = t.empty(int(L.mi_pinsage_embed_items_workspace_bytes(n_items, hidden, sampler.T)), dtype=t.uint8, device=proj.device)

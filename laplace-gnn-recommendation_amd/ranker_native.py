@@ -10,6 +10,10 @@ multi-tensor Adam update included: no at::native kernel is left in the loop.
 The model, its parameters / buffers / state_dict and the optimizer object stay torch's own: gradients land in
 `param.grad`, Adam's moments in `optimizer.state[p]["exp_avg" / "exp_avg_sq"]`, its step count in `state[p]["step"]`.
 Shapes the executor does not take (MI_ERR_UNSUPPORTED, nothing enqueued) fall to FusedRankerStep / autograd.
+
+The training step and NativeRankerForward fill the model half of the descriptor with one function (_fill_model); what this host
+side shares with PinSAGE's executor (Adam's state, the flat gradient buffer, the stale-descriptor test, the collective decline) is
+native_binding.py.
 """
 from __future__ import annotations
 
@@ -24,7 +28,64 @@ from . import _lib, ops
 from ._lib import RankerBatch, RankerModel
 from .model.encoder_decoder import Encoder_Decoder_Model, _key
 from .model.layers import Linear, SAGEConv, _ones4
+from .native_binding import (PEER_DECLINED, PointerSnapshot, adam_unsupported_reason, all_ranks_take_it, bind_param,
+                             bump_adam_steps, collective_prepare, ensure_adam_state, flat_grad_views)
 from .utils.constants import Constants
+
+_NODES = (Constants.node_user, Constants.node_item)
+_NORMS = ("encoder_layer_norm_customer", "encoder_layer_norm_article")
+
+
+def _fill_model(d: RankerModel, model: Encoder_Decoder_Model, grad_of=None) -> None:
+    """The model half of a mi_ranker_model: tables, convs, norms, decoder.  grad_of(parameter) -> the address of its gradient
+    (the training step); None for the forward alone, which has no gradients and leaves num_batches_tracked unset."""
+    enc, dec = model.encoder, model.decoder
+    d.n_enc_layers, d.n_dec_layers = len(enc.layers), len(dec.layers)
+    first = next(iter(enc.layers[0].values()))
+    d.aggr = 1 if first.aggr == "mean" else 0
+    d.batch_normalize = 1 if model.batch_normalize else 0
+    d.max_norm = 1.0
+    for ti, key in enumerate(_NODES):
+        tables = model.embedding_layers[key]
+        d.n_cols[ti] = len(tables)
+        for c, tb in enumerate(tables):
+            if not tb.is_contiguous():
+                raise ValueError("embedding tables must be contiguous")
+            d.tables[ti][c], d.table_rows[ti][c], d.dims[ti][c] = tb.data_ptr(), int(tb.shape[0]), int(tb.shape[1])
+    for l, convs in enumerate(enc.layers):
+        for r, et in enumerate((Constants.edge_key, Constants.rev_edge_key)):
+            conv = convs[_key(tuple(et))]
+            cv = d.conv[l][r]
+            cv.w_l, cv.w_r = conv.lin_l.weight.data_ptr(), conv.lin_r.weight.data_ptr()
+            if conv.lin_l.bias is not None:
+                cv.b_l = conv.lin_l.bias.data_ptr()
+            if grad_of is not None:
+                cv.gw_l, cv.gw_r = grad_of(conv.lin_l.weight), grad_of(conv.lin_r.weight)
+                if conv.lin_l.bias is not None:
+                    cv.gb_l = grad_of(conv.lin_l.bias)
+            cv.c_out, cv.c_src = (int(x) for x in conv.lin_l.weight.shape)
+            cv.c_dst = int(conv.lin_r.weight.shape[1])
+    for ti, name in enumerate(_NORMS):
+        bn, nm = getattr(model, name), d.norm[ti]
+        if bn.weight is not None:
+            nm.gamma, nm.beta = bn.weight.data_ptr(), bn.bias.data_ptr()
+            if grad_of is not None:
+                nm.g_gamma, nm.g_beta = grad_of(bn.weight), grad_of(bn.bias)
+        if bn.track_running_stats and bn.running_mean is not None:
+            nm.running_mean, nm.running_var = bn.running_mean.data_ptr(), bn.running_var.data_ptr()
+            if grad_of is not None:
+                nm.num_batches_tracked = bn.num_batches_tracked.data_ptr()
+        nm.momentum, nm.eps = float(bn.momentum if bn.momentum is not None else 0.1), float(bn.eps)
+    for j, layer in enumerate(dec.layers):
+        ln = d.dec[j]
+        ln.w = layer.weight.data_ptr()
+        if layer.bias is not None:
+            ln.b = layer.bias.data_ptr()
+        if grad_of is not None:
+            ln.gw = grad_of(layer.weight)
+            if layer.bias is not None:
+                ln.gb = grad_of(layer.bias)
+        ln.out, ln.in_ = (int(x) for x in layer.weight.shape)
 
 
 class NativeRankerStep:
@@ -47,7 +108,7 @@ class NativeRankerStep:
         self.seed = int(t.initial_seed() if seed is None else seed) & ((1 << 64) - 1)
         self.iteration = 0
         self._desc: Optional[RankerModel] = None
-        self._snapshot = None      # the pointers the descriptor was built from, as Python ints (see _params_current)
+        self._snapshot = None      # native_binding.PointerSnapshot of every tensor the descriptor points into (_build)
         self._keep = []            # tensors the descriptor points into
         self._ws: Optional[Tensor] = None
         self._ws_dims = None       # the largest (customers, articles, edges, label edges) the workspace was sized for
@@ -73,11 +134,10 @@ class NativeRankerStep:
         why = NativeRankerStep.model_unsupported_reason(model)
         if why:
             return why
-        if type(optimizer) is not t.optim.Adam or len(optimizer.param_groups) != 1:
-            return "optimizer other than a single-group torch.optim.Adam"
+        why = adam_unsupported_reason(optimizer)
+        if why:
+            return why
         g = optimizer.param_groups[0]
-        if g.get("amsgrad") or g.get("weight_decay", 0) or g.get("maximize") or g.get("capturable") or g.get("differentiable"):
-            return "Adam options (amsgrad / weight_decay / maximize / capturable)"
         if isinstance(g["lr"], Tensor):
             return "tensor learning rate"
         if len(g["params"]) > _lib.MI_RANKER_MAX_PARAMS or any(p.dtype != t.float32 or not p.is_cuda for p in g["params"]):
@@ -122,30 +182,18 @@ class NativeRankerStep:
 
     # ------------------------------------------------------------------------------------------
     def _build(self) -> RankerModel:
+        """The descriptor holds raw pointers: built once, and again when a parameter, gradient, optimizer-state tensor, BatchNorm
+        buffer or embedding table was replaced (zero_grad(set_to_none=True), model.to(...), load of a new optimizer state, ...) —
+        self._snapshot says when."""
         model, opt = self.model, self.optimizer
-        enc, dec = model.encoder, model.decoder
         d = RankerModel()
         keep = self._keep = []
-
-        # every gradient is a view into one flat buffer (16-byte aligned pieces): a data-parallel caller exchanges it in
-        # one collective; parameters that are not the optimizer's keep an allocation of their own
-        plist = opt.param_groups[0]["params"]
-        offs, total = {}, 0
-        for p in plist:
-            offs[id(p)] = total
-            total += (p.numel() + 3) // 4 * 4
-        flat = self.flat_grads
-        ok = flat is not None and flat.numel() == total and all(
-            p.grad is not None and p.grad.data_ptr() == flat.data_ptr() + 4 * offs[id(p)] for p in plist)
-        if not ok and plist:
-            flat = t.zeros(total, dtype=t.float32, device=plist[0].device)
-            for p in plist:
-                view = flat[offs[id(p)]: offs[id(p)] + p.numel()].view(p.shape)
-                if p.grad is not None and p.grad.shape == p.shape:
-                    view.copy_(p.grad)
-                p.grad = view
-            self.flat_grads = flat
-        keep.append(flat)
+        # every gradient is a view into one flat buffer (16-byte aligned pieces): a data-parallel caller exchanges it in one
+        # collective; parameters that are not the optimizer's keep an allocation of their own
+        group = opt.param_groups[0]
+        plist = group["params"]
+        self.flat_grads = flat_grad_views(plist, self.flat_grads, keep_values=True)
+        keep.append(self.flat_grads)
 
         def grad_of(p: Tensor) -> int:
             if p.grad is None or p.grad.shape != p.shape or not p.grad.is_contiguous():
@@ -153,107 +201,31 @@ class NativeRankerStep:
             keep.append(p.grad)
             return p.grad.data_ptr()
 
-        d.n_enc_layers, d.n_dec_layers = len(enc.layers), len(dec.layers)
-        first = next(iter(enc.layers[0].values()))
-        d.aggr = 1 if first.aggr == "mean" else 0
-        d.batch_normalize = 1 if model.batch_normalize else 0
-        d.max_norm = 1.0
-        for ti, key in enumerate((Constants.node_user, Constants.node_item)):
-            tables = model.embedding_layers[key]
-            d.n_cols[ti] = len(tables)
-            for c, tb in enumerate(tables):
-                if not tb.is_contiguous():
-                    raise ValueError("embedding tables must be contiguous")
-                d.tables[ti][c] = tb.data_ptr()
-                d.table_rows[ti][c] = int(tb.shape[0])
-                d.dims[ti][c] = int(tb.shape[1])
-        for l, convs in enumerate(enc.layers):
-            for r, et in enumerate((Constants.edge_key, Constants.rev_edge_key)):
-                conv = convs[_key(tuple(et))]
-                cv = d.conv[l][r]
-                cv.w_l, cv.w_r = conv.lin_l.weight.data_ptr(), conv.lin_r.weight.data_ptr()
-                cv.gw_l, cv.gw_r = grad_of(conv.lin_l.weight), grad_of(conv.lin_r.weight)
-                if conv.lin_l.bias is not None:
-                    cv.b_l, cv.gb_l = conv.lin_l.bias.data_ptr(), grad_of(conv.lin_l.bias)
-                cv.c_out, cv.c_src = (int(x) for x in conv.lin_l.weight.shape)
-                cv.c_dst = int(conv.lin_r.weight.shape[1])
-        for ti, bn in enumerate((model.encoder_layer_norm_customer, model.encoder_layer_norm_article)):
-            nm = d.norm[ti]
-            if bn.weight is not None:
-                nm.gamma, nm.beta = bn.weight.data_ptr(), bn.bias.data_ptr()
-                nm.g_gamma, nm.g_beta = grad_of(bn.weight), grad_of(bn.bias)
-            if bn.track_running_stats:
-                nm.running_mean, nm.running_var = bn.running_mean.data_ptr(), bn.running_var.data_ptr()
-                nm.num_batches_tracked = bn.num_batches_tracked.data_ptr()
-            nm.momentum, nm.eps = float(bn.momentum if bn.momentum is not None else 0.1), float(bn.eps)
-        for j, layer in enumerate(dec.layers):
-            ln = d.dec[j]
-            ln.w, ln.gw = layer.weight.data_ptr(), grad_of(layer.weight)
-            if layer.bias is not None:
-                ln.b, ln.gb = layer.bias.data_ptr(), grad_of(layer.bias)
-            ln.out, ln.in_ = (int(x) for x in layer.weight.shape)
-        # the optimizer's parameter list with its state (created the way torch.optim.Adam creates it on its first step)
-        group = opt.param_groups[0]
-        d.n_params = len(group["params"])
-        for i, p in enumerate(group["params"]):
-            st = opt.state[p]
-            if len(st) == 0:
-                on_device = bool(group.get("fused") or group.get("capturable"))
-                st["step"] = t.zeros((), dtype=t.float32, device=p.device) if on_device else t.tensor(0.0, dtype=t.float32)
-                st["exp_avg"] = t.zeros_like(p, memory_format=t.preserve_format)
-                st["exp_avg_sq"] = t.zeros_like(p, memory_format=t.preserve_format)
-            q = d.params[i]
-            q.p, q.g, q.m, q.v, q.n = p.data_ptr(), grad_of(p), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), p.numel()
-        steps = [opt.state[p]["step"] for p in group["params"]]
-        self._adam_step = int(steps[0]) if steps else 0     # one read-back when the steps live on the device (fused=True)
+        _fill_model(d, model, grad_of)
+        d.n_params = len(plist)
+        for q, p in zip(d.params, plist):
+            grad_of(p)
+            bind_param(q, p, p.grad, ensure_adam_state(opt, group, p))
+        self._adam_step = int(opt.state[plist[0]]["step"]) if plist else 0     # one read-back when the steps live on the device (fused=True)
         return d
 
-    def _params_current(self, d: RankerModel) -> bool:
-        """The descriptor holds raw pointers: rebuilt when a parameter, gradient, optimizer-state, BatchNorm buffer or
-        embedding table was replaced (zero_grad(set_to_none=True), model.to(...), load of a new optimizer state, ...).
-        Compared against plain Python ints captured at build time: reading the pointers back out of the ctypes descriptor
-        (four fields x ~25 tensors) was 30 us of a host-bound 0.47 ms iteration (round 4, tools/prof_host_native.py)."""
-        snap = self._snapshot
-        if snap is None:
-            return False
-        params = self.optimizer.param_groups[0]["params"]
-        if len(params) != len(snap[0]):
-            return False
-        state = self.optimizer.state
-        for p, (q, pp, gp, mp, vp) in zip(params, snap[0]):
-            g = p.grad
-            st = state.get(p)
-            if (p is not q or g is None or not st or p.data_ptr() != pp or g.data_ptr() != gp or st["exp_avg"].data_ptr() != mp
-                    or st["exp_avg_sq"].data_ptr() != vp):
-                return False
-        for tensor_of, ptr in snap[1]:
-            if tensor_of().data_ptr() != ptr:
-                return False
-        return True
+    def _snapshot_now(self) -> PointerSnapshot:
+        """Every tensor _build stores a pointer to: the optimizer's with their gradients and moments, the embedding tables, every
+        BatchNorm buffer (each replaceable on its own), and the weights the optimizer does not own (a frozen layer) with their
+        gradients."""
+        model, plist = self.model, self.optimizer.param_groups[0]["params"]
+        owned = {id(p) for p in plist}
+        frozen = [p for p in model.parameters() if id(p) not in owned]
 
-    def _take_snapshot(self) -> None:
-        params = self.optimizer.param_groups[0]["params"]
-        state = self.optimizer.state
-        rows = [(p, p.data_ptr(), p.grad.data_ptr(), state[p]["exp_avg"].data_ptr(), state[p]["exp_avg_sq"].data_ptr()) for p in params]
-        model = self.model
-        others = []
-        for key, name in ((Constants.node_user, "encoder_layer_norm_customer"), (Constants.node_item, "encoder_layer_norm_article")):
-            bn = getattr(model, name)
-            if bn.track_running_stats:      # every buffer _build stores a pointer to, each replaceable on its own
-                others.append((lambda bn=bn: bn.running_mean, bn.running_mean.data_ptr()))
-                others.append((lambda bn=bn: bn.running_var, bn.running_var.data_ptr()))
-                others.append((lambda bn=bn: bn.num_batches_tracked, bn.num_batches_tracked.data_ptr()))
-            tables = model.embedding_layers[key]
-            for c in range(len(tables)):
-                others.append((lambda tables=tables, c=c: tables[c], tables[c].data_ptr()))
-        # weights the descriptor points to without the optimizer owning them (a frozen layer): parameter and gradient
-        owned = {id(p) for p in params}
-        for p in model.parameters():
-            if id(p) not in owned:
-                others.append((lambda p=p: p, p.data_ptr()))
-                if p.grad is not None:
-                    others.append((lambda p=p: p.grad if p.grad is not None else p, p.grad.data_ptr()))
-        self._snapshot = (rows, others)
+        def others():
+            out = [x for p in frozen for x in (p, p.grad)]
+            for key, name in zip(_NODES, _NORMS):
+                bn = getattr(model, name)
+                out += model.embedding_layers[key]
+                if bn.track_running_stats:
+                    out += [bn.running_mean, bn.running_var, bn.num_batches_tracked]
+            return out
+        return PointerSnapshot([others], optimizer=self.optimizer)
 
     # ------------------------------------------------------------------------------------------
     def _prepare(self, x_dict: Dict[str, Tensor], edge_index_dict: dict, edge_label_index: Tensor, labels: Tensor):
@@ -289,9 +261,9 @@ class NativeRankerStep:
             src, dst = ei[0].contiguous(), ei[1].contiguous()
             by_c = ops.coo_to_csr(src, dst, n_c, n_a, want_perm=False)
             by_a = ops.coo_to_csr(dst, src, n_a, n_c, want_perm=False)
-        if self._desc is None or not self._params_current(self._desc):
+        if self._desc is None or not self._snapshot.current():
             self._desc = self._build()
-            self._take_snapshot()
+            self._snapshot = self._snapshot_now()
         d = self._desc
         p = model.encoder.p_dropout_features
         d.p_dropout = float(p) if p else 0.0
@@ -363,33 +335,19 @@ class NativeRankerStep:
         return dist.get_world_size(self.group) if (self.data_parallel and dist.is_initialized()) else 1
 
     def _all_ranks_take_it(self, mine: bool, device) -> bool:
-        """Data-parallel only: the decline is COLLECTIVE.  A rank whose batch lies outside the executor's shapes must not
-        leave its peers alone in the gradient all-reduce (they would wait for the collective's timeout, or reduce against
-        the fallback path's differently sized buffer): one all-reduce(MIN) of a 1-int flag BEFORE anything is enqueued, and
-        every rank takes the same branch."""
-        import torch.distributed as dist
-        flag = t.tensor([1 if mine else 0], dtype=t.int32, device=device)
-        dist.all_reduce(flag, op=dist.ReduceOp.MIN, group=self.group)
-        return bool(int(flag.item()))
+        return all_ranks_take_it(mine, device, self.group)
 
     def step(self, x_dict: Dict[str, Tensor], edge_index_dict: dict, edge_label_index: Tensor, labels: Tensor) -> Optional[Tensor]:
         """One iteration; the loss as a 1-element device tensor, or None when the executor declines this batch (nothing
         has been enqueued then; the caller runs FusedRankerStep / autograd).  With data_parallel=True and more than one
-        rank the decision is collective: every rank returns None when ANY rank's batch is declined, so all of them take the
-        caller's fallback together (`declined` then names the local reason, or says that a peer declined)."""
+        rank the decision is collective (native_binding): every rank returns None when ANY rank's batch is declined, so all of
+        them take the caller's fallback together (`declined` then names the local reason, or says that a peer declined)."""
         self.declined = None       # why the last call returned None (diagnostics)
-        try:
-            prep = self._prepare(x_dict, edge_index_dict, edge_label_index, labels)
-        except BaseException:
-            if self._world() > 1:          # the peers are on their way into the vote: answer it, then fail here
-                self._all_ranks_take_it(False, next(self.model.parameters()).device)
-            raise
-        if self._world() > 1:
-            if not self._all_ranks_take_it(prep is not None, next(self.model.parameters()).device):
-                if prep is not None:
-                    self.declined = "a peer rank declined its batch (collective decision: every rank takes the fallback)"
-                return None
-        elif prep is None:
+        prep, go = collective_prepare(self._world(), lambda mine: self._all_ranks_take_it(mine, next(self.model.parameters()).device),
+                                      lambda: self._prepare(x_dict, edge_index_dict, edge_label_index, labels))
+        if not go:
+            if prep is not None:
+                self.declined = PEER_DECLINED
             return None
         d, b, loss, steps, _keep = prep
         group = self.optimizer.param_groups[0]
@@ -417,11 +375,7 @@ class NativeRankerStep:
                 dist.all_reduce(self.flat_grads, op=dist.ReduceOp.SUM, group=self.group)
             _lib.check(L.mi_ranker_adam_f32(ctypes.byref(d), 1.0 / world, _lib.current_stream()), "mi_ranker_adam_f32")
         self._adam_step += 1
-        if steps and steps[0].is_cuda:      # fused=True keeps its step counts on the device: one foreach launch
-            t._foreach_add_(steps, 1)
-        else:
-            for s in steps:                 # the default Adam's host scalars
-                s += 1
+        bump_adam_steps(steps)
         return loss
 
 
@@ -444,7 +398,7 @@ class NativeRankerForward:
             raise ValueError(f"NativeRankerForward: {why}")
         self.model = model
         self._desc: Optional[RankerModel] = None
-        self._ptrs = None
+        self._snapshot: Optional[PointerSnapshot] = None
         self._ws: Optional[Tensor] = None
         self.declined: Optional[str] = None
 
@@ -460,7 +414,7 @@ class NativeRankerForward:
         """Every tensor the descriptor points into, in a fixed order (its pointers are the descriptor's identity)."""
         model = self.model
         out = []
-        for key in (Constants.node_user, Constants.node_item):
+        for key in _NODES:
             out += list(model.embedding_layers[key])
         for convs in model.encoder.layers:
             for et in (Constants.edge_key, Constants.rev_edge_key):
@@ -473,43 +427,8 @@ class NativeRankerForward:
         return out
 
     def _build(self) -> RankerModel:
-        model = self.model
-        enc, dec = model.encoder, model.decoder
         d = RankerModel()
-        d.n_enc_layers, d.n_dec_layers = len(enc.layers), len(dec.layers)
-        first = next(iter(enc.layers[0].values()))
-        d.aggr = 1 if first.aggr == "mean" else 0
-        d.batch_normalize = 1 if model.batch_normalize else 0
-        d.max_norm = 1.0
-        for ti, key in enumerate((Constants.node_user, Constants.node_item)):
-            tables = model.embedding_layers[key]
-            d.n_cols[ti] = len(tables)
-            for c, tb in enumerate(tables):
-                if not tb.is_contiguous():
-                    raise ValueError("embedding tables must be contiguous")
-                d.tables[ti][c], d.table_rows[ti][c], d.dims[ti][c] = tb.data_ptr(), int(tb.shape[0]), int(tb.shape[1])
-        for l, convs in enumerate(enc.layers):
-            for r, et in enumerate((Constants.edge_key, Constants.rev_edge_key)):
-                conv = convs[_key(tuple(et))]
-                cv = d.conv[l][r]
-                cv.w_l, cv.w_r = conv.lin_l.weight.data_ptr(), conv.lin_r.weight.data_ptr()
-                if conv.lin_l.bias is not None:
-                    cv.b_l = conv.lin_l.bias.data_ptr()
-                cv.c_out, cv.c_src = (int(x) for x in conv.lin_l.weight.shape)
-                cv.c_dst = int(conv.lin_r.weight.shape[1])
-        for ti, bn in enumerate((model.encoder_layer_norm_customer, model.encoder_layer_norm_article)):
-            nm = d.norm[ti]
-            if bn.weight is not None:
-                nm.gamma, nm.beta = bn.weight.data_ptr(), bn.bias.data_ptr()
-            if bn.track_running_stats and bn.running_mean is not None:
-                nm.running_mean, nm.running_var = bn.running_mean.data_ptr(), bn.running_var.data_ptr()
-            nm.momentum, nm.eps = float(bn.momentum if bn.momentum is not None else 0.1), float(bn.eps)
-        for j, layer in enumerate(dec.layers):
-            ln = d.dec[j]
-            ln.w = layer.weight.data_ptr()
-            if layer.bias is not None:
-                ln.b = layer.bias.data_ptr()
-            ln.out, ln.in_ = (int(x) for x in layer.weight.shape)
+        _fill_model(d, self.model)
         d.n_params = 0
         d.p_dropout = 0.0
         return d
@@ -527,9 +446,8 @@ class NativeRankerForward:
         if not xc.is_cuda:
             self.declined = "batch not on the GPU"
             return None
-        ptrs = tuple(x.data_ptr() for x in self._tensors())
-        if self._desc is None or ptrs != self._ptrs:     # a table / weight / buffer was replaced (load_state_dict keeps storages; .to() does not)
-            self._desc, self._ptrs = self._build(), ptrs
+        if self._desc is None or not self._snapshot.current():     # a table / weight / buffer was replaced (load_state_dict keeps storages; .to() does not)
+            self._desc, self._snapshot = self._build(), PointerSnapshot([self._tensors])
         d = self._desc
         n_c, n_a = int(xc.shape[0]), int(xa.shape[0])
         pre = getattr(ei, "_sorted_csr", None)

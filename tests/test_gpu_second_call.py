@@ -12,7 +12,9 @@ A2  data.lightgcn_loader.sample_mini_batch after an in-place edit of edge_index.
 A3  NativeRankerStep's raw-pointer descriptor after a BatchNorm buffer, an embedding table or an optimizer state tensor
     was replaced, one at a time.
 A4  NativeRankerStep's workspace recovery (MI_ERR_WORKSPACE from the validation pass), single process and with the
-    data-parallel vote, without a process group."""
+    data-parallel vote, without a process group.
+A5  NativePinSAGEStep's raw-pointer descriptors (the executor's, Adam's list, the projector's) after a gradient, an Adam moment,
+    the projector's code matrix or a text column's tokens was replaced, one at a time; its vote when _prepare raises."""
 import copy
 
 import pytest
@@ -518,4 +520,132 @@ def test_native_ranker_votes_no_before_an_exception_leaves_prepare(monkeypatch):
     monkeypatch.setattr(NativeRankerStep, "_build", boom)
     with pytest.raises(RuntimeError, match="descriptor build failed"):
         native.step({k: v.clone() for k, v in x.items()}, ei, eli, y)
+    assert votes == [False]
+
+
+# ---- A5 ------------------------------------------------------------------------------------------------------------------
+
+def _pinsage_model(kind):
+    from laplace_amd.pinsage.model import PinSAGEModel
+    I, H, LAYERS = 800, 16, 2
+    t.manual_seed(H + LAYERS)
+    if kind == "id_only":
+        return PinSAGEModel(I, H, LAYERS).to(DEV)
+    from test_gpu_pinsage_text import _features, _text
+    feats = _features(I, (7, 132), 3, _text(I, (60,), 13, tuple(range(9))), 9)     # two code columns, 3 floats, one text column
+    return PinSAGEModel(I, H, LAYERS, features=feats).to(DEV)
+
+
+@pytest.mark.parametrize("kind", ["id_only", "id+cat+dense+text"])
+def test_native_pinsage_descriptor_follows_replaced_buffers(kind):
+    """Six iterations of one long-lived executor (dropout at the model's 0.5: the iteration counter and the seed show too); before
+    iterations 1 to 4 one tensor its descriptors point to is replaced, the old storage kept alive and poisoned.  Every iteration
+    equals, bit for bit, a FRESH executor's on a twin that got the same replacement."""
+    from laplace_amd.pinsage.native import NativePinSAGEStep
+    from laplace_amd.pinsage.sampler import PinSAGESampler
+    from test_gpu_pinsage_text import _shared_graph
+    U, I, B, SEED = 2500, 800, 48, 31
+    users, items = _shared_graph()
+    smp = PinSAGESampler(users, items, U, I, batch_size=B, random_walk_length=2, num_layers=2, seed=SEED)
+    featured = kind != "id_only"
+    model = _pinsage_model(kind)
+    with t.no_grad():
+        model.bias.normal_(0, 0.1)
+    twin = copy.deepcopy(model)
+    opt, opt_twin = t.optim.Adam(model.parameters(), lr=3e-3), t.optim.Adam(twin.parameters(), lr=3e-3)
+    model.train(); twin.train()
+    native = NativePinSAGEStep(model, opt, seed=77)
+    retired = []                                                        # the replaced storages stay alive, and poisoned
+
+    def retire(x, poison):
+        retired.append(x)
+        x.copy_(poison(x)) if callable(poison) else x.fill_(poison)
+
+    def drop_gradients(m, o):
+        o.zero_grad(set_to_none=True)
+
+    def replace_exp_avg(m, o):
+        st = o.state[m.convs[0].Q.weight]
+        old = st["exp_avg"]
+        st["exp_avg"] = old.clone()
+        retire(old, 1e3)
+
+    def replace_bias_exp_avg_sq(m, o):
+        st = o.state[m.bias]
+        old = st["exp_avg_sq"]
+        st["exp_avg_sq"] = old.clone()
+        retire(old, 1e3)
+
+    def replace_bias_grad(m, o):
+        old = m.bias.grad
+        m.bias.grad = t.zeros_like(m.bias)
+        retire(old, 1e3)
+
+    def replace_codes(m, o):
+        pr = m.projector
+        old = pr.x
+        pr.x = old.clone()
+        cards = t.tensor(pr.cardinalities, device=old.device)
+        retire(old, lambda x: (x + 1) % cards)                          # in range, and another code everywhere
+
+    def replace_tokens(m, o):
+        pr = m.projector
+        old = pr.text_tok_0
+        pr.text_tok_0 = old.clone()
+        retire(old, 0)
+
+    changes = [None, drop_gradients, replace_exp_avg] + ([replace_codes, replace_tokens] if featured else
+                                                         [replace_bias_exp_avg_sq, replace_bias_grad]) + [None]
+    for step, change in enumerate(changes):
+        what = (kind, step, getattr(change, "__name__", None))
+        if change is not None:
+            change(model, opt)
+            change(twin, opt_twin)
+        batch = smp.sample_batch(step)
+        iteration = native.iteration
+        la = native.step(batch)
+        assert la is not None, (what, native.declined)
+        fresh = NativePinSAGEStep(twin, opt_twin, seed=77)
+        fresh.iteration = iteration
+        lb = fresh.step(batch)
+        assert lb is not None, (what, fresh.declined)
+        assert float(la) == float(lb), what
+        for (n, p), q in zip(model.named_parameters(), twin.parameters()):
+            assert t.equal(p, q), (what, n)
+            sa, sb = opt.state[p], opt_twin.state[q]
+            assert t.equal(sa["exp_avg"], sb["exp_avg"]) and t.equal(sa["exp_avg_sq"], sb["exp_avg_sq"]), (what, n)
+            assert float(sa["step"]) == float(sb["step"]) == step + 1, (what, n)
+        if featured:                                                    # the table gradients and the scorer bias's: all-zero again
+            pr = model.projector
+            for p in [model.bias] + [p for p in pr.parameter_list() if p is not pr.weight and p is not pr.bias]:
+                assert float(p.grad.abs().max()) == 0.0, what
+    assert len(retired) == 6                                            # three replacements each, model and twin
+    if featured:     # a copy (or a pickle) of a projector that has cached descriptors starts without them, and binds its own
+        assert model.projector._bound is not None
+        clone = copy.deepcopy(model)
+        assert clone.projector._bound is None and model.projector._bound is not None
+        ids = batch["blocks"][0]["src_ids"]
+        assert t.equal(clone.projector.project(ids), model.projector.project(ids))
+        assert clone.projector._bound is not None and clone.projector._bound is not model.projector._bound
+
+
+def test_native_pinsage_votes_no_before_an_exception_leaves_prepare(monkeypatch):
+    """As the ranker's: a rank whose _prepare raises must answer the vote first."""
+    from laplace_amd.pinsage.native import NativePinSAGEStep
+    from laplace_amd.pinsage.sampler import PinSAGESampler
+    from test_gpu_pinsage_text import _shared_graph
+    users, items = _shared_graph()
+    smp = PinSAGESampler(users, items, 2500, 800, batch_size=48, random_walk_length=2, num_layers=2, seed=31)
+    model = _pinsage_model("id_only")
+    model.train()
+    native = NativePinSAGEStep(model, t.optim.Adam(model.parameters(), lr=3e-3))
+    votes = []
+    monkeypatch.setattr(NativePinSAGEStep, "_world", lambda self: 2)
+    monkeypatch.setattr(NativePinSAGEStep, "_all_ranks_take_it", lambda self, mine, device: votes.append(mine) or mine)
+
+    def boom(self):
+        raise RuntimeError("descriptor build failed")
+    monkeypatch.setattr(NativePinSAGEStep, "_build", boom)
+    with pytest.raises(RuntimeError, match="descriptor build failed"):
+        native.step(smp.sample_batch(0))
     assert votes == [False]
