@@ -1214,6 +1214,58 @@ int    mi_pinsage_text_bwd_f32(const mi_text_columns* p, float* const g_tables[]
 int    mi_pinsage_text_clear_f32(const mi_text_columns* p, float* const g_tables[], int64_t n, const int64_t* ids,
                                  mi_stream_t stream);
 
+/* ------------------------------------------------------------------------------------
+ * N5  sparse trainer: lazy Adam for the id and text tables (additive to ABI 14).
+ * replaces: pinsage/model_sparse.py — nn.Embedding(sparse=True) trained by torch.optim.SparseAdam beside a dense Adam.
+ * The update of ONE table row with (summed) gradient row g, every operation one correctly rounded float32 operation, no contraction
+ * (torch.optim._functional.sparse_adam written out; tests/lazy_adam_emulation.py restates it):
+ *     d  = g - m            m' = m + d * c1         c1 = (float)(1 - beta1)
+ *     s  = g*g - v          v' = v + s * c2         c2 = (float)(1 - beta2)
+ *     q  = m' / (sqrt(v') + (float)eps)
+ *     p' = p + q * ss       ss = (float)(-lr * sqrt(1 - beta2^step) / (1 - beta1^step))   in double on the host
+ * A row is updated if and only if it is REFERENCED by the call, also when its summed gradient is exactly zero (its moments
+ * decay and p moves); a row nobody references keeps the bits of p, m and v.  The cost of a call follows the batch, not the table.
+ * lr >= 0, eps >= 0, 0 <= beta < 1, step >= 1 (counts from 1), else MI_ERR_BAD_ARG.
+ *
+ * mi_lazy_adam_rows_f32: table p / m / v [rows, width] (contiguous), n DISTINCT row ids (UNCHECKED: 0 <= ids[r] < rows; a
+ *   repeated id would be a race), their gradient rows compactly in g [n, ldg] — what mi_pinsage_step_f32 hands back through
+ *   rows_out for blocks[0].src_ids: no table-sized gradient exists.  One lane per float4.  width % 4 == 0, 4 <= width <= 512
+ *   (MI_ERR_UNSUPPORTED otherwise); p, m, v, g 16-byte aligned, ldg >= width, ldg % 4 == 0, 0 <= n <= rows.  No workspace.
+ * mi_pinsage_project_bwd_lazy_f32: mi_pinsage_project_bwd_f32 (the same code, the same bits in every gradient buffer), then,
+ *   for every slot — categorical column c, the id table — that has a moment pair in `moments`, the update above on every table
+ *   row the call references, from its summed row in the slot's gradient buffer, which reads ZERO again afterwards (the store is
+ *   fused: no clear is needed for that slot).  The slot's table in `p` is WRITTEN (const in the descriptor only because the other
+ *   entries read it).  A slot with a null pair is left exactly as mi_pinsage_project_bwd_f32 leaves it.  moments = null or all
+ *   pairs null: that call bit for bit (`lazy` is then not read).  Workspace: mi_pinsage_project_bwd_workspace_bytes(p, n).
+ * mi_pinsage_text_bwd_lazy_f32: the same over mi_pinsage_text_bwd_f32; m_tables[c] / v_tables[c] both null or both set per
+ *   column.  The padding slots past the device-side reference count never update a row.  n_ref_max MUST be a true upper bound
+ *   of the reference count here: where the count exceeds it the plain entry leaves truncated sums the caller can still
+ *   discard, this one has already applied them to p / m / v.
+ *   Workspace: mi_pinsage_text_bwd_workspace_bytes(p, n, n_ref_max).
+ * Everything is validated before anything is enqueued.  No float atomics; equal bits on every run.
+ * ---------------------------------------------------------------------------------- */
+typedef struct mi_lazy_adam {
+    double  lr, beta1, beta2, eps;
+    int64_t step;                                    /* of THIS update, counts from 1 */
+} mi_lazy_adam;
+typedef struct mi_item_projector_moments {          /* per slot both or neither; each with the shape of its table */
+    float* m_tables[MI_PROJECTOR_MAX_COLS];
+    float* v_tables[MI_PROJECTOR_MAX_COLS];
+    float* m_id_table;
+    float* v_id_table;
+} mi_item_projector_moments;
+int64_t mi_lazy_adam_sizeof(int32_t which);          /* sizeof of: 0 mi_lazy_adam, 1 mi_item_projector_moments; else -1 */
+int    mi_lazy_adam_rows_f32(int64_t rows, int32_t width, float* p, float* m, float* v, int64_t n, const int64_t* ids,
+                             const float* g, int64_t ldg, const mi_lazy_adam* lazy, mi_stream_t stream);
+int    mi_pinsage_project_bwd_lazy_f32(const mi_item_projector* p, const mi_item_projector_grads* grads,
+                                       const mi_item_projector_moments* moments, const mi_lazy_adam* lazy, int64_t n,
+                                       const int64_t* ids, const float* g, int64_t ldg, void* ws, size_t ws_bytes,
+                                       mi_stream_t stream);
+int    mi_pinsage_text_bwd_lazy_f32(const mi_text_columns* p, float* const g_tables[], float* const m_tables[],
+                                    float* const v_tables[], const mi_lazy_adam* lazy, int64_t n, const int64_t* ids,
+                                    const float* g, int64_t ldg, int64_t n_ref_max, void* ws, size_t ws_bytes,
+                                    mi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

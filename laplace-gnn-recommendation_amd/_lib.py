@@ -203,6 +203,16 @@ class TextColumns(Structure):
 
 TextGradTables = c_void_p * MI_PROJECTOR_MAX_TEXT      # the g_tables argument: one buffer per text column
 
+
+class LazyAdam(Structure):
+    _fields_ = [("lr", c_double), ("beta1", c_double), ("beta2", c_double), ("eps", c_double), ("step", c_int64)]
+
+
+class ItemProjectorMoments(Structure):
+    _fields_ = [("m_tables", c_void_p * MI_PROJECTOR_MAX_COLS), ("v_tables", c_void_p * MI_PROJECTOR_MAX_COLS),
+                ("m_id_table", c_void_p), ("v_id_table", c_void_p)]
+
+
 P = c_void_p
 _PROTOTYPES = {
     # name: (restype, [argtypes])
@@ -321,6 +331,12 @@ _PROTOTYPES = {
     "mi_pinsage_text_clear_f32": (c_int32, [POINTER(TextColumns), POINTER(c_void_p), c_int64, P, P]),
     "mi_adam_dense_f32": (c_int32, [c_int64, c_int64, P, c_int64, P, c_int64, P, P, P,
                                     c_double, c_double, c_double, c_double, c_int64, P]),
+    "mi_lazy_adam_sizeof": (c_int64, [c_int32]),
+    "mi_lazy_adam_rows_f32": (c_int32, [c_int64, c_int32, P, P, P, c_int64, P, P, c_int64, POINTER(LazyAdam), P]),
+    "mi_pinsage_project_bwd_lazy_f32": (c_int32, [POINTER(ItemProjector), POINTER(ItemProjectorGrads), POINTER(ItemProjectorMoments),
+                                                  POINTER(LazyAdam), c_int64, P, P, c_int64, P, c_size_t, P]),
+    "mi_pinsage_text_bwd_lazy_f32": (c_int32, [POINTER(TextColumns), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p),
+                                               POINTER(LazyAdam), c_int64, P, P, c_int64, c_int64, P, c_size_t, P]),
 }
 
 _LIB = None

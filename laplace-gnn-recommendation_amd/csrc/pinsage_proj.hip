@@ -15,6 +15,7 @@
 // launcher (split-K under its rule) over the gathered rows.
 #include "gemm.hpp"
 #include "segsum.hpp"
+#include "lazy_adam.hpp"
 
 namespace {
 
@@ -198,6 +199,116 @@ int check_grads(const mi_item_projector& p, const mi_item_projector_grads* gr, b
     return 0;
 }
 
+using LazyOp = MiLazyRowOp<segsum::Ptrs<float4, kMaxSlots>>;
+
+// The per-row operation of a lazy call.  < 0: the code to return; 0: no slot is lazy (*op not filled); 1: some slot is.
+int lazy_op(const mi_item_projector& p, const mi_item_projector_moments* mo, const mi_lazy_adam* lazy, LazyOp* op) {
+    if (!mo) return 0;
+    bool any = false;
+    for (int s = 0; s < kMaxSlots; ++s) op->p.t[s] = op->m.t[s] = op->v.t[s] = nullptr;
+    auto slot = [&](int s, const float* table, float* m, float* v) -> int {
+        if ((m == nullptr) != (v == nullptr)) return MI_ERR_BAD_ARG;
+        if (!m) return 0;
+        if (!mi_aligned16(m) || !mi_aligned16(v)) return MI_ERR_BAD_ARG;
+        op->p.t[s] = reinterpret_cast<float4*>(const_cast<float*>(table));   // a lazy slot's table is written
+        op->m.t[s] = reinterpret_cast<float4*>(m);
+        op->v.t[s] = reinterpret_cast<float4*>(v);
+        any = true;
+        return 0;
+    };
+    for (int c = 0; c < p.n_cols; ++c) {
+        const int bad = slot(c, p.tables[c], mo->m_tables[c], mo->v_tables[c]);
+        if (bad) return bad;
+    }
+    if (p.id_table) {
+        const int bad = slot(p.n_cols, p.id_table, mo->m_id_table, mo->v_id_table);
+        if (bad) return bad;
+    } else if (mo->m_id_table || mo->v_id_table) {
+        return MI_ERR_BAD_ARG;   // moments for a table the projector does not have
+    }
+    if (!any) return 0;
+    const int bad = mi_lazy_check(lazy);
+    if (bad) return bad;
+    op->c = mi_lazy_consts(*lazy);
+    return 1;
+}
+
+// mi_pinsage_project_bwd_f32 (moments == nullptr) and mi_pinsage_project_bwd_lazy_f32: one body, so that the gradients are the
+// same bits.  With a moment pair for some slot the lazy update runs over the heads of the sorted keys after the combine.
+static int project_bwd(const mi_item_projector* pp, const mi_item_projector_grads* grads, const mi_item_projector_moments* moments,
+                       const mi_lazy_adam* lazy, int64_t n, const int64_t* ids, const float* g, int64_t ldg, void* ws, size_t ws_bytes,
+                       mi_stream_t stream) {
+    int bad = check_projector(pp, n, ids != nullptr);
+    if (bad) return bad;
+    const mi_item_projector& p = *pp;
+    bad = check_grads(p, grads, true);
+    if (bad) return bad;
+    LazyOp op = {};
+    bad = lazy_op(p, moments, lazy, &op);
+    if (bad < 0) return bad;
+    const bool any_lazy = bad > 0;
+    MI_CHECK_ARG(n == 0 || (g && mi_aligned16(g) && ldg >= p.hidden && ldg % 4 == 0));
+    if (!ws || ws_bytes < bwd_ws_bytes(p, n)) return MI_ERR_WORKSPACE;
+    const BwdSizes z = bwd_sizes(p, n);
+    const int H = p.hidden;
+    hipStream_t s = (hipStream_t)stream;
+    MiArena arena(ws, ws_bytes);
+    const segsum::Buffers sb = segsum::take(arena, z.n_ref, H, sort_tmp_cap(z.n_ref));
+    float *slabs = nullptr, *dense_rows = nullptr;
+    char* gemm_ws = nullptr;
+    size_t gemm_ws_bytes = 0;
+    if (p.n_dense > 0) {
+        slabs = arena.take<float>((size_t)std::max<int64_t>(z.n_slabs, 1) * H);
+        dense_rows = arena.take<float>((size_t)std::max<int64_t>(n, 1) * z.ldd);
+        gemm_ws_bytes = mi_gemm_workspace_bytes(H, p.n_dense, n);
+        gemm_ws = arena.take<char>(gemm_ws_bytes ? gemm_ws_bytes : 1);
+        if (!slabs || !dense_rows || !gemm_ws) return MI_ERR_WORKSPACE;
+    }
+    if (!sb.ok()) return MI_ERR_WORKSPACE;
+    if (z.n_ref > 0) {
+        // the key: slot above `shift` bits of code (a column's code, or the item id in the last slot)
+        int64_t widest = p.id_table ? p.n_items : 1;
+        for (int c = 0; c < p.n_cols; ++c) widest = std::max(widest, p.table_rows[c]);
+        const unsigned shift = mi_bits_for(widest), bits = shift + mi_bits_for(kMaxSlots);
+        auto refs = [&]() -> int {
+            hipLaunchKernelGGL(proj_refs_kernel, dim3(grid_for(z.n_ref)), dim3(kBlock), 0, s, n, z.n_ref, (int)p.n_cols, ids, p.x,
+                               shift, sb.k0, sb.r0);
+            return 0;
+        };
+        const uint64_t* sorted = nullptr;
+        int rc = segsum::run<false>(sb, z.n_ref, nullptr, shift, bits, 0, refs, g, ldg, H, segsum::Plain(), grad_tables(p, *grads), s,
+                                    &sorted);
+        if (rc) return rc;
+        if (any_lazy) {
+            rc = segsum::run_heads<false>(sorted, z.n_ref, nullptr, shift, H, grad_tables(p, *grads), op, s);
+            if (rc) return rc;
+        }
+    }
+    if (p.n_dense > 0) {
+        if (z.n_slabs > 0)
+            hipLaunchKernelGGL(proj_colsum_slab_kernel, dim3((unsigned)z.n_slabs), dim3(128), 0, s, n, H, g, ldg, slabs);
+        hipLaunchKernelGGL(proj_colsum_final_kernel, dim3(1), dim3(128), 0, s, z.n_slabs, H, slabs, grads->g_b);
+        const float* rows = p.dense;
+        int64_t ld_rows = p.ld_dense;
+        if (ids && n > 0) {
+            hipLaunchKernelGGL(proj_gather_dense_kernel, dim3(grid_for(n * z.ldd)), dim3(kBlock), 0, s, n, p.n_dense, z.ldd, ids,
+                               p.dense, p.ld_dense, dense_rows);
+            rows = dense_rows;
+            ld_rows = z.ldd;
+        }
+        const int rc = mi_launch_status();
+        if (rc) return rc;
+        MiGemmArgs q;   // g_w[h, f] = sum_r g[r, h] * rows[r, f]
+        memset(&q, 0, sizeof(q));
+        q.M = H; q.N = p.n_dense; q.K = n;
+        q.A = g; q.sa_m = 1; q.sa_k = ldg; q.a_rows = nullptr;
+        q.B = rows; q.sb_n = 1; q.sb_k = ld_rows;
+        q.bias = nullptr; q.C = grads->g_w; q.ldc = p.n_dense; q.accumulate = 0; q.act = 0;
+        return mi_gemm_launch(q, gemm_ws, gemm_ws_bytes, s);
+    }
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -254,66 +365,13 @@ size_t mi_pinsage_project_bwd_workspace_bytes(const mi_item_projector* p, int64_
 
 int mi_pinsage_project_bwd_f32(const mi_item_projector* pp, const mi_item_projector_grads* grads, int64_t n, const int64_t* ids,
                                const float* g, int64_t ldg, void* ws, size_t ws_bytes, mi_stream_t stream) {
-    int bad = check_projector(pp, n, ids != nullptr);
-    if (bad) return bad;
-    const mi_item_projector& p = *pp;
-    bad = check_grads(p, grads, true);
-    if (bad) return bad;
-    MI_CHECK_ARG(n == 0 || (g && mi_aligned16(g) && ldg >= p.hidden && ldg % 4 == 0));
-    if (!ws || ws_bytes < bwd_ws_bytes(p, n)) return MI_ERR_WORKSPACE;
-    const BwdSizes z = bwd_sizes(p, n);
-    const int H = p.hidden;
-    hipStream_t s = (hipStream_t)stream;
-    MiArena arena(ws, ws_bytes);
-    const segsum::Buffers sb = segsum::take(arena, z.n_ref, H, sort_tmp_cap(z.n_ref));
-    float *slabs = nullptr, *dense_rows = nullptr;
-    char* gemm_ws = nullptr;
-    size_t gemm_ws_bytes = 0;
-    if (p.n_dense > 0) {
-        slabs = arena.take<float>((size_t)std::max<int64_t>(z.n_slabs, 1) * H);
-        dense_rows = arena.take<float>((size_t)std::max<int64_t>(n, 1) * z.ldd);
-        gemm_ws_bytes = mi_gemm_workspace_bytes(H, p.n_dense, n);
-        gemm_ws = arena.take<char>(gemm_ws_bytes ? gemm_ws_bytes : 1);
-        if (!slabs || !dense_rows || !gemm_ws) return MI_ERR_WORKSPACE;
-    }
-    if (!sb.ok()) return MI_ERR_WORKSPACE;
-    if (z.n_ref > 0) {
-        // the key: slot above `shift` bits of code (a column's code, or the item id in the last slot)
-        int64_t widest = p.id_table ? p.n_items : 1;
-        for (int c = 0; c < p.n_cols; ++c) widest = std::max(widest, p.table_rows[c]);
-        const unsigned shift = mi_bits_for(widest), bits = shift + mi_bits_for(kMaxSlots);
-        auto refs = [&]() -> int {
-            hipLaunchKernelGGL(proj_refs_kernel, dim3(grid_for(z.n_ref)), dim3(kBlock), 0, s, n, z.n_ref, (int)p.n_cols, ids, p.x,
-                               shift, sb.k0, sb.r0);
-            return 0;
-        };
-        const int rc = segsum::run<false>(sb, z.n_ref, nullptr, shift, bits, 0, refs, g, ldg, H, segsum::Plain(),
-                                          grad_tables(p, *grads), s);
-        if (rc) return rc;
-    }
-    if (p.n_dense > 0) {
-        if (z.n_slabs > 0)
-            hipLaunchKernelGGL(proj_colsum_slab_kernel, dim3((unsigned)z.n_slabs), dim3(128), 0, s, n, H, g, ldg, slabs);
-        hipLaunchKernelGGL(proj_colsum_final_kernel, dim3(1), dim3(128), 0, s, z.n_slabs, H, slabs, grads->g_b);
-        const float* rows = p.dense;
-        int64_t ld_rows = p.ld_dense;
-        if (ids && n > 0) {
-            hipLaunchKernelGGL(proj_gather_dense_kernel, dim3(grid_for(n * z.ldd)), dim3(kBlock), 0, s, n, p.n_dense, z.ldd, ids,
-                               p.dense, p.ld_dense, dense_rows);
-            rows = dense_rows;
-            ld_rows = z.ldd;
-        }
-        const int rc = mi_launch_status();
-        if (rc) return rc;
-        MiGemmArgs q;   // g_w[h, f] = sum_r g[r, h] * rows[r, f]
-        memset(&q, 0, sizeof(q));
-        q.M = H; q.N = p.n_dense; q.K = n;
-        q.A = g; q.sa_m = 1; q.sa_k = ldg; q.a_rows = nullptr;
-        q.B = rows; q.sb_n = 1; q.sb_k = ld_rows;
-        q.bias = nullptr; q.C = grads->g_w; q.ldc = p.n_dense; q.accumulate = 0; q.act = 0;
-        return mi_gemm_launch(q, gemm_ws, gemm_ws_bytes, s);
-    }
-    return 0;
+    return project_bwd(pp, grads, nullptr, nullptr, n, ids, g, ldg, ws, ws_bytes, stream);
+}
+
+int mi_pinsage_project_bwd_lazy_f32(const mi_item_projector* pp, const mi_item_projector_grads* grads,
+                                    const mi_item_projector_moments* moments, const mi_lazy_adam* lazy, int64_t n, const int64_t* ids,
+                                    const float* g, int64_t ldg, void* ws, size_t ws_bytes, mi_stream_t stream) {
+    return project_bwd(pp, grads, moments, lazy, n, ids, g, ldg, ws, ws_bytes, stream);
 }
 
 int mi_pinsage_project_clear_f32(const mi_item_projector* pp, const mi_item_projector_grads* grads, int64_t n, const int64_t* ids,

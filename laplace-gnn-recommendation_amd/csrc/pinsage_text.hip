@@ -15,6 +15,7 @@
 // references are written in (column, r) order, then the position in the bag; the sort, the chunks of 64 and the combine
 // are segsum.hpp's.
 #include "segsum.hpp"
+#include "lazy_adam.hpp"
 
 namespace {
 
@@ -204,41 +205,38 @@ size_t bwd_ws_bytes(const mi_text_columns& p, int64_t n, int64_t n_ref_max) {
            segsum::workspace_bytes(n_ref_max, p.width, tmp_cap(n_pairs, n_ref_max));
 }
 
-}  // namespace
-
-extern "C" {
-
-int64_t mi_pinsage_text_sizeof(int32_t which) { return which == 0 ? (int64_t)sizeof(mi_text_columns) : -1; }
-
-int mi_pinsage_text_f32(const mi_text_columns* pp, int64_t n, const int64_t* ids, float* out, int64_t ldo, int32_t accumulate,
-                        mi_stream_t stream) {
-    const int bad = check_text(pp, n, ids != nullptr);
-    if (bad) return bad;
-    const mi_text_columns& p = *pp;
-    MI_CHECK_ARG(accumulate == 0 || accumulate == 1);
-    if (n == 0) return 0;
-    MI_CHECK_ARG(out && mi_aligned16(out) && ldo >= p.width && ldo % 4 == 0);
-    const int w4 = p.width / 4;
-    if (n * (int64_t)w4 >= ((int64_t)INT32_MAX) * kBlock) return MI_ERR_TOO_LARGE;
-    TextTables tabs;
-    for (int c = 0; c < kT; ++c) tabs.t[c] = c < p.n_text ? reinterpret_cast<const float4*>(p.tables[c]) : nullptr;
-    hipLaunchKernelGGL(text_gather_kernel, dim3(grid_for(n * w4)), dim3(kBlock), 0, (hipStream_t)stream, n, w4, (int)p.n_text, ids,
-                       csr_of(p), tabs, reinterpret_cast<float4*>(out), ldo / 4, (int)accumulate);
-    return mi_launch_status();
-}
-
-size_t mi_pinsage_text_bwd_workspace_bytes(const mi_text_columns* p, int64_t n, int64_t n_ref_max) {
-    if (check_text(p, n, true) != 0 || n_ref_max < 0 || n_ref_max >= INT32_MAX) return 0;
-    return bwd_ws_bytes(*p, n, n_ref_max);
-}
-
-int mi_pinsage_text_bwd_f32(const mi_text_columns* pp, float* const g_tables[], int64_t n, const int64_t* ids, const float* g,
-                            int64_t ldg, int64_t n_ref_max, void* ws, size_t ws_bytes, mi_stream_t stream) {
+// mi_pinsage_text_bwd_f32 (m_tables == nullptr) and mi_pinsage_text_bwd_lazy_f32: one body, the same bits in the gradients.  A
+// column with a moment pair gets the lazy update over the heads of the sorted keys after the combine; the padding slots past
+// the device-side count are behind head_kernel's own bound and never head a run.
+static int text_bwd(const mi_text_columns* pp, float* const g_tables[], float* const m_tables[], float* const v_tables[],
+                    const mi_lazy_adam* lazy, int64_t n, const int64_t* ids, const float* g, int64_t ldg, int64_t n_ref_max, void* ws,
+                    size_t ws_bytes, mi_stream_t stream) {
     int bad = check_text(pp, n, ids != nullptr);
     if (bad) return bad;
     const mi_text_columns& p = *pp;
     bad = check_text_grads(p, g_tables);
     if (bad) return bad;
+    MiLazyRowOp<segsum::Ptrs<float4, kT>> op = {};
+    bool any_lazy = false;
+    if (m_tables || v_tables) {
+        if (!m_tables || !v_tables) return MI_ERR_BAD_ARG;
+        for (int c = 0; c < kT; ++c) op.p.t[c] = op.m.t[c] = op.v.t[c] = nullptr;
+        for (int c = 0; c < p.n_text; ++c) {
+            float *m = m_tables[c], *v = v_tables[c];
+            if ((m == nullptr) != (v == nullptr)) return MI_ERR_BAD_ARG;
+            if (!m) continue;
+            if (!mi_aligned16(m) || !mi_aligned16(v)) return MI_ERR_BAD_ARG;
+            op.p.t[c] = reinterpret_cast<float4*>(const_cast<float*>(p.tables[c]));   // a lazy column's table is written
+            op.m.t[c] = reinterpret_cast<float4*>(m);
+            op.v.t[c] = reinterpret_cast<float4*>(v);
+            any_lazy = true;
+        }
+        if (any_lazy) {
+            bad = mi_lazy_check(lazy);
+            if (bad) return bad;
+            op.c = mi_lazy_consts(*lazy);
+        }
+    }
     MI_CHECK_ARG(n_ref_max >= 0);
     if (n_ref_max >= INT32_MAX) return MI_ERR_TOO_LARGE;
     MI_CHECK_ARG(n == 0 || (g && mi_aligned16(g) && ldg >= p.width && ldg % 4 == 0));
@@ -270,8 +268,50 @@ int mi_pinsage_text_bwd_f32(const mi_text_columns* pp, float* const g_tables[], 
                            pad_key, sb.k0, sb.r0, count);
         return 0;
     };
-    return segsum::run<true>(sb, n_ref, count, shift, bits, need_scan, refs, g, ldg, p.width, DivByLen{lens, n},
-                             grad_tables(p, g_tables), s);
+    const uint64_t* sorted = nullptr;
+    const int rc = segsum::run<true>(sb, n_ref, count, shift, bits, need_scan, refs, g, ldg, p.width, DivByLen{lens, n},
+                                     grad_tables(p, g_tables), s, &sorted);
+    if (rc || !any_lazy) return rc;
+    return segsum::run_heads<true>(sorted, n_ref, count, shift, p.width, grad_tables(p, g_tables), op, s);
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t mi_pinsage_text_sizeof(int32_t which) { return which == 0 ? (int64_t)sizeof(mi_text_columns) : -1; }
+
+int mi_pinsage_text_f32(const mi_text_columns* pp, int64_t n, const int64_t* ids, float* out, int64_t ldo, int32_t accumulate,
+                        mi_stream_t stream) {
+    const int bad = check_text(pp, n, ids != nullptr);
+    if (bad) return bad;
+    const mi_text_columns& p = *pp;
+    MI_CHECK_ARG(accumulate == 0 || accumulate == 1);
+    if (n == 0) return 0;
+    MI_CHECK_ARG(out && mi_aligned16(out) && ldo >= p.width && ldo % 4 == 0);
+    const int w4 = p.width / 4;
+    if (n * (int64_t)w4 >= ((int64_t)INT32_MAX) * kBlock) return MI_ERR_TOO_LARGE;
+    TextTables tabs;
+    for (int c = 0; c < kT; ++c) tabs.t[c] = c < p.n_text ? reinterpret_cast<const float4*>(p.tables[c]) : nullptr;
+    hipLaunchKernelGGL(text_gather_kernel, dim3(grid_for(n * w4)), dim3(kBlock), 0, (hipStream_t)stream, n, w4, (int)p.n_text, ids,
+                       csr_of(p), tabs, reinterpret_cast<float4*>(out), ldo / 4, (int)accumulate);
+    return mi_launch_status();
+}
+
+size_t mi_pinsage_text_bwd_workspace_bytes(const mi_text_columns* p, int64_t n, int64_t n_ref_max) {
+    if (check_text(p, n, true) != 0 || n_ref_max < 0 || n_ref_max >= INT32_MAX) return 0;
+    return bwd_ws_bytes(*p, n, n_ref_max);
+}
+
+int mi_pinsage_text_bwd_f32(const mi_text_columns* pp, float* const g_tables[], int64_t n, const int64_t* ids, const float* g,
+                            int64_t ldg, int64_t n_ref_max, void* ws, size_t ws_bytes, mi_stream_t stream) {
+    return text_bwd(pp, g_tables, nullptr, nullptr, nullptr, n, ids, g, ldg, n_ref_max, ws, ws_bytes, stream);
+}
+
+int mi_pinsage_text_bwd_lazy_f32(const mi_text_columns* pp, float* const g_tables[], float* const m_tables[], float* const v_tables[],
+                                 const mi_lazy_adam* lazy, int64_t n, const int64_t* ids, const float* g, int64_t ldg,
+                                 int64_t n_ref_max, void* ws, size_t ws_bytes, mi_stream_t stream) {
+    return text_bwd(pp, g_tables, m_tables, v_tables, lazy, n, ids, g, ldg, n_ref_max, ws, ws_bytes, stream);
 }
 
 int mi_pinsage_text_clear_f32(const mi_text_columns* pp, float* const g_tables[], int64_t n, const int64_t* ids, mi_stream_t stream) {

@@ -10,7 +10,10 @@
 //      crosses chunk borders leaves one partial row per chunk: the chunk where it starts writes part_tail[chunk], every later
 //      chunk it reaches writes part_head[chunk] (a chunk that lies wholly inside the run: from_prev wins over into_next);
 //   3. combine_kernel: the group of the chunk where such a run starts adds part_tail[chunk] + part_head[chunk + 1] + ... in
-//      chunk order and stores the row.
+//      chunk order and stores the row;
+//   4. (callers that consume the sums at once) head_kernel: one lane group per reference; the group of the reference that heads
+//      its run of equal keys hands the finished row to the caller's per-row operation — the lazy Adam update of
+//      lazy_adam.hpp.  After the combine, because a run that crosses chunk borders is not complete before it.
 // One writer per row and a fixed association that does not depend on scheduling: equal bits on every call
 // (tests/segsum_emulation.py restates it).  The scheme of bpr_chunk_kernel / bpr_combine_kernel (train.hip), with float4 lanes.
 // The reference count is the host's n_ref, or min(*count, n_ref) read on the device when the caller counts its references
@@ -150,6 +153,28 @@ __global__ __launch_bounds__(kBlock) void combine_kernel(int64_t n_ref_max, cons
     gt.at((int)(key >> shift))[(int64_t)(key & mask) * w4 + e] = acc;
 }
 
+// One lane group per sorted reference; all but the group of a run's first reference leave at the head test (n_ref is at most a
+// few times the rows of a block: a compaction of the heads would cost more than the idle groups).  op(slot, off, cell): cell
+// is float4 `off` (= row * w4 + e) of table `slot`'s buffer, inside a summed row; each (slot, row) is seen by exactly one group.
+template <int kSlots, bool kDeviceCount, typename RowOp>
+__global__ __launch_bounds__(kBlock) void head_kernel(int64_t n_ref_max, const int64_t* __restrict__ count, int w4, int lpr,
+                                                      unsigned shift, const uint64_t* __restrict__ keys, Ptrs<float4, kSlots> gt,
+                                                      RowOp op) {
+    int64_t n_ref = n_ref_max;
+    if constexpr (kDeviceCount) n_ref = min(*count, n_ref_max);   // the slots past it hold the padding key: never a head
+    const int64_t t = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    const int64_t j = t / lpr;
+    const int e = (int)(t - j * lpr);
+    if (j >= n_ref || e >= w4) return;
+    const uint64_t key = keys[j];
+    if (j > 0 && keys[j - 1] == key) return;                     // not the head of its run
+    const uint64_t mask = ((uint64_t)1 << shift) - 1;
+    const int slot = (int)(key >> shift);
+    const int64_t row = (int64_t)(key & mask);
+    const int64_t off = row * w4 + e;
+    op(slot, off, gt.at(slot) + off);
+}
+
 // ---- host ------------------------------------------------------------------------------------------------------------------
 // The sort's double buffers (the caller writes its references to k0 / r0), rocprim's temporary storage (tmp_cap bytes: the
 // caller's bound; it may use tmp itself before the sort) and one head and one tail partial row of `width` floats per chunk.
@@ -184,10 +209,12 @@ inline Buffers take(MiArena& arena, int64_t n_ref, int width, size_t tmp_cap) {
 
 // n_ref > 0 references of `bits` key bits.  The sort's size query enqueues nothing; MI_ERR_WORKSPACE when rocprim's need, or
 // other_tmp_need (what the caller found it needs of tmp itself), exceeds tmp_cap.  Only then build_refs() (-> 0 or an error
-// code) enqueues what writes k0 / r0 (and *count), and the sort, the chunks and the combine follow.
+// code) enqueues what writes k0 / r0 (and *count), and the sort, the chunks and the combine follow.  sorted_keys (optional):
+// which of k0 / k1 holds the sorted keys afterwards (for run_heads).
 template <bool kDeviceCount, int kSlots, typename Term, typename BuildRefs>
 int run(const Buffers& b, int64_t n_ref, const int64_t* count, unsigned shift, unsigned bits, size_t other_tmp_need,
-        BuildRefs&& build_refs, const float* g, int64_t ldg, int width, Term term, const Ptrs<float4, kSlots>& gt, hipStream_t s) {
+        BuildRefs&& build_refs, const float* g, int64_t ldg, int width, Term term, const Ptrs<float4, kSlots>& gt, hipStream_t s,
+        const uint64_t** sorted_keys = nullptr) {
     rocprim::double_buffer<uint64_t> keys(b.k0, b.k1);
     rocprim::double_buffer<uint32_t> refs(b.r0, b.r1);
     size_t need = 0;
@@ -205,6 +232,17 @@ int run(const Buffers& b, int64_t n_ref, const int64_t* count, unsigned shift, u
     hipLaunchKernelGGL((combine_kernel<kSlots, kDeviceCount>), grid, dim3(kBlock), 0, s, n_ref, count, w4, lpr, shift,
                        (const uint64_t*)keys.current(), gt, reinterpret_cast<const float4*>(b.part_head),
                        reinterpret_cast<const float4*>(b.part_tail));
+    if (sorted_keys) *sorted_keys = keys.current();
+    return mi_launch_status();
+}
+
+// op on every summed row of the run() that left `keys` (same n_ref, count, shift, width, gt), after its combine.
+template <bool kDeviceCount, int kSlots, typename RowOp>
+int run_heads(const uint64_t* keys, int64_t n_ref, const int64_t* count, unsigned shift, int width, const Ptrs<float4, kSlots>& gt,
+              RowOp op, hipStream_t s) {
+    const int w4 = width / 4, lpr = lanes_per_row(w4);
+    const dim3 grid((unsigned)mi_ceil_div(n_ref * lpr, kBlock));
+    hipLaunchKernelGGL((head_kernel<kSlots, kDeviceCount, RowOp>), grid, dim3(kBlock), 0, s, n_ref, count, w4, lpr, shift, keys, gt, op);
     return mi_launch_status();
 }
 

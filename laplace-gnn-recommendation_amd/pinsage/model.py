@@ -29,22 +29,25 @@ from ..native_binding import PointerSnapshot
 
 
 class _EmbedRowsFn(t.autograd.Function):
-    """weight[ids] on mi_gather_rows_f32; the (sparse) gradient is accumulated with index_add_."""
+    """weight[ids] on mi_gather_rows_f32; the (sparse) gradient is accumulated with index_add_ into a dense buffer, or, for a lazy
+    table (sparse=True), returned as a torch.sparse_coo_tensor over the rows of `ids`, which torch.optim.SparseAdam takes."""
 
     @staticmethod
-    def forward(ctx, weight: Tensor, ids: Tensor):
+    def forward(ctx, weight: Tensor, ids: Tensor, sparse: bool = False):
         out = t.empty(ids.numel(), weight.shape[1], device=weight.device)
         ops.gather_rows(out, weight, ids.to(t.int32).contiguous())
         ctx.save_for_backward(ids)
-        ctx.shape = weight.shape
+        ctx.shape, ctx.sparse = weight.shape, bool(sparse)
         return out
 
     @staticmethod
     def backward(ctx, g: Tensor):
         (ids,) = ctx.saved_tensors
+        if ctx.sparse:      # repeated ids stay repeated entries: SparseAdam coalesces (sums) them
+            return t.sparse_coo_tensor(ids.reshape(1, -1), g.contiguous(), tuple(ctx.shape)), None, None
         gw = t.zeros(ctx.shape, device=g.device)
         gw.index_add_(0, ids, g.contiguous())
-        return gw, None
+        return gw, None, None
 
 
 class TextColumn:
@@ -229,7 +232,10 @@ class ItemFeatures:
 
 class _ProjectFn(t.autograd.Function):
     """ItemProjector.forward on mi_pinsage_project_f32; the backward on mi_pinsage_project_bwd_f32 into fresh zero buffers of
-    the parameters' shapes (dense table gradients, as _EmbedRowsFn's)."""
+    the parameters' shapes (dense table gradients, as _EmbedRowsFn's).  The gradient of a lazy table (PinSAGEModel(sparse_tables=
+    True): the id table, the text tables) is handed on as a torch.sparse_coo_tensor over the rows the call REFERENCES — their
+    summed rows out of the dense buffer, a row whose sum is exactly zero included — so that torch.optim.SparseAdam moves the
+    rows the native step moves.  torch ops: this is the fallback path."""
 
     @staticmethod
     def forward(ctx, projector: "ItemProjector", ids: Optional[Tensor], *params: Tensor):
@@ -242,6 +248,10 @@ class _ProjectFn(t.autograd.Function):
         projector = ctx.projector
         grads = [t.zeros(s, dtype=t.float32, device=g.device) for s in ctx.shapes]
         projector.project_backward(ctx.ids, g.contiguous(), grads)
+        if projector.sparse_tables:
+            for k, rows in enumerate(projector.referenced_rows(ctx.ids)):
+                if rows is not None:
+                    grads[k] = t.sparse_coo_tensor(rows.reshape(1, -1), grads[k][rows], tuple(ctx.shapes[k]))
         return (None, None, *grads)
 
 
@@ -282,6 +292,7 @@ class ItemProjector(nn.Module):
         self.register_buffer("x", features.categorical, persistent=False)
         self.register_buffer("dense", features.dense, persistent=False)
         self._id = [id_embedding] if id_embedding is not None else []    # a list: PinSAGEModel.proj stays its only registration
+        self.sparse_tables = False                 # PinSAGEModel(sparse_tables=True) sets it: the id and text tables are lazy
         self._bound: Optional["_Bound"] = None     # descriptors, workspaces and the pointers they were built from (bind)
         self.n_text = len(features.text)
         if self.n_text:
@@ -309,6 +320,33 @@ class ItemProjector(nn.Module):
             out += [self.weight, self.bias]
         if self.n_text:
             out += list(self.text_tables)
+        return out
+
+    def lazy_flags(self) -> List[bool]:
+        """Per parameter_list() entry: whether it is a lazy table (the id table and the text tables of a sparse_tables model;
+        categorical tables are cardinality-sized — most rows are touched by every batch — and stay dense)."""
+        n_mid = len(self.tables) + (2 if self.weight is not None else 0)
+        return [self.sparse_tables] * len(self._id) + [False] * n_mid + [self.sparse_tables] * self.n_text
+
+    def referenced_rows(self, ids: Optional[Tensor]) -> List[Optional[Tensor]]:
+        """Per parameter_list() entry: the distinct rows (sorted int64) of a lazy table that project(ids) looks up — the items for
+        the id table, the tokens of those items' bags for a text table — or None for a dense parameter.  torch ops."""
+        dev = self.parameter_list()[0].device
+        items = t.arange(self.n_items, device=dev) if ids is None else ids
+        out: List[Optional[Tensor]] = []
+        for k, lazy in enumerate(self.lazy_flags()):
+            if not lazy:
+                out.append(None)
+            elif k < len(self._id):
+                out.append(t.unique(items))
+            else:
+                c = k - (len(self.lazy_flags()) - self.n_text)
+                ptr, tok = getattr(self, f"text_ptr_{c}"), getattr(self, f"text_tok_{c}")
+                it = out[0] if (self._id and out[0] is not None) else t.unique(items)
+                ln = ptr[it + 1] - ptr[it]
+                rep = t.repeat_interleave(t.arange(it.numel(), device=dev), ln)
+                pos = ptr[it][rep] + (t.arange(rep.numel(), device=dev) - (t.cumsum(ln, 0) - ln)[rep])
+                out.append(t.unique(tok[pos].long()))
         return out
 
     @property
@@ -464,15 +502,47 @@ class ItemProjector(nn.Module):
             _lib.check(L.mi_pinsage_text_bwd_f32(ctypes.byref(b.text), tg, n, idp, g.data_ptr(), ldg, ref_max, ws.data_ptr(), ws.numel(),
                                                  stream), "mi_pinsage_text_bwd_f32")
 
-    def clear_rows(self, ids: Optional[Tensor], grads: Sequence[Tensor], bound: Optional["_Bound"] = None) -> None:
-        """The table rows project_backward(ids, ...) wrote, back to zero (mi_pinsage_project_clear_f32)."""
+    def project_backward_lazy(self, ids: Optional[Tensor], g: Tensor, grads: Sequence[Tensor], moments: Sequence,
+                              lazy: Sequence["_lib.LazyAdam"], bound: Optional["_Bound"] = None) -> None:
+        """project_backward, then torch.optim.SparseAdam's update of every referenced row of the lazy tables in the same calls
+        (mi_pinsage_project_bwd_lazy_f32, mi_pinsage_text_bwd_lazy_f32).  moments: per parameter_list() entry (exp_avg, exp_avg_sq)
+        for a lazy table, None otherwise; lazy = (the id table's hyper-parameters and step, the text tables').  A lazy table's
+        buffer in `grads` reads zero again afterwards; the others hold their gradients as after project_backward."""
+        ids, n, idp = self._rows_of(ids)
+        b, L, stream = bound or self.bind(), _lib.lib(), _lib.current_stream()
+        gd, tg = self._grads(b, grads)
+        ldg = int(g.stride(0)) if n else self.hidden
+        moments = list(moments)
+        if self.has_base:
+            mo = _lib.ItemProjectorMoments()
+            if self._id and moments[0] is not None:
+                mo.m_id_table, mo.v_id_table = moments[0][0].data_ptr(), moments[0][1].data_ptr()
+            for c, pair in enumerate(moments[len(self._id): len(self._id) + len(self.tables)]):
+                if pair is not None:       # a categorical table is dense in every model of this package; the entry takes either
+                    mo.m_tables[c], mo.v_tables[c] = pair[0].data_ptr(), pair[1].data_ptr()
+            ws = self._workspace(b, n)
+            _lib.check(L.mi_pinsage_project_bwd_lazy_f32(ctypes.byref(b.base), ctypes.byref(gd), ctypes.byref(mo), ctypes.byref(lazy[0]),
+                                                         n, idp, g.data_ptr(), ldg, ws.data_ptr(), ws.numel(), stream),
+                       "mi_pinsage_project_bwd_lazy_f32")
+        if self.n_text:
+            mt, vt = _lib.TextGradTables(), _lib.TextGradTables()
+            for c, pair in enumerate(moments[len(moments) - self.n_text:]):
+                if pair is not None:
+                    mt[c], vt[c] = pair[0].data_ptr(), pair[1].data_ptr()
+            ws, ref_max = self._text_workspace(b, n, ids is not None)
+            _lib.check(L.mi_pinsage_text_bwd_lazy_f32(ctypes.byref(b.text), tg, mt, vt, ctypes.byref(lazy[1]), n, idp, g.data_ptr(), ldg,
+                                                      ref_max, ws.data_ptr(), ws.numel(), stream), "mi_pinsage_text_bwd_lazy_f32")
+
+    def clear_rows(self, ids: Optional[Tensor], grads: Sequence[Tensor], bound: Optional["_Bound"] = None, text: bool = True) -> None:
+        """The table rows project_backward(ids, ...) wrote, back to zero (mi_pinsage_project_clear_f32); text=False leaves the text
+        tables' buffers out (the lazy backward has zeroed them itself)."""
         ids, n, idp = self._rows_of(ids)
         b, L, stream = bound or self.bind(), _lib.lib(), _lib.current_stream()
         gd, tg = self._grads(b, grads)
         if self.has_base:
             _lib.check(L.mi_pinsage_project_clear_f32(ctypes.byref(b.base), ctypes.byref(gd), n, idp, stream),
                        "mi_pinsage_project_clear_f32")
-        if self.n_text:
+        if self.n_text and text:
             _lib.check(L.mi_pinsage_text_clear_f32(ctypes.byref(b.text), tg, n, idp, stream), "mi_pinsage_text_clear_f32")
 
     def forward(self, ids: Optional[Tensor] = None) -> Tensor:
@@ -539,11 +609,16 @@ class WeightedSAGEConv(nn.Module):
 
 class PinSAGEModel(nn.Module):
     def __init__(self, n_items: int, hidden_dims: int, n_layers: int, features: Optional[ItemFeatures] = None,
-                 use_id: bool = True):
+                 use_id: bool = True, sparse_tables: bool = False):
         """features=None, use_id=True: the id-only model (the id is the one feature the reference's dataset assigns).  With
         `features` the LinearProjector sums the id row (if use_id) with every feature column's projection (ItemProjector):
-        an item without interactions, whose id row is never trained, is then placed by its features."""
+        an item without interactions, whose id row is never trained, is then placed by its features.
+        sparse_tables=True (the reference's pinsage/model_sparse.py: nn.Embedding(sparse=True) + SparseAdam): the id table and
+        every text table are LAZY — trained by torch.optim.SparseAdam(model.sparse_parameters()) beside
+        torch.optim.Adam(model.dense_parameters()); only the rows a batch references move, and a step costs what the batch
+        costs, not what the tables do.  Parameter names, order and initial draws are the same either way."""
         super().__init__()
+        self.sparse_tables = bool(sparse_tables)
         if features is None and not use_id:
             raise ValueError("PinSAGEModel: use_id=False needs features (nothing would be projected)")
         if features is not None and features.n_items != n_items:
@@ -556,16 +631,31 @@ class PinSAGEModel(nn.Module):
         self.bias = nn.Parameter(t.zeros(n_items, 1))          # ItemToItemScorer
         if features is not None:
             self.projector = ItemProjector(features, hidden_dims, self.proj if use_id else None)
+            self.projector.sparse_tables = self.sparse_tables
 
     @property
     def featured(self) -> bool:
         return hasattr(self, "projector")
 
+    def sparse_parameters(self) -> List[nn.Parameter]:
+        """The lazy tables, in parameters() order: the id table and the text tables of a sparse_tables model; else nothing."""
+        if not self.sparse_tables:
+            return []
+        out = [self.proj.weight] if hasattr(self, "proj") else []
+        if self.featured and self.projector.n_text:
+            out += list(self.projector.text_tables)
+        return out
+
+    def dense_parameters(self) -> List[nn.Parameter]:
+        """parameters() without sparse_parameters(), in the same order."""
+        lazy = {id(p) for p in self.sparse_parameters()}
+        return [p for p in self.parameters() if id(p) not in lazy]
+
     def project(self, ids: Tensor) -> Tensor:
         """LinearProjector over the rows `ids`: the id table alone, or the feature projector."""
         if self.featured:
             return self.projector(ids)
-        return _EmbedRowsFn.apply(self.proj.weight, ids)
+        return _EmbedRowsFn.apply(self.proj.weight, ids, self.sparse_tables)
 
     def get_repr(self, blocks: List[dict]) -> Tensor:
         h = self.project(blocks[0]["src_ids"])
@@ -613,8 +703,11 @@ class PinSAGEModel(nn.Module):
         return (self.score(h, seeds, neg) - self.score(h, seeds, pos) + 1).clamp(min=0)
 
 
-def train_epoch(model: PinSAGEModel, optimizer: t.optim.Optimizer, sampler, batches: int, group=None) -> List[float]:
-    """pinsage/model.py:118-131: hinge loss mean over the batch's pairs, Adam.
+def train_epoch(model: PinSAGEModel, optimizer: t.optim.Optimizer, sampler, batches: int, group=None,
+                sparse_optimizer: Optional[t.optim.Optimizer] = None) -> List[float]:
+    """pinsage/model.py:118-131: hinge loss mean over the batch's pairs, Adam.  A sparse_tables model (pinsage/model_sparse.py)
+    brings its pair: optimizer = Adam(model.dense_parameters()), sparse_optimizer = SparseAdam(model.sparse_parameters()); the
+    autograd fallback zeroes and steps both.  Single-process only: a multi-rank run with a sparse optimizer raises.
 
     Under torch.distributed (BASELINE configs[4]: 4 GPUs) the run is data-parallel: every rank owns a replica and a
     sampler with its own seed (the item-item walks need the whole graph, 0.4 GB of int32 CSR, so it is replicated),
@@ -630,10 +723,16 @@ def train_epoch(model: PinSAGEModel, optimizer: t.optim.Optimizer, sampler, batc
     # every rank must take the same path, which it does: the choice depends on the model, the optimizer and the sampler's
     # configuration only.
     multi = dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1
+    if multi and sparse_optimizer is not None:
+        raise ValueError("train_epoch: data-parallel training with a sparse optimizer is not built (the lazy tables' rows would "
+                         "have to be exchanged and summed across ranks before the update)")
+    if getattr(model, "sparse_tables", False) and sparse_optimizer is None and model.sparse_parameters():
+        raise ValueError("train_epoch: a sparse_tables model needs sparse_optimizer (torch.optim.SparseAdam over "
+                         "model.sparse_parameters()); its lazy tables' gradients are sparse tensors")
     native = None
-    if NativePinSAGEStep.supports(model, optimizer):
+    if NativePinSAGEStep.supports(model, optimizer, sparse_optimizer):
         if not multi:
-            native = NativePinSAGEStep(model, optimizer)
+            native = NativePinSAGEStep(model, optimizer, sparse_optimizer)
         elif model.featured:
             native = None    # data-parallel native features are not built: the autograd iteration with its dense all-reduce, on every rank
         elif all(hasattr(sampler, a) for a in ("batch_size", "T", "n_layers")):
@@ -656,8 +755,12 @@ def train_epoch(model: PinSAGEModel, optimizer: t.optim.Optimizer, sampler, batc
             # below — with its dense all-reduce — runs on all of them
             loss = model(b["seeds"], b["pos"], b["neg"], b["blocks"]).mean()
             optimizer.zero_grad()
+            if sparse_optimizer is not None:
+                sparse_optimizer.zero_grad()
             loss.backward()
             allreduce_gradients(model.parameters(), group)
             optimizer.step()
+            if sparse_optimizer is not None:
+                sparse_optimizer.step()
             losses.append(loss.detach())
     return t.stack(losses).cpu().tolist() if losses else []

@@ -20,6 +20,15 @@ into its rows; alone for a text-only model), mi_pinsage_text_bwd_f32 after its b
 clear; the text tables are ordinary entries of mi_adam_multi_f32's list.  All of those calls are ItemProjector's own methods
 (project / project_backward / clear_rows, pinsage/model.py) over its cached descriptors and workspaces: the step only says when.
 
+The sparse trainer (PinSAGEModel(sparse_tables=True) with its pair of optimizers, the reference's pinsage/model_sparse.py): the id
+table and the text tables are LAZY — torch.optim.SparseAdam's update on the rows the batch references and nothing else.  Both model
+kinds then run the executor in rows_out mode with apply_adam = 0; the id-only model hands the compact rows of blocks[0].src_ids
+(distinct) to mi_lazy_adam_rows_f32, a featured model takes mi_pinsage_project_bwd_lazy_f32 / mi_pinsage_text_bwd_lazy_f32 in place
+of the two backwards; then the scorer-bias scatter, mi_adam_multi_f32 over the DENSE set only, and the clear.  Nothing in the
+iteration walks a lazy table: `p.grad` of a lazy table stays None (the id-only model has no table-sized gradient at all; a
+featured model's summed rows pass through a zero-kept buffer the step owns), and sparse_optimizer.state[p] keeps torch's layout
+(`step` a Python int, dense exp_avg / exp_avg_sq), so its state_dict() loads into a fresh SparseAdam and the reverse.
+
 The host side shared with the ranker's executor — Adam's state, the flat gradient buffer, the stale-descriptor test, the
 collective decline — is native_binding.py.
 """
@@ -52,22 +61,29 @@ def _fill_convs(d: PinsageModel, model: PinSAGEModel, with_grads: bool) -> None:
 
 
 class NativePinSAGEStep:
-    def __init__(self, model: PinSAGEModel, optimizer: t.optim.Optimizer, seed: Optional[int] = None, keep_grads: bool = False,
-                 data_parallel: bool = False, group=None):
+    def __init__(self, model: PinSAGEModel, optimizer: t.optim.Optimizer, sparse_optimizer: Optional[t.optim.Optimizer] = None,
+                 seed: Optional[int] = None, keep_grads: bool = False, data_parallel: bool = False, group=None):
         """data_parallel (BASELINE configs[4]: 4 GPUs): every rank runs the executor on its own batch with the projector / bias
         gradients written COMPACTLY (the rows of the batch), the ranks all-gather those lists (a few hundred KB instead of an
         all-reduce of the dense 27 MB table gradient), all-reduce the dense layers' gradients (one flat buffer), and
         mi_pinsage_apply_f32 adds every rank's rows in rank order, applies Adam on the mean gradient and clears the rows:
         replicas stay bitwise identical.  Batches must keep the sampler's size bounds (they size the exchange buffer)."""
+        if data_parallel and sparse_optimizer is not None:
+            raise ValueError("NativePinSAGEStep: data_parallel with a sparse optimizer is not built (the lazy tables' rows of every "
+                             "rank would have to be exchanged and summed before the update)")
         if data_parallel and getattr(model, "featured", False):
             raise ValueError("NativePinSAGEStep: data_parallel with item features is not built (the compact row exchange carries "
                              "id-table rows only); use the autograd iteration with its dense all-reduce")
-        why = self.unsupported_reason(model, optimizer)
+        why = self.unsupported_reason(model, optimizer, sparse_optimizer)
         if why:
             raise ValueError(f"NativePinSAGEStep: {why}")
         if data_parallel and keep_grads:
             raise ValueError("NativePinSAGEStep: keep_grads is a single-process probe")
         self.model, self.optimizer, self.keep_grads = model, optimizer, bool(keep_grads)
+        self.sparse_optimizer = sparse_optimizer
+        self._lazy: list = model.sparse_parameters() if sparse_optimizer is not None else []
+        self._lazy_g: dict = {}                        # featured: lazy table -> the zero-kept buffer its summed rows pass through
+        self._kept_ids: Optional[Tensor] = None        # keep_grads: blocks[0].src_ids of the last step (table_grad)
         self.data_parallel, self.group = bool(data_parallel), group
         self._flat_small: Optional[Tensor] = None     # data-parallel: the dense layers' gradients, one allocation
         self._xbuf = None                              # data-parallel: (send int32 buffer, gathered buffer, capacity in rows)
@@ -85,7 +101,7 @@ class NativePinSAGEStep:
 
     # ------------------------------------------------------------------------------------------
     @staticmethod
-    def unsupported_reason(model, optimizer) -> Optional[str]:
+    def unsupported_reason(model, optimizer, sparse_optimizer=None) -> Optional[str]:
         if not isinstance(model, PinSAGEModel):
             return "not a PinSAGEModel"
         why = adam_unsupported_reason(optimizer)
@@ -93,12 +109,28 @@ class NativePinSAGEStep:
             return why
         g = optimizer.param_groups[0]
         params = list(model.parameters())
-        if len(g["params"]) != len(params) or any(a is not b for a, b in zip(g["params"], params)):
-            return "the optimizer's parameter list is not model.parameters()"
+        lazy = model.sparse_parameters()
+        same = lambda have, want: len(have) == len(want) and all(a is b for a, b in zip(have, want))
+        if lazy:
+            if sparse_optimizer is None:
+                return "a sparse_tables model needs sparse_optimizer: torch.optim.SparseAdam over model.sparse_parameters()"
+            if type(sparse_optimizer) is not t.optim.SparseAdam or len(sparse_optimizer.param_groups) != 1:
+                return "sparse_optimizer other than a single-group torch.optim.SparseAdam"
+            if sparse_optimizer.param_groups[0].get("maximize"):
+                return "SparseAdam option maximize"
+            if not same(sparse_optimizer.param_groups[0]["params"], lazy):
+                return "sparse_optimizer's parameter list is not model.sparse_parameters()"
+            if not same(g["params"], model.dense_parameters()):
+                return "the optimizer's parameter list is not model.dense_parameters()"
+        else:
+            if sparse_optimizer is not None:
+                return "sparse_optimizer given, but the model has no lazy tables (PinSAGEModel(sparse_tables=True))"
+            if not same(g["params"], params):
+                return "the optimizer's parameter list is not model.parameters()"
         hidden = model.hidden
         if hidden % 4 or hidden > 128 or not (1 <= len(model.convs) <= _lib.MI_PINSAGE_MAX_LAYERS):
             return "hidden size / layer count outside the executor's"
-        if (4 * len(model.convs) if model.featured else len(params) - 1) > _lib.MI_PINSAGE_MAX_PARAMS:
+        if (4 * len(model.convs) if (model.featured or lazy) else len(params) - 1) > _lib.MI_PINSAGE_MAX_PARAMS:
             return "too many parameter tensors"
         if model.featured and model.projector.n_items != model.n_items:
             return "features and model disagree on the item count"
@@ -114,16 +146,25 @@ class NativePinSAGEStep:
         return None
 
     @classmethod
-    def supports(cls, model, optimizer) -> bool:
-        return cls.unsupported_reason(model, optimizer) is None
+    def supports(cls, model, optimizer, sparse_optimizer=None) -> bool:
+        return cls.unsupported_reason(model, optimizer, sparse_optimizer) is None
 
     # ------------------------------------------------------------------------------------------
     def _build(self) -> PinsageModel:
         """The executor's descriptor.  Id-only: the id table with its gradient and moments apart (proj / g_proj / m_proj / v_proj),
         every other tensor in `params`.  Featured: over a COMPACT projected table (set per batch, _prepare) — its params are the
         layers' only, it never applies Adam and never touches g_proj / m_proj / v_proj (rows_out mode); every tensor of the
-        optimizer's group is in mi_adam_multi_f32's flat list instead."""
+        optimizer's group is in mi_adam_multi_f32's flat list instead.  With lazy tables (sparse trainer) the id-only model takes
+        the featured layout too — rows_out mode over the REAL id table, the dense group in the flat list — and the lazy tables get
+        torch.optim.SparseAdam's state as that optimizer creates it on its first step."""
         model, opt = self.model, self.optimizer
+        lazy = self._lazy
+        for p in lazy:
+            st = self.sparse_optimizer.state[p]
+            if len(st) == 0:
+                st["step"] = 0
+                st["exp_avg"] = t.zeros_like(p, memory_format=t.preserve_format)
+                st["exp_avg_sq"] = t.zeros_like(p, memory_format=t.preserve_format)
         d = PinsageModel()
         keep = self._keep = []
         group = opt.param_groups[0]
@@ -140,8 +181,16 @@ class NativePinSAGEStep:
         bias, pr = model.bias, (model.projector if model.featured else None)
         # the dense buffers kept all-zero between iterations: the scorer bias's and every table's (id and text tables included)
         tables = [model.proj.weight] if pr is None else [p for p in pr.parameter_list() if p is not pr.weight and p is not pr.bias]
+        if pr is not None:
+            for p in lazy:
+                have = self._lazy_g.get(p)
+                if have is None or have.shape != p.shape or have.device != p.device:
+                    self._lazy_g[p] = t.empty_like(p, memory_format=t.contiguous_format)
+            keep += list(self._lazy_g.values())
         for p in tables + [bias]:
-            p.grad.zero_()
+            buf = self._grad_buffer(p)
+            if buf is not None:
+                buf.zero_()
         d.n_layers, d.hidden, d.n_items = len(model.convs), model.hidden, model.n_items
         d.bias, d.g_bias = bias.data_ptr(), bias.grad.data_ptr()
         _fill_convs(d, model, with_grads=True)
@@ -150,9 +199,16 @@ class NativePinSAGEStep:
             d.hidden, d.n_items = int(proj.shape[1]), int(bias.shape[0])
             if proj.shape[0] != d.n_items + 1:
                 raise ValueError("NativePinSAGEStep: projector table and scorer bias disagree on the item count")
-            sp = opt.state[proj]
-            d.proj, d.g_proj, d.m_proj, d.v_proj = proj.data_ptr(), proj.grad.data_ptr(), sp["exp_avg"].data_ptr(), sp["exp_avg_sq"].data_ptr()
+            sp = self.sparse_optimizer.state[proj] if lazy else opt.state[proj]
+            # lazy: rows_out mode never touches g / m / v (there is no table-sized gradient): any valid address stands in for g
+            d.proj, d.g_proj = proj.data_ptr(), (sp["exp_avg"] if lazy else proj.grad).data_ptr()
+            d.m_proj, d.v_proj = sp["exp_avg"].data_ptr(), sp["exp_avg_sq"].data_ptr()
             mine = [p for p in params if p is not proj]
+            if lazy:
+                mine = [p for cv in model.convs for p in _conv_params(cv)]
+                self._flat_params = (_lib.RankerParam * len(params))()
+                for q, p in zip(self._flat_params, params):
+                    bind_param(q, p, p.grad, opt.state[p])
         else:
             mine = [p for cv in model.convs for p in _conv_params(cv)]
             self._flat_params = (_lib.RankerParam * len(params))()
@@ -160,16 +216,55 @@ class NativePinSAGEStep:
                 bind_param(q, p, p.grad, opt.state[p])
             # the projector's descriptors, checked here and not again until this descriptor is rebuilt (_snapshot_now covers the
             # same tensors); the gradient buffers as one tuple, which the projector recognises by identity
-            self._proj_bound, self._proj_grads = pr.bind(), tuple(p.grad for p in pr.parameter_list())
+            self._proj_bound, self._proj_grads = pr.bind(), tuple(self._grad_buffer(p) for p in pr.parameter_list())
+            sst = self.sparse_optimizer.state if lazy else None
+            self._proj_moments = [(sst[p]["exp_avg"], sst[p]["exp_avg_sq"]) if any(p is q for q in lazy) else None
+                                  for p in pr.parameter_list()]
         for q, p in zip(d.params, mine):
             bind_param(q, p, p.grad, opt.state[p])
         d.n_params = len(mine)
         self._adam_step = int(opt.state[params[0]]["step"]) if params else 0
         return d
 
+    def _grad_buffer(self, p: Tensor) -> Optional[Tensor]:
+        """Where p's gradient lands: p.grad, or for a lazy table the step's own zero-kept buffer (featured) / nothing (id-only)."""
+        if any(p is q for q in self._lazy):
+            return self._lazy_g.get(p)
+        return p.grad
+
+    def _lazy_tensors(self) -> list:
+        """The lazy tables with their moments (KeyError when a state was dropped: the snapshot then reads as stale)."""
+        st = self.sparse_optimizer.state
+        return [x for p in self._lazy for x in (p, st[p]["exp_avg"], st[p]["exp_avg_sq"])]
+
     def _snapshot_now(self) -> PointerSnapshot:
-        """Every tensor of the optimizer's group with its gradient and moments; featured: the projector's data buffers too."""
-        return PointerSnapshot([self.model.projector.feature_buffers] if self.model.featured else [], optimizer=self.optimizer)
+        """Every tensor of the optimizer's group with its gradient and moments; featured: the projector's data buffers too; the
+        lazy tables and their moments."""
+        getters = [self.model.projector.feature_buffers] if self.model.featured else []
+        if self._lazy:
+            getters.append(self._lazy_tensors)
+        return PointerSnapshot(getters, optimizer=self.optimizer)
+
+    def _lazy_args(self, params) -> "_lib.LazyAdam":
+        """torch.optim.SparseAdam's hyper-parameters and the step of THIS update for `params` (which share their step count)."""
+        g, st = self.sparse_optimizer.param_groups[0], self.sparse_optimizer.state
+        z = _lib.LazyAdam()
+        z.lr, (z.beta1, z.beta2), z.eps = float(g["lr"]), (float(b) for b in g["betas"]), float(g["eps"])
+        z.step = int(st[params[0]]["step"]) + 1 if params else 1
+        return z
+
+    def table_grad(self, p: Tensor) -> Tensor:
+        """keep_grads=True: the gradient of lazy table `p` from the last step — the summed rows of the rows the batch referenced —
+        as a coalesced torch.sparse_coo_tensor (what the autograd path's p.grad holds, coalesced).  torch ops: a probe."""
+        if not self.keep_grads or self._kept_ids is None or not any(p is q for q in self._lazy):
+            raise ValueError("NativePinSAGEStep.table_grad: needs keep_grads=True, a step taken, and a lazy table of the model")
+        ids0 = self._kept_ids
+        if not self.model.featured:
+            return t.sparse_coo_tensor(ids0.reshape(1, -1), self._rows[1][: ids0.numel()].clone(), tuple(p.shape)).coalesce()
+        pr = self.model.projector
+        k = [i for i, q in enumerate(pr.parameter_list()) if q is p][0]
+        rows = pr.referenced_rows(ids0)[k]
+        return t.sparse_coo_tensor(rows.reshape(1, -1), self._lazy_g[p][rows], tuple(p.shape)).coalesce()
 
     # ------------------------------------------------------------------------------------------
     def _prepare(self, batch: dict):
@@ -200,12 +295,20 @@ class NativePinSAGEStep:
             self._snapshot = self._snapshot_now()
         elif self.keep_grads:      # the previous call left its rows in the dense buffers
             for p in ([model.bias] + model.projector.parameter_list()) if model.featured else (model.proj.weight, model.bias):
-                p.grad.zero_()
+                buf = self._grad_buffer(p)
+                if buf is not None:
+                    buf.zero_()
+        if self._lazy:
+            idw = model.proj.weight if hasattr(model, "proj") else None
+            steps = {int(self.sparse_optimizer.state[p]["step"]) for p in self._lazy if p is not idw}
+            if len(steps) > 1:
+                self.declined = "text tables with different SparseAdam step counts"
+                return None
         d = self._desc
         group = self.optimizer.param_groups[0]
         d.p_dropout = float(model.convs[0].dropout.p)
         d.lr, (d.beta1, d.beta2), d.eps = float(group["lr"]), (float(b) for b in group["betas"]), float(group["eps"])
-        d.apply_adam = 0 if (self.keep_grads or self.data_parallel or model.featured) else 1
+        d.apply_adam = 0 if (self.keep_grads or self.data_parallel or model.featured or self._lazy) else 1
         d.step = self._adam_step + 1
         b = PinsageStepBatch()
         b.n_blocks = len(blocks)
@@ -231,16 +334,18 @@ class NativePinSAGEStep:
             send = self._exchange_buffer(b, blocks[0]["src_ids"], seeds)
             if send is None:
                 return None
-        if model.featured:
-            # the executor reads row r of a compact table for block 0's r-th source: its ids are 0 .. n0 - 1
+        if model.featured or self._lazy:
+            # featured: the executor reads row r of a compact table for block 0's r-th source: its ids are 0 .. n0 - 1.  Lazy
+            # id-only: the real table and ids, only the gradient rows come back compactly.
             n0, H = int(blocks[0]["src_ids"].numel()), model.hidden
             if self._rows is None or self._rows.shape[1] < n0:
                 cap = max(1024, int(n0 * 1.25))
                 self._rows = t.empty(3, cap, H, dtype=t.float32, device=seeds.device)   # projected rows, their gradient, bias_out
                 self._arange = t.arange(cap, dtype=t.int64, device=seeds.device)
             rows = self._rows
-            b.blocks[0].src_ids = self._arange.data_ptr()
-            d.proj = d.g_proj = d.m_proj = d.v_proj = rows[0].data_ptr()      # g / m / v: never touched in rows_out mode
+            if model.featured:
+                b.blocks[0].src_ids = self._arange.data_ptr()
+                d.proj = d.g_proj = d.m_proj = d.v_proj = rows[0].data_ptr()      # g / m / v: never touched in rows_out mode
             b.rows_out, b.bias_out = rows[1].data_ptr(), rows[2].data_ptr()
         L = _lib.lib()
         need = int(L.mi_pinsage_step_workspace_bytes(ctypes.byref(d), ctypes.byref(b)))
@@ -280,8 +385,11 @@ class NativePinSAGEStep:
         group = self.optimizer.param_groups[0]
         L = _lib.lib()
         pr = self.model.projector if self.model.featured else None
+        lazy = self._lazy
+        if pr is not None or lazy:
+            ids0, rows = batch["blocks"][0]["src_ids"], self._rows
         if pr is not None:
-            ids0, rows, bound = batch["blocks"][0]["src_ids"], self._rows, self._proj_bound
+            bound = self._proj_bound
             pr.project(ids0, out=rows[0], bound=bound)
         rc = L.mi_pinsage_step_f32(ctypes.byref(d), ctypes.byref(b), self._ws.data_ptr(), self._ws.numel(), _lib.current_stream())
         if rc == _lib.MI_ERR_UNSUPPORTED:
@@ -294,20 +402,38 @@ class NativePinSAGEStep:
         self.iteration += 1
         if self.data_parallel:
             self._exchange_and_apply(d)
-        if pr is not None:
+        if pr is not None or lazy:
             seeds = batch["seeds"]
-            pr.project_backward(ids0, rows[1], self._proj_grads, bound=bound)
+            self._kept_ids = ids0 if self.keep_grads else None
+            if pr is None:           # lazy id-only: the compact rows of the distinct ids straight into the row update
+                if not self.keep_grads:
+                    proj, st = self.model.proj.weight, self.sparse_optimizer.state[self.model.proj.weight]
+                    ids0 = ids0.contiguous()
+                    _lib.check(L.mi_lazy_adam_rows_f32(int(proj.shape[0]), int(proj.shape[1]), proj.data_ptr(), st["exp_avg"].data_ptr(),
+                                                       st["exp_avg_sq"].data_ptr(), int(ids0.numel()), ids0.data_ptr(), rows[1].data_ptr(),
+                                                       int(rows[1].stride(0)), ctypes.byref(self._lazy_args([proj])),
+                                                       _lib.current_stream()), "mi_lazy_adam_rows_f32")
+            elif lazy and not self.keep_grads:
+                ids_p = [p for p in lazy if p is pr.id_weight]
+                text_p = [p for p in lazy if p is not pr.id_weight]
+                pr.project_backward_lazy(ids0, rows[1], self._proj_grads, self._proj_moments,
+                                         (self._lazy_args(ids_p), self._lazy_args(text_p)), bound=bound)
+            else:
+                pr.project_backward(ids0, rows[1], self._proj_grads, bound=bound)
             gb = self.model.bias.grad.view(-1)
             gb.index_copy_(0, seeds, rows[2].view(-1)[: seeds.numel()])     # the seeds are distinct
             if not self.keep_grads:
                 _lib.check(L.mi_adam_multi_f32(self._flat_params, len(self._flat_params), float(group["lr"]),
                                                float(group["betas"][0]), float(group["betas"][1]), float(group["eps"]),
                                                self._adam_step + 1, _lib.current_stream()), "mi_adam_multi_f32")
-                pr.clear_rows(ids0, self._proj_grads, bound=bound)
+                if pr is not None and (not lazy or len(pr.tables)):      # the lazy backward zeroed the lazy tables' rows itself
+                    pr.clear_rows(ids0, self._proj_grads, bound=bound, text=not lazy)
                 gb.index_fill_(0, seeds, 0.0)
         if not self.keep_grads:
             self._adam_step += 1
             bump_adam_steps([self.optimizer.state[q]["step"] for q in group["params"]])
+            for q in lazy:
+                self.sparse_optimizer.state[q]["step"] += 1
         return loss
 
     # ------------------------------------------------------------------------------------------
