@@ -1012,6 +1012,41 @@ size_t mi_pinsage_batch_workspace_bytes(int64_t batch, int32_t walk_length, int3
 int    mi_pinsage_sample_batch(const mi_pinsage_batch_desc* desc, uint64_t seed, uint64_t step,
                                const mi_pinsage_batch_out* out, void* ws, size_t ws_bytes, mi_stream_t stream);
 
+/* N5, hard negatives from random-walk ranks (PinSAGE paper, section 3.3; neither the reference nor DGL's example has them):
+ * items related to the head but ranked below its true neighbours by visit count replace a share of the uniform negatives.
+ * The rule, for pair b of the batch at (seed, step), after mi_pinsage_item_pairs wrote heads[b] = h, tails[b] = tl and the
+ * uniform neg_tails[b] (Philox counters laid out as for the other PinSAGE draws: (a, b, c, purpose | step << 8)):
+ *   dead pairs   tl == -1: the pair is left alone.
+ *   selection    pk = Philox(purpose 15, a = b, 0, 0, seed, step); the pair is hard iff share >= 1 or
+ *                pk.c[0] < (uint32)(share * 2^32); otherwise neg_tails[b] stays uniform.
+ *   walks        num_walks walks from h of at most walk_length item -> user -> item traversals under mi_pinsage_neighbors'
+ *                law: before every traversal but the first the walk ends if w.c[2] < (uint32)(restart_prob * 2^32); the hop
+ *                takes w.c[0] (user) and w.c[1] (item); a walk that meets an item without users ends.  Draws:
+ *                w = Philox(purpose 16, a = walk * walk_length + traversal, 0, h, seed, step) — keyed on the head item, so
+ *                two pairs with one head share their walks and differ only in pk.
+ *   counting     every item reached at the end of a traversal is counted; then h and tl are removed from the counts.
+ *   ranking      the remaining m distinct items are ranked by (count desc, id asc); end = min(rank_hi, m); if end <= rank_lo
+ *                the uniform negative stays, otherwise neg_tails[b] = the item at rank rank_lo + pk.c[1] % (end - rank_lo).
+ * One workgroup per pair, visits sorted in LDS: num_walks * walk_length <= 4096, beyond that MI_ERR_UNSUPPORTED.  Argument
+ * errors (num_walks, walk_length <= 0; restart_prob outside [0, 1); share outside [0, 1]; rank_lo < 0; rank_hi <= rank_lo)
+ * and the limit are reported before anything is enqueued.
+ * mi_pinsage_hard_negatives: neg_tails holds the uniform negatives on entry; rank_out (nullable, int32[batch]) receives for
+ *   every pair the rank taken, or -1 where the uniform negative stayed or the pair is dead.
+ * mi_pinsage_sample_batch_hard: mi_pinsage_sample_batch with that launch between the item pairs and the seeds, so that the
+ *   seeds, the positions and the banned label-pair keys come from the final negatives; hn == NULL or share == 0 enqueues
+ *   exactly mi_pinsage_sample_batch's launches.  mi_pinsage_batch_workspace_bytes sizes the workspace. */
+typedef struct mi_pinsage_hard_neg { int32_t num_walks, walk_length, rank_lo, rank_hi; double restart_prob, share; } mi_pinsage_hard_neg;
+int64_t mi_pinsage_hard_sizeof(void);                       /* binding self-check */
+int    mi_pinsage_hard_negatives(int64_t batch, int64_t n_items,
+                                 const int32_t* iu_ptr, const int32_t* iu_idx,
+                                 const int32_t* ui_ptr, const int32_t* ui_idx,
+                                 const mi_pinsage_hard_neg* hn, uint64_t seed, uint64_t step,
+                                 const int64_t* heads, const int64_t* tails, int64_t* neg_tails,
+                                 int32_t* rank_out, mi_stream_t stream);
+int    mi_pinsage_sample_batch_hard(const mi_pinsage_batch_desc* desc, const mi_pinsage_hard_neg* hn,
+                                    uint64_t seed, uint64_t step, const mi_pinsage_batch_out* out,
+                                    void* ws, size_t ws_bytes, mi_stream_t stream);
+
 /* ------------------------------------------------------------------------------------
  * N5  one PinSAGE training iteration as ONE call (round 3).
  * replaces: the loop body of pinsage/model.py:118-131 (train) on PinSAGEModel (pinsage/model.py:16-34): LinearProjector

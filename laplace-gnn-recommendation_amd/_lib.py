@@ -138,6 +138,11 @@ class PinsageBatchOut(Structure):
                 ("blocks", PinsageBlockOut * MI_PINSAGE_MAX_LAYERS)]
 
 
+class PinsageHardNeg(Structure):
+    _fields_ = [("num_walks", c_int32), ("walk_length", c_int32), ("rank_lo", c_int32), ("rank_hi", c_int32),
+                ("restart_prob", c_double), ("share", c_double)]
+
+
 class WgradProblem(Structure):
     _fields_ = [("k", c_int64), ("m", c_int32), ("n1", c_int32), ("n2", c_int32), ("reserved", c_int32),
                 ("dy", c_void_p), ("mask", c_void_p), ("b1", c_void_p), ("b2", c_void_p),
@@ -308,6 +313,10 @@ _PROTOTYPES = {
                                        c_uint64, c_uint64, P, P, P, c_size_t, P]),
     "mi_pinsage_batch_workspace_bytes": (c_size_t, [c_int64, c_int32, c_int32, c_int32, c_int32]),
     "mi_pinsage_sample_batch": (c_int32, [POINTER(PinsageBatchDesc), c_uint64, c_uint64, POINTER(PinsageBatchOut), P, c_size_t, P]),
+    "mi_pinsage_hard_sizeof": (c_int64, []),
+    "mi_pinsage_hard_negatives": (c_int32, [c_int64, c_int64, P, P, P, P, POINTER(PinsageHardNeg), c_uint64, c_uint64, P, P, P, P, P]),
+    "mi_pinsage_sample_batch_hard": (c_int32, [POINTER(PinsageBatchDesc), POINTER(PinsageHardNeg), c_uint64, c_uint64,
+                                               POINTER(PinsageBatchOut), P, c_size_t, P]),
     "mi_pinsage_step_sizeof": (c_int64, [c_int32]),
     "mi_pinsage_step_workspace_bytes": (c_size_t, [POINTER(PinsageModel), POINTER(PinsageStepBatch)]),
     "mi_pinsage_step_f32": (c_int32, [POINTER(PinsageModel), POINTER(PinsageStepBatch), P, c_size_t, P]),

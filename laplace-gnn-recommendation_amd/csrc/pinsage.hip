@@ -12,7 +12,7 @@
 
 namespace {
 
-enum { P_HEAD = 11, P_NEG = 12, P_WALK = 13 };
+enum { P_HEAD = 11, P_NEG = 12, P_WALK = 13, P_HARD_PICK = 15, P_HARD_WALK = 16 };   // 14: named by the oracle
 
 __device__ __forceinline__ MiPhilox pw(uint32_t purpose, uint32_t a, uint32_t b, uint32_t c, uint64_t seed, uint64_t step) {
     const uint32_t c3 = (purpose & 0xFFu) | ((uint32_t)(step & 0xFFFFFFu) << 8);
@@ -386,6 +386,97 @@ __global__ __launch_bounds__(kBT) void pinsage_block_kernel(int n_max, const int
     if (tid == 0) { o.counts[0] = n_src; o.counts[1] = n_edges; }
 }
 
+// ---- hard negatives from random-walk ranks (PinSAGE paper section 3.3; the rule is stated in include/laplace_hip.h) ------
+// One workgroup per pair.  A dead pair (tail -1) or a pair the share draw leaves uniform exits at once (the test is the same
+// for every thread of the workgroup).  Otherwise: the W walks from the pair's head run side by side, strided over the
+// threads (each is a chain of dependent global loads, as in neighbors_kernel), their visits land in W * L slots of LDS
+// (INT32_MAX = the walk ended before that traversal: sorts last); the slots are sorted, every run head finds its run's
+// end by binary search (run length = visit count), head and tail drop out, the survivors are sorted again as
+// ((slots - count) << 32) | id — count descending, id ascending — and thread 0 indexes the rank window.
+constexpr int kHardSlotsMax = 4096;   // W * L limit: int32[4096] + int64[4096] of LDS
+
+__global__ __launch_bounds__(kBT) void pinsage_hard_neg_kernel(Bip g, int num_walks, int walk_length, uint32_t restart_thr,
+                                                               int rank_lo, int rank_hi, int all_hard, uint32_t share_thr,
+                                                               uint64_t seed, uint64_t step, const int64_t* __restrict__ heads,
+                                                               const int64_t* __restrict__ tails, int64_t* __restrict__ negs,
+                                                               int32_t* __restrict__ rank_out) {
+    __shared__ int32_t V[kHardSlotsMax];   // visited ids, sorted
+    __shared__ int64_t K[kHardSlotsMax];   // rank keys
+    const int tid = threadIdx.x;
+    const int64_t b = blockIdx.x;
+    const int32_t tl = (int32_t)tails[b];
+    const MiPhilox pk = pw(P_HARD_PICK, (uint32_t)b, 0, 0, seed, step);
+    if (tl == -1 || !(all_hard || pk.c[0] < share_thr)) {
+        if (rank_out && tid == 0) rank_out[b] = -1;
+        return;
+    }
+    const int32_t h = (int32_t)heads[b];
+    const int slots = num_walks * walk_length, SP = next_pow2(slots);
+    for (int i = slots + tid; i < SP; i += kBT) V[i] = INT32_MAX;
+    for (int wk = tid; wk < num_walks; wk += kBT) {
+        int32_t cur = h;
+        int tr = 0;
+        for (; tr < walk_length; ++tr) {
+            MiPhilox w = pw(P_HARD_WALK, (uint32_t)(wk * walk_length + tr), 0, (uint32_t)h, seed, step);
+            if (tr > 0 && w.c[2] < restart_thr) break;
+            cur = hop(g, cur, w.c[0], w.c[1]);
+            if (cur == -1) break;
+            V[wk * walk_length + tr] = cur;
+        }
+        for (; tr < walk_length; ++tr) V[wk * walk_length + tr] = INT32_MAX;
+    }
+    __syncthreads();
+    lds_bitonic_sort(V, SP);
+    for (int i = tid; i < SP; i += kBT) {
+        const int32_t v = V[i];
+        int64_t key = INT64_MAX;
+        if (v != INT32_MAX && v != h && v != tl && (i == 0 || V[i - 1] != v)) {
+            const int count = lds_lower_bound(V, SP, v + 1) - i;   // ids are below INT32_MAX - 1: v + 1 does not wrap
+            key = ((int64_t)(slots - count) << 32) | (int64_t)v;
+        }
+        K[i] = key;
+    }
+    __syncthreads();
+    lds_bitonic_sort(K, SP);
+    if (tid != 0) return;
+    const int m = lds_lower_bound(K, SP, (int64_t)INT64_MAX);     // distinct items left after head and tail dropped out
+    const int end = min(rank_hi, m);
+    int32_t rank = -1;
+    if (end > rank_lo) {
+        rank = rank_lo + (int32_t)(pk.c[1] % (uint32_t)(end - rank_lo));
+        negs[b] = (int64_t)(K[rank] & 0xFFFFFFFFLL);
+    }
+    if (rank_out) rank_out[b] = rank;
+}
+
+struct HardNegLaunch {   // a validated mi_pinsage_hard_neg, in the kernel's terms
+    int num_walks, walk_length, rank_lo, rank_hi, all_hard;
+    uint32_t restart_thr, share_thr;
+};
+
+// 0 with *hl filled, MI_ERR_BAD_ARG or MI_ERR_UNSUPPORTED; enqueues nothing
+static int hard_neg_prepare(const mi_pinsage_hard_neg* hn, HardNegLaunch* hl) {
+    MI_CHECK_ARG(hn && hn->num_walks > 0 && hn->walk_length > 0);
+    MI_CHECK_ARG(hn->restart_prob >= 0.0 && hn->restart_prob < 1.0);
+    MI_CHECK_ARG(hn->share >= 0.0 && hn->share <= 1.0);
+    MI_CHECK_ARG(hn->rank_lo >= 0 && hn->rank_hi > hn->rank_lo);
+    if ((int64_t)hn->num_walks * hn->walk_length > kHardSlotsMax) return MI_ERR_UNSUPPORTED;
+    hl->num_walks = hn->num_walks;
+    hl->walk_length = hn->walk_length;
+    hl->rank_lo = hn->rank_lo;
+    hl->rank_hi = hn->rank_hi;
+    hl->all_hard = hn->share >= 1.0 ? 1 : 0;
+    hl->restart_thr = (uint32_t)(hn->restart_prob * 4294967296.0);
+    hl->share_thr = hl->all_hard ? 0u : (uint32_t)(hn->share * 4294967296.0);
+    return 0;
+}
+
+static void hard_neg_launch(const HardNegLaunch& hl, int64_t batch, const Bip& g, uint64_t seed, uint64_t step,
+                            const int64_t* heads, const int64_t* tails, int64_t* negs, int32_t* rank_out, hipStream_t s) {
+    hipLaunchKernelGGL(pinsage_hard_neg_kernel, dim3((unsigned)batch), dim3(kBT), 0, s, g, hl.num_walks, hl.walk_length,
+                       hl.restart_thr, hl.rank_lo, hl.rank_hi, hl.all_hard, hl.share_thr, seed, step, heads, tails, negs, rank_out);
+}
+
 }  // namespace
 
 // The neighbour table of EVERY item at one sampler layer (seed list = the identity): csrc/pinsage_infer.hip's catalogue pass.
@@ -460,9 +551,18 @@ size_t mi_pinsage_batch_workspace_bytes(int64_t batch, int32_t walk_length, int3
     return total;
 }
 
-int mi_pinsage_sample_batch(const mi_pinsage_batch_desc* d, uint64_t seed, uint64_t step, const mi_pinsage_batch_out* out,
-                            void* ws, size_t ws_bytes, mi_stream_t stream) {
+}  // extern "C"
+
+// mi_pinsage_sample_batch and mi_pinsage_sample_batch_hard: hn == nullptr (or share 0) enqueues the uniform sampler's launches
+static int sample_batch_impl(const mi_pinsage_batch_desc* d, const mi_pinsage_hard_neg* hn, uint64_t seed, uint64_t step,
+                             const mi_pinsage_batch_out* out, void* ws, size_t ws_bytes, mi_stream_t stream) {
     MI_CHECK_ARG(d && out && ws);
+    HardNegLaunch hl = {};
+    if (hn) {
+        const int rc = hard_neg_prepare(hn, &hl);
+        if (rc != 0) return rc;
+        if (hn->share == 0.0) hn = nullptr;
+    }
     const int64_t B = d->batch;
     const int T = d->num_neighbors, NL = d->num_layers;
     MI_CHECK_ARG(B > 0 && d->n_items > 0 && d->walk_length > 0 && d->num_walks > 0 && T > 0 && NL > 0 && NL <= MI_PINSAGE_MAX_LAYERS);
@@ -491,6 +591,7 @@ int mi_pinsage_sample_batch(const mi_pinsage_batch_desc* d, uint64_t seed, uint6
     Bip g = {d->iu_ptr, d->iu_idx, d->ui_ptr, d->ui_idx};
     hipLaunchKernelGGL(item_pairs_kernel, dim3((unsigned)mi_ceil_div(B, 256)), dim3(256), 0, s, B, d->n_items, g, seed, step, heads,
                        tails, negs);
+    if (hn) hard_neg_launch(hl, B, g, seed, step, heads, tails, negs, nullptr, s);
     hipLaunchKernelGGL(pinsage_seeds_kernel, dim3(1), dim3(kBT), 0, s, (int)B, d->n_items, heads, tails, negs, out->seeds, out->pos_u,
                        out->pos_v, out->neg_v, banned, out->counts);
     static bool attr_set = false;
@@ -525,6 +626,36 @@ int mi_pinsage_sample_batch(const mi_pinsage_batch_desc* d, uint64_t seed, uint6
         n_dev = out->counts + 2 + 2 * l;
         n_max *= (1 + T);
     }
+    return mi_launch_status();
+}
+
+extern "C" {
+
+int mi_pinsage_sample_batch(const mi_pinsage_batch_desc* d, uint64_t seed, uint64_t step, const mi_pinsage_batch_out* out,
+                            void* ws, size_t ws_bytes, mi_stream_t stream) {
+    return sample_batch_impl(d, nullptr, seed, step, out, ws, ws_bytes, stream);
+}
+
+int mi_pinsage_sample_batch_hard(const mi_pinsage_batch_desc* d, const mi_pinsage_hard_neg* hn, uint64_t seed, uint64_t step,
+                                 const mi_pinsage_batch_out* out, void* ws, size_t ws_bytes, mi_stream_t stream) {
+    return sample_batch_impl(d, hn, seed, step, out, ws, ws_bytes, stream);
+}
+
+int64_t mi_pinsage_hard_sizeof(void) { return (int64_t)sizeof(mi_pinsage_hard_neg); }
+
+int mi_pinsage_hard_negatives(int64_t batch, int64_t n_items, const int32_t* iu_ptr, const int32_t* iu_idx,
+                              const int32_t* ui_ptr, const int32_t* ui_idx, const mi_pinsage_hard_neg* hn, uint64_t seed,
+                              uint64_t step, const int64_t* heads, const int64_t* tails, int64_t* neg_tails, int32_t* rank_out,
+                              mi_stream_t stream) {
+    MI_CHECK_ARG(batch >= 0 && n_items > 0);
+    HardNegLaunch hl = {};
+    const int rc = hard_neg_prepare(hn, &hl);
+    if (rc != 0) return rc;
+    if (batch == 0) return 0;
+    MI_CHECK_ARG(iu_ptr && iu_idx && ui_ptr && ui_idx && heads && tails && neg_tails);
+    if (n_items >= INT32_MAX || batch >= INT32_MAX) return MI_ERR_TOO_LARGE;
+    Bip g = {iu_ptr, iu_idx, ui_ptr, ui_idx};
+    hard_neg_launch(hl, batch, g, seed, step, heads, tails, neg_tails, rank_out, (hipStream_t)stream);
     return mi_launch_status();
 }
 

@@ -19,10 +19,49 @@ from .._lib import check
 from ..data.dataset import AdjList
 
 
+class HardNegatives:
+    """Hard negatives from random-walk ranks (PinSAGE paper, section 3.3; the rule is stated in include/laplace_hip.h): a
+    selected pair's negative becomes an item at a rank in [rank_lo, rank_hi) of the head's own walk visits (count desc, id
+    asc; head and tail excluded), num_walks walks of walk_length traversals, at most 4096 visits in all.  `share` of the
+    pairs are selected; it may be reassigned between epochs (the curriculum) and is read at every launch."""
+
+    def __init__(self, num_walks: int = 256, walk_length: int = 2, restart_prob: float = 0.5, rank_lo: int = 10,
+                 rank_hi: int = 50, share: float = 1.0):
+        self.num_walks, self.walk_length, self.restart_prob = int(num_walks), int(walk_length), float(restart_prob)
+        self.rank_lo, self.rank_hi = int(rank_lo), int(rank_hi)
+        if self.num_walks <= 0 or self.walk_length <= 0:
+            raise ValueError("num_walks and walk_length must be positive")
+        if self.num_walks * self.walk_length > 4096:
+            raise ValueError("num_walks * walk_length exceeds the kernel's 4096 visit slots")
+        if not 0.0 <= self.restart_prob < 1.0:
+            raise ValueError("restart_prob outside [0, 1)")
+        if self.rank_lo < 0 or self.rank_hi <= self.rank_lo or self.rank_hi > 2**31 - 1:
+            raise ValueError("need 0 <= rank_lo < rank_hi < 2^31")
+        self.share = share
+
+    @property
+    def share(self) -> float:
+        return self._share
+
+    @share.setter
+    def share(self, value: float) -> None:
+        value = float(value)
+        if not 0.0 <= value <= 1.0:      # (a NaN fails both comparisons)
+            raise ValueError("share outside [0, 1]")
+        self._share = value
+
+    def struct(self) -> "_lib.PinsageHardNeg":
+        return _lib.PinsageHardNeg(self.num_walks, self.walk_length, self.rank_lo, self.rank_hi, self.restart_prob, self._share)
+
+
 class PinSAGESampler:
     def __init__(self, users_adj_list, articles_adj_list, num_users: int, num_items: int, *, batch_size: int = 32,
                  random_walk_length: int = 2, random_walk_restart_prob: float = 0.5, num_random_walks: int = 10,
-                 num_neighbors: int = 3, num_layers: int = 2, device: str = "cuda", seed: int = 0):
+                 num_neighbors: int = 3, num_layers: int = 2, device: str = "cuda", seed: int = 0,
+                 hard_negatives: Optional[HardNegatives] = None):
+        if hard_negatives is not None and not isinstance(hard_negatives, HardNegatives):
+            raise TypeError("hard_negatives must be a HardNegatives or None")
+        self.hard_negatives = hard_negatives
         self.device = t.device(device)
         users, items = AdjList(users_adj_list, num_users), AdjList(articles_adj_list, num_items)
         to32 = lambda a: t.from_numpy(np.ascontiguousarray(a.astype(np.int32))).to(self.device)
@@ -39,16 +78,36 @@ class PinSAGESampler:
     def _stream(self):
         return _lib.current_stream()
 
-    def item_pairs(self, step: int) -> Tuple[Tensor, Tensor, Tensor]:
-        """(heads, tails, neg_tails), pairs whose walk died removed (pinsage/sampler.py:26-41)."""
+    def _item_pairs_full(self, step: int, ranks: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Tensor]:
+        """All batch_size pairs, dead ones (tail -1) included; with hard negatives on, the selected pairs' negatives replaced."""
         B, dev = self.batch_size, self.device
         heads, tails, negs = (t.empty(B, dtype=t.int64, device=dev) for _ in range(3))
         check(_lib.lib().mi_pinsage_item_pairs(B, self.num_items, self.iu_ptr.data_ptr(), self.iu_idx.data_ptr(),
                                                self.ui_ptr.data_ptr(), self.ui_idx.data_ptr(), self.seed & (2**64 - 1),
                                                step, heads.data_ptr(), tails.data_ptr(), negs.data_ptr(), self._stream()),
               "mi_pinsage_item_pairs")
+        if self.hard_negatives is not None:
+            hn = self.hard_negatives.struct()
+            check(_lib.lib().mi_pinsage_hard_negatives(B, self.num_items, self.iu_ptr.data_ptr(), self.iu_idx.data_ptr(),
+                                                       self.ui_ptr.data_ptr(), self.ui_idx.data_ptr(), ctypes.byref(hn),
+                                                       self.seed & (2**64 - 1), step, heads.data_ptr(), tails.data_ptr(),
+                                                       negs.data_ptr(), None if ranks is None else ranks.data_ptr(),
+                                                       self._stream()), "mi_pinsage_hard_negatives")
+        return heads, tails, negs
+
+    def item_pairs(self, step: int) -> Tuple[Tensor, Tensor, Tensor]:
+        """(heads, tails, neg_tails), pairs whose walk died removed (pinsage/sampler.py:26-41)."""
+        heads, tails, negs = self._item_pairs_full(step)
         keep = tails != -1
         return heads[keep], tails[keep], negs[keep]
+
+    def hard_negative_ranks(self, step: int) -> Tensor:
+        """int32[batch_size]: for every pair of the batch at `step` the rank its hard negative was taken from, -1 where the
+        uniform negative stayed (pair not selected, window empty, no hard negatives configured) or the pair is dead."""
+        ranks = t.full((self.batch_size,), -1, dtype=t.int32, device=self.device)
+        if self.hard_negatives is not None:
+            self._item_pairs_full(step, ranks)
+        return ranks
 
     def neighbors(self, seeds: Tensor, layer: int, step: int) -> Tuple[Tensor, Tensor]:
         n, dev = seeds.numel(), self.device
@@ -113,7 +172,7 @@ class PinSAGESampler:
         return dict(out=out, seeds=seeds, pos_u=pos_u, pos_v=pos_v, neg_v=neg_v, counts=counts, bufs=bufs, ws=ws, host=host)
 
     def _launch_batch(self, step: int, buf: Optional[dict] = None, pos32: Optional[Tensor] = None) -> Optional[dict]:
-        """Enqueue the whole batch (one C call, six launches for two layers) and the copy of its counts to pinned host
+        """Enqueue the whole batch (one C call, six launches for two layers, one more with hard negatives) and the copy of its counts to pinned host
         memory on the current stream; None when the sizes are outside the single-workgroup kernels'."""
         if self.n_layers > _lib.MI_PINSAGE_MAX_LAYERS:
             return None
@@ -121,8 +180,14 @@ class PinSAGESampler:
         desc = _lib.PinsageBatchDesc(self.batch_size, self.num_items, self.iu_ptr.data_ptr(), self.iu_idx.data_ptr(),
                                      self.ui_ptr.data_ptr(), self.ui_idx.data_ptr(), self.L, self.W, self.T, self.n_layers, self.p,
                                      (self._pos32 if pos32 is None else pos32).data_ptr())
-        rc = _lib.lib().mi_pinsage_sample_batch(ctypes.byref(desc), self.seed & (2**64 - 1), step, ctypes.byref(buf["out"]),
-                                                buf["ws"].data_ptr(), buf["ws"].numel(), self._stream())
+        if self.hard_negatives is None:
+            rc = _lib.lib().mi_pinsage_sample_batch(ctypes.byref(desc), self.seed & (2**64 - 1), step, ctypes.byref(buf["out"]),
+                                                    buf["ws"].data_ptr(), buf["ws"].numel(), self._stream())
+        else:
+            hn = self.hard_negatives.struct()
+            rc = _lib.lib().mi_pinsage_sample_batch_hard(ctypes.byref(desc), ctypes.byref(hn), self.seed & (2**64 - 1), step,
+                                                         ctypes.byref(buf["out"]), buf["ws"].data_ptr(), buf["ws"].numel(),
+                                                         self._stream())
         if rc == _lib.MI_ERR_UNSUPPORTED:
             return None
         check(rc, "mi_pinsage_sample_batch")
