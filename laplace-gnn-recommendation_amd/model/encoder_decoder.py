@@ -86,13 +86,17 @@ class _BatchNormFn(t.autograd.Function):
 
 def batch_norm(bn: BatchNorm1d, x: Tensor) -> Tensor:
     """bn(x) for a torch BatchNorm1d module (its parameters, buffers and state_dict stay torch's), computed by the
-    hand-written kernels."""
+    hand-written kernels.  They hold a channel's scale and shift in LDS for up to ops.BATCHNORM_MAX_CHANNELS channels; the
+    reference's BatchNorm1d takes any width, so a wider layer runs torch's own batch_norm (and its autograd backward) on the
+    same buffers, with num_batches_tracked and the momentum handled here exactly as for the kernel path."""
     training = bn.training or not bn.track_running_stats
     momentum = 0.0
     if training and bn.track_running_stats:
         bn.num_batches_tracked.add_(1)
         momentum = bn.momentum if bn.momentum is not None else 1.0 / float(bn.num_batches_tracked)
     rm, rv = (bn.running_mean, bn.running_var) if bn.track_running_stats else (None, None)
+    if x.shape[-1] > ops.BATCHNORM_MAX_CHANNELS:
+        return F.batch_norm(x, rm, rv, bn.weight, bn.bias, training, float(momentum), float(bn.eps))
     return _BatchNormFn.apply(x, bn.weight, bn.bias, rm, rv, float(momentum), float(bn.eps), training)
 
 

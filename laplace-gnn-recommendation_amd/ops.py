@@ -1246,6 +1246,7 @@ def match_cooccurrence(users_ptr: Tensor, users_idx: Tensor, nbr_id: Tensor, nbr
 
 
 _BN_WS = {}
+BATCHNORM_MAX_CHANNELS = 512   # kBnMaxC of csrc/norm.hip: mi_batchnorm_*_f32 return MI_ERR_UNSUPPORTED beyond it
 
 
 def _bn_ws(c: int, device) -> Tensor:
