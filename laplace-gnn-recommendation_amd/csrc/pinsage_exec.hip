@@ -120,7 +120,8 @@ __global__ __launch_bounds__(kBlock) void pin_score_kernel(int64_t n_pairs, int 
 
 // Gradient of the mean hinge with respect to hf (one block per seed row, the pairs walked in order: deterministic) and to
 // the scorer bias (dense buffer, the seed's own entry: seeds are distinct); block 0 also reduces the loss.
-//   active pair p (margin > 0), g = 1 / n_pairs:  d hf[u] += g (hf[w] - hf[v]),  d hf[w] += g hf[u],  d hf[v] -= g hf[u],
+//   active pair p (margin >= 0: the hinge is clamp(min=0), and torch's clamp passes the gradient AT the bound, so a margin of
+//   exactly 0 is active — it adds nothing to the loss), g = 1 / n_pairs:  d hf[u] += g (hf[w] - hf[v]),  d hf[w] += g hf[u],  d hf[v] -= g hf[u],
 //   d bias[seed(w)] += g,  d bias[seed(v)] -= g  (the head's bias enters both scores and cancels).
 __global__ __launch_bounds__(128) void pin_score_grad_kernel(int64_t n_seeds, int64_t n_pairs, int h, const float* __restrict__ hd,
                                                              const float* __restrict__ hN, const int64_t* __restrict__ seeds,
@@ -141,7 +142,7 @@ __global__ __launch_bounds__(128) void pin_score_grad_kernel(int64_t n_seeds, in
     for (int64_t base = 0; base < n_pairs; base += 128) {
         const int64_t p = base + c;
         bool hit = false;
-        if (p < n_pairs && margin[p] > 0.f) hit = pu[p] == s || pv[p] == s || nv[p] == s;
+        if (p < n_pairs && margin[p] >= 0.f) hit = pu[p] == s || pv[p] == s || nv[p] == s;
         const unsigned long long m = __ballot(hit);
         const int lane = c & 63, wave = c >> 6;
         if (lane == 0) wave_cnt[wave] = __popcll(m);
