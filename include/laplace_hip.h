@@ -952,6 +952,59 @@ int    mi_sampler_emit_csr(const mi_sampler_desc* d, void* ws, size_t ws_bytes, 
                            int32_t* customer_rowptr, int32_t* customer_col, int32_t* article_rowptr,
                            int32_t* article_col, int32_t* article_cursor, mi_stream_t stream);
 
+/* N1b  attribute node types of the ranker's batches (Config.other_edge_types; the reference's default dataset puts
+ *      them into every batch: data/dataset_neo.py:67-91,140-168).  A relation (article, name, T) is a CSR over the
+ *      articles: rel_ptr int32[num_articles + 1], rel_idx int32[nnz], every row STRICTLY ascending, ids in
+ *      [0, n_targets) (checked by the caller: the kernels index bitmaps with them), 1 <= n_targets <= 2^31 - 1.  Up to
+ *      MI_SAMPLER_MAX_RELATIONS relations per call.  The rule, per sample s of the collated batch, whose articles are
+ *      a_0 < ... < a_{m-1} at batch-local indices article_ptr[s] + j (all of them: label articles too, train or
+ *      evaluation mode):
+ *        T nodes of s   the sorted distinct ids of the union of rel[a_j]; t_ptr[s] = their number in samples < s;
+ *                       t_ids[t_ptr[s] + r] = the r-th of them (global id);
+ *        edges of s     for j ascending and, within j, e in rel[a_j] ascending:
+ *                       (article_ptr[s] + j, t_ptr[s] + rank_s(e)); the samples' edges follow one another in sample order.
+ *      Attribute nodes are never expanded into further articles, and the walk's draws do not depend on the relations.
+ *   mi_sampler_count_relations_async   after mi_sampler_count / mi_sampler_count_async of the same batch, same stream,
+ *                       same ws (read only): builds the per-sample T sets in rel_ws (which it clears itself: a batch
+ *                       that was counted and never emitted leaves nothing behind) and copies
+ *                       totals_pinned[2 r + {0, 1}] = {T nodes, edges} of relation r to caller-owned pinned host
+ *                       memory when the stream gets there (-1: the count does not fit int32) — behind the same event
+ *                       as the walk's four totals, no host wait of its own.
+ *   mi_sampler_emit_relations   same ws / rel_ws, untouched in between; totals_host = the walk's four totals,
+ *                       rel_totals_host[2 n_rel] the ones above.  Writes per relation, with nt / ne its totals and
+ *                       na = totals_host[1]:
+ *                         t_ids int64[nt], t_ptr int64[batch + 1];
+ *                         edge3 int64[3, ne]: row 0 the article, row 1 the T node (batch-local), row 2 = row 0 again, so
+ *                           rows 0..1 are the relation's edge_index and rows 1..2 the reversed relation's (as
+ *                           mi_sampler_emit3 does for buys / rev_buys);
+ *                         articles x T: article_rowptr int32[na + 1], article_col int32[ne];
+ *                         T x articles: t_rowptr int32[nt + 1], t_col int32[ne]; both sorted by (row, column) — what
+ *                           mi_coo_to_csr_i32 would build from edge3.  t_cursor: int32[nt] scratch.
+ *                       The transposed rows are filled in edge order, which is ascending article order: no sort, and no
+ *                       atomic whose order could reach the output.  Pointers may be null where the size is 0.
+ * Everything is validated before anything is enqueued (pointers, alignment, n_rel, n_targets, workspace sizes). */
+#define MI_SAMPLER_MAX_RELATIONS 4
+typedef struct mi_sampler_relation {
+    const int32_t* rel_ptr;
+    const int32_t* rel_idx;
+    int64_t n_targets;
+} mi_sampler_relation;
+
+typedef struct mi_sampler_relation_out {
+    int64_t* t_ids; int64_t* t_ptr; int64_t* edge3;
+    int32_t* article_rowptr; int32_t* article_col;
+    int32_t* t_rowptr; int32_t* t_col; int32_t* t_cursor;
+} mi_sampler_relation_out;
+
+size_t mi_sampler_relations_workspace_bytes(const mi_sampler_desc* d, const mi_sampler_relation* rels, int32_t n_rel);
+int    mi_sampler_count_relations_async(const mi_sampler_desc* d, const mi_sampler_relation* rels, int32_t n_rel,
+                                        void* ws, size_t ws_bytes, void* rel_ws, size_t rel_ws_bytes,
+                                        int32_t* totals_pinned, mi_stream_t stream);
+int    mi_sampler_emit_relations(const mi_sampler_desc* d, const mi_sampler_relation* rels, int32_t n_rel,
+                                 void* ws, size_t ws_bytes, const int64_t* totals_host, void* rel_ws,
+                                 size_t rel_ws_bytes, const int64_t* rel_totals_host,
+                                 const mi_sampler_relation_out* outs, mi_stream_t stream);
+
 /* ------------------------------------------------------------------------------------
  * N5  PinSAGE samplers (reference: pinsage/sampler.py:16-106 over DGL's random_walk and
  *     PinSAGESampler; DGL is absent and the reference's pinsage/ cannot import — SURVEY F11 — so the

@@ -79,6 +79,18 @@ class SamplerDesc(Structure):
                 ("cand_ptr", c_void_p), ("cand_idx", c_void_p)]
 
 
+MI_SAMPLER_MAX_RELATIONS = 4
+
+
+class SamplerRelation(Structure):
+    _fields_ = [("rel_ptr", c_void_p), ("rel_idx", c_void_p), ("n_targets", c_int64)]
+
+
+class SamplerRelationOut(Structure):
+    _fields_ = [("t_ids", c_void_p), ("t_ptr", c_void_p), ("edge3", c_void_p), ("article_rowptr", c_void_p),
+                ("article_col", c_void_p), ("t_rowptr", c_void_p), ("t_col", c_void_p), ("t_cursor", c_void_p)]
+
+
 MI_RANKER_MAX_LAYERS, MI_RANKER_MAX_COLS, MI_RANKER_MAX_PARAMS = 4, 16, 48
 
 
@@ -307,6 +319,11 @@ _PROTOTYPES = {
     "mi_sampler_emit": (c_int32, [POINTER(SamplerDesc), P, P, c_size_t, POINTER(c_int64), P, P, P, P, P, P, P, P]),
     "mi_sampler_emit3": (c_int32, [POINTER(SamplerDesc), P, P, c_size_t, POINTER(c_int64), P, P, P, P, P, P, P, c_int32, P]),
     "mi_sampler_emit_csr": (c_int32, [POINTER(SamplerDesc), P, c_size_t, POINTER(c_int64), P, P, P, P, P, P]),
+    "mi_sampler_relations_workspace_bytes": (c_size_t, [POINTER(SamplerDesc), POINTER(SamplerRelation), c_int32]),
+    "mi_sampler_count_relations_async": (c_int32, [POINTER(SamplerDesc), POINTER(SamplerRelation), c_int32, P, c_size_t, P, c_size_t,
+                                                   P, P]),
+    "mi_sampler_emit_relations": (c_int32, [POINTER(SamplerDesc), POINTER(SamplerRelation), c_int32, P, c_size_t, POINTER(c_int64),
+                                            P, c_size_t, POINTER(c_int64), POINTER(SamplerRelationOut), P]),
     "mi_pinsage_item_pairs": (c_int32, [c_int64, c_int64, P, P, P, P, c_uint64, c_uint64, P, P, P, P]),
     "mi_pinsage_neighbors_workspace_bytes": (c_size_t, [c_int64, c_int32, c_int32]),
     "mi_pinsage_neighbors": (c_int32, [c_int64, P, P, P, P, P, c_int32, c_double, c_int32, c_int32, c_int32,

@@ -963,6 +963,266 @@ int fill_params(Smp& p, const mi_sampler_desc* d) {
     return 0;
 }
 
+// ---- N1b: attribute node types (Config.other_edge_types) -----------------------------------------------
+// A relation (article, name, T) is a CSR over articles with strictly ascending rows.  Per sample s, whose articles are
+// the set bits of bm_art[s] (rank = pre_a + popcount, phase A):
+//   T nodes of s   the sorted distinct ids of the union of its articles' rows: a bitmap over [0, n_targets) per sample
+//                  (atomicOr: the result does not depend on the order) + popcount prefix, as the articles themselves
+//   edges of s     articles ascending, within an article its row ascending: (article rank, T rank)
+// Attribute nodes are never expanded into further articles.  Nothing here touches the walk's tables.
+constexpr int kRelThreads = 256;
+
+struct SmpRel {
+    const int32_t* rptr; const int32_t* ridx;
+    int32_t WT;
+    uint32_t* bm_t;   // [B][WT] the sample's T nodes
+    int32_t* pre_t;   // [B][WT] set bits before the word
+    int32_t* cnt;     // [B][2]  {T nodes, relation edges} of the sample
+    int32_t* off;     // [2][B+1] their exclusive prefixes over the samples
+};
+struct SmpRels {
+    SmpRel r[MI_SAMPLER_MAX_RELATIONS];
+    int32_t n_rel;
+    int32_t* totals;  // [2 * n_rel] {T nodes, edges} per relation: one copy to the host (-1: more than int32 holds)
+};
+struct SmpRelOut {
+    int64_t* t_ids; int64_t* t_ptr; int64_t* edge3;
+    int32_t* a_rowptr; int32_t* a_col;   // articles x T
+    int32_t* t_rowptr; int32_t* t_col;   // T x articles
+    int32_t* t_cur;                      // [T nodes] per-row counts, then fill cursors
+    int32_t n_t, n_e, n_a;
+};
+struct SmpRelOuts { SmpRelOut o[MI_SAMPLER_MAX_RELATIONS]; };
+
+// exclusive prefix of one value per thread over the block; scan[kRelThreads] = the total.  Barriers on both sides.
+__device__ __forceinline__ int rel_block_scan(int v, int32_t* scan) {
+    const int tid = threadIdx.x;
+    __syncthreads();
+    scan[tid + 1] = v;
+    if (tid == 0) scan[0] = 0;
+    __syncthreads();
+    for (int off = 1; off < kRelThreads; off <<= 1) {
+        const int x = (tid + 1 > off) ? scan[tid + 1 - off] : 0;
+        __syncthreads();
+        scan[tid + 1] += x;
+        __syncthreads();
+    }
+    return scan[tid];
+}
+
+// grid (B, n_rel): the sample's T bitmap (cleared HERE first: a batch whose emit never ran leaves nothing behind),
+// its popcount prefix, and the two counts
+__global__ __launch_bounds__(kRelThreads) void smp_rel_count_kernel(Smp p, SmpRels rs) {
+    __shared__ int32_t scan[kRelThreads + 1];
+    const int s = blockIdx.x, tid = threadIdx.x;
+    const SmpRel R = rs.r[blockIdx.y];
+    uint32_t* bm = R.bm_t + (int64_t)s * R.WT;
+    int32_t* pre = R.pre_t + (int64_t)s * R.WT;
+    for (int w = tid; w < R.WT; w += kRelThreads) bm[w] = 0u;
+    __syncthreads();
+    const uint32_t* bma = p.bm_art + (int64_t)s * p.WA;
+    const int per = (p.WA + kRelThreads - 1) / kRelThreads;
+    const int w0 = min(tid * per, p.WA), w1 = min(w0 + per, p.WA);
+    int ne = 0;
+    for (int w = w0; w < w1; ++w) {
+        uint32_t word = bma[w];
+        while (word) {
+            const int32_t a = w * 32 + (__ffs(word) - 1);
+            word &= word - 1;
+            const int32_t qb = R.rptr[a], qe = R.rptr[a + 1];
+            for (int32_t q = qb; q < qe; ++q) {
+                const int32_t e = R.ridx[q];
+                // few targets, many articles (50 colour groups): most bits are set already, and the atomics of a sample
+                // would queue up on a word or two.  A stale 0 only costs the atomic it would have issued anyway.
+                if (!(bm[e >> 5] & (1u << (e & 31)))) atomicOr(bm + (e >> 5), 1u << (e & 31));
+            }
+            ne += qe - qb;
+        }
+    }
+    rel_block_scan(ne, scan);
+    const int ne_sample = scan[kRelThreads];
+    const int per_t = (R.WT + kRelThreads - 1) / kRelThreads;
+    const int t0 = min(tid * per_t, R.WT), t1 = min(t0 + per_t, R.WT);
+    int c = 0;
+    for (int w = t0; w < t1; ++w) c += __popc(bm[w]);
+    int run = rel_block_scan(c, scan);
+    for (int w = t0; w < t1; ++w) {
+        pre[w] = run;
+        run += __popc(bm[w]);
+    }
+    if (tid == 0) {
+        R.cnt[(int64_t)s * 2 + 0] = scan[kRelThreads];
+        R.cnt[(int64_t)s * 2 + 1] = ne_sample;
+    }
+}
+
+__global__ void smp_rel_offsets_kernel(Smp p, SmpRels rs) {  // B is small: one thread per counter
+    const int c = threadIdx.x;
+    if (c >= 2 * rs.n_rel) return;
+    const SmpRel R = rs.r[c >> 1];
+    const int k = c & 1;
+    int64_t run = 0;
+    for (int s = 0; s < p.B; ++s) {
+        R.off[k * (p.B + 1) + s] = (int32_t)(run > INT32_MAX ? INT32_MAX : run);
+        run += R.cnt[(int64_t)s * 2 + k];
+    }
+    R.off[k * (p.B + 1) + p.B] = (int32_t)(run > INT32_MAX ? INT32_MAX : run);
+    rs.totals[c] = run > INT32_MAX ? -1 : (int32_t)run;
+}
+
+// One pass over the sample's edges in emit order, a block's width at a time: an edge's place in its T row is the row's
+// cursor plus the number of earlier edges of the tile with the same T node, and the LAST such edge of the tile moves
+// the cursor on — one writer per cursor per tile, no atomics, rows filled in edge order (= articles ascending).
+// fill = false only counts (the cursors end as the row lengths).
+__device__ __forceinline__ void rel_tile_pass(const SmpRelOut& o, int32_t off_t, int32_t off_e, int ne, bool fill,
+                                              int32_t* keys) {
+    const int tid = threadIdx.x;
+    for (int base = 0; base < ne; base += kRelThreads) {   // block-uniform
+        const int e = base + tid;
+        const int32_t key = e < ne ? o.a_col[off_e + e] - off_t : -1;
+        keys[tid] = key;
+        __syncthreads();
+        int rank = 0;
+        bool last = true;
+        int32_t cur = 0;
+        if (key >= 0) {
+            for (int q = 0; q < kRelThreads; ++q) {
+                const bool same = keys[q] == key;
+                rank += (same && q < tid) ? 1 : 0;
+                last = last && !(same && q > tid);
+            }
+            cur = o.t_cur[off_t + key];
+        }
+        __syncthreads();   // every cursor of the tile is read before one is moved
+        if (key >= 0) {
+            if (fill) o.t_col[cur + rank] = (int32_t)o.edge3[off_e + e];
+            if (last) o.t_cur[off_t + key] = cur + rank + 1;
+        }
+        __syncthreads();
+    }
+}
+
+// grid (B, n_rel): everything of one sample and one relation, in order
+__global__ __launch_bounds__(kRelThreads) void smp_rel_emit_kernel(Smp p, SmpRels rs, SmpRelOuts os) {
+    __shared__ int32_t scan[kRelThreads + 1];
+    __shared__ int32_t keys[kRelThreads];
+    const int s = blockIdx.x, tid = threadIdx.x;
+    const SmpRel R = rs.r[blockIdx.y];
+    const SmpRelOut o = os.o[blockIdx.y];
+    // the buffers were sized from these totals on the host: anything else and nothing is written (block-uniform)
+    if (R.off[p.B] != o.n_t || R.off[(p.B + 1) + p.B] != o.n_e || p.off[1 * (p.B + 1) + p.B] != o.n_a) return;
+    const int32_t off_a = p.off[1 * (p.B + 1) + s];
+    const int32_t off_t = R.off[s], off_e = R.off[(p.B + 1) + s];
+    const int nt = R.cnt[(int64_t)s * 2 + 0], ne = R.cnt[(int64_t)s * 2 + 1];
+    const uint32_t* bm = R.bm_t + (int64_t)s * R.WT;
+    const int32_t* pre = R.pre_t + (int64_t)s * R.WT;
+    // T nodes: global ids in ascending order; the per-sample offsets
+    for (int w = tid; w < R.WT; w += kRelThreads) {
+        uint32_t word = bm[w];
+        int32_t r = off_t + pre[w];
+        while (word) {
+            o.t_ids[r++] = (int64_t)w * 32 + (__ffs(word) - 1);
+            word &= word - 1;
+        }
+    }
+    for (int i = tid; i < nt; i += kRelThreads) o.t_cur[off_t + i] = 0;
+    if (tid == 0) {
+        o.t_ptr[s] = off_t;
+        if (s == p.B - 1) {
+            o.t_ptr[p.B] = o.n_t;
+            o.a_rowptr[o.n_a] = o.n_e;
+            o.t_rowptr[o.n_t] = o.n_e;
+        }
+    }
+    // edges: every thread owns a run of article words; its first edge = the edges of the runs before it
+    const uint32_t* bma = p.bm_art + (int64_t)s * p.WA;
+    const int32_t* prea = p.pre_a + (int64_t)s * p.WA;
+    const int per = (p.WA + kRelThreads - 1) / kRelThreads;
+    const int w0 = min(tid * per, p.WA), w1 = min(w0 + per, p.WA);
+    int mine = 0;
+    for (int w = w0; w < w1; ++w) {
+        uint32_t word = bma[w];
+        while (word) {
+            const int32_t a = w * 32 + (__ffs(word) - 1);
+            word &= word - 1;
+            mine += R.rptr[a + 1] - R.rptr[a];
+        }
+    }
+    int32_t at = off_e + rel_block_scan(mine, scan);
+    for (int w = w0; w < w1; ++w) {
+        uint32_t word = bma[w];
+        int32_t row = off_a + prea[w];
+        while (word) {
+            const int32_t a = w * 32 + (__ffs(word) - 1);
+            word &= word - 1;
+            o.a_rowptr[row] = at;
+            for (int32_t q = R.rptr[a]; q < R.rptr[a + 1]; ++q) {
+                const int32_t e = R.ridx[q];
+                const int32_t col = off_t + pre[e >> 5] + __popc(bm[e >> 5] & ((1u << (e & 31)) - 1u));
+                o.edge3[at] = row;
+                o.edge3[(int64_t)o.n_e + at] = col;
+                o.edge3[2 * (int64_t)o.n_e + at] = row;
+                o.a_col[at] = col;
+                ++at;
+            }
+            ++row;
+        }
+    }
+    __syncthreads();
+    // the transpose: row lengths, row starts, ordered fill
+    rel_tile_pass(o, off_t, off_e, ne, false, keys);
+    const int per_r = (nt + kRelThreads - 1) / kRelThreads;
+    const int i0 = min(tid * per_r, nt), i1 = min(i0 + per_r, nt);
+    int c = 0;
+    for (int i = i0; i < i1; ++i) c += o.t_cur[off_t + i];
+    int32_t run = off_e + rel_block_scan(c, scan);
+    for (int i = i0; i < i1; ++i) {
+        const int32_t len = o.t_cur[off_t + i];
+        o.t_rowptr[off_t + i] = run;
+        o.t_cur[off_t + i] = run;
+        run += len;
+    }
+    __syncthreads();
+    rel_tile_pass(o, off_t, off_e, ne, true, keys);
+}
+
+// relation workspace: the totals, then per relation bitmap, prefix, counts, offsets
+size_t smp_rel_layout(const Smp& p, const mi_sampler_relation* rels, int n_rel, SmpRels* out, char* base) {
+    size_t off = 0;
+    auto take = [&](size_t bytes) {
+        char* r = base ? base + off : nullptr;
+        off += mi_align_up(bytes, 256);
+        return r;
+    };
+    char* tot = take(2 * MI_SAMPLER_MAX_RELATIONS * 4);
+    if (out) { out->n_rel = n_rel; out->totals = (int32_t*)tot; }
+    const size_t B = p.B;
+    for (int r = 0; r < n_rel; ++r) {
+        const size_t WT = (size_t)((rels[r].n_targets + 31) / 32);
+        char* a0 = take(B * WT * 4);
+        char* a1 = take(B * WT * 4);
+        char* a2 = take(B * 2 * 4);
+        char* a3 = take(2 * (B + 1) * 4);
+        if (out) {
+            SmpRel& R = out->r[r];
+            R.rptr = rels[r].rel_ptr; R.ridx = rels[r].rel_idx; R.WT = (int32_t)WT;
+            R.bm_t = (uint32_t*)a0; R.pre_t = (int32_t*)a1; R.cnt = (int32_t*)a2; R.off = (int32_t*)a3;
+        }
+    }
+    return off;
+}
+
+static inline bool smp_aligned(const void* ptr, size_t a) { return (reinterpret_cast<uintptr_t>(ptr) & (a - 1)) == 0; }
+
+int check_relations(const mi_sampler_relation* rels, int32_t n_rel) {
+    MI_CHECK_ARG(rels && n_rel >= 1 && n_rel <= MI_SAMPLER_MAX_RELATIONS);
+    for (int r = 0; r < n_rel; ++r) {
+        MI_CHECK_ARG(rels[r].rel_ptr && rels[r].rel_idx && smp_aligned(rels[r].rel_ptr, 4) && smp_aligned(rels[r].rel_idx, 4));
+        MI_CHECK_ARG(rels[r].n_targets >= 1 && rels[r].n_targets <= (int64_t)INT32_MAX);
+    }
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1069,6 +1329,73 @@ int mi_sampler_emit_csr(const mi_sampler_desc* d, void* ws, size_t ws_bytes, con
         hipLaunchKernelGGL(smp_csr_sort_rows_kernel, dim3((o.n_articles + 3) / 4), dim3(256), 0, s, o);
         hipLaunchKernelGGL(smp_csr_refill_kernel, dim3(p.B), dim3(kSelThreads), 0, s, p, o);
     }
+    return mi_launch_status();
+}
+
+size_t mi_sampler_relations_workspace_bytes(const mi_sampler_desc* d, const mi_sampler_relation* rels, int32_t n_rel) {
+    Smp p;
+    if (fill_params(p, d) || check_relations(rels, n_rel)) return 0;
+    return smp_rel_layout(p, rels, n_rel, nullptr, nullptr);
+}
+
+// After phase A on the same stream: per relation the samples' T bitmaps and the {T nodes, edges} totals.
+int mi_sampler_count_relations_async(const mi_sampler_desc* d, const mi_sampler_relation* rels, int32_t n_rel, void* ws,
+                                     size_t ws_bytes, void* rel_ws, size_t rel_ws_bytes, int32_t* totals_pinned,
+                                     mi_stream_t stream) {
+    Smp p;
+    int rc = fill_params(p, d);
+    if (rc) return rc;
+    rc = check_relations(rels, n_rel);
+    if (rc) return rc;
+    MI_CHECK_ARG(ws && rel_ws && totals_pinned && mi_aligned16(ws) && mi_aligned16(rel_ws) && smp_aligned(totals_pinned, 4));
+    if (ws_bytes < smp_scratch_layout(p, nullptr, nullptr)) return MI_ERR_WORKSPACE;
+    if (rel_ws_bytes < smp_rel_layout(p, rels, n_rel, nullptr, nullptr)) return MI_ERR_WORKSPACE;
+    smp_scratch_layout(p, &p, static_cast<char*>(ws));
+    SmpRels rs;
+    memset(&rs, 0, sizeof(rs));
+    smp_rel_layout(p, rels, n_rel, &rs, static_cast<char*>(rel_ws));
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(smp_rel_count_kernel, dim3(p.B, n_rel), dim3(kRelThreads), 0, s, p, rs);
+    hipLaunchKernelGGL(smp_rel_offsets_kernel, dim3(1), dim3(64), 0, s, p, rs);
+    MI_HIP(hipMemcpyAsync(totals_pinned, rs.totals, 2 * (size_t)n_rel * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    return mi_launch_status();
+}
+
+// After mi_sampler_count_relations_async, same workspaces: the relations' node ids, offsets, edges and sorted CSRs.
+int mi_sampler_emit_relations(const mi_sampler_desc* d, const mi_sampler_relation* rels, int32_t n_rel, void* ws,
+                              size_t ws_bytes, const int64_t* totals_host, void* rel_ws, size_t rel_ws_bytes,
+                              const int64_t* rel_totals_host, const mi_sampler_relation_out* outs, mi_stream_t stream) {
+    Smp p;
+    int rc = fill_params(p, d);
+    if (rc) return rc;
+    rc = check_relations(rels, n_rel);
+    if (rc) return rc;
+    MI_CHECK_ARG(ws && rel_ws && totals_host && rel_totals_host && outs && mi_aligned16(ws) && mi_aligned16(rel_ws));
+    MI_CHECK_ARG(totals_host[1] >= 0 && totals_host[1] < INT32_MAX);
+    SmpRelOuts os;
+    memset(&os, 0, sizeof(os));
+    for (int r = 0; r < n_rel; ++r) {
+        const int64_t nt = rel_totals_host[2 * r], ne = rel_totals_host[2 * r + 1];
+        if (nt < 0 || ne < 0 || nt >= INT32_MAX || ne >= INT32_MAX) return MI_ERR_TOO_LARGE;
+        const mi_sampler_relation_out& u = outs[r];
+        MI_CHECK_ARG(u.t_ptr && u.article_rowptr && u.t_rowptr);
+        MI_CHECK_ARG(nt == 0 || (u.t_ids && u.t_cursor));
+        MI_CHECK_ARG(ne == 0 || (u.edge3 && u.article_col && u.t_col));
+        MI_CHECK_ARG(smp_aligned(u.t_ids, 8) && smp_aligned(u.t_ptr, 8) && smp_aligned(u.edge3, 8));
+        MI_CHECK_ARG(smp_aligned(u.article_rowptr, 4) && smp_aligned(u.article_col, 4) && smp_aligned(u.t_rowptr, 4) &&
+                     smp_aligned(u.t_col, 4) && smp_aligned(u.t_cursor, 4));
+        SmpRelOut& o = os.o[r];
+        o.t_ids = u.t_ids; o.t_ptr = u.t_ptr; o.edge3 = u.edge3;
+        o.a_rowptr = u.article_rowptr; o.a_col = u.article_col; o.t_rowptr = u.t_rowptr; o.t_col = u.t_col; o.t_cur = u.t_cursor;
+        o.n_t = (int32_t)nt; o.n_e = (int32_t)ne; o.n_a = (int32_t)totals_host[1];
+    }
+    if (ws_bytes < smp_scratch_layout(p, nullptr, nullptr)) return MI_ERR_WORKSPACE;
+    if (rel_ws_bytes < smp_rel_layout(p, rels, n_rel, nullptr, nullptr)) return MI_ERR_WORKSPACE;
+    smp_scratch_layout(p, &p, static_cast<char*>(ws));
+    SmpRels rs;
+    memset(&rs, 0, sizeof(rs));
+    smp_rel_layout(p, rels, n_rel, &rs, static_cast<char*>(rel_ws));
+    hipLaunchKernelGGL(smp_rel_emit_kernel, dim3(p.B, n_rel), dim3(kRelThreads), 0, (hipStream_t)stream, p, rs, os);
     return mi_launch_status();
 }
 

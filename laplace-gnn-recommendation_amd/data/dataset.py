@@ -20,6 +20,7 @@ import torch as t
 
 from ..hetero import HeteroData
 from ..utils.constants import Constants
+from .relations import attach_relations, resolve_relations
 
 
 class AdjList:
@@ -86,6 +87,7 @@ class GraphDataset:
         self._id_max = int(all_edges[1].max())
         self._rng = np.random.default_rng(seed)
         self._mark = np.zeros(n_users, dtype=bool)
+        self._relations = resolve_relations(config, graph)   # Config.other_edge_types: attribute node types (data/relations.py)
 
     def __len__(self) -> int:
         return self._n_items
@@ -185,4 +187,6 @@ class GraphDataset:
         data[Constants.rev_edge_key].edge_index = edge_index.flip(0)
         data[Constants.rev_edge_key].edge_label_index = label_index.flip(0)
         data[Constants.rev_edge_key].edge_label = labels
+        if self._relations:
+            attach_relations(data, self._relations, article_buckets)
         return data

@@ -14,10 +14,11 @@ import torch as t
 from torch import Tensor
 
 from .. import _lib
-from .._lib import SamplerDesc, check
+from .._lib import SamplerDesc, SamplerRelation, SamplerRelationOut, check
 from ..hetero import HeteroData
 from ..utils.constants import Constants
 from .dataset import AdjList
+from .relations import resolve_relations
 
 
 def candidate_csr(matchers, num_users: int):
@@ -109,6 +110,23 @@ class DeviceGraphSampler:
         self._desc = self._make_desc(self.batch_size)
         self._ws = t.empty(int(_lib.lib().mi_sampler_workspace_bytes(ctypes.byref(self._desc))), dtype=t.uint8, device=dev)
         self.step = 0
+        # Config.other_edge_types: attribute node types (article, name, T), data/relations.py.  The CSRs and graph[T].x go to
+        # the device once; none (the default) leaves every path below as it was.
+        self._rels = resolve_relations(config, graph)
+        self._rel_arr, self._rel_ws, self._rel_dev, self._pinned_serial = None, None, [], None
+        if self._rels:
+            if len(self._rels) > _lib.MI_SAMPLER_MAX_RELATIONS:
+                raise ValueError(f"other_edge_types: {len(self._rels)} relations, the device sampler takes "
+                                 f"{_lib.MI_SAMPLER_MAX_RELATIONS}")
+            self._rel_arr = (SamplerRelation * len(self._rels))()
+            for i, r in enumerate(self._rels):
+                ptr, idx = to32(r.ptr), to32(r.idx if r.idx.size else np.zeros(1, dtype=np.int64))
+                self._rel_dev.append((ptr, idx, r.x.to(dev)))
+                self._rel_arr[i] = SamplerRelation(ptr.data_ptr(), idx.data_ptr(), r.n_targets)
+            n_ws = int(_lib.lib().mi_sampler_relations_workspace_bytes(ctypes.byref(self._desc), self._rel_arr, len(self._rels)))
+            if n_ws == 0:
+                raise _lib.MiError("mi_sampler_relations_workspace_bytes declined the relations")
+            self._rel_ws = t.empty(n_ws, dtype=t.uint8, device=dev)
 
     def _make_desc(self, batch: int) -> SamplerDesc:
         c = self.config
@@ -135,14 +153,71 @@ class DeviceGraphSampler:
         desc = self._desc if B == self.batch_size else self._make_desc(B)
         L = _lib.lib()
         stream = _lib.current_stream()
+        if self._rels:  # walk and relation counts enqueued together, ONE wait for all the totals
+            if self._pinned_serial is None:
+                self._pinned_serial = t.empty(4 + 2 * len(self._rels), dtype=t.int32).pin_memory()
+            pinned = self._pinned_serial
+            check(L.mi_sampler_count_async(ctypes.byref(desc), seeds.data_ptr(), self.seed & (2**64 - 1), int(step) & (2**64 - 1),
+                                           self._ws.data_ptr(), self._ws.numel(), pinned.data_ptr(), stream), "mi_sampler_count_async")
+            self._count_relations(desc, self._ws, self._rel_ws, pinned, stream)
+            t.cuda.current_stream(self.device).synchronize()
+            got = pinned.tolist()
+            return self._emit(seeds, desc, got[:4], stream, raw, rel_totals=got[4:])
         totals = (ctypes.c_int64 * 4)()
         check(L.mi_sampler_count(ctypes.byref(desc), seeds.data_ptr(), self.seed & (2**64 - 1), int(step) & (2**64 - 1),
                                  self._ws.data_ptr(), self._ws.numel(), totals, stream), "mi_sampler_count")
         return self._emit(seeds, desc, [int(x) for x in totals], stream, raw)
 
-    def _emit(self, seeds: Tensor, desc: SamplerDesc, totals, stream: int, raw: bool = False, ws: Optional[Tensor] = None):
+    def _count_relations(self, desc: SamplerDesc, ws: Tensor, rel_ws: Tensor, pinned: Tensor, stream: int) -> None:
+        """Right behind phase A on `stream`: the relations' {T nodes, edges} totals land in pinned[4:]."""
+        check(_lib.lib().mi_sampler_count_relations_async(ctypes.byref(desc), self._rel_arr, len(self._rels), ws.data_ptr(),
+                                                          ws.numel(), rel_ws.data_ptr(), rel_ws.numel(),
+                                                          pinned.data_ptr() + 16, stream), "mi_sampler_count_relations_async")
+
+    def _emit_relations(self, desc: SamplerDesc, totals, rel_totals, stream: int, ws: Tensor, rel_ws: Tensor):
+        """Phase B of the relations: ([per relation: T_ids, T_ptr, edge3, (by article, by T) CSRs], storages)."""
+        from .. import ops
+        n_rel, na, B, dev = len(self._rels), int(totals[1]), int(desc.batch), self.device
+        if any(int(x) < 0 for x in rel_totals):
+            raise _lib.MiError("other_edge_types: a batch's relation edges do not fit int32")
+        r4 = lambda n: (n + 3) & ~3
+        s64, s32 = [], []
+        for i in range(n_rel):
+            nt, ne = int(rel_totals[2 * i]), int(rel_totals[2 * i + 1])
+            s64 += [r4(nt), r4(B + 1), r4(3 * ne)]
+            s32 += [r4(na + 1), r4(ne), r4(nt + 1), r4(ne), r4(max(nt, 1))]
+        b64, b32 = t.empty(sum(s64), dtype=t.int64, device=dev), t.empty(sum(s32), dtype=t.int32, device=dev)
+        outs = (SamplerRelationOut * n_rel)()
+        res, o64, o32 = [], 0, 0
+        for i in range(n_rel):
+            nt, ne = int(rel_totals[2 * i]), int(rel_totals[2 * i + 1])
+            p64, p32 = [], []
+            for n_alloc in s64[3 * i:3 * i + 3]:
+                p64.append(o64)
+                o64 += n_alloc
+            for n_alloc in s32[5 * i:5 * i + 5]:
+                p32.append(o32)
+                o32 += n_alloc
+            t_ids, t_ptr = b64[p64[0]:p64[0] + nt], b64[p64[1]:p64[1] + B + 1]
+            edge3 = b64[p64[2]:p64[2] + 3 * ne].view(3, ne)
+            a_rowptr, a_col = b32[p32[0]:p32[0] + na + 1], b32[p32[1]:p32[1] + ne]
+            t_rowptr, t_col, t_cur = b32[p32[2]:p32[2] + nt + 1], b32[p32[3]:p32[3] + ne], b32[p32[4]:p32[4] + max(nt, 1)]
+            outs[i] = SamplerRelationOut(t_ids.data_ptr() if nt else None, t_ptr.data_ptr(), edge3.data_ptr() if ne else None,
+                                         a_rowptr.data_ptr(), a_col.data_ptr() if ne else None, t_rowptr.data_ptr(),
+                                         t_col.data_ptr() if ne else None, t_cur.data_ptr())
+            csr = (ops.DeviceCSR(na, nt, a_rowptr, a_col), ops.DeviceCSR(nt, na, t_rowptr, t_col))
+            res.append((t_ids, t_ptr, edge3, csr))
+        tot = (ctypes.c_int64 * 4)(*[int(x) for x in totals])
+        rtot = (ctypes.c_int64 * (2 * n_rel))(*[int(x) for x in rel_totals])
+        check(_lib.lib().mi_sampler_emit_relations(ctypes.byref(desc), self._rel_arr, n_rel, ws.data_ptr(), ws.numel(), tot,
+                                                   rel_ws.data_ptr(), rel_ws.numel(), rtot, outs, stream),
+              "mi_sampler_emit_relations")
+        return res, [b64, b32]
+
+    def _emit(self, seeds: Tensor, desc: SamplerDesc, totals, stream: int, raw: bool = False, ws: Optional[Tensor] = None,
+              rel_totals=None, rel_ws: Optional[Tensor] = None):
         """Phase B on `stream` (the current torch stream must be that stream: the feature gathers follow it).  ws: the
-        workspace phase A of this batch ran in (default: the sampler's own)."""
+        workspace phase A of this batch ran in (default: the sampler's own); rel_totals / rel_ws: the same for the relations."""
         ws = self._ws if ws is None else ws
         nu, na, ne, nl = totals
         B = seeds.numel()
@@ -185,11 +260,19 @@ class DeviceGraphSampler:
             # (rows = customers, rows = articles): by-source and by-destination forms of the customer -> article relation
             csr = (ops.DeviceCSR(nu, na, u_rowptr, u_col), ops.DeviceCSR(na, nu, a_rowptr, a_col))
             blocks.append(b32)
+        rels = None
+        if self._rels:
+            rels, rel_blocks = self._emit_relations(desc, totals, rel_totals, stream, ws, self._rel_ws if rel_ws is None else rel_ws)
+            blocks += rel_blocks
         if raw:
             out = {"user_ids": user_ids, "article_ids": article_ids, "edge_index": edge_index,
                     "edge_label_index": label_index, "edge_label": labels, "user_ptr": user_ptr, "article_ptr": article_ptr}
             if csr is not None:
                 out["csr_by_customer"], out["csr_by_article"] = csr
+            if rels is not None:
+                out["relations"] = {r.key: {"T_ids": ids, "T_ptr": ptr, "edge_index": e3[0:2], "edge3": e3,
+                                            "csr_by_article": c[0], "csr_by_target": c[1]}
+                                    for r, (ids, ptr, e3, c) in zip(self._rels, rels)}
             return out
         data = HeteroData()
         xc, xa = self.user_x[user_ids], self.article_x[article_ids]
@@ -207,8 +290,22 @@ class DeviceGraphSampler:
         data[Constants.rev_edge_key].edge_index = rev
         data[Constants.rev_edge_key].edge_label_index = label3[1:3]
         data[Constants.rev_edge_key].edge_label = labels
-        data._blocks = blocks + [xc, xa]  # the storages behind every tensor of the batch (the iterator's record_stream calls)
+        extra_x = []
+        if rels is not None:   # no edge_label* on these stores (data/dataset_neo.py:85-91)
+            for r, (_, _, x_all), (ids, ptr, e3, c) in zip(self._rels, self._rel_dev, rels):
+                xt = x_all[ids]
+                data[r.target].x = xt
+                data[r.target].n_id = ids
+                data[r.target].ptr = ptr
+                fwd, rev = e3[0:2], e3[1:3]
+                fwd._sorted_csr = c       # (by article, by T)
+                rev._reverse_of = fwd
+                data[r.key].edge_index = fwd
+                data[r.rev_key].edge_index = rev
+                extra_x.append(xt)
+        data._blocks = blocks + [xc, xa] + extra_x  # the storages behind every tensor of the batch (the iterator's record_stream calls)
         data._seed_users, data._user_ptr = seeds, user_ptr   # per-sample structure (run_submission.make_predictions' sync-free path)
+        data._article_ptr = article_ptr                       # with data[T].ptr: which articles / attribute nodes belong to which sample
         data._max_candidates = int(self.max_neg)             # capacity of a sample's label-0 list
         return data
 
@@ -247,9 +344,10 @@ class DeviceGraphSampler:
         DEPTH = 3   # batches in flight: the walk of batch i + 3 is enqueued while the consumer trains on batch i (see below)
         if getattr(self, "_side", None) is None:
             self._side = t.cuda.Stream(device=self.device)
-            self._pinned = [t.empty(4, dtype=t.int32).pin_memory() for _ in range(DEPTH)]
+            self._pinned = [t.empty(4 + 2 * len(self._rels), dtype=t.int32).pin_memory() for _ in range(DEPTH)]
             # a workspace per batch in flight: phase A of batch j + DEPTH may be enqueued before phase B of batch j + 1 ...
             self._ws_ring = [self._ws] + [t.empty_like(self._ws) for _ in range(DEPTH - 1)]
+            self._rel_ws_ring = [self._rel_ws] + [t.empty_like(self._rel_ws) for _ in range(DEPTH - 1)] if self._rels else None
         side = self._side
         step0 = self.step
 
@@ -267,6 +365,8 @@ class DeviceGraphSampler:
             check(L.mi_sampler_count_async(ctypes.byref(desc), seeds.data_ptr(), self.seed & (2**64 - 1),
                                            int(step0 + i) & (2**64 - 1), self._ws_ring[i % DEPTH].data_ptr(), self._ws_ring[i % DEPTH].numel(),
                                            self._pinned[i % DEPTH].data_ptr(), side_raw), "mi_sampler_count_async")
+            if self._rels:  # behind the walk, before the event: the same wait covers both sets of totals
+                self._count_relations(desc, self._ws_ring[i % DEPTH], self._rel_ws_ring[i % DEPTH], self._pinned[i % DEPTH], side_raw)
             ev = t.cuda.Event()
             ev.record(side)
             return seeds, desc, ev
@@ -276,7 +376,11 @@ class DeviceGraphSampler:
             ev.synchronize()
             totals = self._pinned[i % DEPTH].tolist()
             with t.cuda.stream(side):
-                data = self._emit(seeds, desc, totals, side_raw, ws=self._ws_ring[i % DEPTH])
+                if self._rels:
+                    data = self._emit(seeds, desc, totals[:4], side_raw, ws=self._ws_ring[i % DEPTH], rel_totals=totals[4:],
+                                      rel_ws=self._rel_ws_ring[i % DEPTH])
+                else:
+                    data = self._emit(seeds, desc, totals, side_raw, ws=self._ws_ring[i % DEPTH])
                 ready = t.cuda.Event()
                 ready.record(side)
             return data, ready

@@ -101,6 +101,8 @@ def _rows_ok(x: Tensor, name: str) -> int:
     except AttributeError:
         pass
     _need(x, t.float32, name, contiguous=False)
+    if x.dim() == 2 and x.shape[0] == 0:   # no rows (a node type absent from the batch): any strides, e.g. autograd's (0, 0)
+        return max(int(x.shape[1]), 1)
     if x.dim() != 2 or (x.shape[1] > 1 and x.stride(1) != 1):
         raise ValueError(f"{name}: expected a row-major 2-D matrix, got shape {tuple(x.shape)} strides {x.stride()}")
     return x.stride(0) if x.shape[0] > 1 else max(x.shape[1], x.stride(0))
@@ -651,6 +653,14 @@ def spmm(a: DeviceCSR, X: Tensor, *, Y: Optional[Tensor] = None, addend: Optiona
         raise ValueError("addend width differs from X")
     if Y is None and S is None and adam is None:
         raise ValueError("spmm needs an output (Y and/or S)")
+    if X.shape[0] == 0 and a.nnz == 0 and x_map is None and row_list is None and adam is None:
+        # an adjacency without columns (a batch whose attribute relation holds no node): A @ X = 0, and X has no storage
+        # to hand to the kernel
+        if Y is not None:
+            Y.zero_()
+        if S is not None:
+            S.copy_(addend * scale) if addend is not None else S.zero_()
+        return
     adam_args = None
     if adam is not None:
         if row_list is not None:
