@@ -1354,6 +1354,49 @@ int    mi_pinsage_text_bwd_lazy_f32(const mi_text_columns* p, float* const g_tab
                                     const float* g, int64_t ldg, int64_t n_ref_max, void* ws, size_t ws_bytes,
                                     mi_stream_t stream);
 
+/* ------------------------------------------------------------------------------------
+ * N5  recent-items recommender (additive to ABI 14; csrc/recent_items.hip).
+ * replaces: nothing in the reference.  pinsage/evaluation.py:18-53 (LatestNNRecommender) represents a user by the LAST item
+ *           of their row; the PinSAGE paper serves a user from several recent pins.  These three entries are the layer
+ *           between "a user's row" and "K items" for that: the user's last n_recent DISTINCT items, pooled either before
+ *           the top-K (mean) or after one top-K per slot (max).  Rows are in transaction order (the rule of
+ *           LatestNNRecommender); per-edge timestamps are not supported.
+ * The rule, restated in numpy by tests/recent_items_emulation.py:
+ *   history   The window of user u is the last min(len, 64) entries of row u; position p = 0 is the last entry.  The entry at
+ *             position p is kept iff no position p' < p of the window holds the same item (distinct items, the most recent
+ *             occurrence wins).  The kept entries in ascending p fill slots r = 0 .. n_slots[u] - 1, at most n_recent of
+ *             them: slot 0 is the latest item, n_slots[u] >= 1 for a row with an entry.  items is slot-major
+ *             [n_recent, n_users] (items[r] is a vector of query ids); unused slots hold the slot-0 item and never
+ *             contribute.  An empty row gets n_slots = 0 and item 0 in every slot (the Python layer refuses such graphs).
+ *   weights   w[r] = (float)pow((double)decay, r), computed by the caller: a device table of n_recent (n_lists) floats.
+ *   mean      acc = 0, W = 0; for r ascending over the user's slots: p = w[r] * h[item_r][c], acc = acc + p, W = W + w[r],
+ *             every operation one float32 rounding (no contraction); q[u][c] = acc / W, correctly rounded.  The answer is
+ *             the top-K of q[u] . h[i] with the user's row excluded.  n_slots[u] is clamped to 1 .. n_recent.
+ *   max       every slot r retrieves its own list: the top k_in of h[items[r][u]] . h[i], the user's row excluded, with
+ *             scores.  The candidates of user u are the entries of lists r < n_slots[u] whose id is not -1; an item's score
+ *             is the maximum over those entries of (w[r] * score) + 0.0f (one float32 multiply; the addition turns -0 into
+ *             +0); the answer is the k_out candidates by (score desc, id asc), -1 / -inf pads when fewer exist.  The
+ *             definition is the procedure.  For decay == 1 it is the exact top-K of max_r h[item_r] . h[i] over the
+ *             eligible items: whatever outranks item i in the list of its arg-max slot also outranks it in the result.
+ * mi_recent_items: one wavefront per user, no atomics, one writer per output.  ui_ptr / ui_idx: the user -> item CSR,
+ *   1 <= n_recent <= MI_RECENT_MAX_SLOTS; items_out int64 [n_recent, n_users], n_slots_out int32 [n_users].
+ * mi_pool_recent_f32: q_out [n_users, d] (leading dimension ldq) from table rows of leading dimension ld; d % 4 == 0, table
+ *   and q_out 16-byte aligned, ld and ldq multiples of 4 and >= d.
+ * mi_topk_merge_max_f32: ids int64 / scores float32 [n_lists][n_q][k_in], ids below 2^31 or -1; out_ids int64 [n_q, k_out],
+ *   out_scores (nullable) float32 [n_q, k_out].  One workgroup per user sorts the entries twice in LDS, sized by the padded
+ *   entry count: n_lists * k_in <= 4096, k_out <= k_in.  No float atomics, no global scratch: two calls give equal bits.
+ * Returned before anything is enqueued: MI_ERR_BAD_ARG (n_recent / n_lists / k_in / k_out < 1, k_out > k_in, a negative
+ *   count, a null or misaligned pointer, a leading dimension below d), MI_ERR_UNSUPPORTED (n_recent > MI_RECENT_MAX_SLOTS,
+ *   d % 4 != 0, n_lists * k_in > 4096), MI_ERR_TOO_LARGE (2^31 users or more).  Zero users: 0, nothing enqueued.
+ * ---------------------------------------------------------------------------------- */
+#define MI_RECENT_MAX_SLOTS 16
+int    mi_recent_items(int64_t n_users, const int32_t* ui_ptr, const int32_t* ui_idx, int32_t n_recent, int64_t* items_out,
+                       int32_t* n_slots_out, mi_stream_t stream);
+int    mi_pool_recent_f32(int64_t n_users, int32_t n_recent, int64_t d, const int64_t* items, const int32_t* n_slots,
+                          const float* w, const float* table, int64_t ld, float* q_out, int64_t ldq, mi_stream_t stream);
+int    mi_topk_merge_max_f32(int64_t n_q, int32_t n_lists, int32_t k_in, int32_t k_out, const int64_t* ids, const float* scores,
+                             const int32_t* n_slots, const float* w, int64_t* out_ids, float* out_scores, mi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -56,6 +56,8 @@ MI_ERR_BAD_ARG = -1
 MI_ERR_TOO_LARGE = -2
 MI_ERR_WORKSPACE = -3
 MI_TOPK_ITEMS_PREPARED = 1
+MI_RECENT_MAX_SLOTS = 16       # mi_recent_items / mi_pool_recent_f32: slots per user
+MI_TOPK_MERGE_MAX_ENTRIES = 4096   # mi_topk_merge_max_f32: n_lists * k_in
 MI_TOPK_PATH_MATERIALISED, MI_TOPK_PATH_ONE_PASS, MI_TOPK_PATH_FUSED, MI_TOPK_PATH_FUSED_DMA, MI_TOPK_PATH_PREFILTER = range(5)
 MI_RANK_OBJECTIVES = {"reference": 0, "bpr": 1, "softmax": 2}
 MI_RANK_MAX_NEG = 16
@@ -363,6 +365,9 @@ _PROTOTYPES = {
                                                   POINTER(LazyAdam), c_int64, P, P, c_int64, P, c_size_t, P]),
     "mi_pinsage_text_bwd_lazy_f32": (c_int32, [POINTER(TextColumns), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p),
                                                POINTER(LazyAdam), c_int64, P, P, c_int64, c_int64, P, c_size_t, P]),
+    "mi_recent_items": (c_int32, [c_int64, P, P, c_int32, P, P, P]),
+    "mi_pool_recent_f32": (c_int32, [c_int64, c_int32, c_int64, P, P, P, P, c_int64, P, c_int64, P]),
+    "mi_topk_merge_max_f32": (c_int32, [c_int64, c_int32, c_int32, c_int32, P, P, P, P, P, P, P]),
 }
 
 _LIB = None

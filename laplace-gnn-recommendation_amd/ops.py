@@ -1086,6 +1086,58 @@ def topk_prefilter_scores(uid: Optional[Tensor], user_emb: Tensor, item_emb: Ten
     return sc, eps
 
 
+def recent_items(ui_ptr: Tensor, ui_idx: Tensor, n_recent: int) -> Tuple[Tensor, Tensor]:
+    """N5 recent-items recommender — the last n_recent distinct items of every row of a user -> item CSR (the last 64 entries
+    are looked at, the most recent occurrence of an item counts): (items int64 [n_recent, n_users], slot 0 the latest item,
+    unused slots filled with it; n_slots int32 [n_users])."""
+    _need(ui_ptr, t.int32, "ui_ptr")
+    _need(ui_idx, t.int32, "ui_idx")
+    n_users = ui_ptr.numel() - 1
+    if n_users < 0:
+        raise ValueError("ui_ptr needs n_users + 1 entries")
+    items = t.empty(int(n_recent), n_users, dtype=t.int64, device=ui_ptr.device)
+    n_slots = t.empty(n_users, dtype=t.int32, device=ui_ptr.device)
+    check(_lib.lib().mi_recent_items(n_users, ui_ptr.data_ptr(), ui_idx.data_ptr() if ui_idx.numel() else ui_ptr.data_ptr(),
+                                     int(n_recent), _ptr(items), _ptr(n_slots), _stream()), "mi_recent_items")
+    return items, n_slots
+
+
+def pool_recent(items: Tensor, n_slots: Tensor, w: Tensor, table: Tensor) -> Tensor:
+    """N5 recent-items recommender, pool = "mean" — q[u] = (sum_r w[r] * table[items[r, u]]) / (sum_r w[r]) over the user's
+    n_slots[u] slots, r ascending, every operation one float32 rounding.  Returns q float32 [n_users, d]."""
+    _need(items, t.int64, "items")
+    _need(n_slots, t.int32, "n_slots")
+    _need(w, t.float32, "w")
+    ld = _rows_ok(table, "table")
+    if items.dim() != 2 or n_slots.numel() != items.shape[1] or w.numel() != items.shape[0]:
+        raise ValueError("items must be [n_recent, n_users] with one n_slots entry per user and one weight per slot")
+    n_recent, n_users = items.shape
+    d = table.shape[1]
+    q = t.empty(n_users, d, dtype=t.float32, device=table.device)
+    check(_lib.lib().mi_pool_recent_f32(n_users, n_recent, d, _ptr(items), _ptr(n_slots), w.data_ptr(), table.data_ptr(), ld,
+                                        _ptr(q), d, _stream()), "mi_pool_recent_f32")
+    return q
+
+
+def topk_merge_max(ids: Tensor, scores: Tensor, n_slots: Tensor, w: Tensor, k_out: int, want_scores: bool = True):
+    """N5 recent-items recommender, pool = "max" — merges per-slot top-K lists (ids int64 / scores float32
+    [n_lists, n_q, k_in], -1 pads): an item's score is the maximum of w[r] * score over its entries in the lists
+    r < n_slots[q]; returns the k_out best by (score desc, id asc) as ids [n_q, k_out] (-1 pads) and optionally scores
+    (-inf pads).  n_lists * k_in <= 4096, k_out <= k_in."""
+    _need(ids, t.int64, "ids")
+    _need(scores, t.float32, "scores")
+    _need(n_slots, t.int32, "n_slots")
+    _need(w, t.float32, "w")
+    if ids.dim() != 3 or scores.shape != ids.shape or n_slots.numel() != ids.shape[1] or w.numel() != ids.shape[0]:
+        raise ValueError("ids and scores must be [n_lists, n_q, k_in] with one n_slots entry per query and one weight per list")
+    n_lists, n_q, k_in = ids.shape
+    out_ids = t.empty(n_q, int(k_out), dtype=t.int64, device=ids.device)
+    out_sc = t.empty(n_q, int(k_out), dtype=t.float32, device=ids.device) if want_scores else None
+    check(_lib.lib().mi_topk_merge_max_f32(n_q, n_lists, k_in, int(k_out), _ptr(ids), _ptr(scores), _ptr(n_slots), w.data_ptr(),
+                                           _ptr(out_ids), _ptr(out_sc), _stream()), "mi_topk_merge_max_f32")
+    return (out_ids, out_sc) if want_scores else out_ids
+
+
 def segment_max(a: DeviceCSR, X: Tensor, want_arg: bool = True):
     """K5 (aggr="max") — Y[r] = max over the sources of destination r (0 for none); arg = winning source ids."""
     ldx = _rows_ok(X, "X")

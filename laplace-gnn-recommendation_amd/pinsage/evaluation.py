@@ -1,6 +1,7 @@
 """PinSAGE evaluation — reference: pinsage/evaluation.py (LatestNNRecommender, prec, evaluate_nn) and the evaluation half of
 pinsage/model.py:120-134.  The graph is the port's user -> item CSR (an AdjList, a PinSAGESampler's ui_ptr / ui_idx, or a
-(ptr, idx) pair) instead of a DGL graph; the scoring is K10 (ops.topk_excl: exact top-K with per-user exclusion)."""
+(ptr, idx) pair) instead of a DGL graph; the scoring is K10 (ops.topk_excl: exact top-K with per-user exclusion).
+RecentItemsRecommender is the port's own: a user's last few distinct items instead of the latest one."""
 from __future__ import annotations
 
 from typing import Optional, Tuple
@@ -9,7 +10,7 @@ import numpy as np
 import torch as t
 from torch import Tensor
 
-from .. import ops
+from .. import _lib, ops
 from ..data.dataset import AdjList
 
 
@@ -60,6 +61,91 @@ class LatestNNRecommender:
         return ops.topk_excl(latest, h, h, int(K), excl)
 
 
+class RecentItemsRecommender:
+    """A user is represented by their last `n_recent` DISTINCT items instead of the latest one alone (the PinSAGE paper
+    serves a user from several recent pins; the reference has LatestNNRecommender only).  The rule is stated step for step
+    in include/laplace_hip.h ("N5 recent-items recommender") and restated in numpy by tests/recent_items_emulation.py:
+
+      history  the last min(len, 64) entries of the user's row, most recent first; an entry whose item occurs at a more recent
+               position is dropped; the first n_recent survivors are the user's slots (slot 0 = the latest item).
+      weights  w[r] = float32(decay ** r): slot r counts decay ** r as much as the latest item.
+      "mean"   the weighted mean of the slots' rows of h_item is the query of ONE top-K call.
+      "max"    every slot retrieves its own K nearest items (LatestNNRecommender's rule applied to that slot); an item's
+               score is the largest w[r] * score among the lists it appears in, and the K best by (score desc, id asc) are the
+               answer.  For decay == 1 that is the exact top-K of max_r h_item[item_r] . h_item[i].
+
+    The items of the user's whole row are excluded, ties go to the lower id, -1 pads when fewer than K items are eligible: as
+    LatestNNRecommender, whose ids n_recent = 1 returns for both pools.  Recency is ROW ORDER (rows are kept in transaction
+    order, the rule of this module); per-edge timestamps are not supported.  A user without any interaction raises
+    ValueError.  The recommender keeps no state between calls."""
+
+    # recommend() with pool = "max" walks the users in chunks so that the per-slot lists of a chunk — ids int64 and scores
+    # float32 [n_recent, chunk, K] — stay below this many bytes whatever the number of users (8 slots at K = 10: 279 620
+    # users per chunk).  The chunk's top-K workspace is ops.topk_excl's own (ops.TOPK_WS_BYTES per stream).
+    MAX_LIST_BYTES = 256 << 20
+
+    def __init__(self, n_recent: int = 8, pool: str = "max", decay: float = 1.0):
+        if not isinstance(n_recent, (int, np.integer)) or not 1 <= n_recent <= _lib.MI_RECENT_MAX_SLOTS:
+            raise ValueError(f"n_recent must be an integer in 1 .. {_lib.MI_RECENT_MAX_SLOTS}, got {n_recent!r}")
+        if pool not in ("max", "mean"):
+            raise ValueError(f"pool must be 'max' or 'mean', got {pool!r}")
+        if not 0.0 < float(decay) <= 1.0:    # NaN fails both comparisons
+            raise ValueError(f"decay must be in (0, 1], got {decay!r}")
+        self.n_recent, self.pool, self.decay = int(n_recent), pool, float(decay)
+
+    def weights(self) -> np.ndarray:
+        """float32 [n_recent]: w[r] = (float)pow((double)decay, r)."""
+        return np.array([self.decay ** r for r in range(self.n_recent)], dtype=np.float64).astype(np.float32)
+
+    def recent_items(self, graph, device=None) -> Tuple[Tensor, Tensor]:
+        """(items int64 [n_recent, n_users], n_slots int32 [n_users]): items[r] is the r-th most recent distinct item of every
+        user, slots r >= n_slots[u] repeat items[0, u].  Computed on the GPU (mi_recent_items): `device`, by default the
+        graph's own, must be one."""
+        return self._recent(*_csr(graph, device if device is not None else _device_of(graph)))
+
+    def _recent(self, ptr: Tensor, idx: Tensor) -> Tuple[Tensor, Tensor]:
+        if bool((ptr[1:] == ptr[:-1]).any()):
+            raise ValueError("every user needs at least one interaction (a user's recent items represent them)")
+        return ops.recent_items(ptr, idx, self.n_recent)
+
+    def recommend(self, graph, K: int, h_user: Optional[Tensor], h_item: Tensor, want_scores: bool = False):
+        """LongTensor [n_users, K] of item ids by (score desc, id asc), the user's row excluded, -1 pads; with want_scores
+        also the float32 [n_users, K] scores (-inf at pads; "mean": q . h_item[i], "max": the largest w[r] * score).  h_user
+        is unused, as in LatestNNRecommender."""
+        if K <= 0:
+            raise ValueError("K must be positive")
+        K = int(K)
+        h = h_item.detach().to(t.float32).contiguous()
+        ptr, idx = _csr(graph, h.device)
+        items, n_slots = self._recent(ptr, idx)
+        n_users = ptr.numel() - 1
+        excl = ops.DeviceCSR(n_users, h.shape[0], ptr, idx)
+        w = t.from_numpy(self.weights()).to(h.device)
+        if self.pool == "mean":
+            q = ops.pool_recent(items, n_slots, w, h)
+            return ops.topk_excl(t.arange(n_users, dtype=t.int64, device=h.device), q, h, K, excl, want_scores=want_scores)
+        if self.n_recent * K > _lib.MI_TOPK_MERGE_MAX_ENTRIES:
+            raise ValueError(f"n_recent * K = {self.n_recent * K} is above the merge's {_lib.MI_TOPK_MERGE_MAX_ENTRIES} entries")
+        chunk = max(1, min(n_users, self.MAX_LIST_BYTES // (self.n_recent * K * 12)))
+        outs = []
+        for u0 in range(0, n_users, chunk):
+            u1 = min(n_users, u0 + chunk)
+            ids = t.empty(self.n_recent, u1 - u0, K, dtype=t.int64, device=h.device)
+            sc = t.empty(self.n_recent, u1 - u0, K, dtype=t.float32, device=h.device)
+            ex = ops.row_slice(excl, u0, u1)    # rowptr keeps absolute offsets: a chunk's exclusion is a slice
+            for r in range(self.n_recent):
+                a, b = ops.topk_excl(items[r, u0:u1], h, h, K, ex, want_scores=True)
+                ids[r].copy_(a)
+                sc[r].copy_(b)
+            outs.append(ops.topk_merge_max(ids, sc, n_slots[u0:u1], w, K, want_scores=True))
+        if len(outs) == 1:
+            out_ids, out_sc = outs[0]
+        else:
+            out_ids = t.cat([o[0] for o in outs]) if outs else t.empty(0, K, dtype=t.int64, device=h.device)
+            out_sc = t.cat([o[1] for o in outs]) if outs else t.empty(0, K, dtype=t.float32, device=h.device)
+        return (out_ids, out_sc) if want_scores else out_ids
+
+
 def _latest(ptr: Tensor, idx: Tensor) -> Tensor:
     if bool((ptr[1:] == ptr[:-1]).any()):
         raise ValueError("every user needs at least one interaction (a user's latest item represents them)")
@@ -94,10 +180,12 @@ def prec(recommendations: Tensor, ground_truth) -> float:
     return float(hit.any(1).double().mean())
 
 
-def evaluate_nn(model, sampler, ground_truth, K: int = 10, *, graph=None, step: Optional[int] = None) -> float:
+def evaluate_nn(model, sampler, ground_truth, K: int = 10, *, graph=None, step: Optional[int] = None, recommender=None) -> float:
     """pinsage/evaluation.py:58-72 after pinsage/model.py:120-134: every item's representation (model.item_representations),
-    the latest-item recommendations over `graph` (default: the sampler's training graph) and their hits@K against
-    `ground_truth` (the held-out user -> item rows)."""
+    the recommendations over `graph` (default: the sampler's training graph) and their hits@K against `ground_truth` (the
+    held-out user -> item rows).  recommender: anything with LatestNNRecommender's recommend(graph, K, h_user, h_item);
+    None = LatestNNRecommender(), the reference's."""
     h_item = model.item_representations(sampler, step=step)
-    recs = LatestNNRecommender().recommend(sampler if graph is None else graph, K, None, h_item)
+    rec = LatestNNRecommender() if recommender is None else recommender
+    recs = rec.recommend(sampler if graph is None else graph, K, None, h_item)
     return prec(recs, ground_truth)
