@@ -286,6 +286,21 @@ typedef struct mi_spmm_ex {
                                        MI_SPMM_SPLIT_ROWS: no partial rows, no atomics, bitwise reproducible.  Serves every form
                                        (x_map, addend_map, adam; with row_list the listed rows whose long_index is -2) */
     int32_t        n_thin;          /* 0 (and a null mi_spmm_ex) = the plan has no thin rows */
+    int32_t        row_slices;      /* 0 or 1 (and a null mi_spmm_ex) = the short-row launch as it is; 2 or 4 (anything else is
+                                       MI_ERR_BAD_ARG) = its SLICED form for adjacencies whose short rows gather popularity-ordered
+                                       rows (the user rows of a recommendation graph): the workgroup on XCD x (blockIdx.x & 7)
+                                       computes column slice x % row_slices of its rows only — d / row_slices columns of X, addend,
+                                       p, m, v, Y and S — so one XCD's L2 sees 1 / row_slices of every gathered row and holds
+                                       row_slices times as many; the workgroups of a slice share the row tiles alternately.  A
+                                       workgroup stages the row pointers and (col, val) entries of a tile of consecutive rows in
+                                       LDS once and sorts the tile's rows by length; each output row is still summed by ONE
+                                       sub-group in list order: bitwise the result of row_slices = 0.  A hint for speed: applies to
+                                       planned launches without row_list (dense, addend_map, x_map, adam) whose d / 4 is a
+                                       multiple of row_slices and whose plan->chunk fits the staging buffer (2048 entries);
+                                       ignored elsewhere. */
+    int32_t        slice_rows;      /* with row_slices: > 0 = only rows [0, slice_rows) run in the sliced form, the rows behind them
+                                       in the plain one (a [users; items] adjacency: the item rows are long and gather from the
+                                       user table, which has no popular part); 0 = all rows; < 0 is MI_ERR_BAD_ARG */
 } mi_spmm_ex;
 #define MI_SPMM_SHORT_ROWS 1
 #define MI_SPMM_SPLIT_ROWS 2

@@ -123,6 +123,8 @@ struct Ex {
     uint8_t* slot_live;         // [plan->n_items], behind the partial rows: 0 = the work item gathered nothing and wrote no partial row
     const int32_t* thin_rows;   // [n_thin]: the plan's thin rows (chunk < degree <= thin_max), longest first: summed whole by spmm_thin_kernel
     int32_t n_thin;
+    int32_t row_slices;         // host side only: 2 or 4 = the short rows run in the sliced form (planned, unlisted launches)
+    int32_t slice_rows;         // host side only: > 0 = only rows [0, slice_rows) do; the rows behind them keep the plain form
 };
 
 // Largest n over the sub-groups of the wavefront (loop bounds must be wave-uniform around __shfl).
@@ -331,14 +333,184 @@ __device__ __forceinline__ void spmm_rows_body(const int64_t block_id, const int
         }
     }
 }
-template <int LPR, int VPL, int UNROLL, int RPS, bool SPARSE, bool ADAM>
+// SLICED form of the short-row launch (mi_spmm_ex.row_slices = SL = 2 or 4; planned dense / x_map launches).  The workgroup on
+// XCD x (blockIdx.x & 7) computes column slice x % SL of its rows only: d4 / SL float4 per row of X, addend, p, m, v, Y and S,
+// so one XCD's L2 sees 1 / SL of every gathered row's width and holds SL times the rows (the user rows of a recommendation
+// graph gather Zipf-distributed item rows: their misses are capacity misses).  The 8 / SL XCDs of a slice take the row tiles
+// alternately.  What the narrower sub-groups would lose as full passes of the form above (profiles/row_slices_c4.md: four
+// sequential 32-column passes 3.6 -> 6.6 ms) is paid once per TILE here: a workgroup stages the row pointers and the
+// contiguous (col, val) span of kSliceTile consecutive rows in LDS with coalesced loads (x_map applied on the way), in rounds of
+// at most kSliceCap entries, and sorts the round's rows by length, so that the rows a wavefront walks together are equally
+// long.  A sub-group of LPR lanes (d4 / SL of them active) then sums each of its rows alone, in list order, from LDS entries:
+// the same fma chain per output element as the form above.  The next row's first gathers are issued BEFORE the previous
+// row's stores (one in-order vmcnt: profiles/r03_spmm_rows_persistent.md), except with the Adam epilogue.
+// Measured on C4 (profiles/row_slices_c4.md): 2 slices take the user-row pass 3.5 -> 3.05 ms and its L2-miss bytes 15.75 ->
+// 12.65 GB; 4 slices move fewer bytes still and lose (3.9 ms): one fixed quarter of every row is served at half the L2's rate.
+#ifndef MI_SPMM_SLICE_TILE
+#define MI_SPMM_SLICE_TILE 128
+#endif
+#ifndef MI_SPMM_SLICE_CAP
+#define MI_SPMM_SLICE_CAP 2048
+#endif
+#ifndef MI_SPMM_SLICE_UNROLL
+#define MI_SPMM_SLICE_UNROLL 4
+#endif
+constexpr int kSliceTile = MI_SPMM_SLICE_TILE;  // rows per tile, at most kBlock
+constexpr int kSliceCap = MI_SPMM_SLICE_CAP;    // staged entries per round; a plan's chunk must not exceed it
+static_assert(kSliceTile <= kBlock && kSliceTile <= 65535, "one thread ranks one row of the tile");
+
+template <int LPR, int UNROLL, bool SPARSE, bool ADAM, int SL>
+__device__ __forceinline__ void spmm_rows_sliced_body(int64_t n_rows, int d4,
+                                                      const int32_t* __restrict__ rowptr,
+                                                      const int32_t* __restrict__ col,
+                                                      const float* __restrict__ val,
+                                                      const float4* __restrict__ X4, int64_t ldx4,
+                                                      const Epilogue& ep, int32_t chunk, const Ex& ex) {
+    constexpr int NB = MI_WAVE / LPR, SG = NB * kWavesPerBlock, PER = 8 / SL;
+    __shared__ int32_t s_rp[kSliceTile + 1];
+    __shared__ int32_t s_len[kSliceTile];    // entries of a short row, 0 for a row of the split path
+    __shared__ uint16_t s_order[kSliceTile]; // the round's rows, longest first
+    __shared__ int32_t s_col[kSliceCap];
+    __shared__ float s_val[kSliceCap];
+    const int xcd = blockIdx.x & 7;
+    const int slice = xcd % SL;
+    const int64_t tile = (int64_t)(blockIdx.x >> 3) * PER + xcd / SL;
+    const int64_t t0 = tile * kSliceTile;
+    if (t0 >= n_rows) return;  // whole workgroup
+    const int nt = (int)min((int64_t)kSliceTile, n_rows - t0);
+    const int w = d4 / SL;     // float4 per row of this slice
+    const int lane = mi_lane();
+    const int li = lane % LPR;
+    const int sgi = (threadIdx.x / MI_WAVE) * NB + lane / LPR;
+    const bool lane_on = li < w;
+    const int e = slice * w + li;  // this lane's float4 of a row
+    for (int i = threadIdx.x; i <= nt; i += kBlock) s_rp[i] = rowptr[t0 + i];
+    __syncthreads();
+    for (int i = threadIdx.x; i < nt; i += kBlock) {
+        const int n = s_rp[i + 1] - s_rp[i];
+        s_len[i] = (n <= chunk) ? n : 0;
+    }
+    __syncthreads();
+    int r0 = 0;
+    while (r0 < nt) {  // block-uniform: everything that steers it is read from LDS
+        if (s_rp[r0 + 1] - s_rp[r0] > chunk) {  // a row of the split path: not staged
+            ++r0;
+            continue;
+        }
+        const int32_t g0 = s_rp[r0];
+        int lo = r0 + 1, hi = nt;  // the round: rows [r0, r1), the most whose span fits (r0 itself does: chunk <= kSliceCap)
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (s_rp[mid] - g0 <= kSliceCap) lo = mid; else hi = mid - 1;
+        }
+        const int r1 = lo, m = r1 - r0;
+        const int span = s_rp[r1] - g0;
+        for (int p = threadIdx.x; p < span; p += kBlock) {
+            int32_t c = col[g0 + p];
+            if (SPARSE && ex.x_map) c = ex.x_map[c];  // compact row of X, or < 0 for a row that is all zeros
+            s_col[p] = c;
+            s_val[p] = val[g0 + p];
+        }
+        if ((int)threadIdx.x < m) {
+            const int i = threadIdx.x, key = s_len[r0 + i];
+            int rank = 0;
+            for (int j = 0; j < m; ++j) {
+                const int kj = s_len[r0 + j];
+                rank += (kj > key || (kj == key && j < i)) ? 1 : 0;
+            }
+            s_order[rank] = (uint16_t)i;
+        }
+        __syncthreads();
+        // a sub-group's rows: sorted positions sgi, sgi + SG, ...; the first batch of a row is in registers before its walk
+        float wv[UNROLL];
+        float4 xv[UNROLL], a;
+        int pos = sgi, off = 0, n = 0;
+        int64_t r = 0;
+        bool mine = false;
+        auto open_row = [&]() {  // descriptor of row `pos`, its addend and its first UNROLL gathers
+            n = 0;
+            mine = false;
+            if (pos < m) {
+                const int i = r0 + s_order[pos];
+                n = s_len[i];
+                off = s_rp[i] - g0;
+                r = t0 + i;
+                mine = lane_on && s_rp[i + 1] - s_rp[i] <= chunk;  // a split row may be staged because it lies between short rows
+            }
+            a = mi_f4_zero();
+            if (mine && (ep.S || ep.p) && ep.addend) {
+                const int64_t ar = ex.addend_map ? (int64_t)ex.addend_map[r] : r;
+                if (ar >= 0) a = mi_load4<3>(ep.addend + ar * ep.lda4 + e);
+            }
+#pragma unroll
+            for (int u = 0; u < UNROLL; ++u) {
+                const bool in = u < n;
+                const int32_t c = in ? s_col[off + u] : -1;
+                wv[u] = (in && c >= 0) ? s_val[off + u] : 0.f;
+                xv[u] = (c >= 0 && lane_on) ? X4[(int64_t)c * ldx4 + e] : mi_f4_zero();
+            }
+        };
+        open_row();
+        while (pos < m) {
+            float4 acc = mi_f4_zero();
+#pragma unroll
+            for (int u = 0; u < UNROLL; ++u) mi_f4_fma(acc, wv[u], xv[u]);
+            for (int k = UNROLL; k < n; k += UNROLL) {
+#pragma unroll
+                for (int u = 0; u < UNROLL; ++u) {
+                    const bool in = k + u < n;
+                    const int32_t c = in ? s_col[off + k + u] : -1;
+                    wv[u] = (in && c >= 0) ? s_val[off + k + u] : 0.f;
+                    xv[u] = (c >= 0 && lane_on) ? X4[(int64_t)c * ldx4 + e] : mi_f4_zero();
+                }
+#pragma unroll
+                for (int u = 0; u < UNROLL; ++u) mi_f4_fma(acc, wv[u], xv[u]);
+            }
+            const int64_t rs = r;
+            const float4 as = a;
+            const bool mine_s = mine;
+            pos += SG;
+            // the next row's gathers leave before this row's stores; with the Adam epilogue (p, m, v loads of its own) the
+            // prefetched batch would only cost registers across it (81 against 64: five wavefronts per SIMD instead of eight)
+            if constexpr (!ADAM) open_row();
+            if (mine_s) {
+                if (ep.Y) mi_store4<2>(ep.Y + rs * ep.ldy4 + e, acc, ep.streaming);
+                if (ep.S || ADAM) {
+                    float4 o;
+                    o.x = ep.scale * (as.x + acc.x);
+                    o.y = ep.scale * (as.y + acc.y);
+                    o.z = ep.scale * (as.z + acc.z);
+                    o.w = ep.scale * (as.w + acc.w);
+                    if (ep.S) mi_store4<2>(ep.S + rs * ep.lds4 + e, o, ep.streaming);
+                    if (ADAM) {
+                        const float rw = ep.reg_w ? ep.reg_w[rs] : 0.f;
+                        const int64_t i = rs * d4 + e;
+                        float4 pp = ep.p[rs * ep.ldp4 + e], mm = ep.m[i], vv = ep.v[i];
+                        mi_adam_update4(pp, o, mm, vv, ep.reg_w != nullptr, rw, ep.adam);
+                        ep.p[rs * ep.ldp4 + e] = pp;
+                        ep.m[i] = mm;
+                        ep.v[i] = vv;
+                    }
+                }
+            }
+            if constexpr (ADAM) open_row();
+        }
+        __syncthreads();  // the next round overwrites the staged entries and the order
+        r0 = r1;
+    }
+}
+
+template <int LPR, int VPL, int UNROLL, int RPS, bool SPARSE, bool ADAM, int SL = 0>
 __global__ __launch_bounds__(kBlock) void spmm_rows_kernel(int64_t n_out, int d4,
                                                            const int32_t* __restrict__ rowptr,
                                                            const int32_t* __restrict__ col,
                                                            const float* __restrict__ val,
                                                            const float4* __restrict__ X4, int64_t ldx4,
                                                            Epilogue ep, int32_t chunk, Ex ex, int32_t coop) {
-    spmm_rows_body<LPR, VPL, UNROLL, RPS, SPARSE, ADAM>(blockIdx.x, gridDim.x, n_out, d4, rowptr, col, val, X4, ldx4, ep, chunk, ex, coop);
+    if constexpr (SL > 1)
+        spmm_rows_sliced_body<LPR, UNROLL, SPARSE, ADAM, SL>(n_out, d4, rowptr, col, val, X4, ldx4, ep, chunk, ex);
+    else
+        spmm_rows_body<LPR, VPL, UNROLL, RPS, SPARSE, ADAM>(blockIdx.x, gridDim.x, n_out, d4, rowptr, col, val, X4, ldx4, ep, chunk, ex, coop);
 }
 // Twin launch (pairs.hpp): two plan-less dense products in one grid — the first `split` workgroups take product a, the rest
 // product b.  The same body as the single launch (same instantiation), so each product's rows are bitwise the single launch's.
@@ -1479,6 +1651,44 @@ int launch_spmm_mode(int64_t n_rows, int d4, const int32_t* rowptr, const int32_
             }
         }
     }
+    if constexpr (VPL == 1) {
+        // sliced form: whole float4 groups per slice, a chunk that fits the staging buffer; everything else keeps the launch below
+        const int sl = ex.row_slices;
+        if (do_short && n_out > 0 && !short_done && plan && !listed && (sl == 2 || sl == 4) && d4 % sl == 0 &&
+            chunk <= kSliceCap && (!SPARSE || ex.x_map)) {
+            // rows behind slice_rows (the item rows of a [users; items] adjacency: long rows that gather from a table without a
+            // popular part) stay with the plain kernel: the same launch on shifted pointers
+            const int64_t n_sl = ex.slice_rows > 0 ? std::min<int64_t>(ex.slice_rows, n_out) : n_out;
+            const int64_t tiles = mi_ceil_div(n_sl, kSliceTile);
+            const dim3 gs((unsigned)(mi_ceil_div(tiles, 8 / sl) * 8));  // blockIdx.x & 7 = the XCD, as for the banded plan
+            // sub-groups of LPR / SL lanes: d4 / sl of them active (d4 <= LPR)
+            if (sl == 2)
+                hipLaunchKernelGGL((spmm_rows_kernel<LPR / 2, 1, MI_SPMM_SLICE_UNROLL, 1, SPARSE, ADAM, 2>), gs, dim3(kBlock), 0, s, n_sl, d4,
+                                   rowptr, col, val, X4, ldx4, ep, chunk, ex, 0);
+            else
+                hipLaunchKernelGGL((spmm_rows_kernel<LPR / 4, 1, MI_SPMM_SLICE_UNROLL, 1, SPARSE, ADAM, 4>), gs, dim3(kBlock), 0, s, n_sl, d4,
+                                   rowptr, col, val, X4, ldx4, ep, chunk, ex, 0);
+            if (n_sl < n_out) {
+                Epilogue er = ep;
+                Ex exr = ex;
+                if (er.Y) er.Y += n_sl * er.ldy4;
+                if (er.S) er.S += n_sl * er.lds4;
+                if (exr.addend_map) exr.addend_map += n_sl;
+                else if (er.addend) er.addend += n_sl * er.lda4;
+                if (er.p) {
+                    er.p += n_sl * er.ldp4;
+                    er.m += n_sl * d4;
+                    er.v += n_sl * d4;
+                    if (er.reg_w) er.reg_w += n_sl;
+                }
+                const int64_t n_rest = n_out - n_sl;
+                hipLaunchKernelGGL((spmm_rows_kernel<LPR, VPL, UNROLL_ROWS, ROWS_RPS, SPARSE, ADAM>),
+                                   dim3((unsigned)mi_ceil_div(n_rest, SG * ROWS_RPS)), dim3(kBlock), 0, s, n_rest, d4, rowptr + n_sl,
+                                   col, val, X4, ldx4, er, chunk, exr, 0);
+            }
+            short_done = true;
+        }
+    }
     if (do_short && n_out > 0 && !short_done) {
         dim3 gr((unsigned)mi_ceil_div(n_out, SG * ROWS_RPS));
         if (MI_SPMM_XCD_RANGES && !listed) gr.x = (gr.x + 7u) / 8u * 8u;
@@ -1730,6 +1940,10 @@ int mi_spmm_csr_ex_f32(int64_t n_rows, int64_t d, const int32_t* rowptr, const i
             ex.hot_rows = exh->hot_rows;   // the caller's contract: hot_base + max(hot_rows, 0) <= rows of X
             ex.hot_threads = exh->hot_threads;
         }
+        MI_CHECK_ARG(exh->row_slices == 0 || exh->row_slices == 1 || exh->row_slices == 2 || exh->row_slices == 4);
+        MI_CHECK_ARG(exh->slice_rows >= 0);
+        ex.row_slices = exh->row_slices;  // a hint: ignored where the sliced form does not apply
+        ex.slice_rows = exh->slice_rows;
         if (exh->n_thin > 0) {   // the plan was counted with thin_max > 0: its thin rows travel with every launch
             MI_CHECK_ARG(plan && exh->thin_rows);
             ex.thin_rows = exh->thin_rows;

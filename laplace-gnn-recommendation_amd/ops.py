@@ -152,6 +152,7 @@ class SpmmPlan:
     nnz_long: int = 0
     thin_rows: Optional[Tensor] = None            # int32: rows with chunk < degree <= thin_max, longest first (mi_spmm_ex.thin_rows)
     thin_max: int = 0
+    slice_reuse: dict = field(default_factory=dict)   # first hot row -> gathers per gathered column of the rows in front of it (spmm, ROW_SLICES)
 
     @property
     def n_thin_rows(self) -> int:
@@ -294,6 +295,31 @@ def row_slice(a: DeviceCSR, r0: int, r1: int) -> DeviceCSR:
 PERSISTENT_ROWS = _os_environ.get("LAPLACE_PERSISTENT_ROWS", "0") == "1"
 HOT_ROWS = int(_os_environ.get("LAPLACE_HOT_ROWS", 304))        # rows offered to the cache (the kernel clips to its LDS share); 0 = off
 HOT_THREADS = int(_os_environ.get("LAPLACE_HOT_THREADS", 0))    # workgroup size of the persistent launch; 0 = the library's default
+
+
+# Sliced short-row launch (include/laplace_hip.h, mi_spmm_ex.row_slices): 2 or 4 = the workgroups of an XCD compute one
+# column slice of their rows, so the XCD's L2 holds that many times the gathered rows; 0 = the plain launch.  Applies to planned
+# adjacencies that carry the `hot` hint (popularity-ordered items), for the rows in front of the hot rows (the user rows of a
+# [users; items] adjacency; all rows where the hot rows start at 0).  Bitwise the plain launch; profiles/row_slices_c4.md.
+# Measured on C4 (step, two streams): 2 slices gain 0.18 ms per plain dense launch and lose 0.36 ms with the Adam epilogue and
+# 0.29 ms with x_map; 4 slices lose everywhere.  Hence the defaults: 2 slices, plain dense launches only.
+ROW_SLICES = int(_os_environ.get("LAPLACE_SPMM_ROW_SLICES", 2))
+ROW_SLICES_FORMS = int(_os_environ.get("LAPLACE_SPMM_ROW_SLICES_FORMS", 1))  # bit 0 plain dense launches, 1 Adam epilogue, 2 x_map
+# Slices turn capacity misses into hits; where a column is gathered only a few times per pass most misses are first touches and
+# the staging is pure cost.  Measured: C4 (1 000 gathers per item row and pass) gains 1.2 % per step, C2 (100) loses 2 %; nothing
+# was measured in between, the bar sits between the two.
+ROW_SLICES_MIN_REUSE = float(_os_environ.get("LAPLACE_SPMM_ROW_SLICES_MIN_REUSE", 400))
+
+
+def _row_slices_pay(a: "DeviceCSR", plan: "SpmmPlan", slice_rows: int) -> bool:
+    """Entries of the sliced rows per column they gather from >= ROW_SLICES_MIN_REUSE (one read-back per plan and hint)."""
+    if ROW_SLICES_MIN_REUSE <= 0:
+        return True
+    if slice_rows not in plan.slice_reuse:
+        nnz = int(a.rowptr[slice_rows]) if slice_rows else a.nnz
+        cols = a.n_cols - (min(int(a.hot[0]), a.n_cols) if slice_rows else 0)
+        plan.slice_reuse[slice_rows] = nnz / max(cols, 1)
+    return plan.slice_reuse[slice_rows] >= ROW_SLICES_MIN_REUSE
 
 
 def hot_item_rows(num_users: int, num_items: int) -> Optional[Tuple[int, int]]:
@@ -625,6 +651,9 @@ def spmm(a: DeviceCSR, X: Tensor, *, Y: Optional[Tensor] = None, addend: Optiona
     x_rare (with x_map): few columns are live (mi_spmm_ex.x_bits) — the split rows' work items test a bitmap of the map
     first, gather only live entries and skip work items without any; bitwise the result without the hint.
 
+    ROW_SLICES (module switch, 2 or 4) with a.hot set: the short rows of a planned launch run in the sliced form
+    (mi_spmm_ex.row_slices) — a speed hint as well, bitwise the same result.
+
     Re-weighting: a plan holds copies of the split rows' values.  `a.val = tensor` and in-place torch ops on `a.val` are
     noticed by the next call (three integer / identity comparisons per call, _sync_plan_values); after a write torch cannot
     see — a kernel or C-ABI caller given a.val.data_ptr(), a write through an aliasing tensor — call a.invalidate_values()."""
@@ -720,16 +749,22 @@ def spmm(a: DeviceCSR, X: Tensor, *, Y: Optional[Tensor] = None, addend: Optiona
         check(L.mi_map_live_bits_i32(a.n_cols, _ptr(x_map), _ptr(x_bits), _stream()), "mi_map_live_bits_i32")
 
     n_thin = plan.n_thin_rows if plan is not None else 0
+    form = 4 if x_map is not None else (2 if adam is not None else 1)
+    row_slices = ROW_SLICES if (ROW_SLICES in (2, 4) and a.hot is not None and plan is not None and row_list is None
+                                and (ROW_SLICES_FORMS & form)) else 0
+    slice_rows = max(0, min(int(a.hot[0]), a.n_rows)) if row_slices else 0   # the rows in front of the hot rows: the user rows
+    if row_slices and not _row_slices_pay(a, plan, slice_rows):
+        row_slices = slice_rows = 0
 
     def launch(parts: int, stream: int) -> None:
         exs = None
         if (x_map is not None or addend_map is not None or row_list is not None or adam_args is not None or parts
-                or sweep is not None or hot_rows != 0 or HOT_THREADS or n_thin):
+                or sweep is not None or hot_rows != 0 or HOT_THREADS or n_thin or row_slices):
             exs = SpmmExStruct(_ptr(x_map), _ptr(addend_map), _ptr(row_list), _ptr(n_list_dev),
                                row_list.numel() if row_list is not None else 0,
                                ctypes.pointer(adam_args) if adam_args is not None else None, parts, hot_rows,
                                ctypes.pointer(sweep) if sweep is not None else None, hot_base, HOT_THREADS, _ptr(x_bits),
-                               _ptr(plan.thin_rows) if n_thin else None, n_thin)
+                               _ptr(plan.thin_rows) if n_thin else None, n_thin, row_slices, slice_rows)
         check(L.mi_spmm_csr_ex_f32(a.n_rows, d, _ptr(a.rowptr), col_ptr, val_ptr, X.data_ptr(), ldx,
                                    _ptr(Y), ldy, _ptr(addend), lda, _ptr(S), lds, float(scale),
                                    ctypes.byref(plan.struct) if plan is not None else None,

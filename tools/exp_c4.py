@@ -1,6 +1,7 @@
 """Propagate experiments on BASELINE configs[3] (C4: 8 M x 100 K, 100 M edges) at N = 1, under the product's locality order:
-    python3 tools/exp_c4.py [--slices 1|2|4] [--band B] [--half users|items|both] [--n 5] [--edges E --users U]
+    python3 tools/exp_c4.py [--slices 1|2|4] [--row-slices 0|2|4] [--band B] [--half users|items|both] [--n 5] [--edges E --users U]
   --slices s  : the product is run as s launches over D/s-wide column slices of X / Y (ldx stays D)
+  --row-slices S : the short rows run in the sliced form (ops.ROW_SLICES, mi_spmm_ex.row_slices): ONE launch, slices pinned to XCDs
   --band B    : columns per band of the banded work-item plan (default: the product's)
   --half      : which row half of the adjacency is timed (the item rows = the split rows, the user rows = the short rows)
 One-stream mode (kernels back to back).  Run under tools/prof3.sh for per-kernel time and FETCH / WRITE traffic."""
@@ -12,6 +13,7 @@ from laplace_amd.interactions import Interactions
 
 ap = argparse.ArgumentParser()
 ap.add_argument('--slices', type=int, default=1)
+ap.add_argument('--row-slices', type=int, default=0)
 ap.add_argument('--band', type=int, default=-1)
 ap.add_argument('--half', default='both')
 ap.add_argument('--n', type=int, default=5)
@@ -22,6 +24,7 @@ ap.add_argument('--sweep-band', type=int, default=0)
 ap.add_argument('--hybrid', type=int, default=-1, help='>= 0: hybrid plan (sweep for the hub rows + tail mode: 0 banded, 1 whole rows)')
 args = ap.parse_args()
 ops.SPMM_TWO_STREAMS = 0
+ops.ROW_SLICES, ops.ROW_SLICES_FORMS = args.row_slices, 7
 ops.SWEEP_PACE = args.pace
 if args.sweep_band:
     ops.SWEEP_BAND = args.sweep_band
@@ -33,6 +36,7 @@ inter = Interactions(ei, U, I)
 order = inter.locality_order()
 inter = inter.permuted(order)
 adj, _ = inter.adjacency('bipartite').gcn_normalized(False)
+adj.hot = ops.hot_item_rows(U, I)   # what the trainer sets under the locality order
 del ei
 n, d = adj.n_rows, 128
 a_users, a_items = ops.row_slice(adj, 0, U), ops.row_slice(adj, U, n)
@@ -77,5 +81,5 @@ for _ in range(3):
     s_.record()
     for _ in range(args.n): product()
     e_.record(); t.cuda.synchronize(); ts.append(s_.elapsed_time(e_) / args.n)
-print(f'C4 half={args.half} slices={args.slices} band={args.band} chunk={args.chunk} hybrid={args.hybrid} pace={args.pace} sweep_band={ops.SWEEP_BAND}: product ms min {min(ts):.4f} med {sorted(ts)[1]:.4f}  '
+print(f'C4 half={args.half} slices={args.slices} row_slices={args.row_slices} band={args.band} chunk={args.chunk} hybrid={args.hybrid} pace={args.pace} sweep_band={ops.SWEEP_BAND}: product ms min {min(ts):.4f} med {sorted(ts)[1]:.4f}  '
       f'max err vs f64 {err:.2e}', flush=True)
