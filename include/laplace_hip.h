@@ -503,7 +503,8 @@ int    mi_gemm_f32(int32_t trans_a, int32_t trans_b, int64_t m, int64_t n, int64
  * (k2 = 0: none) — lin_l(agg) + lin_r(x_dst) of SAGEConv (model/layers.py:11-24) as ONE product.  a_mask (nullable):
  * same storage layout as A; A's element is read as 0 where the mask element is <= 0 — the backward of a relu fused
  * into the producing product.  Operands must be float4-addressable (leading dimensions and k multiples of 4, 16-byte
- * aligned bases); otherwise MI_ERR_UNSUPPORTED and the caller uses mi_gemm_f32.  Long-k / tiny-output problems are
+ * aligned bases); otherwise MI_ERR_UNSUPPORTED — for the whole call, before anything is enqueued, whichever problem it is —
+ * and the caller uses mi_gemm_f32.  Long-k / tiny-output problems are
  * split over k like mi_gemm_f32 (same slice rule, one grouped reduce).  ws: mi_gemm_group_workspace_bytes(). */
 typedef struct mi_gemm_problem {
     int32_t trans_a, trans_b;
@@ -523,6 +524,56 @@ int mi_gemm_group_f32(const mi_gemm_problem* problems, int32_t n, void* ws, size
 /* 1 when mi_gemm_group_f32 would take every problem (float4-addressable operands), 0 when it would return
  * MI_ERR_UNSUPPORTED; enqueues nothing. */
 int mi_gemm_group_supported(const mi_gemm_problem* problems, int32_t n);
+
+/* What mi_gemm_f32 will do with these arguments; host-only, enqueues nothing (the precedent is mi_topk_path).  The launcher asks
+ * the same function, so the answer is what runs.  A and B are tested for alignment only, never read.  a_gathered != 0: A's rows
+ * come through a row map (the score products of K10; mi_gemm_f32 itself passes none).  ws_bytes: the workspace the call will
+ * get, 0 for none.
+ *
+ *   kernel    chosen when
+ *   KK KR     both operands float4-addressable: 16-byte aligned bases; a K-contiguous operand (A without trans_a, B with
+ *   RK RR     trans_b) has ld % 4 == 0, a row-contiguous one ld % 4 == 0 and no row map; k % 4 == 0 unless BOTH are
+ *             row-contiguous.  First letter A, second B: K = K-contiguous, R = row-contiguous.
+ *   GENERIC   everything else
+ *   NONE      m == 0 or n == 0: nothing is launched (splits = 0)
+ *
+ * splits / k_per_split: with T = ceil(m / 64) * ceil(n / 64) output tiles, K is cut when T <= 8 and k >= 512 (at least 128 of K
+ * per slice) or 9 <= T <= 127 and k >= 2048 (at least 256 per slice), and the workspace holds the slabs:
+ * s = min(ceil(512 / T), k / 128 or k / 256); k_per_split = ceil(k / s) rounded up to 32; splits = ceil(k / k_per_split).
+ * Otherwise splits = 1, k_per_split = k.
+ * Returns 0, or the negative code mi_gemm_f32 would return for these arguments: MI_ERR_BAD_ARG (a negative size, a null out or
+ * operand, a leading dimension below the operand's width), MI_ERR_TOO_LARGE (more than 65 535 row tiles). */
+#define MI_GEMM_KERNEL_NONE    (-1)
+#define MI_GEMM_KERNEL_GENERIC 0  /* gemm_f32_kernel                */
+#define MI_GEMM_KERNEL_FAST_KK 1  /* gemm_fast_kernel<true, true>   */
+#define MI_GEMM_KERNEL_FAST_KR 2  /* gemm_fast_kernel<true, false>  */
+#define MI_GEMM_KERNEL_FAST_RK 3  /* gemm_fast_kernel<false, true>  */
+#define MI_GEMM_KERNEL_FAST_RR 4  /* gemm_fast_kernel<false, false> */
+typedef struct mi_gemm_plan_info {
+    int32_t kernel, splits;
+    int64_t k_per_split;
+} mi_gemm_plan_info;
+int mi_gemm_plan(int32_t trans_a, int32_t trans_b, int64_t m, int64_t n, int64_t k,
+                 const float* A, int64_t lda, const float* B, int64_t ldb,
+                 int32_t a_gathered, size_t ws_bytes, mi_gemm_plan_info* out);
+
+/* The layout mi_gemm_group_f32 gives these problems (workspace assumed sufficient); host-only, enqueues nothing; it is the
+ * launch's own layout pass.  out[i] for problem i: `launch` = which launch of 8 it rides in; splits / k_per_split as run (a
+ * two-pair problem is never split; a K-contiguous operand keeps k_per_split a multiple of 4); share_set = index, within its
+ * launch, of the share set it belongs to, -1 for none.  A share set is a run of >= 2 consecutive split single-pair problems
+ * over the same A (pointer, k, strides, mask): all members get the coarsest member's k_per_split, and their workgroups are
+ * laid slice-major from a multiple of 8 on, ceil(splits / 8) * 8 * (sum of the members' tiles) of them, the excess idle.
+ * first_wg / n_wg: the problem's range of linear workgroups in its launch (a set's members all report the set's range; idle
+ * workgroups that pad the start of a following set are not counted); an empty problem has splits = 0, n_wg = 0.
+ * Returns MI_ERR_UNSUPPORTED / MI_ERR_BAD_ARG exactly where the launch would, before anything is laid out: a call is taken
+ * whole or not at all. */
+typedef struct mi_gemm_group_plan_info {
+    int32_t launch, splits;
+    int64_t k_per_split;
+    int32_t share_set, reserved;
+    int64_t first_wg, n_wg;
+} mi_gemm_group_plan_info;
+int mi_gemm_group_plan(const mi_gemm_problem* problems, int32_t n, mi_gemm_group_plan_info* out);
 
 /* ------------------------------------------------------------------------------------
  * K10  batched exact top-K with per-user exclusion.

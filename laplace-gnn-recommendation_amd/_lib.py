@@ -73,6 +73,19 @@ class GemmProblem(Structure):
                 ("accumulate", c_int32), ("act", c_int32)]
 
 
+MI_GEMM_KERNEL_NONE = -1
+MI_GEMM_KERNEL_GENERIC, MI_GEMM_KERNEL_FAST_KK, MI_GEMM_KERNEL_FAST_KR, MI_GEMM_KERNEL_FAST_RK, MI_GEMM_KERNEL_FAST_RR = range(5)
+
+
+class GemmPlanInfo(Structure):
+    _fields_ = [("kernel", c_int32), ("splits", c_int32), ("k_per_split", c_int64)]
+
+
+class GemmGroupPlanInfo(Structure):
+    _fields_ = [("launch", c_int32), ("splits", c_int32), ("k_per_split", c_int64), ("share_set", c_int32),
+                ("reserved", c_int32), ("first_wg", c_int64), ("n_wg", c_int64)]
+
+
 class SamplerDesc(Structure):
     _fields_ = [("batch", c_int32), ("n_hops", c_int32), ("num_neighbors", c_int32), ("k", c_int32),
                 ("randomization", c_int32), ("max_pos", c_int32), ("max_neg", c_int32), ("reserved", c_int32),
@@ -279,6 +292,9 @@ _PROTOTYPES = {
                               c_int32, c_int32, P, c_size_t, P]),
     "mi_gemm_group_workspace_bytes": (c_size_t, [POINTER(GemmProblem), c_int32]),
     "mi_gemm_group_f32": (c_int32, [POINTER(GemmProblem), c_int32, P, c_size_t, P]),
+    "mi_gemm_plan": (c_int32, [c_int32, c_int32, c_int64, c_int64, c_int64, P, c_int64, P, c_int64, c_int32, c_size_t,
+                               POINTER(GemmPlanInfo)]),
+    "mi_gemm_group_plan": (c_int32, [POINTER(GemmProblem), c_int32, POINTER(GemmGroupPlanInfo)]),
     "mi_topk_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64]),
     "mi_topk_excl_f32": (c_int32, [c_int64, c_int64, c_int64, c_int64, P, P, c_int64, P, c_int64, P, P, P, P, P,
                                    c_size_t, P]),

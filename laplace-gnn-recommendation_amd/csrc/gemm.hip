@@ -490,20 +490,20 @@ int mi_gemm_splits(int64_t M, int64_t N, int64_t K) {
     return s < 2 ? 1 : (int)s;
 }
 
-int mi_gemm_launch(MiGemmArgs g, void* ws, size_t ws_bytes, hipStream_t stream) {
+// The launcher's whole decision, from sizes, strides and alignment alone: how K is sliced and which tile kernel runs.
+// mi_gemm_launch launches what this says and mi_gemm_plan (include/laplace_hip.h) reports it, so the report is what runs.
+// ws_bytes: the workspace the caller really has (0 without one).
+int mi_gemm_decide(const MiGemmArgs& g, size_t ws_bytes, MiGemmDecision* d) {
+    d->kernel = MI_GEMM_KERNEL_NONE; d->splits = 0; d->k_per_split = 0;
     if (g.M == 0 || g.N == 0) return 0;
-    dim3 grid((unsigned)mi_ceil_div(g.N, BN), (unsigned)mi_ceil_div(g.M, BM), 1);
-    if (grid.y > 65535u) return MI_ERR_TOO_LARGE;  // HIP grid.y limit: M <= 4.19M rows per launch
+    if (mi_ceil_div(g.M, BM) > 65535) return MI_ERR_TOO_LARGE;  // HIP grid.y limit: M <= 4.19M rows per launch
     int splits = mi_gemm_splits(g.M, g.N, g.K);
-    if (splits > 1 && (ws == nullptr || ws_bytes < (size_t)splits * g.M * g.N * sizeof(float))) splits = 1;
-    g.splits = splits;
-    g.k_per_split = g.K;
-    g.partial = nullptr;
+    if (splits > 1 && ws_bytes < (size_t)splits * g.M * g.N * sizeof(float)) splits = 1;
+    d->splits = 1;
+    d->k_per_split = g.K;
     if (splits > 1) {
-        g.k_per_split = mi_ceil_div(mi_ceil_div(g.K, splits), BK) * BK;
-        g.splits = (int)mi_ceil_div(g.K, g.k_per_split);
-        g.partial = static_cast<float*>(ws);
-        grid.z = (unsigned)g.splits;
+        d->k_per_split = mi_ceil_div(mi_ceil_div(g.K, splits), BK) * BK;
+        d->splits = (int)mi_ceil_div(g.K, d->k_per_split);
     }
     // fast path: float4-addressable operands.  K-contiguous operand: row stride % 4; output-contiguous
     // operand (stride 1 along its rows): k stride % 4 and no row gather.
@@ -511,18 +511,32 @@ int mi_gemm_launch(MiGemmArgs g, void* ws, size_t ws_bytes, hipStream_t stream) 
     const bool a_ok = a_kfast ? (g.sa_m % 4 == 0) : (g.sa_m == 1 && g.sa_k % 4 == 0 && g.a_rows == nullptr);
     const bool b_ok = b_kfast ? (g.sb_n % 4 == 0) : (g.sb_n == 1 && g.sb_k % 4 == 0);
     // float4 along k needs K (and every slice start) to be a multiple of 4; operands read along rows do not
-    const bool k_ok = (!a_kfast && !b_kfast) || (g.K % 4 == 0 && g.k_per_split % 4 == 0);
+    const bool k_ok = (!a_kfast && !b_kfast) || (g.K % 4 == 0 && d->k_per_split % 4 == 0);
     const bool fast = a_ok && b_ok && k_ok && mi_aligned16(g.A) && mi_aligned16(g.B);
-    if (!fast)
-        hipLaunchKernelGGL(gemm_f32_kernel, grid, dim3(256), 0, stream, g);
-    else if (a_kfast && b_kfast)
-        hipLaunchKernelGGL((gemm_fast_kernel<true, true>), grid, dim3(256), 0, stream, g);
-    else if (a_kfast)
-        hipLaunchKernelGGL((gemm_fast_kernel<true, false>), grid, dim3(256), 0, stream, g);
-    else if (b_kfast)
-        hipLaunchKernelGGL((gemm_fast_kernel<false, true>), grid, dim3(256), 0, stream, g);
-    else
-        hipLaunchKernelGGL((gemm_fast_kernel<false, false>), grid, dim3(256), 0, stream, g);
+    if (!fast) d->kernel = MI_GEMM_KERNEL_GENERIC;
+    else if (a_kfast && b_kfast) d->kernel = MI_GEMM_KERNEL_FAST_KK;
+    else if (a_kfast) d->kernel = MI_GEMM_KERNEL_FAST_KR;
+    else if (b_kfast) d->kernel = MI_GEMM_KERNEL_FAST_RK;
+    else d->kernel = MI_GEMM_KERNEL_FAST_RR;
+    return 0;
+}
+
+int mi_gemm_launch(MiGemmArgs g, void* ws, size_t ws_bytes, hipStream_t stream) {
+    MiGemmDecision d;
+    const int rc = mi_gemm_decide(g, ws ? ws_bytes : 0, &d);
+    if (rc != 0) return rc;
+    if (d.kernel == MI_GEMM_KERNEL_NONE) return 0;
+    const dim3 grid((unsigned)mi_ceil_div(g.N, BN), (unsigned)mi_ceil_div(g.M, BM), (unsigned)d.splits);
+    g.splits = d.splits;
+    g.k_per_split = d.k_per_split;
+    g.partial = d.splits > 1 ? static_cast<float*>(ws) : nullptr;
+    switch (d.kernel) {
+    case MI_GEMM_KERNEL_GENERIC: hipLaunchKernelGGL(gemm_f32_kernel, grid, dim3(256), 0, stream, g); break;
+    case MI_GEMM_KERNEL_FAST_KK: hipLaunchKernelGGL((gemm_fast_kernel<true, true>), grid, dim3(256), 0, stream, g); break;
+    case MI_GEMM_KERNEL_FAST_KR: hipLaunchKernelGGL((gemm_fast_kernel<true, false>), grid, dim3(256), 0, stream, g); break;
+    case MI_GEMM_KERNEL_FAST_RK: hipLaunchKernelGGL((gemm_fast_kernel<false, true>), grid, dim3(256), 0, stream, g); break;
+    default:                     hipLaunchKernelGGL((gemm_fast_kernel<false, false>), grid, dim3(256), 0, stream, g); break;
+    }
     if (g.splits > 1) {
         const int64_t total = g.M * g.N;
         hipLaunchKernelGGL(gemm_splitk_reduce_kernel, dim3((unsigned)mi_ceil_div(total, 32)), dim3(256), 0, stream, g);
@@ -588,108 +602,181 @@ extern "C" int mi_gemm_group_supported(const mi_gemm_problem* probs, int32_t n) 
     return 1;
 }
 
+namespace {
+
+// The host layout pass of ONE launch (cnt <= kMaxGroup problems): slicing, slabs, share sets, workgroup ranges.  Everything
+// gemm_group_kernel and gemm_group_reduce_kernel are told is decided here; mi_gemm_group_f32 launches lay.ga as it stands and
+// mi_gemm_group_plan reports it.  wp / left: the workspace cursor, carried from launch to launch.  plan_only: no workspace is
+// at hand — slabs stay null and nothing is checked against `left`.  blocks == 0: nothing to launch.
+struct GroupLayout {
+    MiGemmGroupArgs ga;
+    int64_t blocks, outs;
+    bool any_split;
+};
+
+int group_layout(const mi_gemm_problem* probs, int cnt, char*& wp, size_t& left, bool plan_only, GroupLayout& lay) {
+    MiGemmGroupArgs& ga = lay.ga;
+    memset(&ga, 0, sizeof(ga));
+    int64_t blocks = 0, outs = 0;
+    bool any_split = false;
+    lay.blocks = lay.outs = 0;
+    lay.any_split = false;
+    for (int i = 0; i < cnt; ++i) {
+        const mi_gemm_problem& d = probs[i];
+        MI_CHECK_ARG(d.act == 0 || d.act == 1);
+        if (d.m == 0 || d.n == 0) {  // nothing to write: an empty problem occupies no workgroups
+            ga.block_start[i] = blocks; ga.out_start[i] = outs;
+            ga.p[i].M = 0; ga.p[i].N = 0; ga.p[i].tiles_n = 1; ga.p[i].tiles_mn = 1; ga.p[i].splits = 1;
+            continue;
+        }
+        if (!group_fill(d, ga.p[i])) return MI_ERR_UNSUPPORTED;
+        MiGemmGroupProblem& g = ga.p[i];
+        int sp = group_splits(d);
+        if (sp > 1) {
+            g.k_per_split = mi_ceil_div(mi_ceil_div(d.k, sp), BK) * BK;
+            if (g.pair[0].sa_k == 1 || g.pair[0].sb_k == 1) g.k_per_split = mi_ceil_div(g.k_per_split, 4) * 4;
+            sp = (int)mi_ceil_div(d.k, g.k_per_split);
+            const size_t need = mi_align_up((size_t)sp * (size_t)d.m * (size_t)d.n * sizeof(float), 256);
+            if (sp > 1 && !plan_only && (!wp || left < need)) return MI_ERR_WORKSPACE;
+            if (sp > 1) {
+                if (!plan_only) { g.partial = reinterpret_cast<float*>(wp); wp += need; left -= need; }
+                any_split = true;
+            }
+        }
+        g.splits = sp > 1 ? sp : 1;
+        ga.block_start[i] = blocks;
+        ga.out_start[i] = outs;
+        blocks += (int64_t)g.tiles_mn * g.splits;
+        if (g.splits > 1) outs += d.m * d.n;
+    }
+    ga.n = cnt;
+    for (int i = cnt; i <= kMaxGroup; ++i) { ga.block_start[i] = blocks; ga.out_start[i] = outs; }
+    lay.outs = outs;
+    lay.any_split = any_split;
+    if (blocks == 0) return 0;
+    // share sets (MiGemmShareSet): runs of split problems over the same A / K get ONE slicing (the coarsest of the
+    // members': slabs were sized for at least as many slices) and the slice-major layout; the workgroup ranges are
+    // re-laid from the first problem on
+    auto same_a = [&](const MiGemmGroupProblem& x, const MiGemmGroupProblem& y) {
+        return x.M > 0 && y.M > 0 && x.splits > 1 && y.splits > 1 && x.n_pairs == 1 && y.n_pairs == 1 &&
+               x.pair[0].A == y.pair[0].A && x.pair[0].K == y.pair[0].K && x.pair[0].sa_m == y.pair[0].sa_m &&
+               x.pair[0].sa_k == y.pair[0].sa_k && x.a_mask == y.a_mask;
+    };
+    for (int i = 0; i < cnt;) {
+        int j = i + 1;
+        while (j < cnt && same_a(ga.p[i], ga.p[j])) ++j;
+        if (j - i >= 2) {
+            int64_t kps = 0;
+            for (int m = i; m < j; ++m) kps = std::max(kps, ga.p[m].k_per_split);
+            for (int m = i; m < j; ++m) {
+                ga.p[m].k_per_split = kps;
+                ga.p[m].splits = (int)mi_ceil_div(ga.p[m].pair[0].K, kps);
+            }
+        }
+        i = j;
+    }
+    for (int i = 0; i < kMaxGroup; ++i) ga.set_of[i] = -1;
+    ga.n_sets = 0;
+    {
+        int64_t run = 0;
+        int i = 0;
+        while (i < cnt) {
+            MiGemmGroupProblem& a0 = ga.p[i];
+            int j = i + 1;
+            if (a0.M > 0 && a0.splits > 1 && a0.n_pairs == 1) {
+                while (j < cnt && ga.p[j].M > 0 && ga.p[j].splits == a0.splits && ga.p[j].k_per_split == a0.k_per_split &&
+                       ga.p[j].n_pairs == 1 && ga.p[j].pair[0].A == a0.pair[0].A && ga.p[j].pair[0].K == a0.pair[0].K &&
+                       ga.p[j].pair[0].sa_m == a0.pair[0].sa_m && ga.p[j].pair[0].sa_k == a0.pair[0].sa_k &&
+                       ga.p[j].a_mask == a0.a_mask)
+                    ++j;
+            }
+            if (j - i >= 2 && ga.n_sets < kMaxSets) {
+                MiGemmShareSet& st = ga.set[ga.n_sets];
+                st.first = i; st.count = j - i; st.S = a0.splits; st.G = 0;
+                for (int m = i; m < j; ++m) { st.tile_off[m - i] = st.G; st.G += ga.p[m].tiles_mn; ga.set_of[m] = ga.n_sets; }
+                for (int m = j - i; m <= kMaxGroup; ++m) st.tile_off[m] = st.G;
+                run = (run + 7) / 8 * 8;
+                st.start = run;
+                for (int m = i; m < j; ++m) ga.block_start[m] = run;   // the whole set answers to one range
+                run += (int64_t)((st.S + 7) / 8) * 8 * st.G;
+                ++ga.n_sets;
+                i = j;
+            } else {
+                ga.block_start[i] = run;
+                run += (int64_t)a0.tiles_mn * (a0.M > 0 ? a0.splits : 0);
+                ++i;
+            }
+        }
+        blocks = run;
+        for (int m = cnt; m <= kMaxGroup; ++m) ga.block_start[m] = blocks;
+    }
+    if (blocks >= INT32_MAX) return MI_ERR_TOO_LARGE;
+    lay.blocks = blocks;
+    return 0;
+}
+
+// What both entries below refuse before the first launch is laid out: a call is taken whole or not at all.  (Before, a problem
+// the grouped kernel cannot take was met only when its own launch of 8 was laid out; with more than 8 problems the earlier
+// launches had then been enqueued already, and a caller that falls back to mi_gemm_f32 would have added an `accumulate`
+// problem's product twice.)
+int group_precheck(const mi_gemm_problem* probs, int32_t n) {
+    MI_CHECK_ARG(n >= 0 && (n == 0 || probs));
+    for (int i = 0; i < n; ++i) MI_CHECK_ARG(probs[i].act == 0 || probs[i].act == 1);
+    return mi_gemm_group_supported(probs, n) ? 0 : MI_ERR_UNSUPPORTED;
+}
+
+}  // namespace
+
 extern "C" int mi_gemm_group_f32(const mi_gemm_problem* probs, int32_t n, void* ws, size_t ws_bytes,
                                  mi_stream_t stream) {
-    MI_CHECK_ARG(n >= 0 && (n == 0 || probs));
+    const int pre = group_precheck(probs, n);
+    if (pre != 0) return pre;
     hipStream_t s = (hipStream_t)stream;
     char* wp = static_cast<char*>(ws);
     size_t left = ws_bytes;
+    GroupLayout lay;
     for (int base = 0; base < n; base += kMaxGroup) {
         const int cnt = std::min(kMaxGroup, n - base);
-        MiGemmGroupArgs ga;
-        memset(&ga, 0, sizeof(ga));
-        int64_t blocks = 0, outs = 0;
-        bool any_split = false;
-        for (int i = 0; i < cnt; ++i) {
-            const mi_gemm_problem& d = probs[base + i];
-            MI_CHECK_ARG(d.act == 0 || d.act == 1);
-            if (d.m == 0 || d.n == 0) {  // nothing to write: an empty problem occupies no workgroups
-                ga.block_start[i] = blocks; ga.out_start[i] = outs;
-                ga.p[i].M = 0; ga.p[i].N = 0; ga.p[i].tiles_n = 1; ga.p[i].tiles_mn = 1; ga.p[i].splits = 1;
-                continue;
-            }
-            if (!group_fill(d, ga.p[i])) return MI_ERR_UNSUPPORTED;
-            MiGemmGroupProblem& g = ga.p[i];
-            int sp = group_splits(d);
-            if (sp > 1) {
-                g.k_per_split = mi_ceil_div(mi_ceil_div(d.k, sp), BK) * BK;
-                if (g.pair[0].sa_k == 1 || g.pair[0].sb_k == 1) g.k_per_split = mi_ceil_div(g.k_per_split, 4) * 4;
-                sp = (int)mi_ceil_div(d.k, g.k_per_split);
-                const size_t need = mi_align_up((size_t)sp * (size_t)d.m * (size_t)d.n * sizeof(float), 256);
-                if (sp > 1 && (!wp || left < need)) return MI_ERR_WORKSPACE;
-                if (sp > 1) { g.partial = reinterpret_cast<float*>(wp); wp += need; left -= need; any_split = true; }
-            }
-            g.splits = sp > 1 ? sp : 1;
-            ga.block_start[i] = blocks;
-            ga.out_start[i] = outs;
-            blocks += (int64_t)g.tiles_mn * g.splits;
-            if (g.splits > 1) outs += d.m * d.n;
-        }
-        ga.n = cnt;
-        for (int i = cnt; i <= kMaxGroup; ++i) { ga.block_start[i] = blocks; ga.out_start[i] = outs; }
-        if (blocks == 0) continue;
-        // share sets (MiGemmShareSet): runs of split problems over the same A / K get ONE slicing (the coarsest of the
-        // members': slabs were sized for at least as many slices) and the slice-major layout; the workgroup ranges are
-        // re-laid from the first problem on
-        auto same_a = [&](const MiGemmGroupProblem& x, const MiGemmGroupProblem& y) {
-            return x.M > 0 && y.M > 0 && x.splits > 1 && y.splits > 1 && x.n_pairs == 1 && y.n_pairs == 1 &&
-                   x.pair[0].A == y.pair[0].A && x.pair[0].K == y.pair[0].K && x.pair[0].sa_m == y.pair[0].sa_m &&
-                   x.pair[0].sa_k == y.pair[0].sa_k && x.a_mask == y.a_mask;
-        };
-        for (int i = 0; i < cnt;) {
-            int j = i + 1;
-            while (j < cnt && same_a(ga.p[i], ga.p[j])) ++j;
-            if (j - i >= 2) {
-                int64_t kps = 0;
-                for (int m = i; m < j; ++m) kps = std::max(kps, ga.p[m].k_per_split);
-                for (int m = i; m < j; ++m) {
-                    ga.p[m].k_per_split = kps;
-                    ga.p[m].splits = (int)mi_ceil_div(ga.p[m].pair[0].K, kps);
-                }
-            }
-            i = j;
-        }
-        for (int i = 0; i < kMaxGroup; ++i) ga.set_of[i] = -1;
-        ga.n_sets = 0;
-        {
-            int64_t run = 0;
-            int i = 0;
-            while (i < cnt) {
-                MiGemmGroupProblem& a0 = ga.p[i];
-                int j = i + 1;
-                if (a0.M > 0 && a0.splits > 1 && a0.n_pairs == 1) {
-                    while (j < cnt && ga.p[j].M > 0 && ga.p[j].splits == a0.splits && ga.p[j].k_per_split == a0.k_per_split &&
-                           ga.p[j].n_pairs == 1 && ga.p[j].pair[0].A == a0.pair[0].A && ga.p[j].pair[0].K == a0.pair[0].K &&
-                           ga.p[j].pair[0].sa_m == a0.pair[0].sa_m && ga.p[j].pair[0].sa_k == a0.pair[0].sa_k &&
-                           ga.p[j].a_mask == a0.a_mask)
-                        ++j;
-                }
-                if (j - i >= 2 && ga.n_sets < kMaxSets) {
-                    MiGemmShareSet& st = ga.set[ga.n_sets];
-                    st.first = i; st.count = j - i; st.S = a0.splits; st.G = 0;
-                    for (int m = i; m < j; ++m) { st.tile_off[m - i] = st.G; st.G += ga.p[m].tiles_mn; ga.set_of[m] = ga.n_sets; }
-                    for (int m = j - i; m <= kMaxGroup; ++m) st.tile_off[m] = st.G;
-                    run = (run + 7) / 8 * 8;
-                    st.start = run;
-                    for (int m = i; m < j; ++m) ga.block_start[m] = run;   // the whole set answers to one range
-                    run += (int64_t)((st.S + 7) / 8) * 8 * st.G;
-                    ++ga.n_sets;
-                    i = j;
-                } else {
-                    ga.block_start[i] = run;
-                    run += (int64_t)a0.tiles_mn * (a0.M > 0 ? a0.splits : 0);
-                    ++i;
-                }
-            }
-            blocks = run;
-            for (int m = cnt; m <= kMaxGroup; ++m) ga.block_start[m] = blocks;
-        }
-        if (blocks >= INT32_MAX) return MI_ERR_TOO_LARGE;
-        hipLaunchKernelGGL(gemm_group_kernel, dim3((unsigned)blocks), dim3(256), 0, s, ga);
-        if (any_split)
-            hipLaunchKernelGGL(gemm_group_reduce_kernel, dim3((unsigned)mi_ceil_div(outs, 32)), dim3(256), 0, s, ga, outs);
+        const int rc = group_layout(probs + base, cnt, wp, left, false, lay);
+        if (rc != 0) return rc;
+        if (lay.blocks == 0) continue;
+        hipLaunchKernelGGL(gemm_group_kernel, dim3((unsigned)lay.blocks), dim3(256), 0, s, lay.ga);
+        if (lay.any_split)
+            hipLaunchKernelGGL(gemm_group_reduce_kernel, dim3((unsigned)mi_ceil_div(lay.outs, 32)), dim3(256), 0, s, lay.ga,
+                               lay.outs);
     }
     return mi_launch_status();
+}
+
+extern "C" int mi_gemm_group_plan(const mi_gemm_problem* probs, int32_t n, mi_gemm_group_plan_info* out) {
+    const int pre = group_precheck(probs, n);
+    if (pre != 0) return pre;
+    MI_CHECK_ARG(n == 0 || out);
+    char* wp = nullptr;
+    size_t left = 0;
+    GroupLayout lay;
+    for (int base = 0; base < n; base += kMaxGroup) {
+        const int cnt = std::min(kMaxGroup, n - base);
+        const int rc = group_layout(probs + base, cnt, wp, left, true, lay);
+        if (rc != 0) return rc;
+        for (int i = 0; i < cnt; ++i) {
+            const MiGemmGroupProblem& g = lay.ga.p[i];
+            mi_gemm_group_plan_info& o = out[base + i];
+            const bool empty = g.M == 0 || g.N == 0;
+            o.launch = base / kMaxGroup;
+            o.splits = empty ? 0 : g.splits;
+            o.k_per_split = empty ? 0 : g.k_per_split;
+            o.share_set = lay.blocks == 0 ? -1 : lay.ga.set_of[i];
+            o.reserved = 0;
+            o.first_wg = lay.ga.block_start[i];
+            if (empty) o.n_wg = 0;
+            else if (o.share_set >= 0) {
+                const MiGemmShareSet& st = lay.ga.set[o.share_set];
+                o.n_wg = (int64_t)((st.S + 7) / 8) * 8 * st.G;
+            } else o.n_wg = (int64_t)g.tiles_mn * g.splits;
+        }
+    }
+    return 0;
 }
 
 extern "C" size_t mi_gemm_workspace_bytes(int64_t m, int64_t n, int64_t k) {
@@ -698,15 +785,12 @@ extern "C" size_t mi_gemm_workspace_bytes(int64_t m, int64_t n, int64_t k) {
     return s > 1 ? mi_align_up((size_t)s * (size_t)m * (size_t)n * sizeof(float), 256) : 0;
 }
 
-extern "C" int mi_gemm_f32(int32_t trans_a, int32_t trans_b, int64_t m, int64_t n, int64_t k,
-                           const float* A, int64_t lda, const float* B, int64_t ldb, const float* bias,
-                           float* C, int64_t ldc, int32_t accumulate, int32_t act, void* ws,
-                           size_t ws_bytes, mi_stream_t stream) {
-    MI_CHECK_ARG(m >= 0 && n >= 0 && k >= 0);
-    if (m == 0 || n == 0) return 0;
-    MI_CHECK_ARG(C && ldc >= n && (k == 0 || (A && B)));
-    MI_CHECK_ARG(act == 0 || act == 1);
-    MiGemmArgs g;
+namespace {
+
+// The operand half of mi_gemm_f32's arguments as strides, with its checks (non-empty output); shared with mi_gemm_plan.
+int gemm_operands(int32_t trans_a, int32_t trans_b, int64_t m, int64_t n, int64_t k, const float* A, int64_t lda,
+                  const float* B, int64_t ldb, MiGemmArgs& g) {
+    MI_CHECK_ARG(k == 0 || (A && B));
     g.M = m; g.N = n; g.K = k;
     g.A = A; g.a_rows = nullptr;
     if (trans_a) { g.sa_m = 1; g.sa_k = lda; MI_CHECK_ARG(k == 0 || lda >= m); }   // A stored [k, m]
@@ -714,6 +798,40 @@ extern "C" int mi_gemm_f32(int32_t trans_a, int32_t trans_b, int64_t m, int64_t 
     g.B = B;
     if (trans_b) { g.sb_n = ldb; g.sb_k = 1; MI_CHECK_ARG(k == 0 || ldb >= k); }   // B stored [n, k] (Linear.weight)
     else         { g.sb_n = 1; g.sb_k = ldb; MI_CHECK_ARG(k == 0 || ldb >= n); }   // B stored [k, n]
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int mi_gemm_f32(int32_t trans_a, int32_t trans_b, int64_t m, int64_t n, int64_t k,
+                           const float* A, int64_t lda, const float* B, int64_t ldb, const float* bias,
+                           float* C, int64_t ldc, int32_t accumulate, int32_t act, void* ws,
+                           size_t ws_bytes, mi_stream_t stream) {
+    MI_CHECK_ARG(m >= 0 && n >= 0 && k >= 0);
+    if (m == 0 || n == 0) return 0;
+    MI_CHECK_ARG(C && ldc >= n);
+    MI_CHECK_ARG(act == 0 || act == 1);
+    MiGemmArgs g;
+    const int rc = gemm_operands(trans_a, trans_b, m, n, k, A, lda, B, ldb, g);
+    if (rc != 0) return rc;
     g.bias = bias; g.C = C; g.ldc = ldc; g.accumulate = accumulate; g.act = act;
     return mi_gemm_launch(g, ws, ws_bytes, (hipStream_t)stream);
+}
+
+extern "C" int mi_gemm_plan(int32_t trans_a, int32_t trans_b, int64_t m, int64_t n, int64_t k, const float* A, int64_t lda,
+                            const float* B, int64_t ldb, int32_t a_gathered, size_t ws_bytes, mi_gemm_plan_info* out) {
+    MI_CHECK_ARG(out);
+    out->kernel = MI_GEMM_KERNEL_NONE; out->splits = 0; out->k_per_split = 0;
+    MI_CHECK_ARG(m >= 0 && n >= 0 && k >= 0);
+    if (m == 0 || n == 0) return 0;
+    MiGemmArgs g{};
+    int rc = gemm_operands(trans_a, trans_b, m, n, k, A, lda, B, ldb, g);
+    if (rc != 0) return rc;
+    static const int64_t some_gather = 0;   // only its presence is looked at
+    if (a_gathered) g.a_rows = &some_gather;
+    MiGemmDecision d;
+    rc = mi_gemm_decide(g, ws_bytes, &d);
+    if (rc != 0) return rc;
+    out->kernel = d.kernel; out->splits = d.splits; out->k_per_split = d.k_per_split;
+    return 0;
 }

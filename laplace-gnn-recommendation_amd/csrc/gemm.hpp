@@ -23,4 +23,12 @@ struct MiGemmArgs {
 
 // Number of K slices the launcher will use for this shape (1 = no split) and the workspace it needs.
 int mi_gemm_splits(int64_t M, int64_t N, int64_t K);
+// What mi_gemm_launch will do with these arguments and this much workspace: the tile kernel (MI_GEMM_KERNEL_* of
+// include/laplace_hip.h; NONE for an empty output) and the K slicing.  Host-only; 0 or MI_ERR_TOO_LARGE.
+struct MiGemmDecision {
+    int kernel;
+    int splits;
+    int64_t k_per_split;
+};
+int mi_gemm_decide(const MiGemmArgs& g, size_t ws_bytes, MiGemmDecision* d);
 int mi_gemm_launch(MiGemmArgs g, void* ws, size_t ws_bytes, hipStream_t stream);

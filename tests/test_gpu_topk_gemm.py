@@ -8,6 +8,10 @@ import torch as t
 
 from oracle import lightgcn_ref as R
 
+import sys
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import gemm_cases as G  # noqa: E402
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 
@@ -281,21 +285,12 @@ def test_gemm_split_k_weight_gradient_shape():
     got = ops.gemm(dY.to(DEV), X.to(DEV), trans_a=True, trans_b=False)
     again = ops.gemm(dY.to(DEV), X.to(DEV), trans_a=True, trans_b=False)
     assert t.equal(got, again)
-    blocks = ((M + 63) // 64) * ((N + 63) // 64)
-    s = min(-(-512 // blocks), K // 128)  # outputs of <= 8 tiles: one 128-wide panel of K per slice at least
-    kps = -(-(-(-K // s)) // 32) * 32
     # slabs = one fma chain per K slice; the reduce adds every 8th slab in order per lane group, then the 8
-    # group sums in group order (csrc/gemm.hip:gemm_splitk_reduce_kernel)
-    slabs = [R.gemm_fma(dY[k0:k0 + kps], X[k0:k0 + kps], trans_a=True, trans_b=False) for k0 in range(0, K, kps)]
-    groups = []
-    for grp in range(8):
-        acc = t.zeros(M, N)
-        for z in range(grp, len(slabs), 8):
-            acc = acc + slabs[z]
-        groups.append(acc)
-    want = groups[0]
-    for q in range(1, 8):
-        want = want + groups[q]
+    # group sums in group order (csrc/gemm.hip:gemm_splitk_reduce_kernel): tests/gemm_cases.py restates the slicing rule
+    # (outputs of <= 8 tiles: one 128-wide panel of K per slice at least) and the association
+    splits, kps = G.slicing(M, N, K)
+    assert (splits, kps) == (118, 256)
+    want = G.split_reference(dY.t(), X, splits, kps)
     assert t.equal(got.cpu(), want)
     assert t.allclose(got.cpu().double(), dY.double().T @ X.double(), atol=2e-3, rtol=1e-5)
 
@@ -416,6 +411,12 @@ def test_gemm_group_pairs_mask_split_and_layouts():
     # unaligned operands are refused as a whole (the caller falls back to gemm())
     odd = t.randn(50, 7, device=DEV)
     assert not ops.gemm_group([ops.gemm_problem(odd, t.randn(9, 7, device=DEV), t.empty(50, 9, device=DEV))])
+    # and so is a mask off its 16-byte grid, behind a problem that would have been taken: nothing is written
+    big = t.randn(n_d * co + 4, device=DEV)
+    off_mask = big[1:1 + n_d * co].view(n_d, co)
+    untouched, untouched2 = t.full((40, 24), float("nan"), device=DEV), t.full((n_d, cs), float("nan"), device=DEV)
+    assert not ops.gemm_group([ops.gemm_problem(SA, SB, untouched), ops.gemm_problem(DY, WL, untouched2, trans_b=False, a_mask=off_mask)])
+    assert bool(t.isnan(untouched).all()) and bool(t.isnan(untouched2).all())
 
 
 @pytest.mark.parametrize("k,m,n1,n2,bias,mask", [(1, 32, 4, 4, True, False), (127, 64, 84, 76, True, True), (128, 128, 128, 128, True, True),
