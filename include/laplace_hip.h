@@ -463,6 +463,60 @@ int    mi_rank_loss_fwd_bwd_f32(int64_t batch, int32_t n_neg, int32_t objective,
                                 void* ws, size_t ws_bytes, mi_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * Popularity-weighted negatives and the logQ-corrected sampled softmax (SURVEY F9 behind a flag).
+ *
+ * Table (built once on the host in float64; ops.negative_table): with deg_i item i's degree in the TRAINING
+ * interactions and 0 <= power <= 1,
+ *   w_i    = deg_i ** power for deg_i > 0, else 0;     S = sum_i w_i  (float64, index order)
+ *   q_i    = 0 if deg_i == 0, else max(1, floor(w_i / S * 2^31))
+ *   cum[i] = q_0 + ... + q_i  (uint32);  total = cum[n_items - 1] < 2^32 for every n_items < 2^31
+ *   logq[i] = float32(log(max(q_i, 1) / total)), the logarithm taken in float64 — an item of weight 0 gets the value
+ *             of weight 1, so that a caller-supplied batch that names such an item stays finite.
+ *
+ * Draw (mi_sample_bpr_batch_pop): the counters of mi_sample_bpr_batch_ex, so the edge stream — users and pos — is
+ * bit-identical to the uniform sampler's at the same (seed, step).  Negative m of edge e, attempt t, takes the Philox
+ * counter (e, t | m << 16) of the negative stream, words (c0, c1, ..):
+ *   r    = ((c0 << 32) | c1) % total
+ *   cand = the smallest i with cum[i] > r   (bisection over cum in global memory; an item of weight 0 is never it)
+ * redrawn while cand is one of the user's items, for at most the 4096 attempts of the other samplers; the last
+ * candidate stays.  No quirk bits.  edges_in_order as in mi_sample_bpr_batch.  total is read from cum[n_items - 1] on
+ * the device (no host wait); a zero total writes negative 0 for every slot.  One thread per (slot, m), one writer per
+ * output, no atomics: two calls give equal bits.
+ * Checked before any launch: MI_ERR_UNSUPPORTED for n_neg > 16; MI_ERR_BAD_ARG for null or misaligned pointers
+ * (4 bytes for the int32 / uint32 arrays, 8 for the outputs) and for batch, n_neg, nnz or n_items below 1;
+ * MI_ERR_TOO_LARGE for n_items >= 2^31 (and nnz >= 2^31 - 1, as in the other samplers).
+ *
+ * Loss (mi_rank_loss_fwd_bwd_lq_f32): mi_rank_loss_fwd_bwd_f32 plus logq float[n_items] (nullable), addressed by item
+ * id whatever node_map is.  With logq, MI_RANK_SOFTMAX takes the logits
+ *   s+_b - logq[pos_b]   and   s-_{b,m} - logq[neg_{b,m}]
+ * in place of the raw scores: one fp32 subtraction each, applied after the wave sums; max subtraction, ascending-m
+ * sum and coefficient formulas unchanged (the correction is a constant per logit, so the gradient keeps its form).
+ * This makes the sampled softmax an estimate of the full softmax under the proposal q instead of penalising popular
+ * items twice.  The rejection of the user's own items is NOT reflected in logq — the usual approximation.
+ * logq == NULL: the kernels and the bits of mi_rank_loss_fwd_bwd_f32.  logq != NULL with another objective, or with
+ * the loss-only form that accumulates reg_w (g_final == NULL, reg_w != NULL: the one path with float atomics), returns
+ * MI_ERR_UNSUPPORTED before anything is enqueued.  Workspace: mi_rank_loss_workspace_bytes.
+ * ---------------------------------------------------------------------------------- */
+int mi_sample_bpr_batch_pop(int64_t batch, int32_t n_neg, int64_t nnz,
+                            const int32_t* rowptr, const int32_t* col,
+                            const int32_t* row_of_edge,
+                            int64_t n_items, const uint32_t* cum /* [n_items] */, int32_t edges_in_order,
+                            uint64_t seed, uint64_t step,
+                            int64_t* users, int64_t* pos, int64_t* neg /* [batch, n_neg] */,
+                            mi_stream_t stream);
+int mi_rank_loss_fwd_bwd_lq_f32(int64_t batch, int32_t n_neg, int32_t objective, int64_t d, int64_t n_users,
+                                const int64_t* users, const int64_t* pos, const int64_t* neg,
+                                const float* final_emb, int64_t ldf,
+                                const float* e0, int64_t lde,
+                                float lambda, float g_scale, float reg_scale,
+                                float* loss_out,
+                                float* g_final, int64_t ldg,
+                                float* reg_w,
+                                const int32_t* node_map,
+                                const float* logq /* [n_items], nullable */,
+                                void* ws, size_t ws_bytes, mi_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * a9  dense Adam step (torch.optim.Adam semantics, no weight decay, no amsgrad).
  * replaces: optimizer.step() at run_pipeline_lightgcn.py:159.
  *   g   = grad[i] + (reg_w ? reg_w[row(i)] * p[i] : 0)

@@ -287,6 +287,10 @@ _PROTOTYPES = {
     "mi_rank_loss_workspace_bytes": (c_size_t, [c_int64, c_int32]),
     "mi_rank_loss_fwd_bwd_f32": (c_int32, [c_int64, c_int32, c_int32, c_int64, c_int64, P, P, P, P, c_int64, P, c_int64,
                                            c_float, c_float, c_float, P, P, c_int64, P, P, P, c_size_t, P]),
+    "mi_sample_bpr_batch_pop": (c_int32, [c_int64, c_int32, c_int64, P, P, P, c_int64, P, c_int32, c_uint64, c_uint64,
+                                          P, P, P, P]),
+    "mi_rank_loss_fwd_bwd_lq_f32": (c_int32, [c_int64, c_int32, c_int32, c_int64, c_int64, P, P, P, P, c_int64, P, c_int64,
+                                              c_float, c_float, c_float, P, P, c_int64, P, P, P, P, c_size_t, P]),
     "mi_gemm_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64]),
     "mi_gemm_f32": (c_int32, [c_int32, c_int32, c_int64, c_int64, c_int64, P, c_int64, P, c_int64, P, P, c_int64,
                               c_int32, c_int32, P, c_size_t, P]),

@@ -2,6 +2,8 @@
 //   K9   mi_sample_bpr_batch   data/lightgcn_loader.py:95-112 (+ PyG structured_negative_sampling)
 //   a7/8 mi_bpr_fwd_bwd_f32    run_pipeline_lightgcn.py:133-155, utils/metrics_lightgcn.py:9-45
 //   a9   mi_adam_dense_f32     run_pipeline_lightgcn.py:157-159 (torch.optim.Adam)
+// and, not in the reference (SURVEY F9 behind a flag): the ranking objectives over M negatives (mi_rank_loss_fwd_bwd_f32),
+// popularity-weighted negatives (mi_sample_bpr_batch_pop) and the logQ-corrected softmax (mi_rank_loss_fwd_bwd_lq_f32).
 #include "common.hpp"
 #include <cmath>
 #include <rocprim/rocprim.hpp>
@@ -82,6 +84,45 @@ __global__ void sample_bpr_ex_kernel(int64_t batch, int n_neg, int64_t nnz, cons
         if (!hit && (quirk & 1) && cand == 0 && u > 0) hit = csr_contains(rowptr, col, u - 1, (int32_t)neg_range);
         if (!hit && (quirk & 2) && (int64_t)cand == u) hit = true;
         if (!hit) break;
+    }
+    if (m == 0) {
+        users[b] = u;
+        pos[b] = col[e];
+    }
+    neg[i] = cand;
+}
+
+// Popularity-weighted negatives (mi_sample_bpr_batch_pop): the counters of sample_bpr_ex_kernel, so users and pos carry
+// the uniform sampler's bits; the 64-bit draw is reduced mod total = cum[n_items - 1] and the candidate is the smallest i
+// with cum[i] > r, by bisection over cum in global memory (ceil(log2 n_items) dependent loads; 400 KB at 100 K items).
+// r < total = cum[n_items - 1], so the answer exists and lies in [lo, hi] throughout; items of weight 0 have
+// cum[i] == cum[i - 1] (or 0 at i = 0) and can never be the SMALLEST index above r.
+__global__ void sample_bpr_pop_kernel(int64_t batch, int n_neg, int64_t nnz, const int32_t* __restrict__ rowptr,
+                                      const int32_t* __restrict__ col, const int32_t* __restrict__ row_of_edge,
+                                      int32_t n_items, const uint32_t* __restrict__ cum, int32_t edges_in_order,
+                                      uint64_t seed, uint64_t step, int64_t* __restrict__ users,
+                                      int64_t* __restrict__ pos, int64_t* __restrict__ neg) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= batch * n_neg) return;
+    const int64_t b = i / n_neg;
+    const uint32_t m = (uint32_t)(i - b * n_neg);
+    const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+    const uint32_t s0 = (uint32_t)step, s1 = (uint32_t)(step >> 32);
+    MiPhilox r = mi_philox4x32((uint32_t)b, (uint32_t)((uint64_t)b >> 32), s0, s1 ^ kTagEdge, k0, k1);
+    const uint64_t e = edges_in_order ? (uint64_t)b : (((uint64_t)r.c[0] << 32) | r.c[1]) % (uint64_t)nnz;
+    const int64_t u = row_of_edge[e];
+    const uint32_t total = cum[n_items - 1];
+    int32_t cand = 0;
+    for (int t = 0; total != 0 && t < kMaxNegAttempts; ++t) {
+        MiPhilox q = mi_philox4x32((uint32_t)e, (uint32_t)t | (m << 16), s0, s1 ^ kTagNeg, k0, k1);
+        const uint32_t x = (uint32_t)((((uint64_t)q.c[0] << 32) | q.c[1]) % (uint64_t)total);
+        int32_t lo = 0, hi = n_items - 1;
+        while (lo < hi) {
+            const int32_t mid = lo + ((hi - lo) >> 1);
+            if (cum[mid] > x) hi = mid; else lo = mid + 1;
+        }
+        cand = lo;
+        if (!csr_contains(rowptr, col, u, cand)) break;
     }
     if (m == 0) {
         users[b] = u;
@@ -356,14 +397,16 @@ __device__ __forceinline__ float sigmoid_stable(float x) {
 
 // One wavefront per batch slot; the user's final row stays in registers (VPT = ceil(d / 64) floats per lane) while the
 // positive and the M negatives stream past it.  Lane m keeps s-_{b,m}: scalars only, nothing indexed by m.
-template <int VPT>
+// LQ (mi_rank_loss_fwd_bwd_lq_f32, softmax only): the logits are s+_b - logq[pos_b] and s-_{b,m} - logq[neg_{b,m}], one
+// fp32 subtraction each after the wave sums; LQ = false compiles to the kernel of before.
+template <int VPT, bool LQ>
 __global__ __launch_bounds__(kBlock) void rank_slot_kernel(
     int64_t batch, int n_neg, int objective, int d, int64_t n_users, const int64_t* __restrict__ users,
     const int64_t* __restrict__ pos, const int64_t* __restrict__ neg, const float* __restrict__ fin, int64_t ldf,
     const float* __restrict__ e0, int64_t lde, float inv_count, float g_scale, float reg_coef,
     float* __restrict__ term_out /* minus the slot's loss term, before the mean */, float* __restrict__ reg_out,
     float* __restrict__ coef_out, float* __restrict__ reg_w /* only when no gradient pass follows */,
-    const int32_t* __restrict__ node_map) {
+    const int32_t* __restrict__ node_map, const float* __restrict__ logq /* [n_items], by item id; LQ only */) {
     const int64_t b = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / MI_WAVE;
     if (b >= batch) return;
     const int lane = mi_lane();
@@ -405,6 +448,10 @@ __global__ __launch_bounds__(kBlock) void rank_slot_kernel(
     }
     rg = mi_wave_sum(rg);
     const bool mine = lane < n_neg;
+    if (LQ) {   // constant per logit: the coefficient formulas below keep their form
+        sp -= logq[pos[b]];
+        if (mine) my_sn -= logq[neg[b * n_neg + lane]];
+    }
     float term, a, dm;   // term: wave-uniform; a = coef[b][0]: wave-uniform; dm = coef[b][1 + lane]
     if (objective == kRankSoftmax) {
         float mx = sp;
@@ -728,6 +775,21 @@ int mi_sample_bpr_batch_ex(int64_t batch, int32_t n_neg, int64_t nnz, const int3
     return mi_launch_status();
 }
 
+int mi_sample_bpr_batch_pop(int64_t batch, int32_t n_neg, int64_t nnz, const int32_t* rowptr, const int32_t* col,
+                            const int32_t* row_of_edge, int64_t n_items, const uint32_t* cum, int32_t edges_in_order,
+                            uint64_t seed, uint64_t step, int64_t* users, int64_t* pos, int64_t* neg, mi_stream_t stream) {
+    if (n_neg > kMaxNeg) return MI_ERR_UNSUPPORTED;
+    MI_CHECK_ARG(n_neg >= 1 && batch >= 1 && nnz >= 1 && n_items >= 1 && (!edges_in_order || batch <= nnz));
+    MI_CHECK_ARG(rowptr && col && row_of_edge && cum && users && pos && neg);
+    MI_CHECK_ARG(((uintptr_t)rowptr | (uintptr_t)col | (uintptr_t)row_of_edge | (uintptr_t)cum) % 4 == 0);
+    MI_CHECK_ARG(((uintptr_t)users | (uintptr_t)pos | (uintptr_t)neg) % 8 == 0);
+    if (nnz >= INT32_MAX || n_items > INT32_MAX) return MI_ERR_TOO_LARGE;
+    dim3 g((unsigned)mi_ceil_div(batch * n_neg, kBlock));
+    hipLaunchKernelGGL(sample_bpr_pop_kernel, g, dim3(kBlock), 0, (hipStream_t)stream, batch, (int)n_neg, nnz, rowptr, col,
+                       row_of_edge, (int32_t)n_items, cum, edges_in_order, seed, step, users, pos, neg);
+    return mi_launch_status();
+}
+
 size_t mi_batch_nodes_workspace_bytes(int64_t n_nodes) {
     const size_t n1 = (size_t)(n_nodes > 0 ? n_nodes : 0) + 1;
     return 2 * mi_align_up(n1 * sizeof(int32_t), 256) + ((size_t)16 << 20);
@@ -891,13 +953,17 @@ size_t mi_rank_loss_workspace_bytes(int64_t batch, int32_t n_neg) {
            2 * mi_align_up(chunks * 512 * sizeof(float), 256);
 }
 
-int mi_rank_loss_fwd_bwd_f32(int64_t batch, int32_t n_neg, int32_t objective, int64_t d, int64_t n_users,
-                             const int64_t* users, const int64_t* pos, const int64_t* neg, const float* final_emb,
-                             int64_t ldf, const float* e0, int64_t lde, float lambda, float g_scale, float reg_scale,
-                             float* loss_out, float* g_final, int64_t ldg, float* reg_w, const int32_t* node_map,
-                             void* ws, size_t ws_bytes, mi_stream_t stream) {
+// both entries; logq == nullptr launches what mi_rank_loss_fwd_bwd_f32 always launched
+static int rank_loss_run(int64_t batch, int32_t n_neg, int32_t objective, int64_t d, int64_t n_users,
+                         const int64_t* users, const int64_t* pos, const int64_t* neg, const float* final_emb,
+                         int64_t ldf, const float* e0, int64_t lde, float lambda, float g_scale, float reg_scale,
+                         float* loss_out, float* g_final, int64_t ldg, float* reg_w, const int32_t* node_map,
+                         const float* logq, void* ws, size_t ws_bytes, mi_stream_t stream) {
     if (n_neg < 1 || n_neg > kMaxNeg) return MI_ERR_UNSUPPORTED;
     if (objective != kRankReference && objective != kRankBpr && objective != kRankSoftmax) return MI_ERR_UNSUPPORTED;
+    if (logq && objective != kRankSoftmax) return MI_ERR_UNSUPPORTED;
+    // the loss-only form accumulates reg_w with float atomics in the slot pass: not on the corrected path
+    if (logq && !g_final && reg_w) return MI_ERR_UNSUPPORTED;
     MI_CHECK_ARG(batch > 0 && d > 0 && n_users >= 0);
     MI_CHECK_ARG(users && pos && neg && final_emb && e0 && loss_out && ws);
     MI_CHECK_ARG(ldf >= d && lde >= d && (!g_final || ldg >= d));
@@ -923,14 +989,21 @@ int mi_rank_loss_fwd_bwd_f32(int64_t batch, int32_t n_neg, int32_t objective, in
     const float inv_count = 1.0f / (float)(objective == kRankSoftmax ? batch : batch * n_neg);
     const int vpt = d <= 64 ? 1 : (d <= 128 ? 2 : (d <= 256 ? 4 : 8));
     dim3 g((unsigned)mi_ceil_div(batch * MI_WAVE, kBlock));
-#define MI_RANK_SLOT(V)                                                                                                    \
-    hipLaunchKernelGGL(rank_slot_kernel<V>, g, dim3(kBlock), 0, s, batch, (int)n_neg, (int)objective, (int)d, n_users,      \
-                       users, pos, neg, final_emb, ldf, e0, lde, inv_count, g_scale, reg_scale * lambda, termv, rgv,        \
-                       g_final ? coef : nullptr, g_final ? nullptr : reg_w, node_map)
-    if (vpt == 1) MI_RANK_SLOT(1);
-    else if (vpt == 2) MI_RANK_SLOT(2);
-    else if (vpt == 4) MI_RANK_SLOT(4);
-    else MI_RANK_SLOT(8);
+#define MI_RANK_SLOT(V, LQ)                                                                                                \
+    hipLaunchKernelGGL((rank_slot_kernel<V, LQ>), g, dim3(kBlock), 0, s, batch, (int)n_neg, (int)objective, (int)d,         \
+                       n_users, users, pos, neg, final_emb, ldf, e0, lde, inv_count, g_scale, reg_scale * lambda, termv,    \
+                       rgv, g_final ? coef : nullptr, g_final ? nullptr : reg_w, node_map, logq)
+    if (logq) {
+        if (vpt == 1) MI_RANK_SLOT(1, true);
+        else if (vpt == 2) MI_RANK_SLOT(2, true);
+        else if (vpt == 4) MI_RANK_SLOT(4, true);
+        else MI_RANK_SLOT(8, true);
+    } else {
+        if (vpt == 1) MI_RANK_SLOT(1, false);
+        else if (vpt == 2) MI_RANK_SLOT(2, false);
+        else if (vpt == 4) MI_RANK_SLOT(4, false);
+        else MI_RANK_SLOT(8, false);
+    }
 #undef MI_RANK_SLOT
     if (g_final) {
         hipLaunchKernelGGL(rank_refs_kernel, dim3((unsigned)mi_ceil_div(n_ref, 256)), dim3(256), 0, s, batch, (int)n_neg,
@@ -963,6 +1036,24 @@ int mi_rank_loss_fwd_bwd_f32(int64_t batch, int32_t n_neg, int32_t objective, in
     // the slot terms are stored negated, so every objective closes with loss = -sum(term) / count + lambda * sum(reg)
     hipLaunchKernelGGL(bpr_finish_kernel, dim3(1), dim3(1024), 0, s, batch, termv, rgv, inv_count, lambda, loss_out);
     return mi_launch_status();
+}
+
+int mi_rank_loss_fwd_bwd_f32(int64_t batch, int32_t n_neg, int32_t objective, int64_t d, int64_t n_users,
+                             const int64_t* users, const int64_t* pos, const int64_t* neg, const float* final_emb,
+                             int64_t ldf, const float* e0, int64_t lde, float lambda, float g_scale, float reg_scale,
+                             float* loss_out, float* g_final, int64_t ldg, float* reg_w, const int32_t* node_map,
+                             void* ws, size_t ws_bytes, mi_stream_t stream) {
+    return rank_loss_run(batch, n_neg, objective, d, n_users, users, pos, neg, final_emb, ldf, e0, lde, lambda, g_scale,
+                         reg_scale, loss_out, g_final, ldg, reg_w, node_map, nullptr, ws, ws_bytes, stream);
+}
+
+int mi_rank_loss_fwd_bwd_lq_f32(int64_t batch, int32_t n_neg, int32_t objective, int64_t d, int64_t n_users,
+                                const int64_t* users, const int64_t* pos, const int64_t* neg, const float* final_emb,
+                                int64_t ldf, const float* e0, int64_t lde, float lambda, float g_scale, float reg_scale,
+                                float* loss_out, float* g_final, int64_t ldg, float* reg_w, const int32_t* node_map,
+                                const float* logq, void* ws, size_t ws_bytes, mi_stream_t stream) {
+    return rank_loss_run(batch, n_neg, objective, d, n_users, users, pos, neg, final_emb, ldf, e0, lde, lambda, g_scale,
+                         reg_scale, loss_out, g_final, ldg, reg_w, node_map, logq, ws, ws_bytes, stream);
 }
 
 int mi_adam_dense_f32(int64_t n_rows, int64_t d, float* p, int64_t ldp, const float* grad,

@@ -811,14 +811,87 @@ def rank_objective_code(objective: str) -> int:
     return _lib.MI_RANK_OBJECTIVES[objective]
 
 
+@dataclass
+class NegativeTable:
+    """The proposal of the popularity-weighted negative sampler (include/laplace_hip.h, "Popularity-weighted negatives"):
+    item i is drawn with probability q_i / total.  cum holds the uint32 running sums of q as an int32 tensor of the same
+    bits (torch has no uint32 arithmetic; nothing here computes on it); logq[i] = log(max(q_i, 1) / total) in fp32."""
+    cum: Tensor
+    logq: Tensor
+    total: int
+    power: Optional[float]
+    n_items: int
+
+
+def negative_counts(item_degree, power: float):
+    """The integer weights q of the header's rule from item degrees, on the host in float64 (set-up, not a hot path):
+    w = deg ** power where deg > 0, q = max(1, floor(w / sum(w) * 2^31)) there and 0 elsewhere."""
+    import numpy as np
+    if isinstance(power, bool) or not isinstance(power, (int, float)) or not 0.0 <= float(power) <= 1.0:
+        raise ValueError(f"power must be a number in [0, 1], got {power!r}")
+    deg = item_degree.detach().cpu().numpy() if isinstance(item_degree, Tensor) else np.asarray(item_degree)
+    if deg.ndim != 1 or deg.shape[0] < 1 or deg.shape[0] >= 2**31:
+        raise ValueError("item_degree: one degree per item, 1 <= n_items < 2^31")
+    deg = deg.astype(np.float64)
+    if not np.all(np.isfinite(deg)) or (deg < 0).any():
+        raise ValueError("item_degree: finite degrees >= 0 expected")
+    has = deg > 0
+    if not has.any():
+        raise ValueError("item_degree: every item has degree 0, nothing to draw from")
+    w = np.where(has, np.power(np.where(has, deg, 1.0), float(power)), 0.0)
+    s = float(np.cumsum(w)[-1])   # the sum in index order (np.sum adds pairwise)
+    return np.where(has, np.maximum(1.0, np.floor(w / s * 2.0 ** 31)), 0.0).astype(np.int64)
+
+
+def negative_table_from_counts(q, device, power: Optional[float] = None) -> NegativeTable:
+    """NegativeTable from given integer weights q [n_items] (all >= 0, 0 < sum < 2^32)."""
+    import numpy as np
+    q = q.detach().cpu().numpy() if isinstance(q, Tensor) else np.asarray(q)
+    if q.ndim != 1 or q.shape[0] < 1 or q.shape[0] >= 2**31 or q.dtype.kind not in "iu":
+        raise ValueError("q: a 1-D integer array, 1 <= n_items < 2^31")
+    q = q.astype(np.int64)
+    if (q < 0).any():
+        raise ValueError("q: weights >= 0 expected")
+    cum = np.cumsum(q)
+    total = int(cum[-1])
+    if total <= 0:
+        raise ValueError("q: every weight is 0, nothing to draw from")
+    if total >= 2**32:
+        raise ValueError(f"q: total weight {total} does not fit 32 bits")
+    logq = np.log(np.maximum(q, 1).astype(np.float64) / float(total)).astype(np.float32)
+    return NegativeTable(cum=t.from_numpy(cum.astype(np.uint32).view(np.int32)).to(device),
+                         logq=t.from_numpy(logq).to(device), total=total, power=power, n_items=int(q.shape[0]))
+
+
+def negative_table(item_degree, power: float = 0.75, device=None) -> NegativeTable:
+    """Negatives drawn ∝ degree ** power (0 = uniform over the items that have a degree, 1 = ∝ degree; 0.75 is the usual
+    choice).  item_degree: degrees in the TRAINING interactions, in the id space the sampler's CSR uses.  device: where the
+    table lives (default: item_degree's if it is a tensor, else "cuda")."""
+    q = negative_counts(item_degree, power)
+    if device is None:
+        device = item_degree.device if isinstance(item_degree, Tensor) else "cuda"
+    return negative_table_from_counts(q, device, power=float(power))
+
+
 def sample_bpr_batch(r: DeviceCSR, row_of_edge: Tensor, batch: int, neg_range: int, seed: int, step: int,
                      quirk: bool = False, out: Optional[Tuple[Tensor, Tensor, Tensor]] = None,
-                     edges_in_order: bool = False, no_self_loops: bool = False, n_neg: int = 1
-                     ) -> Tuple[Tensor, Tensor, Tensor]:
+                     edges_in_order: bool = False, no_self_loops: bool = False, n_neg: int = 1,
+                     table: Optional[NegativeTable] = None) -> Tuple[Tensor, Tensor, Tensor]:
     """K9 — replaces sample_mini_batch (data/lightgcn_loader.py:95-112) on device.  quirk: the reference's key
     collision; no_self_loops: structured_negative_sampling(contains_neg_self_loops=False) — never negative id == user id.
-    n_neg > 1: neg is [batch, n_neg], independent draws per slot whose column 0 is the n_neg = 1 result."""
+    n_neg > 1: neg is [batch, n_neg], independent draws per slot whose column 0 is the n_neg = 1 result.
+    table: negatives drawn from the table's proposal instead of uniformly (mi_sample_bpr_batch_pop); users and pos are
+    the uniform sampler's at the same (seed, step).  neg_range must be the table's n_items; no quirk bits."""
     check_n_neg(n_neg)
+    if table is not None:
+        if not isinstance(table, NegativeTable):
+            raise TypeError(f"table: expected a NegativeTable, got {type(table)}")
+        if int(neg_range) != table.n_items:
+            raise ValueError(f"neg_range {neg_range} differs from the table's n_items {table.n_items}")
+        if quirk or no_self_loops:
+            raise ValueError("a negative table does not combine with quirk / no_self_loops")
+        if batch < 1:
+            raise ValueError("batch must be positive")
     if r.nnz == 0:
         raise ValueError("cannot sample from an empty edge set")
     if neg_range <= 0:
@@ -829,7 +902,19 @@ def sample_bpr_batch(r: DeviceCSR, row_of_edge: Tensor, batch: int, neg_range: i
                t.empty(batch if n_neg == 1 else (batch, n_neg), dtype=t.int64, device=dev))
     users, pos, neg = out
     quirks = (1 if quirk else 0) | (2 if no_self_loops else 0)
-    if n_neg == 1:
+    if table is not None:
+        _need(table.cum, t.int32, "table.cum")
+        for n, x in (("users", users), ("pos", pos), ("neg", neg)):
+            _need(x, t.int64, "out: " + n)
+        if table.cum.numel() != table.n_items:
+            raise ValueError("table: cum must hold n_items words")
+        if users.numel() != batch or pos.numel() != batch or neg.numel() != batch * n_neg:
+            raise ValueError("out: users [batch], pos [batch], neg [batch * n_neg] expected")
+        check(_lib.lib().mi_sample_bpr_batch_pop(batch, n_neg, r.nnz, _ptr(r.rowptr), _ptr(r.col), _ptr(row_of_edge),
+                                                 table.n_items, _ptr(table.cum), 1 if edges_in_order else 0,
+                                                 int(seed) & (2**64 - 1), int(step) & (2**64 - 1), _ptr(users),
+                                                 _ptr(pos), _ptr(neg), _stream()), "mi_sample_bpr_batch_pop")
+    elif n_neg == 1:
         check(_lib.lib().mi_sample_bpr_batch(batch, r.nnz, _ptr(r.rowptr), _ptr(r.col), _ptr(row_of_edge),
                                              int(neg_range), quirks,
                                              1 if edges_in_order else 0,
@@ -875,9 +960,14 @@ def bpr_fwd_bwd(users: Tensor, pos: Tensor, neg: Tensor, final_emb: Tensor, e0: 
 def rank_loss_fwd_bwd(users: Tensor, pos: Tensor, neg: Tensor, final_emb: Tensor, e0: Tensor, n_users: int,
                       lambda_val: float, *, objective: str = "reference", g_final: Optional[Tensor] = None,
                       reg_w: Optional[Tensor] = None, g_scale: float = 1.0, reg_scale: float = 1.0,
-                      loss_out: Optional[Tensor] = None, node_map: Optional[Tensor] = None) -> Tensor:
-    """bpr_fwd_bwd with a choice of objective ("reference", "bpr", "softmax") and neg [B] or [B, M], M <= 16."""
+                      loss_out: Optional[Tensor] = None, node_map: Optional[Tensor] = None,
+                      logq: Optional[Tensor] = None) -> Tensor:
+    """bpr_fwd_bwd with a choice of objective ("reference", "bpr", "softmax") and neg [B] or [B, M], M <= 16.
+    logq (float32, one entry per item of e0, addressed by item id): the logQ correction of the sampled softmax —
+    the logits become s - logq[item] (mi_rank_loss_fwd_bwd_lq_f32); "softmax" only, and with g_final or without reg_w."""
     code = rank_objective_code(objective)
+    if logq is not None and objective != "softmax":
+        raise ValueError(f"logq corrects the sampled softmax only, not objective={objective!r}")
     batch = users.numel()
     if pos.numel() != batch or neg.dim() not in (1, 2) or neg.shape[0] != batch:
         raise ValueError("users [B], pos [B], neg [B] or [B, M] expected")
@@ -895,10 +985,22 @@ def rank_loss_fwd_bwd(users: Tensor, pos: Tensor, neg: Tensor, final_emb: Tensor
         loss_out = t.empty(1, dtype=t.float32, device=dev)
     L = _lib.lib()
     ws = _ws(L.mi_rank_loss_workspace_bytes(batch, n_neg), dev)
-    check(L.mi_rank_loss_fwd_bwd_f32(batch, n_neg, code, d, n_users, _ptr(users), _ptr(pos), _ptr(neg),
-                                     final_emb.data_ptr(), ldf, e0.data_ptr(), lde, float(lambda_val), float(g_scale),
-                                     float(reg_scale), loss_out.data_ptr(), _ptr(g_final), ldg, _ptr(reg_w),
-                                     _ptr(node_map), ws.data_ptr(), ws.numel(), _stream()), "mi_rank_loss_fwd_bwd_f32")
+    if logq is None:
+        check(L.mi_rank_loss_fwd_bwd_f32(batch, n_neg, code, d, n_users, _ptr(users), _ptr(pos), _ptr(neg),
+                                         final_emb.data_ptr(), ldf, e0.data_ptr(), lde, float(lambda_val), float(g_scale),
+                                         float(reg_scale), loss_out.data_ptr(), _ptr(g_final), ldg, _ptr(reg_w),
+                                         _ptr(node_map), ws.data_ptr(), ws.numel(), _stream()), "mi_rank_loss_fwd_bwd_f32")
+        return loss_out
+    _need(logq, t.float32, "logq")
+    if logq.dim() != 1 or logq.numel() != e0.shape[0] - n_users:
+        raise ValueError(f"logq: one entry per item expected ({e0.shape[0] - n_users}), got shape {tuple(logq.shape)}")
+    if g_final is None and reg_w is not None:
+        raise ValueError("logq: the loss-only form takes no reg_w (pass g_final, or leave reg_w out)")
+    check(L.mi_rank_loss_fwd_bwd_lq_f32(batch, n_neg, code, d, n_users, _ptr(users), _ptr(pos), _ptr(neg),
+                                        final_emb.data_ptr(), ldf, e0.data_ptr(), lde, float(lambda_val), float(g_scale),
+                                        float(reg_scale), loss_out.data_ptr(), _ptr(g_final), ldg, _ptr(reg_w),
+                                        _ptr(node_map), logq.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
+          "mi_rank_loss_fwd_bwd_lq_f32")
     return loss_out
 
 

@@ -39,7 +39,8 @@ def evaluation(model: LightGCN, edge_index: Tensor, sparse_edge_index: SparseTen
                ) -> Tuple[float, float, float, float]:
     """loss over every edge of the split (one structured negative each) on the split's own
     adjacency, plus recall / precision / ndcg @ k (run_pipeline_lightgcn.py:20-73).  objective: the loss's form
-    (default: the reference's); embeddings: the tables the ranking metrics score with (default: layer 0)."""
+    (default: the reference's); embeddings: the tables the ranking metrics score with (default: layer 0).
+    The negatives are uniform and the loss carries no logQ correction whatever sampler the training run used."""
     with t.no_grad():
         users_final, users_0, items_final, items_0 = model.forward(sparse_edge_index)
         n_users, n_items = model.num_users, model.num_items
@@ -58,10 +59,15 @@ def evaluation(model: LightGCN, edge_index: Tensor, sparse_edge_index: SparseTen
 
 def train(config: LightGCNConfig = lightgcn_config, *, edge_index: Tensor, num_users: int, num_articles: int,
           compat: str = "reference", device: str = "cuda", seed: int = 0, save_dir: Optional[str] = None,
-          verbose: bool = True, objective: str = "reference", n_neg: int = 1, predictor: str = "layer0") -> Stats:
+          verbose: bool = True, objective: str = "reference", n_neg: int = 1, predictor: str = "layer0",
+          negatives: str = "uniform", neg_power: float = 0.75) -> Stats:
     """objective / n_neg: the training loss (trainer.LightGCNTrainer).  predictor="propagated": evaluation,
     the ranking metrics and the saved predictions score with mean_k(A^k E0) of the training adjacency — the scores the
-    loss trains — instead of the layer-0 tables."""
+    loss trains — instead of the layer-0 tables.
+    negatives="popularity": training negatives drawn ∝ (training degree) ** neg_power over every item, with the logQ
+    correction when objective == "softmax"; the reference's negative range and sampler quirk do not apply to that
+    sampler and are left out.  evaluation() keeps its uniform negatives and uncorrected loss in every case, so
+    validation and test losses stay comparable across samplers."""
     if predictor not in PREDICTORS:
         raise ValueError(f"predictor must be one of {PREDICTORS}, got {predictor!r}")
     if verbose:
@@ -75,9 +81,12 @@ def train(config: LightGCNConfig = lightgcn_config, *, edge_index: Tensor, num_u
     model.train()
     train_inter = Interactions(train_edges, num_users, num_articles)
     # reference sampler: negatives from [0, max train item id) with its key-collision quirk
+    popular = negatives == "popularity"
     trainer = LightGCNTrainer(model, train_sparse, train_inter, lr=config.learning_rate, Lambda=config.Lambda,
-                              batch_size=config.batch_size, seed=seed, neg_range=int(train_edges[1].max()),
-                              reference_sampler_quirks=(compat == "reference"), objective=objective, n_neg=n_neg)
+                              batch_size=config.batch_size, seed=seed,
+                              neg_range=None if popular else int(train_edges[1].max()),
+                              reference_sampler_quirks=(compat == "reference" and not popular), objective=objective,
+                              n_neg=n_neg, negatives=negatives, neg_power=neg_power)
 
     def scoring_tables():
         return propagated_embeddings(model, train_sparse) if predictor == "propagated" else None

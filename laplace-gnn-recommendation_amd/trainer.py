@@ -4,7 +4,8 @@ the GPU and no host round trip.
     forward   K fused SpMM launches (layer sum in the epilogue)      model/lightgcn.py:46-80
     sample    B edges + structured negatives on device               data/lightgcn_loader.py:95-112
     loss      gathers + BPR forward/backward in one kernel           run_pipeline_lightgcn.py:133-155
-              (objective="bpr" / "softmax" and n_neg = M <= 16 negatives per positive: opt-in)
+              (objective="bpr" / "softmax" and n_neg = M <= 16 negatives per positive: opt-in, SURVEY F9;
+               negatives="popularity": negatives drawn ∝ degree ** neg_power, and with the softmax the logQ correction)
     backward  K SpMM launches on A^T, G/(K+1) folded in as addend    (autograd of the forward)
     update    dense Adam over the whole table, L2 term folded in     run_pipeline_lightgcn.py:157-159
 
@@ -42,6 +43,7 @@ columns are renamed): equal to rounding, and still bitwise reproducible run to r
 """
 from __future__ import annotations
 
+import math
 from typing import Optional, Tuple
 
 import torch as t
@@ -58,15 +60,36 @@ def _lib_bytes_batch_nodes(n_nodes: int) -> int:
     return int(_lib.lib().mi_batch_nodes_workspace_bytes(n_nodes))
 
 
+NEGATIVES = ("uniform", "popularity")
+
+
 class LightGCNTrainer:
     def __init__(self, model: LightGCN, adj: SparseTensor, train: Interactions, *, lr: float, Lambda: float,
                  batch_size: int, betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8, seed: int = 0,
                  neg_range: Optional[int] = None, reference_sampler_quirks: bool = False,
                  sparse_batch: bool = True, fuse_adam: bool = True, reorder: Optional[bool] = None,
-                 objective: str = "reference", n_neg: int = 1):
+                 objective: str = "reference", n_neg: int = 1, negatives: str = "uniform", neg_power: float = 0.75,
+                 logq_correction: Optional[bool] = None):
+        """negatives="popularity": negatives drawn ∝ (training degree) ** neg_power from `neg_table`, built in the id space
+        the kernels train in.  logq_correction: the softmax's logits become s - log q(item); None = on iff
+        objective == "softmax" and negatives == "popularity".  The defaults launch the step as it was."""
         ops.rank_objective_code(objective)   # ValueError for an unknown name
         ops.check_n_neg(n_neg)
+        if negatives not in NEGATIVES:
+            raise ValueError(f"negatives must be one of {NEGATIVES}, got {negatives!r}")
+        if isinstance(neg_power, bool) or not isinstance(neg_power, (int, float)) or not 0.0 <= neg_power <= 1.0:
+            raise ValueError(f"neg_power must be a number in [0, 1], got {neg_power!r}")
+        if logq_correction is None:
+            logq_correction = objective == "softmax" and negatives == "popularity"
+        elif logq_correction and objective != "softmax":
+            raise ValueError(f"logq_correction corrects the sampled softmax, not objective={objective!r}")
+        if negatives == "popularity":
+            if reference_sampler_quirks:
+                raise ValueError('negatives="popularity" does not combine with reference_sampler_quirks')
+            if neg_range is not None and int(neg_range) != model.num_items:
+                raise ValueError(f'negatives="popularity" draws from every item: neg_range {neg_range} != {model.num_items}')
         self.objective, self.n_neg = objective, n_neg
+        self.negatives, self.neg_power, self.logq_correction = negatives, float(neg_power), bool(logq_correction)
         self.model = model
         self.table = model.table()
         if not self.table.is_cuda:
@@ -128,6 +151,14 @@ class LightGCNTrainer:
         self.step_count = 0
         self._r = train.csr()
         self._row_of_edge = train.row_of_edge()
+        # the proposal of the negatives and its log, by TRAINING id (`train` is already relabelled here)
+        self.neg_table, self.logq = None, None
+        if self.negatives == "popularity":
+            degree = t.bincount(self._r.col.long(), minlength=train.num_items)
+            self.neg_table = ops.negative_table(degree, self.neg_power, device=dev)
+        if self.logq_correction:   # uniform negatives: q = 1 / neg_range for every item
+            self.logq = (self.neg_table.logq if self.neg_table is not None
+                         else t.full((train.num_items,), -math.log(self.neg_range), dtype=t.float32, device=dev))
 
     # -- locality order --------------------------------------------------------------------------
     def to_training_order(self) -> None:
@@ -159,12 +190,18 @@ class LightGCNTrainer:
         return propagate_mean(self.adj_fwd, self.table, self.K, out=self.final, scratch=(self.buf_a, self.buf_b))
 
     def _sample(self) -> Tuple[Tensor, Tensor, Tensor]:
+        if self.neg_table is not None:
+            return ops.sample_bpr_batch(self._r, self._row_of_edge, self.batch_size, self.neg_range, self.seed,
+                                        self.step_count, out=self.batch_idx, n_neg=self.n_neg, table=self.neg_table)
         return ops.sample_bpr_batch(self._r, self._row_of_edge, self.batch_size, self.neg_range, self.seed,
                                     self.step_count, quirk=self.quirk, out=self.batch_idx, n_neg=self.n_neg)
 
     def _loss(self, users, pos, neg, final, **kw) -> None:
         """Loss and its gradient on `final`; the default objective keeps the one-negative entry (same launches, same bits)."""
-        if self.objective == "reference" and self.n_neg == 1:
+        if self.logq is not None:
+            ops.rank_loss_fwd_bwd(users, pos, neg, final, self.table, self.model.num_users, self.Lambda,
+                                  objective=self.objective, reg_w=self.reg_w, loss_out=self.loss, logq=self.logq, **kw)
+        elif self.objective == "reference" and self.n_neg == 1:
             ops.bpr_fwd_bwd(users, pos, neg, final, self.table, self.model.num_users, self.Lambda, reg_w=self.reg_w,
                             loss_out=self.loss, **kw)
         else:

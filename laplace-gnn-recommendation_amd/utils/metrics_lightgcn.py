@@ -55,7 +55,7 @@ class _RankingLossFn(t.autograd.Function):
     (users | positives | negatives, slot-major) addressed by arange, as in _BprLossFn."""
 
     @staticmethod
-    def forward(ctx, uf, u0, pf, p0, nf, n0, lambda_val: float, objective: str):
+    def forward(ctx, uf, u0, pf, p0, nf, n0, lambda_val: float, objective: str, logq: Optional[Tensor] = None):
         B, D = uf.shape
         M = nf.shape[1]
         final = t.cat([uf, pf, nf.reshape(B * M, D)]).contiguous()
@@ -66,7 +66,7 @@ class _RankingLossFn(t.autograd.Function):
         g_final = t.zeros_like(final)
         reg_w = t.zeros((2 + M) * B, device=dev)
         loss = ops.rank_loss_fwd_bwd(users, users, neg, final, e0, B, lambda_val, objective=objective, g_final=g_final,
-                                     reg_w=reg_w)
+                                     reg_w=reg_w, logq=logq)
         ctx.save_for_backward(g_final, reg_w, e0)
         ctx.dims = (B, M, D)
         return loss.reshape(())
@@ -78,24 +78,37 @@ class _RankingLossFn(t.autograd.Function):
         gf = g_final * grad_out
         g0 = (reg_w[:, None] * e0) * grad_out
         return (gf[:B], g0[:B], gf[B:2 * B], g0[B:2 * B], gf[2 * B:].reshape(B, M, D), g0[2 * B:].reshape(B, M, D),
-                None, None)
+                None, None, None)
 
 
 def ranking_loss(users_emb_final: Tensor, users_emb_0: Tensor, pos_items_emb_final: Tensor, pos_items_emb_0: Tensor,
                  neg_items_emb_final: Tensor, neg_items_emb_0: Tensor, lambda_val: float,
-                 objective: str = "reference") -> Tensor:
+                 objective: str = "reference", logq: Optional[Tuple[Tensor, Tensor]] = None) -> Tensor:
     """bpr_loss with a choice of objective and M negatives per positive (negatives [B, D] or [B, M, D], M <= 16):
     "reference" -mean softplus(x) as the reference writes it, "bpr" -mean log sigmoid(x), "softmax" the sampled softmax
-    over (positive, negatives); x = <u, p> - <u, n>.  The L2 term is the reference's sum form over all 2 + M rows."""
+    over (positive, negatives); x = <u, p> - <u, n>.  The L2 term is the reference's sum form over all 2 + M rows.
+    logq = (pos_logq [B], neg_logq [B] or [B, M]), float32 constants (no gradient): the softmax's logits become
+    <u, p> - pos_logq and <u, n> - neg_logq, the logQ correction of negatives drawn from a proposal q."""
     ops.rank_objective_code(objective)
+    if logq is not None and objective != "softmax":
+        raise ValueError(f"logq corrects the sampled softmax only, not objective={objective!r}")
     if neg_items_emb_final.dim() not in (2, 3) or neg_items_emb_0.shape != neg_items_emb_final.shape:
         raise ValueError("negatives: [B, D] or [B, M, D], the same shape for both tables")
     two_d = neg_items_emb_final.dim() == 2
     nf = neg_items_emb_final[:, None, :] if two_d else neg_items_emb_final
     n0 = neg_items_emb_0[:, None, :] if two_d else neg_items_emb_0
     ops.check_n_neg(int(nf.shape[1]))
+    if logq is None:
+        return _RankingLossFn.apply(users_emb_final, users_emb_0, pos_items_emb_final, pos_items_emb_0, nf, n0,
+                                    float(lambda_val), objective)
+    pos_logq, neg_logq = logq
+    B, M = int(nf.shape[0]), int(nf.shape[1])
+    if pos_logq.numel() != B or neg_logq.numel() != B * M:
+        raise ValueError(f"logq: pos_logq [{B}] and neg_logq [{B}, {M}] expected")
+    # the position-addressed table of _RankingLossFn: positives are items [0, B), negative (b, m) is item B + b M + m
+    table = t.cat([pos_logq.detach().reshape(B), neg_logq.detach().reshape(B * M)]).to(t.float32).contiguous()
     return _RankingLossFn.apply(users_emb_final, users_emb_0, pos_items_emb_final, pos_items_emb_0, nf, n0,
-                                float(lambda_val), objective)
+                                float(lambda_val), objective, table)
 
 
 # ----------------------------------------------------------------------------------------------
