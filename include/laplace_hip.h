@@ -337,7 +337,8 @@ int mi_scatter_rows_f32(int64_t n_max, const int32_t* n_dev, const int32_t* begi
 /* Unique node set of a BPR batch: gmap int32[n_nodes] = compact slot of node r (slots ordered by
  * node id) or -1; nodes int32[>= 3*batch] = slot -> node; count = device int32[2]:
  * count[0] = unique nodes, count[1] = unique USER nodes (their slots come first).
- * Users are nodes [0, n_users), item i is node n_users + i. */
+ * Users are nodes [0, n_users), item i is node n_users + i.
+ * mi_batch_nodes_i32 is mi_batch_nodes_ex_i32 (below) with n_neg = 1. */
 size_t mi_batch_nodes_workspace_bytes(int64_t n_nodes);
 int    mi_batch_nodes_i32(int64_t batch, int64_t n_users, int64_t n_nodes,
                           const int64_t* users, const int64_t* pos, const int64_t* neg,
@@ -365,6 +366,7 @@ int    mi_batch_nodes_i32(int64_t batch, int64_t n_users, int64_t n_nodes,
  * edges_in_order != 0: slot b takes edge b of the CSR instead of a random one (batch <= nnz) —
  * one negative per edge of a split, as evaluation() does (run_pipeline_lightgcn.py:40-44).
  * Outputs int64[B] each (the reference's index dtype).
+ * This entry is mi_sample_bpr_batch_ex with n_neg = 1 (below), kept for the boundary: same checks, same kernel.
  * ---------------------------------------------------------------------------------- */
 #define MI_SAMPLE_KEY_COLLISION 1
 #define MI_SAMPLE_NO_SELF_LOOPS 2
@@ -396,7 +398,10 @@ int mi_sample_bpr_batch(int64_t batch, int64_t nnz,
  * [count, d] tables addressed by node_map[node]; e0 and reg_w stay addressed by node id.
  * No float atomics on the gradient: the 3*batch row references are radix-sorted by row, summed in
  * 64-reference chunks in reference order and combined in chunk order, one writer per row — the
- * result is bitwise reproducible.  d <= 512.
+ * result is bitwise reproducible.  d <= 512, with or without g_final (MI_ERR_UNSUPPORTED beyond).
+ * This entry is the (MI_RANK_REFERENCE, n_neg = 1) case of mi_rank_loss_fwd_bwd_f32 (below), kept for the
+ * boundary: the same host path, kernels and bits, and mi_bpr_workspace_bytes(b) ==
+ * mi_rank_loss_workspace_bytes(b, 1).
  * ---------------------------------------------------------------------------------- */
 size_t mi_bpr_workspace_bytes(int64_t batch);
 int    mi_bpr_fwd_bwd_f32(int64_t batch, int64_t d, int64_t n_users,

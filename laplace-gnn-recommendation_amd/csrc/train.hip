@@ -4,6 +4,9 @@
 //   a9   mi_adam_dense_f32     run_pipeline_lightgcn.py:157-159 (torch.optim.Adam)
 // and, not in the reference (SURVEY F9 behind a flag): the ranking objectives over M negatives (mi_rank_loss_fwd_bwd_f32),
 // popularity-weighted negatives (mi_sample_bpr_batch_pop) and the logQ-corrected softmax (mi_rank_loss_fwd_bwd_lq_f32).
+// The reference's entries are the (MI_RANK_REFERENCE, one negative) case of the general ones and launch what those launch
+// at n_neg = 1: one sampler kernel, one marking kernel, one loss host path (rank_loss_run).  That case alone keeps two loss
+// kernels of its own, bpr_slot_kernel and bpr_chunk_kernel, because they are faster there.
 #include "common.hpp"
 #include <cmath>
 #include <rocprim/rocprim.hpp>
@@ -30,99 +33,66 @@ __device__ __forceinline__ bool csr_contains(const int32_t* __restrict__ rowptr,
     return lo < end && col[lo] == key;
 }
 
-__global__ void sample_bpr_kernel(int64_t batch, int64_t nnz, const int32_t* __restrict__ rowptr,
-                                  const int32_t* __restrict__ col,
-                                  const int32_t* __restrict__ row_of_edge, int64_t neg_range,
-                                  int32_t quirk, int32_t edges_in_order, uint64_t seed, uint64_t step,
-                                  int64_t* __restrict__ users, int64_t* __restrict__ pos,
-                                  int64_t* __restrict__ neg) {
-    const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= batch) return;
-    const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-    const uint32_t s0 = (uint32_t)step, s1 = (uint32_t)(step >> 32);
-    MiPhilox r = mi_philox4x32((uint32_t)b, (uint32_t)((uint64_t)b >> 32), s0, s1 ^ kTagEdge, k0, k1);
-    const uint64_t e = edges_in_order ? (uint64_t)b : (((uint64_t)r.c[0] << 32) | r.c[1]) % (uint64_t)nnz;
-    const int64_t u = row_of_edge[e];
-    const int32_t p = col[e];
-    int32_t cand = 0;
-    for (int t = 0; t < kMaxNegAttempts; ++t) {
-        MiPhilox q = mi_philox4x32((uint32_t)e, (uint32_t)t, s0, s1 ^ kTagNeg, k0, k1);
-        cand = (int32_t)((((uint64_t)q.c[0] << 32) | q.c[1]) % (uint64_t)neg_range);
-        bool hit = csr_contains(rowptr, col, u, cand);
+// One sampler kernel for the three entries, one thread per (slot, m).  Slot b takes edge e from the EDGE stream, counter
+// (b); negative m of edge e, attempt t, takes the counter (e, t | m << 16) of the NEG! stream (t < 4096 < 2^16), so users,
+// pos and column 0 of neg do not depend on n_neg, and the same edge drawn twice in a step gets the same negatives.  Draw
+// says how the 64-bit word becomes a candidate and which candidates are redrawn beyond the user's own items:
+//   modulus()      the word is reduced mod this; 0 = nothing to draw from, negative 0 for every slot
+//   candidate(x)   the item of x in [0, modulus)
+//   also_rejected  the draw's own rejection rules
+struct UniformDraw {   // mi_sample_bpr_batch, mi_sample_bpr_batch_ex: x is the item; the two quirk bits of the header
+    int64_t neg_range;
+    int32_t quirk;
+    __device__ uint64_t modulus() const { return (uint64_t)neg_range; }
+    __device__ int32_t candidate(uint64_t x) const { return (int32_t)x; }
+    __device__ bool also_rejected(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col, int64_t u,
+                                  int32_t cand) const {
         // reference key collision: (u-1, item neg_range) aliases (u, 0) in row*num_nodes+col
-        if (!hit && (quirk & 1) && cand == 0 && u > 0) hit = csr_contains(rowptr, col, u - 1, (int32_t)neg_range);
+        if ((quirk & 1) && cand == 0 && u > 0 && csr_contains(rowptr, col, u - 1, (int32_t)neg_range)) return true;
         // contains_neg_self_loops=False: the key u*num_nodes+u of every node u < num_nodes is in the rejection set too
-        if (!hit && (quirk & 2) && (int64_t)cand == u) hit = true;
-        if (!hit) break;
+        return (quirk & 2) && (int64_t)cand == u;
     }
-    users[b] = u;
-    pos[b] = p;
-    neg[b] = cand;
-}
+};
 
-// M negatives per slot (mi_sample_bpr_batch_ex): one thread per (slot, m).  Negative m of edge e, attempt t, takes the
-// counter (e, t | m << 16) of the NEG! stream (t < 4096 < 2^16), so column 0 is the one-negative sampler's draw.
-__global__ void sample_bpr_ex_kernel(int64_t batch, int n_neg, int64_t nnz, const int32_t* __restrict__ rowptr,
-                                     const int32_t* __restrict__ col, const int32_t* __restrict__ row_of_edge,
-                                     int64_t neg_range, int32_t quirk, int32_t edges_in_order, uint64_t seed,
-                                     uint64_t step, int64_t* __restrict__ users, int64_t* __restrict__ pos,
-                                     int64_t* __restrict__ neg) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= batch * n_neg) return;
-    const int64_t b = i / n_neg;
-    const uint32_t m = (uint32_t)(i - b * n_neg);
-    const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-    const uint32_t s0 = (uint32_t)step, s1 = (uint32_t)(step >> 32);
-    MiPhilox r = mi_philox4x32((uint32_t)b, (uint32_t)((uint64_t)b >> 32), s0, s1 ^ kTagEdge, k0, k1);
-    const uint64_t e = edges_in_order ? (uint64_t)b : (((uint64_t)r.c[0] << 32) | r.c[1]) % (uint64_t)nnz;
-    const int64_t u = row_of_edge[e];
-    int32_t cand = 0;
-    for (int t = 0; t < kMaxNegAttempts; ++t) {
-        MiPhilox q = mi_philox4x32((uint32_t)e, (uint32_t)t | (m << 16), s0, s1 ^ kTagNeg, k0, k1);
-        cand = (int32_t)((((uint64_t)q.c[0] << 32) | q.c[1]) % (uint64_t)neg_range);
-        bool hit = csr_contains(rowptr, col, u, cand);
-        if (!hit && (quirk & 1) && cand == 0 && u > 0) hit = csr_contains(rowptr, col, u - 1, (int32_t)neg_range);
-        if (!hit && (quirk & 2) && (int64_t)cand == u) hit = true;
-        if (!hit) break;
-    }
-    if (m == 0) {
-        users[b] = u;
-        pos[b] = col[e];
-    }
-    neg[i] = cand;
-}
-
-// Popularity-weighted negatives (mi_sample_bpr_batch_pop): the counters of sample_bpr_ex_kernel, so users and pos carry
-// the uniform sampler's bits; the 64-bit draw is reduced mod total = cum[n_items - 1] and the candidate is the smallest i
-// with cum[i] > r, by bisection over cum in global memory (ceil(log2 n_items) dependent loads; 400 KB at 100 K items).
-// r < total = cum[n_items - 1], so the answer exists and lies in [lo, hi] throughout; items of weight 0 have
-// cum[i] == cum[i - 1] (or 0 at i = 0) and can never be the SMALLEST index above r.
-__global__ void sample_bpr_pop_kernel(int64_t batch, int n_neg, int64_t nnz, const int32_t* __restrict__ rowptr,
-                                      const int32_t* __restrict__ col, const int32_t* __restrict__ row_of_edge,
-                                      int32_t n_items, const uint32_t* __restrict__ cum, int32_t edges_in_order,
-                                      uint64_t seed, uint64_t step, int64_t* __restrict__ users,
-                                      int64_t* __restrict__ pos, int64_t* __restrict__ neg) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= batch * n_neg) return;
-    const int64_t b = i / n_neg;
-    const uint32_t m = (uint32_t)(i - b * n_neg);
-    const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-    const uint32_t s0 = (uint32_t)step, s1 = (uint32_t)(step >> 32);
-    MiPhilox r = mi_philox4x32((uint32_t)b, (uint32_t)((uint64_t)b >> 32), s0, s1 ^ kTagEdge, k0, k1);
-    const uint64_t e = edges_in_order ? (uint64_t)b : (((uint64_t)r.c[0] << 32) | r.c[1]) % (uint64_t)nnz;
-    const int64_t u = row_of_edge[e];
-    const uint32_t total = cum[n_items - 1];
-    int32_t cand = 0;
-    for (int t = 0; total != 0 && t < kMaxNegAttempts; ++t) {
-        MiPhilox q = mi_philox4x32((uint32_t)e, (uint32_t)t | (m << 16), s0, s1 ^ kTagNeg, k0, k1);
-        const uint32_t x = (uint32_t)((((uint64_t)q.c[0] << 32) | q.c[1]) % (uint64_t)total);
+// Popularity-weighted negatives (mi_sample_bpr_batch_pop): the word is reduced mod total = cum[n_items - 1] and the
+// candidate is the smallest i with cum[i] > x, by bisection over cum in global memory (ceil(log2 n_items) dependent loads;
+// 400 KB at 100 K items).  x < total = cum[n_items - 1], so the answer exists and lies in [lo, hi] throughout; items of
+// weight 0 have cum[i] == cum[i - 1] (or 0 at i = 0) and can never be the SMALLEST index above x.
+struct PopularityDraw {
+    int32_t n_items;
+    const uint32_t* __restrict__ cum;
+    __device__ uint64_t modulus() const { return cum[n_items - 1]; }
+    __device__ int32_t candidate(uint64_t x) const {
         int32_t lo = 0, hi = n_items - 1;
         while (lo < hi) {
             const int32_t mid = lo + ((hi - lo) >> 1);
-            if (cum[mid] > x) hi = mid; else lo = mid + 1;
+            if (cum[mid] > (uint32_t)x) hi = mid; else lo = mid + 1;
         }
-        cand = lo;
-        if (!csr_contains(rowptr, col, u, cand)) break;
+        return lo;
+    }
+    __device__ bool also_rejected(const int32_t*, const int32_t*, int64_t, int32_t) const { return false; }
+};
+
+template <class Draw>
+__global__ void sample_batch_kernel(int64_t batch, int n_neg, int64_t nnz, const int32_t* __restrict__ rowptr,
+                                    const int32_t* __restrict__ col, const int32_t* __restrict__ row_of_edge, Draw draw,
+                                    int32_t edges_in_order, uint64_t seed, uint64_t step, int64_t* __restrict__ users,
+                                    int64_t* __restrict__ pos, int64_t* __restrict__ neg) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= batch * n_neg) return;
+    const int64_t b = i / n_neg;
+    const uint32_t m = (uint32_t)(i - b * n_neg);
+    const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+    const uint32_t s0 = (uint32_t)step, s1 = (uint32_t)(step >> 32);
+    MiPhilox r = mi_philox4x32((uint32_t)b, (uint32_t)((uint64_t)b >> 32), s0, s1 ^ kTagEdge, k0, k1);
+    const uint64_t e = edges_in_order ? (uint64_t)b : (((uint64_t)r.c[0] << 32) | r.c[1]) % (uint64_t)nnz;
+    const int64_t u = row_of_edge[e];
+    const uint64_t mod = draw.modulus();
+    int32_t cand = 0;
+    for (int t = 0; mod != 0 && t < kMaxNegAttempts; ++t) {
+        MiPhilox q = mi_philox4x32((uint32_t)e, (uint32_t)t | (m << 16), s0, s1 ^ kTagNeg, k0, k1);
+        cand = draw.candidate((((uint64_t)q.c[0] << 32) | q.c[1]) % mod);
+        if (!csr_contains(rowptr, col, u, cand) && !draw.also_rejected(rowptr, col, u, cand)) break;
     }
     if (m == 0) {
         users[b] = u;
@@ -141,6 +111,10 @@ __device__ __forceinline__ float softplus_grad_ref(float x) {  // torch softplus
     return z / (z + 1.f);
 }
 
+// The slot pass of (reference, M = 1, no logq), the default step: rank_slot_kernel's sums in the same order with one
+// coefficient per slot, coef[b] = g_scale * dL/dx_b, for bpr_chunk_kernel.  It and bpr_chunk_kernel are kept beside the
+// general kernels because those are slower at M = 1 (profiles/objectives.md section 5: 19.0 + 62.2 us against 17.4 + 41.3 us
+// at B = 16 384, D = 128); rank_loss_run picks them, whichever entry was called.
 // One wavefront per batch slot.  Each lane covers d/64 (rounded up) strided elements.
 __global__ __launch_bounds__(kBlock) void bpr_slot_kernel(
     int64_t batch, int d, int64_t n_users, const int64_t* __restrict__ users,
@@ -194,11 +168,11 @@ __global__ __launch_bounds__(kBlock) void bpr_slot_kernel(
     }
 }
 
-// Single block, fixed order: loss = -sum(softplus)/B + lambda*sum(reg).
 // ---- gradient of the final embeddings, without float atomics -------------------------------------------------
-// A batch touches 3B rows with repeats (the most popular item is the positive of hundreds of samples).  The 3B
-// references (sample b, role) are keyed by the row they touch — its compact slot under node_map, its node id otherwise —
-// and sorted (stable radix sort: the references of a row stay in (role, b) order).  The sorted list is cut into chunks
+// A batch touches (2 + M) B rows with repeats (the most popular item is the positive of hundreds of samples).  The
+// (2 + M) B references (sample b, role) are keyed by the row they touch — its compact slot under node_map, its node id
+// otherwise — by rank_refs_kernel and sorted (stable radix sort: the references of a row stay in (role, b) order).  The
+// sorted list is cut into chunks
 // of 64 references, one wavefront each: a run of equal keys that lies inside a chunk is summed in order and added to its
 // row by that wavefront alone; a run that crosses chunk borders leaves one partial row per chunk, and the wavefront of
 // the chunk where the run starts adds those up in chunk order.  One writer per row, fixed orders throughout: the whole
@@ -206,19 +180,8 @@ __global__ __launch_bounds__(kBlock) void bpr_slot_kernel(
 constexpr int kRefChunk = 64;
 constexpr int kMaxDPerLane = 8;  // d <= 512
 
-__global__ void bpr_refs_kernel(int64_t batch, int64_t n_users, const int64_t* __restrict__ users,
-                                const int64_t* __restrict__ pos, const int64_t* __restrict__ neg,
-                                const int32_t* __restrict__ node_map, uint32_t* __restrict__ keys,
-                                uint32_t* __restrict__ refs) {
-    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;  // reference id = role * batch + b
-    if (r >= 3 * batch) return;
-    const int role = (int)(r / batch);
-    const int64_t b = r - role * batch;
-    const int64_t node = role == 0 ? users[b] : (role == 1 ? n_users + pos[b] : n_users + neg[b]);
-    keys[r] = (uint32_t)(node_map ? node_map[node] : node);
-    refs[r] = (uint32_t)r;
-}
-
+// The chunk pass of (reference, M = 1, no logq), 3B references: a reference has at most two terms (the user's row takes
+// p - n), so the lane that holds a reference holds its terms and the in-order pass needs no term numbering.
 template <int VPT>  // floats of a row per lane: ceil(d / 64)
 __global__ __launch_bounds__(kBlock) void bpr_chunk_kernel(
     int64_t batch, int d, int64_t n_users, const int64_t* __restrict__ users, const int64_t* __restrict__ pos,
@@ -353,6 +316,7 @@ __global__ __launch_bounds__(kBlock) void bpr_combine_kernel(int64_t n_ref, int 
     }
 }
 
+// Single block, fixed order: loss = -sum(softplus)/B + lambda*sum(reg).
 __global__ __launch_bounds__(1024) void bpr_finish_kernel(int64_t batch,
                                                           const float* __restrict__ softplus_v,
                                                           const float* __restrict__ reg_v,
@@ -641,22 +605,12 @@ __global__ __launch_bounds__(kBlock) void rank_chunk_kernel(
 }
 
 // ------------------------------------------------------------------ batch node set ------
-__global__ void mark_batch_nodes_kernel(int64_t batch, int64_t n_users, const int64_t* __restrict__ users,
-                                        const int64_t* __restrict__ pos, const int64_t* __restrict__ neg,
-                                        int32_t* __restrict__ flag) {
-    const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= batch) return;
-    flag[users[b]] = 1;  // same value from every writer: order does not matter
-    flag[n_users + pos[b]] = 1;
-    flag[n_users + neg[b]] = 1;
-}
-
 __global__ void mark_batch_nodes_ex_kernel(int64_t batch, int n_neg, int64_t n_users, const int64_t* __restrict__ users,
                                            const int64_t* __restrict__ pos, const int64_t* __restrict__ neg,
                                            int32_t* __restrict__ flag) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;   // (slot, m)
     if (i >= batch * n_neg) return;
-    flag[n_users + neg[i]] = 1;
+    flag[n_users + neg[i]] = 1;  // same value from every writer: order does not matter
     if (i % n_neg == 0) {
         const int64_t b = i / n_neg;
         flag[users[b]] = 1;
@@ -742,23 +696,29 @@ __global__ __launch_bounds__(kBlock) void adam_kernel(int64_t n_rows, int d4, fl
     }
 }
 
+// ------------------------------------------------------------------ host helpers -------
+template <class Draw>   // arguments checked by the caller; batch * n_neg >= 1
+int sample_batch_launch(int64_t batch, int n_neg, int64_t nnz, const int32_t* rowptr, const int32_t* col,
+                        const int32_t* row_of_edge, Draw draw, int32_t edges_in_order, uint64_t seed, uint64_t step,
+                        int64_t* users, int64_t* pos, int64_t* neg, mi_stream_t stream) {
+    hipLaunchKernelGGL(sample_batch_kernel<Draw>, dim3((unsigned)mi_ceil_div(batch * n_neg, kBlock)), dim3(kBlock), 0,
+                       (hipStream_t)stream, batch, n_neg, nnz, rowptr, col, row_of_edge, draw, edges_in_order, seed, step,
+                       users, pos, neg);
+    return mi_launch_status();
+}
+
+// f(std::integral_constant<int, VPT>), VPT = the floats of a d-wide row per lane, ceil(d / 64) rounded up to 1, 2, 4 or 8
+template <class F>
+void with_vpt(int64_t d, F&& f) {
+    if (d <= 64) f(std::integral_constant<int, 1>{});
+    else if (d <= 128) f(std::integral_constant<int, 2>{});
+    else if (d <= 256) f(std::integral_constant<int, 4>{});
+    else f(std::integral_constant<int, 8>{});
+}
+
 }  // namespace
 
 extern "C" {
-
-int mi_sample_bpr_batch(int64_t batch, int64_t nnz, const int32_t* rowptr, const int32_t* col,
-                        const int32_t* row_of_edge, int64_t neg_range, int32_t quirk_user_rows,
-                        int32_t edges_in_order, uint64_t seed, uint64_t step, int64_t* users, int64_t* pos,
-                        int64_t* neg, mi_stream_t stream) {
-    MI_CHECK_ARG(batch >= 0 && (!edges_in_order || batch <= nnz));
-    if (batch == 0) return 0;
-    MI_CHECK_ARG(nnz > 0 && neg_range > 0 && rowptr && col && row_of_edge && users && pos && neg);
-    if (nnz >= INT32_MAX || neg_range >= INT32_MAX) return MI_ERR_TOO_LARGE;
-    dim3 g((unsigned)mi_ceil_div(batch, kBlock));
-    hipLaunchKernelGGL(sample_bpr_kernel, g, dim3(kBlock), 0, (hipStream_t)stream, batch, nnz, rowptr, col,
-                       row_of_edge, neg_range, quirk_user_rows, edges_in_order, seed, step, users, pos, neg);
-    return mi_launch_status();
-}
 
 int mi_sample_bpr_batch_ex(int64_t batch, int32_t n_neg, int64_t nnz, const int32_t* rowptr, const int32_t* col,
                            const int32_t* row_of_edge, int64_t neg_range, int32_t quirk_user_rows,
@@ -769,10 +729,17 @@ int mi_sample_bpr_batch_ex(int64_t batch, int32_t n_neg, int64_t nnz, const int3
     if (batch == 0) return 0;
     MI_CHECK_ARG(nnz > 0 && neg_range > 0 && rowptr && col && row_of_edge && users && pos && neg);
     if (nnz >= INT32_MAX || neg_range >= INT32_MAX) return MI_ERR_TOO_LARGE;
-    dim3 g((unsigned)mi_ceil_div(batch * n_neg, kBlock));
-    hipLaunchKernelGGL(sample_bpr_ex_kernel, g, dim3(kBlock), 0, (hipStream_t)stream, batch, (int)n_neg, nnz, rowptr, col,
-                       row_of_edge, neg_range, quirk_user_rows, edges_in_order, seed, step, users, pos, neg);
-    return mi_launch_status();
+    return sample_batch_launch(batch, n_neg, nnz, rowptr, col, row_of_edge, UniformDraw{neg_range, quirk_user_rows},
+                               edges_in_order, seed, step, users, pos, neg, stream);
+}
+
+// the one-negative form: same checks, same kernel, n_neg = 1
+int mi_sample_bpr_batch(int64_t batch, int64_t nnz, const int32_t* rowptr, const int32_t* col,
+                        const int32_t* row_of_edge, int64_t neg_range, int32_t quirk_user_rows,
+                        int32_t edges_in_order, uint64_t seed, uint64_t step, int64_t* users, int64_t* pos,
+                        int64_t* neg, mi_stream_t stream) {
+    return mi_sample_bpr_batch_ex(batch, 1, nnz, rowptr, col, row_of_edge, neg_range, quirk_user_rows, edges_in_order, seed,
+                                  step, users, pos, neg, stream);
 }
 
 int mi_sample_bpr_batch_pop(int64_t batch, int32_t n_neg, int64_t nnz, const int32_t* rowptr, const int32_t* col,
@@ -784,10 +751,8 @@ int mi_sample_bpr_batch_pop(int64_t batch, int32_t n_neg, int64_t nnz, const int
     MI_CHECK_ARG(((uintptr_t)rowptr | (uintptr_t)col | (uintptr_t)row_of_edge | (uintptr_t)cum) % 4 == 0);
     MI_CHECK_ARG(((uintptr_t)users | (uintptr_t)pos | (uintptr_t)neg) % 8 == 0);
     if (nnz >= INT32_MAX || n_items > INT32_MAX) return MI_ERR_TOO_LARGE;
-    dim3 g((unsigned)mi_ceil_div(batch * n_neg, kBlock));
-    hipLaunchKernelGGL(sample_bpr_pop_kernel, g, dim3(kBlock), 0, (hipStream_t)stream, batch, (int)n_neg, nnz, rowptr, col,
-                       row_of_edge, (int32_t)n_items, cum, edges_in_order, seed, step, users, pos, neg);
-    return mi_launch_status();
+    return sample_batch_launch(batch, n_neg, nnz, rowptr, col, row_of_edge, PopularityDraw{(int32_t)n_items, cum},
+                               edges_in_order, seed, step, users, pos, neg, stream);
 }
 
 size_t mi_batch_nodes_workspace_bytes(int64_t n_nodes) {
@@ -795,7 +760,6 @@ size_t mi_batch_nodes_workspace_bytes(int64_t n_nodes) {
     return 2 * mi_align_up(n1 * sizeof(int32_t), 256) + ((size_t)16 << 20);
 }
 
-// n_neg == 0: the one-negative marking kernel of mi_batch_nodes_i32
 static int batch_nodes_run(int64_t batch, int n_neg, int64_t n_users, int64_t n_nodes, const int64_t* users,
                            const int64_t* pos, const int64_t* neg, int32_t* gmap, int32_t* nodes,
                            int32_t* count, void* ws, size_t ws_bytes, mi_stream_t stream) {
@@ -809,12 +773,8 @@ static int batch_nodes_run(int64_t batch, int n_neg, int64_t n_users, int64_t n_
     int32_t* slot = arena.take<int32_t>(n1);
     if (!flag || !slot) return MI_ERR_WORKSPACE;
     MI_HIP(hipMemsetAsync(flag, 0, (size_t)n1 * sizeof(int32_t), s));
-    if (n_neg == 0)
-        hipLaunchKernelGGL(mark_batch_nodes_kernel, dim3((unsigned)mi_ceil_div(batch, kBlock)), dim3(kBlock), 0, s, batch,
-                           n_users, users, pos, neg, flag);
-    else
-        hipLaunchKernelGGL(mark_batch_nodes_ex_kernel, dim3((unsigned)mi_ceil_div(batch * n_neg, kBlock)), dim3(kBlock), 0,
-                           s, batch, n_neg, n_users, users, pos, neg, flag);
+    hipLaunchKernelGGL(mark_batch_nodes_ex_kernel, dim3((unsigned)mi_ceil_div(batch * n_neg, kBlock)), dim3(kBlock), 0, s,
+                       batch, n_neg, n_users, users, pos, neg, flag);
     size_t tmp_bytes = 0;
     MI_HIP(rocprim::exclusive_scan(nullptr, tmp_bytes, flag, slot, 0, (size_t)n1, rocprim::plus<int32_t>(), s));
     char* tmp = arena.take<char>(tmp_bytes ? tmp_bytes : 1);
@@ -828,7 +788,7 @@ static int batch_nodes_run(int64_t batch, int n_neg, int64_t n_users, int64_t n_
 int mi_batch_nodes_i32(int64_t batch, int64_t n_users, int64_t n_nodes, const int64_t* users,
                        const int64_t* pos, const int64_t* neg, int32_t* gmap, int32_t* nodes,
                        int32_t* count, void* ws, size_t ws_bytes, mi_stream_t stream) {
-    return batch_nodes_run(batch, 0, n_users, n_nodes, users, pos, neg, gmap, nodes, count, ws, ws_bytes, stream);
+    return batch_nodes_run(batch, 1, n_users, n_nodes, users, pos, neg, gmap, nodes, count, ws, ws_bytes, stream);
 }
 
 int mi_batch_nodes_ex_i32(int64_t batch, int32_t n_neg, int64_t n_users, int64_t n_nodes, const int64_t* users,
@@ -869,79 +829,6 @@ int mi_scatter_rows_f32(int64_t n_max, const int32_t* n_dev, const int32_t* begi
 
 static size_t bpr_sort_tmp_bytes(int64_t n_ref) { return ((size_t)1 << 20) + mi_align_up((size_t)n_ref * 2, 256); }
 
-size_t mi_bpr_workspace_bytes(int64_t batch) {
-    const size_t b = (size_t)(batch > 0 ? batch : 1);
-    const size_t chunks = (3 * b + 63) / 64;
-    // softplus, reg, coef per sample; (key, reference) double buffers of the 3B row references; rocPRIM scratch;
-    // head / tail partial rows per 64-reference chunk (d <= 512)
-    return 3 * mi_align_up(b * sizeof(float), 256) + 4 * mi_align_up(3 * b * sizeof(uint32_t), 256) + bpr_sort_tmp_bytes(3 * (int64_t)b) +
-           2 * mi_align_up(chunks * 512 * sizeof(float), 256);
-}
-
-int mi_bpr_fwd_bwd_f32(int64_t batch, int64_t d, int64_t n_users, const int64_t* users,
-                       const int64_t* pos, const int64_t* neg, const float* final_emb, int64_t ldf,
-                       const float* e0, int64_t lde, float lambda, float g_scale, float reg_scale,
-                       float* loss_out, float* g_final, int64_t ldg, float* reg_w,
-                       const int32_t* node_map, void* ws, size_t ws_bytes, mi_stream_t stream) {
-    MI_CHECK_ARG(batch > 0 && d > 0 && n_users >= 0);
-    MI_CHECK_ARG(users && pos && neg && final_emb && e0 && loss_out && ws);
-    MI_CHECK_ARG(ldf >= d && lde >= d && (!g_final || ldg >= d));
-    if (3 * batch >= INT32_MAX) return MI_ERR_TOO_LARGE;
-    if (g_final && d > MI_WAVE * kMaxDPerLane) return MI_ERR_UNSUPPORTED;
-    if (ws_bytes < mi_bpr_workspace_bytes(batch)) return MI_ERR_WORKSPACE;
-    const int64_t n_ref = 3 * batch, n_chunks = mi_ceil_div(n_ref, kRefChunk);
-    MiArena arena(ws, ws_bytes);
-    float* spv = arena.take<float>(batch);
-    float* rgv = arena.take<float>(batch);
-    float* coef = arena.take<float>(batch);
-    uint32_t* k0 = arena.take<uint32_t>(n_ref);
-    uint32_t* k1 = arena.take<uint32_t>(n_ref);
-    uint32_t* r0 = arena.take<uint32_t>(n_ref);
-    uint32_t* r1 = arena.take<uint32_t>(n_ref);
-    const size_t tmp_cap = bpr_sort_tmp_bytes(n_ref);
-    char* tmp = arena.take<char>(tmp_cap);
-    float* part_head = arena.take<float>((size_t)n_chunks * 512);
-    float* part_tail = arena.take<float>((size_t)n_chunks * 512);
-    if (!spv || !rgv || !coef || !k0 || !k1 || !r0 || !r1 || !tmp || !part_head || !part_tail) return MI_ERR_WORKSPACE;
-    hipStream_t s = (hipStream_t)stream;
-    const float inv_b = 1.0f / (float)batch;
-    dim3 g((unsigned)mi_ceil_div(batch * MI_WAVE, kBlock));
-    hipLaunchKernelGGL(bpr_slot_kernel, g, dim3(kBlock), 0, s, batch, (int)d, n_users, users, pos, neg,
-                       final_emb, ldf, e0, lde, inv_b, g_scale, reg_scale * lambda, spv, rgv,
-                       g_final ? coef : nullptr, g_final ? nullptr : reg_w, node_map);
-    if (g_final) {
-        hipLaunchKernelGGL(bpr_refs_kernel, dim3((unsigned)mi_ceil_div(n_ref, 256)), dim3(256), 0, s, batch, n_users, users,
-                           pos, neg, node_map, k0, r0);
-        // compact slots are < 3B; node ids need all 32 bits
-        unsigned bits = 32;
-        if (node_map) {
-            bits = 1;
-            while (((int64_t)1 << bits) < n_ref) ++bits;
-        }
-        rocprim::double_buffer<uint32_t> keys(k0, k1), refs(r0, r1);
-        size_t need = 0;
-        MI_HIP(rocprim::radix_sort_pairs(nullptr, need, keys, refs, (size_t)n_ref, 0, bits, s));
-        if (need > tmp_cap) return MI_ERR_WORKSPACE;
-        MI_HIP(rocprim::radix_sort_pairs(tmp, need, keys, refs, (size_t)n_ref, 0, bits, s));
-        dim3 gc((unsigned)mi_ceil_div(n_chunks * MI_WAVE, kBlock));
-#define MI_BPR_GO(V)                                                                                                       \
-    do {                                                                                                                    \
-        hipLaunchKernelGGL(bpr_chunk_kernel<V>, gc, dim3(kBlock), 0, s, batch, (int)d, n_users, users, pos, neg, final_emb, \
-                           ldf, coef, keys.current(), refs.current(), node_map, g_final, ldg, part_head, part_tail,        \
-                           reg_w, 2.0f * (reg_scale * lambda));                                                             \
-        hipLaunchKernelGGL(bpr_combine_kernel<V>, gc, dim3(kBlock), 0, s, n_ref, (int)d, keys.current(), part_head,         \
-                           part_tail, g_final, ldg);                                                                        \
-    } while (0)
-        if (d <= 64) MI_BPR_GO(1);
-        else if (d <= 128) MI_BPR_GO(2);
-        else if (d <= 256) MI_BPR_GO(4);
-        else MI_BPR_GO(8);
-#undef MI_BPR_GO
-    }
-    hipLaunchKernelGGL(bpr_finish_kernel, dim3(1), dim3(1024), 0, s, batch, spv, rgv, inv_b, lambda, loss_out);
-    return mi_launch_status();
-}
-
 size_t mi_rank_loss_workspace_bytes(int64_t batch, int32_t n_neg) {
     const size_t b = (size_t)(batch > 0 ? batch : 1);
     const size_t m = (size_t)(n_neg >= 1 && n_neg <= kMaxNeg ? n_neg : 1);
@@ -953,7 +840,7 @@ size_t mi_rank_loss_workspace_bytes(int64_t batch, int32_t n_neg) {
            2 * mi_align_up(chunks * 512 * sizeof(float), 256);
 }
 
-// both entries; logq == nullptr launches what mi_rank_loss_fwd_bwd_f32 always launched
+// all three loss entries; logq == nullptr launches what mi_rank_loss_fwd_bwd_f32 always launched
 static int rank_loss_run(int64_t batch, int32_t n_neg, int32_t objective, int64_t d, int64_t n_users,
                          const int64_t* users, const int64_t* pos, const int64_t* neg, const float* final_emb,
                          int64_t ldf, const float* e0, int64_t lde, float lambda, float g_scale, float reg_scale,
@@ -987,24 +874,23 @@ static int rank_loss_run(int64_t batch, int32_t n_neg, int32_t objective, int64_
     hipStream_t s = (hipStream_t)stream;
     // the mean runs over the B*M pairs, or over the B slots for the softmax
     const float inv_count = 1.0f / (float)(objective == kRankSoftmax ? batch : batch * n_neg);
-    const int vpt = d <= 64 ? 1 : (d <= 128 ? 2 : (d <= 256 ? 4 : 8));
-    dim3 g((unsigned)mi_ceil_div(batch * MI_WAVE, kBlock));
-#define MI_RANK_SLOT(V, LQ)                                                                                                \
-    hipLaunchKernelGGL((rank_slot_kernel<V, LQ>), g, dim3(kBlock), 0, s, batch, (int)n_neg, (int)objective, (int)d,         \
-                       n_users, users, pos, neg, final_emb, ldf, e0, lde, inv_count, g_scale, reg_scale * lambda, termv,    \
-                       rgv, g_final ? coef : nullptr, g_final ? nullptr : reg_w, node_map, logq)
-    if (logq) {
-        if (vpt == 1) MI_RANK_SLOT(1, true);
-        else if (vpt == 2) MI_RANK_SLOT(2, true);
-        else if (vpt == 4) MI_RANK_SLOT(4, true);
-        else MI_RANK_SLOT(8, true);
-    } else {
-        if (vpt == 1) MI_RANK_SLOT(1, false);
-        else if (vpt == 2) MI_RANK_SLOT(2, false);
-        else if (vpt == 4) MI_RANK_SLOT(4, false);
-        else MI_RANK_SLOT(8, false);
-    }
-#undef MI_RANK_SLOT
+    const float reg_coef = reg_scale * lambda;
+    // the default step's case keeps its two faster kernels (same bits; one coefficient per slot instead of two)
+    const bool bpr_form = n_neg == 1 && objective == kRankReference && !logq;
+    const dim3 g((unsigned)mi_ceil_div(batch * MI_WAVE, kBlock));
+    float* const coef_out = g_final ? coef : nullptr;
+    float* const slot_reg_w = g_final ? nullptr : reg_w;
+    if (bpr_form)
+        hipLaunchKernelGGL(bpr_slot_kernel, g, dim3(kBlock), 0, s, batch, (int)d, n_users, users, pos, neg, final_emb, ldf,
+                           e0, lde, inv_count, g_scale, reg_coef, termv, rgv, coef_out, slot_reg_w, node_map);
+    else
+        with_vpt(d, [&](auto vpt) {
+            constexpr int V = decltype(vpt)::value;
+            auto slot = logq ? rank_slot_kernel<V, true> : rank_slot_kernel<V, false>;
+            hipLaunchKernelGGL(slot, g, dim3(kBlock), 0, s, batch, (int)n_neg, (int)objective, (int)d, n_users, users, pos,
+                               neg, final_emb, ldf, e0, lde, inv_count, g_scale, reg_coef, termv, rgv, coef_out, slot_reg_w,
+                               node_map, logq);
+        });
     if (g_final) {
         hipLaunchKernelGGL(rank_refs_kernel, dim3((unsigned)mi_ceil_div(n_ref, 256)), dim3(256), 0, s, batch, (int)n_neg,
                            n_users, users, pos, neg, node_map, k0, r0);
@@ -1018,20 +904,20 @@ static int rank_loss_run(int64_t batch, int32_t n_neg, int32_t objective, int64_
         MI_HIP(rocprim::radix_sort_pairs(nullptr, need, keys, refs, (size_t)n_ref, 0, bits, s));
         if (need > tmp_cap) return MI_ERR_WORKSPACE;
         MI_HIP(rocprim::radix_sort_pairs(tmp, need, keys, refs, (size_t)n_ref, 0, bits, s));
-        dim3 gc((unsigned)mi_ceil_div(n_chunks * MI_WAVE, kBlock));
-#define MI_RANK_GO(V)                                                                                                      \
-    do {                                                                                                                    \
-        hipLaunchKernelGGL(rank_chunk_kernel<V>, gc, dim3(kBlock), 0, s, batch, (int)n_neg, (int)d, n_users, users, pos,    \
-                           neg, final_emb, ldf, coef, keys.current(), refs.current(), node_map, g_final, ldg, part_head,    \
-                           part_tail, reg_w, 2.0f * (reg_scale * lambda));                                                  \
-        hipLaunchKernelGGL(bpr_combine_kernel<V>, gc, dim3(kBlock), 0, s, n_ref, (int)d, keys.current(), part_head,         \
-                           part_tail, g_final, ldg);                                                                        \
-    } while (0)
-        if (vpt == 1) MI_RANK_GO(1);
-        else if (vpt == 2) MI_RANK_GO(2);
-        else if (vpt == 4) MI_RANK_GO(4);
-        else MI_RANK_GO(8);
-#undef MI_RANK_GO
+        const dim3 gc((unsigned)mi_ceil_div(n_chunks * MI_WAVE, kBlock));
+        with_vpt(d, [&](auto vpt) {
+            constexpr int V = decltype(vpt)::value;
+            if (bpr_form)
+                hipLaunchKernelGGL(bpr_chunk_kernel<V>, gc, dim3(kBlock), 0, s, batch, (int)d, n_users, users, pos, neg,
+                                   final_emb, ldf, coef, keys.current(), refs.current(), node_map, g_final, ldg, part_head,
+                                   part_tail, reg_w, 2.0f * reg_coef);
+            else
+                hipLaunchKernelGGL(rank_chunk_kernel<V>, gc, dim3(kBlock), 0, s, batch, (int)n_neg, (int)d, n_users, users,
+                                   pos, neg, final_emb, ldf, coef, keys.current(), refs.current(), node_map, g_final, ldg,
+                                   part_head, part_tail, reg_w, 2.0f * reg_coef);
+            hipLaunchKernelGGL(bpr_combine_kernel<V>, gc, dim3(kBlock), 0, s, n_ref, (int)d, keys.current(), part_head,
+                               part_tail, g_final, ldg);
+        });
     }
     // the slot terms are stored negated, so every objective closes with loss = -sum(term) / count + lambda * sum(reg)
     hipLaunchKernelGGL(bpr_finish_kernel, dim3(1), dim3(1024), 0, s, batch, termv, rgv, inv_count, lambda, loss_out);
@@ -1044,6 +930,18 @@ int mi_rank_loss_fwd_bwd_f32(int64_t batch, int32_t n_neg, int32_t objective, in
                              float* loss_out, float* g_final, int64_t ldg, float* reg_w, const int32_t* node_map,
                              void* ws, size_t ws_bytes, mi_stream_t stream) {
     return rank_loss_run(batch, n_neg, objective, d, n_users, users, pos, neg, final_emb, ldf, e0, lde, lambda, g_scale,
+                         reg_scale, loss_out, g_final, ldg, reg_w, node_map, nullptr, ws, ws_bytes, stream);
+}
+
+// the reference's loss: the (MI_RANK_REFERENCE, one negative) case, kept for the boundary
+size_t mi_bpr_workspace_bytes(int64_t batch) { return mi_rank_loss_workspace_bytes(batch, 1); }
+
+int mi_bpr_fwd_bwd_f32(int64_t batch, int64_t d, int64_t n_users, const int64_t* users,
+                       const int64_t* pos, const int64_t* neg, const float* final_emb, int64_t ldf,
+                       const float* e0, int64_t lde, float lambda, float g_scale, float reg_scale,
+                       float* loss_out, float* g_final, int64_t ldg, float* reg_w,
+                       const int32_t* node_map, void* ws, size_t ws_bytes, mi_stream_t stream) {
+    return rank_loss_run(batch, 1, kRankReference, d, n_users, users, pos, neg, final_emb, ldf, e0, lde, lambda, g_scale,
                          reg_scale, loss_out, g_final, ldg, reg_w, node_map, nullptr, ws, ws_bytes, stream);
 }
 

@@ -931,40 +931,16 @@ def sample_bpr_batch(r: DeviceCSR, row_of_edge: Tensor, batch: int, neg_range: i
     return users, pos, neg
 
 
-def bpr_fwd_bwd(users: Tensor, pos: Tensor, neg: Tensor, final_emb: Tensor, e0: Tensor, n_users: int,
-                lambda_val: float, *, g_final: Optional[Tensor] = None, reg_w: Optional[Tensor] = None,
-                g_scale: float = 1.0, reg_scale: float = 1.0, loss_out: Optional[Tensor] = None,
-                node_map: Optional[Tensor] = None) -> Tensor:
-    """a7+a8 — batch gather + bpr_loss (utils/metrics_lightgcn.py:9-45) forward and backward."""
-    for n, x in (("users", users), ("pos", pos), ("neg", neg)):
-        _need(x, t.int64, n)
-    batch = users.numel()
-    d = final_emb.shape[1]
-    ldf = _rows_ok(final_emb, "final_emb")
-    lde = _rows_ok(e0, "e0")
-    ldg = _rows_ok(g_final, "g_final") if g_final is not None else 0
-    if reg_w is not None:
-        _need(reg_w, t.float32, "reg_w")
-    dev = final_emb.device
-    if loss_out is None:
-        loss_out = t.empty(1, dtype=t.float32, device=dev)
-    L = _lib.lib()
-    ws = _ws(L.mi_bpr_workspace_bytes(batch), dev)
-    check(L.mi_bpr_fwd_bwd_f32(batch, d, n_users, _ptr(users), _ptr(pos), _ptr(neg), final_emb.data_ptr(), ldf,
-                               e0.data_ptr(), lde, float(lambda_val), float(g_scale), float(reg_scale),
-                               loss_out.data_ptr(), _ptr(g_final), ldg, _ptr(reg_w), _ptr(node_map), ws.data_ptr(),
-                               ws.numel(), _stream()), "mi_bpr_fwd_bwd_f32")
-    return loss_out
-
-
 def rank_loss_fwd_bwd(users: Tensor, pos: Tensor, neg: Tensor, final_emb: Tensor, e0: Tensor, n_users: int,
                       lambda_val: float, *, objective: str = "reference", g_final: Optional[Tensor] = None,
                       reg_w: Optional[Tensor] = None, g_scale: float = 1.0, reg_scale: float = 1.0,
                       loss_out: Optional[Tensor] = None, node_map: Optional[Tensor] = None,
-                      logq: Optional[Tensor] = None) -> Tensor:
-    """bpr_fwd_bwd with a choice of objective ("reference", "bpr", "softmax") and neg [B] or [B, M], M <= 16.
+                      logq: Optional[Tensor] = None, _bpr_entry: bool = False) -> Tensor:
+    """a7+a8 — batch gather + loss forward and backward with a choice of objective ("reference", "bpr", "softmax") and
+    neg [B] or [B, M], M <= 16; ("reference", M = 1) is bpr_loss (utils/metrics_lightgcn.py:9-45).
     logq (float32, one entry per item of e0, addressed by item id): the logQ correction of the sampled softmax —
-    the logits become s - logq[item] (mi_rank_loss_fwd_bwd_lq_f32); "softmax" only, and with g_final or without reg_w."""
+    the logits become s - logq[item] (mi_rank_loss_fwd_bwd_lq_f32); "softmax" only, and with g_final or without reg_w.
+    _bpr_entry: bpr_fwd_bwd's switch to the C entry of the same case, mi_bpr_fwd_bwd_f32."""
     code = rank_objective_code(objective)
     if logq is not None and objective != "softmax":
         raise ValueError(f"logq corrects the sampled softmax only, not objective={objective!r}")
@@ -985,6 +961,14 @@ def rank_loss_fwd_bwd(users: Tensor, pos: Tensor, neg: Tensor, final_emb: Tensor
         loss_out = t.empty(1, dtype=t.float32, device=dev)
     L = _lib.lib()
     ws = _ws(L.mi_rank_loss_workspace_bytes(batch, n_neg), dev)
+    if _bpr_entry:
+        if (objective, n_neg, logq) != ("reference", 1, None):
+            raise ValueError("bpr_fwd_bwd is the reference objective over one negative per slot")
+        check(L.mi_bpr_fwd_bwd_f32(batch, d, n_users, _ptr(users), _ptr(pos), _ptr(neg), final_emb.data_ptr(), ldf,
+                                   e0.data_ptr(), lde, float(lambda_val), float(g_scale), float(reg_scale),
+                                   loss_out.data_ptr(), _ptr(g_final), ldg, _ptr(reg_w), _ptr(node_map), ws.data_ptr(),
+                                   ws.numel(), _stream()), "mi_bpr_fwd_bwd_f32")
+        return loss_out
     if logq is None:
         check(L.mi_rank_loss_fwd_bwd_f32(batch, n_neg, code, d, n_users, _ptr(users), _ptr(pos), _ptr(neg),
                                          final_emb.data_ptr(), ldf, e0.data_ptr(), lde, float(lambda_val), float(g_scale),
@@ -1002,6 +986,15 @@ def rank_loss_fwd_bwd(users: Tensor, pos: Tensor, neg: Tensor, final_emb: Tensor
                                         _ptr(node_map), logq.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
           "mi_rank_loss_fwd_bwd_lq_f32")
     return loss_out
+
+
+def bpr_fwd_bwd(users: Tensor, pos: Tensor, neg: Tensor, final_emb: Tensor, e0: Tensor, n_users: int,
+                lambda_val: float, *, g_final: Optional[Tensor] = None, reg_w: Optional[Tensor] = None,
+                g_scale: float = 1.0, reg_scale: float = 1.0, loss_out: Optional[Tensor] = None,
+                node_map: Optional[Tensor] = None) -> Tensor:
+    """rank_loss_fwd_bwd(objective="reference") over one negative per slot, through the reference's own C entry."""
+    return rank_loss_fwd_bwd(users, pos, neg, final_emb, e0, n_users, lambda_val, g_final=g_final, reg_w=reg_w,
+                             g_scale=g_scale, reg_scale=reg_scale, loss_out=loss_out, node_map=node_map, _bpr_entry=True)
 
 
 def adam_step(p: Tensor, grad: Tensor, m: Tensor, v: Tensor, *, step: int, lr: float, beta1: float = 0.9,

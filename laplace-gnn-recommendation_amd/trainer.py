@@ -197,16 +197,9 @@ class LightGCNTrainer:
                                     self.step_count, quirk=self.quirk, out=self.batch_idx, n_neg=self.n_neg)
 
     def _loss(self, users, pos, neg, final, **kw) -> None:
-        """Loss and its gradient on `final`; the default objective keeps the one-negative entry (same launches, same bits)."""
-        if self.logq is not None:
-            ops.rank_loss_fwd_bwd(users, pos, neg, final, self.table, self.model.num_users, self.Lambda,
-                                  objective=self.objective, reg_w=self.reg_w, loss_out=self.loss, logq=self.logq, **kw)
-        elif self.objective == "reference" and self.n_neg == 1:
-            ops.bpr_fwd_bwd(users, pos, neg, final, self.table, self.model.num_users, self.Lambda, reg_w=self.reg_w,
-                            loss_out=self.loss, **kw)
-        else:
-            ops.rank_loss_fwd_bwd(users, pos, neg, final, self.table, self.model.num_users, self.Lambda,
-                                  objective=self.objective, reg_w=self.reg_w, loss_out=self.loss, **kw)
+        """Loss and its gradient on `final` (self.logq is None without the logQ correction)."""
+        ops.rank_loss_fwd_bwd(users, pos, neg, final, self.table, self.model.num_users, self.Lambda,
+                              objective=self.objective, reg_w=self.reg_w, loss_out=self.loss, logq=self.logq, **kw)
 
     def sample(self) -> Tuple[Tensor, Tensor, Tensor]:
         """(users, pos, neg) of the next step's batch, ORIGINAL ids."""

@@ -271,7 +271,7 @@ _MAX_NEG_ATTEMPTS = 4096
 
 def sample_bpr_batch_philox(rowptr: Tensor, col: Tensor, batch: int, neg_range: int, seed: int, step: int,
                             quirk: bool = False, edges_in_order: bool = False, no_self_loops: bool = False):
-    """Bit-exact restatement of csrc/train.hip:sample_bpr_kernel (integer work => exact parity).
+    """Bit-exact restatement of csrc/train.hip:sample_batch_kernel at n_neg = 1, uniform draw (integer work => exact parity).
     rowptr/col: the users x items interaction CSR with sorted columns."""
     rp, c = rowptr.numpy().astype(np.int64), col.numpy().astype(np.int64)
     nnz = int(c.shape[0])

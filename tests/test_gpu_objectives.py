@@ -5,7 +5,10 @@ Tolerances are those of tests/test_gpu_lightgcn.py: loss 1e-6 * max(1, |loss|), 
 training steps <= 1e-4 on the embeddings.  The float64 twin below is the yardstick of the kernel tests; the trainer
 tests run the same twin in fp32 under torch autograd and torch.optim.Adam.
 """
+import hashlib
+import json
 import os
+import struct
 import subprocess
 import sys
 
@@ -128,10 +131,30 @@ def test_rank_loss_gradient_scale_and_width_512():
 
 
 # ---------------------------------------------------------------------------- 2, 3: identities
+def _recorded():
+    """tests/golden/bpr_entry_bits.json (tools/record_loss_bits.py): what the one-negative entry and the default trainer
+    step produced at the last commit where that entry had a host body and a whole kernel set of its own."""
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "bpr_entry_bits.json")) as f:
+        return json.load(f)
+
+
+def _bits(x):
+    """Bit pattern of an fp32 value (a Python float that came from one converts back exactly)."""
+    return f"{struct.unpack('<I', struct.pack('<f', float(x)))[0]:08x}"
+
+
+def _sha(x):
+    return hashlib.sha256(x.detach().cpu().contiguous().numpy().tobytes()).hexdigest()
+
+
 @pytest.mark.parametrize("with_map", [False, True])
 @pytest.mark.parametrize("D", [32, 64, 100, 128, 200, 512])
 def test_reference_objective_one_negative_is_bitwise_the_bpr_entry(D, with_map):
+    """Both C entries of the (reference, one negative) case go through one host path and launch the same kernels, so beside
+    each other they are compared with the recorded bits of the entry as it was: loss, g_final and reg_w of every case, and
+    the loss of the loss-only form where one was recorded (its reg_w comes from float atomics)."""
     ops = _ops()
+    rec = _recorded()
     B, lam = 300, 1e-3
     U, I, final, e0, users, pos, neg = _small_batch(B, 1, D, seed=D, U=40, I=25)
     ud, pd, nd, e0d = users.to(DEV), pos.to(DEV), neg.to(DEV), e0.to(DEV)
@@ -141,17 +164,28 @@ def test_reference_objective_one_negative_is_bitwise_the_bpr_entry(D, with_map):
         rows_n = 3 * B
         src = t.zeros(rows_n, D, device=DEV)
         src[: int(cnt[0])] = final.to(DEV)[nodes[: int(cnt[0])].long()]
-    for g_scale in (1.0, 1.0 / 3):
+    for gi, g_scale in enumerate((1.0, 1.0 / 3)):
+        want = rec["entry"][f"D{D}_map{int(with_map)}_gscale{gi}"]
         ga, gb = t.zeros(rows_n, D, device=DEV), t.zeros(rows_n, D, device=DEV)
         ra, rb = t.zeros(U + I, device=DEV), t.zeros(U + I, device=DEV)
         la = ops.bpr_fwd_bwd(ud, pd, nd[:, 0].contiguous(), src, e0d, U, lam, g_final=ga, reg_w=ra, g_scale=g_scale,
                              node_map=gmap)
+        assert (_bits(la), _sha(ga), _sha(ra)) == (want["loss_bits"], want["g_final_sha256"], want["reg_w_sha256"])
         for neg_form in (nd, nd[:, 0].contiguous()):   # [B, 1] and [B]
             gb.zero_(); rb.zero_()
             lb = ops.rank_loss_fwd_bwd(ud, pd, neg_form, src, e0d, U, lam, objective="reference", g_final=gb, reg_w=rb,
                                        g_scale=g_scale, node_map=gmap)
             assert t.equal(la, lb) and t.equal(ga, gb) and t.equal(ra, rb)
+            assert (_bits(lb), _sha(gb), _sha(rb)) == (want["loss_bits"], want["g_final_sha256"], want["reg_w_sha256"])
     assert float(ga.abs().max()) > 0.0
+    want = rec["entry_loss_only"].get(f"D{D}_map{int(with_map)}")
+    assert (want is not None) == (D in (64, 128))
+    if want is not None:   # g_final=None: the slot pass and the finish alone
+        neg1 = nd[:, 0].contiguous()
+        la = ops.bpr_fwd_bwd(ud, pd, neg1, src, e0d, U, lam, reg_w=t.zeros(U + I, device=DEV), node_map=gmap)
+        lb = ops.rank_loss_fwd_bwd(ud, pd, neg1, src, e0d, U, lam, objective="reference",
+                                   reg_w=t.zeros(U + I, device=DEV), node_map=gmap)
+        assert _bits(la) == want["loss_bits"] and _bits(lb) == want["loss_bits"]
 
 
 @pytest.mark.parametrize("D", [32, 128])
@@ -399,8 +433,11 @@ def test_step_forms_agree_and_repeat_bitwise(objective, M):
 
 
 def test_default_objective_is_the_step_as_it_was():
-    """objective="reference", n_neg=1 spelled out takes the one-negative entry: the same bits as leaving them out."""
+    """objective="reference", n_neg=1 spelled out gives the same bits as leaving them out, and both the bits the default
+    step gave while the one-negative entry had a host body of its own (tests/golden/bpr_entry_bits.json)."""
     a = _run("reference", 1, steps=3)
+    want = _recorded()["default_trainer"]
+    assert [_bits(x) for x in a[0]] == want["loss_bits"] and _sha(a[2]) == want["table_sha256"]
     from laplace_amd.trainer import LightGCNTrainer
     U, I, E, D, B = 900, 500, 15000, 64, 512
     model, inter, adj, ei = _model_and_graph(U, I, E, D, 3, seed=41, compat="bipartite")
