@@ -99,18 +99,27 @@ __host__ inline MiAdamConsts mi_adam_consts(double lr, double beta1, double beta
 }
 __device__ __forceinline__ void mi_adam_update4(float4& pp, float4 gg, float4& mm, float4& vv, bool has_w, float w,
                                                 const MiAdamConsts& c) {
+    // One rounding per operation: the same bits wherever this is inlined, and tests/adam_refs.py restates it in NumPy float32.
+    // The plain operators under contract(off), sqrtf and / — not __fmul_rn / __fadd_rn / __fsqrt_rn, which without
+    // OCML_BASIC_ROUNDED_OPERATIONS are the plain operators (contracted to v_fma_f32 by the default -ffp-contract) and the native
+    // 1-ulp square root; see lazy_adam.hpp.
+#pragma clang fp contract(off)
     if (has_w) {
         gg.x = fmaf(w, pp.x, gg.x);
         gg.y = fmaf(w, pp.y, gg.y);
         gg.z = fmaf(w, pp.z, gg.z);
         gg.w = fmaf(w, pp.w, gg.w);
     }
-    // explicit roundings (no fma contraction): the same bits wherever this is inlined
 #define MI_ADAM_1(f)                                                                                   \
-    mm.f = __fadd_rn(__fmul_rn(c.b1, mm.f), __fmul_rn(c.omb1, gg.f));                                  \
-    vv.f = __fadd_rn(__fmul_rn(c.b2, vv.f), __fmul_rn(__fmul_rn(c.omb2, gg.f), gg.f));                 \
-    pp.f = __fsub_rn(pp.f, __fmul_rn(c.step_size,                                                      \
-                                     __fdiv_rn(mm.f, __fadd_rn(__fdiv_rn(__fsqrt_rn(vv.f), c.bc2_sqrt), c.eps))));
+    {                                                                                                  \
+        const float b1m = c.b1 * mm.f, g1 = c.omb1 * gg.f;                                             \
+        mm.f = b1m + g1;                                                                               \
+        const float b2v = c.b2 * vv.f, g2 = (c.omb2 * gg.f) * gg.f;                                    \
+        vv.f = b2v + g2;                                                                               \
+        const float den = sqrtf(vv.f) / c.bc2_sqrt + c.eps;                                            \
+        const float upd = c.step_size * (mm.f / den);                                                  \
+        pp.f = pp.f - upd;                                                                             \
+    }
     MI_ADAM_1(x) MI_ADAM_1(y) MI_ADAM_1(z) MI_ADAM_1(w)
 #undef MI_ADAM_1
 }
