@@ -522,6 +522,48 @@ int mi_rank_loss_fwd_bwd_lq_f32(int64_t batch, int32_t n_neg, int32_t objective,
                                 void* ws, size_t ws_bytes, mi_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * In-batch sampled softmax (SURVEY F9 behind a flag): the other positives of the batch are every slot's negatives,
+ * scored on the exact-f32 matrix instruction.  No negative is drawn and the node set is the 2 * batch references.
+ *
+ * A batch is users[B], pos[B] (int64); no neg.  group = G, a multiple of 32 with 32 <= G <= 4096.
+ *   group g holds the slots [g*G, min((g+1)*G, B)): the last one may be partial, down to a single slot;
+ *   the candidates of slot b are the slots j of its own group, with the logit
+ *     l[b,j] = <f[users_b], f[n_users + pos_j]> - logq[pos_j]
+ *   (f a row of final_emb; logq float[n_items] by item id whatever node_map is, nullable: NULL subtracts nothing);
+ *   a candidate j != b is MASKED (left out of the sum, coefficient 0) when pos_j == pos_b (the slot's own positive) or
+ *   users_j == users_b (pos_j is then an item that user bought).  The user's OTHER items that happen to be in the group
+ *   are not rejected, and the masks are not reflected in logq — the usual approximations, as for the popularity sampler.
+ *   loss = (1/B) sum_b [ logsumexp_{j unmasked, incl. j = b} l[b,j] - l[b,b] ]
+ *          + lambda * sum_b (|e0[users_b]|^2 + |e0[n_users + pos_b]|^2)
+ *   with the maximum subtracted before the exponentials; a slot with no unmasked candidate besides itself adds 0.
+ *   c[b,j] = g_scale/B * (softmax_b[j] - [j == b]) for unmasked j;
+ *   dL/df[users_b] += sum_j c[b,j] f[n_users + pos_j];   dL/df[n_users + pos_j] += sum_b c[b,j] f[users_b].
+ * g_final, reg_w, node_map, g_scale, reg_scale and loss_out behave as in mi_rank_loss_fwd_bwd_f32: g_final all zero on
+ * entry, only touched rows written; reg_w[row] = (occurrences among the 2B references) * 2*lambda*reg_scale; reg_scale does
+ * not scale the L2 term of the loss VALUE.  The loss-only form is g_final == NULL and needs reg_w == NULL
+ * (MI_ERR_UNSUPPORTED otherwise).  d % 4 == 0 and d <= 256 (MI_ERR_UNSUPPORTED otherwise).  final_emb, e0 and ws 16-byte
+ * aligned, ldf and lde multiples of 4.  Every check — null or misaligned pointers, batch < 1, group, d, workspace — is made
+ * before anything is enqueued.
+ * The scores never reach memory: each pass (row statistics, the two gradient sweeps) recomputes its 32 x 32 score tiles
+ * in the same k order, so all three see the same bits.  No float atomics: per-slot gradient rows, one writer each, are
+ * summed per node by the sorted-reference segmented sum of the other losses (role 0 user, 1 positive).  Every order of
+ * summation is a function of (B, G, d) and the ids only: two calls give equal bits.
+ * mi_inbatch_softmax_workspace_bytes: 0 for arguments outside these limits.
+ * ---------------------------------------------------------------------------------- */
+size_t mi_inbatch_softmax_workspace_bytes(int64_t batch, int64_t d, int32_t group);
+int    mi_inbatch_softmax_fwd_bwd_f32(int64_t batch, int32_t group, int64_t d, int64_t n_users,
+                                      const int64_t* users, const int64_t* pos,
+                                      const float* final_emb, int64_t ldf,
+                                      const float* e0, int64_t lde,
+                                      float lambda, float g_scale, float reg_scale,
+                                      float* loss_out,
+                                      float* g_final, int64_t ldg,
+                                      float* reg_w,
+                                      const int32_t* node_map,
+                                      const float* logq /* [n_items], nullable */,
+                                      void* ws, size_t ws_bytes, mi_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * a9  dense Adam step (torch.optim.Adam semantics, no weight decay, no amsgrad).
  * replaces: optimizer.step() at run_pipeline_lightgcn.py:159.
  *   g   = grad[i] + (reg_w ? reg_w[row(i)] * p[i] : 0)

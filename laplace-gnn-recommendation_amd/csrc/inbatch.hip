@@ -1,0 +1,531 @@
+// In-batch sampled softmax for the LightGCN trainer (mi_inbatch_softmax_fwd_bwd_f32; the rule is in the header): the other
+// positives of a slot's group of G slots are its negatives.  The G x G scores of a group are products of 32 x 32 tiles on
+// the exact-f32 matrix instruction (v_mfma_f32_32x32x2_f32: bit for bit a k-ordered fmaf chain) and never leave the
+// registers; every pass that needs them computes them again.
+//   1. gather_kernel   the B user rows and B positive rows of final_emb become two contiguous [B, d] images (through
+//                      node_map when given); ids as int32, logq[pos_b] and the slot's L2 term beside them
+//   2. stats_kernel    one wavefront per 32 user slots: their scores against every 32-candidate tile of the group, masks
+//                      and - logq in registers, a running maximum and sum per lane -> lse[b] and the slot's loss term
+//   3. sweep_kernel    one wavefront per 32 OWNED slots, twice: the user rows of a tile (dL/df[users_b]) and the positive
+//                      rows of a tile (dL/df[pos_j]).  The owned rows sit on the lane (the B operand, staged once in LDS),
+//                      the other side's rows stream past as the A operand, so the score tile has the streamed row in its
+//                      16 registers and the owned slot on its lane: the coefficient tile is then the A operand of the
+//                      gradient product as it stands (the sum runs over the accumulator's row index), no transpose, no LDS.
+//                      One wavefront owns its 32 output rows for the whole sweep: one writer per slot row.
+//   4. refs / sort / chunk / combine   the 2B slot rows become rows of g_final: the sorted-reference segmented sum of
+//                      train.hip (bpr_chunk_kernel), with a slot row as each reference's only term; reg_w from the run lengths
+//   5. finish_kernel   loss = sum(term) / B + lambda * sum(reg), one block, fixed order
+// No float atomics; every order of summation is a function of (B, G, d) and the ids: two calls give equal bits.
+// k order of a score: lane half h takes the float4 chunks 2q + h of a row, q ascending, the four floats in order, and the
+// instruction adds half 0's product before half 1's.  The three passes share it, so they see the same score bits.
+#include "common.hpp"
+#include <cmath>
+#include <rocprim/rocprim.hpp>
+
+namespace {
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+constexpr int kTile = 32;        // slots per tile: the rows and the columns of the matrix instruction
+constexpr int kChunkBlock = 256;
+constexpr int kRefChunk = 64;    // references per chunk of the segmented sum
+constexpr int kMaxD = 256;
+constexpr int kMinGroup = 32, kMaxGroup = 4096;
+
+// row of the 32 x 32 accumulator that register `reg` of lane half h holds (the column is lane & 31)
+__device__ __forceinline__ int acc_row(int reg, int h) { return (reg & 3) + 8 * (reg >> 2) + 4 * h; }
+
+// ------------------------------------------------------------------ 1. gather ----------------------------------------------
+// one wavefront per slot, float4 lanes
+__global__ __launch_bounds__(256) void inbatch_gather_kernel(
+    int64_t batch, int d4, int64_t n_users, const int64_t* __restrict__ users, const int64_t* __restrict__ pos,
+    const float4* __restrict__ fin, int64_t ldf4, const float4* __restrict__ e0, int64_t lde4,
+    const int32_t* __restrict__ node_map, const float* __restrict__ logq, float4* __restrict__ u_img,
+    float4* __restrict__ v_img, int32_t* __restrict__ uid, int32_t* __restrict__ pid, float* __restrict__ lq,
+    float* __restrict__ reg_out) {
+    const int64_t b = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / MI_WAVE;
+    if (b >= batch) return;
+    const int lane = mi_lane();
+    const int64_t u = users[b], p = n_users + pos[b];
+    const float4* uf = fin + (node_map ? (int64_t)node_map[u] : u) * ldf4;
+    const float4* pf = fin + (node_map ? (int64_t)node_map[p] : p) * ldf4;
+    const float4* u0 = e0 + u * lde4;
+    const float4* p0 = e0 + p * lde4;
+    float rg = 0.f;
+    for (int e = lane; e < d4; e += MI_WAVE) {
+        u_img[b * d4 + e] = uf[e];
+        v_img[b * d4 + e] = pf[e];
+        const float4 x = u0[e], y = p0[e];
+        rg = fmaf(x.x, x.x, rg); rg = fmaf(x.y, x.y, rg); rg = fmaf(x.z, x.z, rg); rg = fmaf(x.w, x.w, rg);
+        rg = fmaf(y.x, y.x, rg); rg = fmaf(y.y, y.y, rg); rg = fmaf(y.z, y.z, rg); rg = fmaf(y.w, y.w, rg);
+    }
+    rg = mi_wave_sum(rg);
+    if (lane == 0) {
+        uid[b] = (int32_t)users[b];
+        pid[b] = (int32_t)pos[b];
+        lq[b] = logq ? logq[pos[b]] : 0.f;
+        reg_out[b] = rg;
+    }
+}
+
+// ------------------------------------------------------------------ score tiles --------------------------------------------
+// The owned tile in LDS: 32 rows of 2 nq float4 chunks (zero beyond the row's d4 chunks and beyond the batch), rows
+// 2 nq + 1 float4 apart so that the 16-byte reads of a half wavefront spread over the banks.
+__device__ __forceinline__ void load_owned_tile(float4* __restrict__ tile, const float4* __restrict__ img, int64_t row0,
+                                                int64_t batch, int d4, int nq) {
+    const int per_row = 2 * nq, stride = per_row + 1;
+    for (int i = mi_lane(); i < kTile * per_row; i += MI_WAVE) {
+        const int r = i / per_row, ch = i - r * per_row;
+        const bool in = row0 + r < batch && ch < d4;
+        tile[r * stride + ch] = in ? img[(row0 + r) * d4 + ch] : mi_f4_zero();
+    }
+}
+
+// acc[reg] = <streamed row row0 + acc_row(reg, h), owned row of lane & 31>.  The streamed rows are the A operand, read from
+// the image (a row past the batch reads as zero), the owned rows the B operand from LDS.
+__device__ __forceinline__ f32x16 score_tile(const float4* __restrict__ img, int64_t row0, int64_t batch, int d4, int nq,
+                                             const float4* __restrict__ tile) {
+    const int lane = mi_lane(), c = lane & 31, h = lane >> 5;
+    const bool live = row0 + c < batch;
+    const float4* ap = img + (live ? row0 + c : batch - 1) * d4;
+    const float4* bp = tile + c * (2 * nq + 1);
+    f32x16 acc;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+    for (int q = 0; q < nq; ++q) {
+        const int ch = 2 * q + h;
+        const float4 a = (live && ch < d4) ? ap[ch] : mi_f4_zero();
+        const float4 b = bp[ch];
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b.x, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, b.y, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, b.z, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, b.w, acc, 0, 0, 0);
+    }
+    return acc;
+}
+
+// ------------------------------------------------------------------ 2. row statistics --------------------------------------
+// One wavefront per 32 user slots.  Lane (c, h) keeps the running maximum and sum of user b0 + c over the candidates its
+// half sees (rows 4h..4h+3 of every 8 of each candidate tile, tiles ascending); the halves are merged at the end, half 0 first.
+__global__ __launch_bounds__(MI_WAVE) void inbatch_stats_kernel(
+    int64_t batch, int group, int d4, int nq, const float4* __restrict__ u_img, const float4* __restrict__ v_img,
+    const int32_t* __restrict__ uid, const int32_t* __restrict__ pid, const float* __restrict__ lq,
+    float* __restrict__ lse_out, float* __restrict__ term_out) {
+    extern __shared__ float4 tile[];
+    const int lane = mi_lane(), c = lane & 31, h = lane >> 5;
+    const int64_t b0 = (int64_t)blockIdx.x * kTile;
+    const int64_t g0 = b0 / group * group, g1 = min(g0 + group, batch);
+    load_owned_tile(tile, u_img, b0, batch, d4, nq);
+    __syncthreads();
+    const int64_t b = b0 + c;
+    const int64_t bb = min(b, batch - 1);
+    const int32_t my_u = uid[bb], my_p = pid[bb];
+    const float ninf = -INFINITY;
+    float m = ninf, s = 0.f, diag = ninf;
+    for (int64_t j0 = g0; j0 < g1; j0 += kTile) {
+        const f32x16 acc = score_tile(v_img, j0, batch, d4, nq, tile);
+        float x[16];
+        float tmax = ninf;
+#pragma unroll
+        for (int q4 = 0; q4 < 4; ++q4) {   // the arrays are padded to whole tiles: these reads stay inside them
+            const int64_t base = j0 + 8 * q4 + 4 * h;
+            const int4 pj = *reinterpret_cast<const int4*>(pid + base);
+            const int4 uj = *reinterpret_cast<const int4*>(uid + base);
+            const float4 lj = *reinterpret_cast<const float4*>(lq + base);
+            const int32_t pjs[4] = {pj.x, pj.y, pj.z, pj.w}, ujs[4] = {uj.x, uj.y, uj.z, uj.w};
+            const float ljs[4] = {lj.x, lj.y, lj.z, lj.w};
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int64_t j = base + i;
+                const float l = acc[4 * q4 + i] - ljs[i];
+                const bool out = j >= batch || (j != b && (pjs[i] == my_p || ujs[i] == my_u));
+                x[4 * q4 + i] = out ? ninf : l;
+                tmax = fmaxf(tmax, x[4 * q4 + i]);
+                if (j == b) diag = l;
+            }
+        }
+        if (tmax > ninf) {
+            const float mn = fmaxf(m, tmax);
+            s *= expf(m - mn);             // m = -inf: s is 0 and stays 0
+#pragma unroll
+            for (int i = 0; i < 16; ++i) s += expf(x[i] - mn);   // a masked candidate adds exp(-inf) = 0
+            m = mn;
+        }
+    }
+    const float mo = __shfl_xor(m, 32, MI_WAVE), so = __shfl_xor(s, 32, MI_WAVE);
+    const float m_lo = h ? mo : m, m_hi = h ? m : mo, s_lo = h ? so : s, s_hi = h ? s : so;
+    diag = fmaxf(diag, __shfl_xor(diag, 32, MI_WAVE));
+    if (b < batch && h == 0) {   // the slot itself is never masked: the maximum is finite
+        const float mx = fmaxf(m_lo, m_hi);
+        const float sum = s_lo * expf(m_lo - mx) + s_hi * expf(m_hi - mx);
+        const float lse = mx + logf(sum);
+        lse_out[b] = lse;
+        term_out[b] = lse - diag;
+    }
+}
+
+// ------------------------------------------------------------------ 3. gradient sweeps -------------------------------------
+// blockIdx.y = 0: the owned slots are users (dL/df[users_b] = sum_j c[b,j] f[pos_j], streamed rows = positives);
+// blockIdx.y = 1: the owned slots are positives (dL/df[pos_j] = sum_b c[b,j] f[users_b], streamed rows = users).
+// The coefficient tile cf has the streamed slot in its registers and the owned slot on its lane; step s of the gradient product
+// takes register s as the A operand (k = lane half h <-> streamed row acc_row(s, h)) and, as the B operand, 32 columns of
+// that streamed row: out[n][reg] += cf * row.  NT = the 32-column tiles of a row.
+template <int NT>
+__global__ __launch_bounds__(MI_WAVE) void inbatch_sweep_kernel(
+    int64_t batch, int group, int d, int nq, const float4* __restrict__ u_img, const float4* __restrict__ v_img,
+    const int32_t* __restrict__ uid, const int32_t* __restrict__ pid, const float* __restrict__ lq,
+    const float* __restrict__ lse, float w /* g_scale / B */, float* __restrict__ g_slot /* [2B, d]: users, positives */) {
+    extern __shared__ float4 tile[];
+    const int lane = mi_lane(), c = lane & 31, h = lane >> 5;
+    const int d4 = d / 4;
+    const bool own_user = blockIdx.y == 0;
+    const float4* own = own_user ? u_img : v_img;
+    const float4* str = own_user ? v_img : u_img;
+    const int64_t o0 = (int64_t)blockIdx.x * kTile;
+    const int64_t g0 = o0 / group * group, g1 = min(g0 + group, batch);
+    load_owned_tile(tile, own, o0, batch, d4, nq);
+    __syncthreads();
+    const int64_t o = o0 + c;
+    const int64_t oo = min(o, batch - 1);
+    const int32_t my_u = uid[oo], my_p = pid[oo];
+    const float my_lq = lq[oo], my_lse = lse[oo];
+    f32x16 out[NT];
+#pragma unroll
+    for (int n = 0; n < NT; ++n)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) out[n][i] = 0.f;
+    const float* strf = reinterpret_cast<const float*>(str);
+    for (int64_t r0 = g0; r0 < g1; r0 += kTile) {
+        const f32x16 acc = score_tile(str, r0, batch, d4, nq, tile);
+        f32x16 cf;
+#pragma unroll
+        for (int q4 = 0; q4 < 4; ++q4) {
+            const int64_t base = r0 + 8 * q4 + 4 * h;
+            const int4 pr = *reinterpret_cast<const int4*>(pid + base);
+            const int4 ur = *reinterpret_cast<const int4*>(uid + base);
+            const float4 lr = *reinterpret_cast<const float4*>(lq + base);
+            const float4 sr = *reinterpret_cast<const float4*>(lse + base);
+            const int32_t prs[4] = {pr.x, pr.y, pr.z, pr.w}, urs[4] = {ur.x, ur.y, ur.z, ur.w};
+            const float lrs[4] = {lr.x, lr.y, lr.z, lr.w}, srs[4] = {sr.x, sr.y, sr.z, sr.w};
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int64_t r = base + i;
+                // the logit as stats_kernel formed it: score - logq[candidate's item]; then the user's lse
+                const float l = acc[4 * q4 + i] - (own_user ? lrs[i] : my_lq);
+                const float e = expf(l - (own_user ? my_lse : srs[i]));
+                const bool outside = r >= batch || o >= batch || (r != o && (prs[i] == my_p || urs[i] == my_u));
+                cf[4 * q4 + i] = outside ? 0.f : w * (e - (r == o ? 1.f : 0.f));
+            }
+        }
+#pragma unroll
+        for (int s = 0; s < 16; ++s) {
+            const int64_t r = r0 + acc_row(s, h);
+            const bool live = r < batch;
+            const float* row = strf + (live ? r : batch - 1) * d;
+#pragma unroll
+            for (int n = 0; n < NT; ++n) {
+                const int k = n * 32 + c;
+                const float x = (live && k < d) ? row[k] : 0.f;
+                out[n] = __builtin_amdgcn_mfma_f32_32x32x2f32(cf[s], x, out[n], 0, 0, 0);
+            }
+        }
+    }
+    float* dst = g_slot + (own_user ? 0 : batch * d);
+#pragma unroll
+    for (int n = 0; n < NT; ++n) {
+        const int k = n * 32 + c;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const int64_t orow = o0 + acc_row(i, h);
+            if (orow < batch && k < d) dst[orow * d + k] = out[n][i];
+        }
+    }
+}
+
+// ------------------------------------------------------------------ 4. slot rows -> node rows ------------------------------
+__global__ void inbatch_refs_kernel(int64_t batch, int64_t n_users, const int64_t* __restrict__ users,
+                                    const int64_t* __restrict__ pos, const int32_t* __restrict__ node_map,
+                                    uint32_t* __restrict__ keys, uint32_t* __restrict__ refs) {
+    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;   // reference id = role * batch + b = its row of g_slot
+    if (r >= 2 * batch) return;
+    const int64_t node = r < batch ? users[r] : n_users + pos[r - batch];
+    keys[r] = (uint32_t)(node_map ? node_map[node] : node);
+    refs[r] = (uint32_t)r;
+}
+
+// bpr_chunk_kernel (train.hip) with one term per reference, the slot row itself: one wavefront per chunk of 64 sorted
+// references; a run of equal keys inside the chunk is summed in order and stored by this wavefront alone, a run that crosses
+// chunk borders leaves a head / tail partial for combine_kernel.
+template <int VPT>  // floats of a row per lane: ceil(d / 64)
+__global__ __launch_bounds__(kChunkBlock) void inbatch_chunk_kernel(
+    int64_t batch, int d, int64_t n_users, const int64_t* __restrict__ users, const int64_t* __restrict__ pos,
+    const float* __restrict__ g_slot, const uint32_t* __restrict__ keys, const uint32_t* __restrict__ refs,
+    float* __restrict__ g_final, int64_t ldg, float* __restrict__ part_head, float* __restrict__ part_tail,
+    float* __restrict__ reg_w, float reg_unit /* 2 * lambda * reg_scale: one reference's share */) {
+    const int64_t n_ref = 2 * batch;
+    const int64_t chunk = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / MI_WAVE;
+    const int64_t j0 = chunk * kRefChunk;
+    if (j0 >= n_ref) return;
+    const int lane = mi_lane();
+    const int n_here = (int)min((int64_t)kRefChunk, n_ref - j0);
+    uint32_t my_key = 0xFFFFFFFFu;
+    int64_t my_src = 0;
+    if (lane < n_here) {
+        my_key = keys[j0 + lane];
+        my_src = refs[j0 + lane];
+        // the reference that opens the node's run finds the run's end by bisection and is the entry's only writer
+        if (reg_w) {
+            const int64_t j = j0 + lane;
+            if (j == 0 || keys[j - 1] != my_key) {
+                int64_t lo = j + 1, hi = n_ref;   // first position in (j, n_ref] whose key differs
+                while (lo < hi) {
+                    const int64_t mid = (lo + hi) >> 1;
+                    if (keys[mid] == my_key) lo = mid + 1; else hi = mid;
+                }
+                const int64_t node = my_src < batch ? users[my_src] : n_users + pos[my_src - batch];
+                reg_w[node] = (float)(lo - j) * reg_unit;
+            }
+        }
+    }
+    const bool head_open = j0 > 0 && keys[j0 - 1] == __shfl(my_key, 0, MI_WAVE);
+    const bool next_same = (j0 + n_here < n_ref) && keys[j0 + n_here] == __shfl(my_key, n_here - 1, MI_WAVE);
+    float acc[VPT];
+#pragma unroll
+    for (int v = 0; v < VPT; ++v) acc[v] = 0.f;
+    int run_start = 0;
+    constexpr int U = 8;  // references whose rows are in flight together
+    for (int q0 = 0; q0 < n_here; q0 += U) {
+        float x[U][VPT];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int q = min(q0 + u, n_here - 1);
+            const bool live = q0 + u < n_here;
+            const float* row = g_slot + __shfl(my_src, q, MI_WAVE) * d;
+#pragma unroll
+            for (int v = 0; v < VPT; ++v) {
+                const int k = lane + v * MI_WAVE;
+                x[u][v] = (live && k < d) ? row[k] : 0.f;
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int q = q0 + u;
+            if (q >= n_here) break;
+            const uint32_t kq = __shfl(my_key, q, MI_WAVE);
+#pragma unroll
+            for (int v = 0; v < VPT; ++v) acc[v] += x[u][v];
+            const bool last_of_run = (q + 1 == n_here) || __shfl(my_key, q + 1, MI_WAVE) != kq;
+            if (!last_of_run) continue;
+            const bool from_prev = run_start == 0 && head_open;
+            const bool into_next = (q + 1 == n_here) && next_same;
+            float* dst;
+            if (from_prev) dst = part_head + chunk * d;          // finished by the chunk where the run starts
+            else if (into_next) dst = part_tail + chunk * d;     // this chunk starts the run; the combine finishes it
+            else dst = g_final + (int64_t)kq * ldg;              // the run lies inside this chunk: the row's only writer
+#pragma unroll
+            for (int v = 0; v < VPT; ++v) {
+                const int k = lane + v * MI_WAVE;
+                if (k < d) dst[k] = acc[v];   // g_final is zero on entry (header contract): a store
+                acc[v] = 0.f;
+            }
+            run_start = q + 1;
+        }
+    }
+}
+
+// One wavefront per chunk whose trailing run starts in it and runs on: tail partial + the head partials of the following
+// chunks, in chunk order (bpr_combine_kernel of train.hip).
+template <int VPT>
+__global__ __launch_bounds__(kChunkBlock) void inbatch_combine_kernel(int64_t n_ref, int d, const uint32_t* __restrict__ keys,
+                                                                      const float* __restrict__ part_head,
+                                                                      const float* __restrict__ part_tail,
+                                                                      float* __restrict__ g_final, int64_t ldg) {
+    const int64_t chunk = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / MI_WAVE;
+    const int64_t j0 = chunk * kRefChunk;
+    if (j0 >= n_ref) return;
+    const int64_t j_last = min(j0 + kRefChunk, n_ref) - 1;
+    if (j_last + 1 >= n_ref) return;                       // nothing after this chunk
+    const uint32_t row = keys[j_last];
+    if (keys[j_last + 1] != row) return;                   // the trailing run ends here
+    if (keys[j0] == row && j0 > 0 && keys[j0 - 1] == row) return;  // the run started in an earlier chunk: not the owner
+    const int lane = mi_lane();
+    float acc[VPT];
+#pragma unroll
+    for (int v = 0; v < VPT; ++v) {
+        const int k = lane + v * MI_WAVE;
+        acc[v] = k < d ? part_tail[chunk * d + k] : 0.f;
+    }
+    for (int64_t nb = chunk + 1; nb * kRefChunk < n_ref && keys[nb * kRefChunk] == row; ++nb) {
+#pragma unroll
+        for (int v = 0; v < VPT; ++v) {
+            const int k = lane + v * MI_WAVE;
+            if (k < d) acc[v] += part_head[nb * d + k];
+        }
+        if (keys[min((nb + 1) * kRefChunk, n_ref) - 1] != row) break;   // the run ends inside chunk nb
+    }
+    float* dst = g_final + (int64_t)row * ldg;
+#pragma unroll
+    for (int v = 0; v < VPT; ++v) {
+        const int k = lane + v * MI_WAVE;
+        if (k < d) dst[k] = acc[v];
+    }
+}
+
+// ------------------------------------------------------------------ 5. loss ------------------------------------------------
+// Single block, fixed order (bpr_finish_kernel's scheme): loss = sum(term) / B + lambda * sum(reg).
+__global__ __launch_bounds__(1024) void inbatch_finish_kernel(int64_t batch, const float* __restrict__ term_v,
+                                                              const float* __restrict__ reg_v, float inv_batch, float lambda,
+                                                              float* __restrict__ loss_out) {
+    __shared__ float sh_a[1024];
+    __shared__ float sh_b[1024];
+    const int t = threadIdx.x;
+    float a = 0.f, r = 0.f;
+#pragma unroll 4
+    for (int64_t i = t; i < batch; i += 1024) {
+        a += term_v[i];
+        r += reg_v[i];
+    }
+    sh_a[t] = a;
+    sh_b[t] = r;
+    __syncthreads();
+    for (int s = 512; s > 0; s >>= 1) {
+        if (t < s) {
+            sh_a[t] += sh_a[t + s];
+            sh_b[t] += sh_b[t + s];
+        }
+        __syncthreads();
+    }
+    if (t == 0) loss_out[0] = sh_a[0] * inv_batch + lambda * sh_b[0];
+}
+
+// ------------------------------------------------------------------ host ---------------------------------------------------
+bool args_in_range(int64_t batch, int64_t d, int32_t group) {
+    return batch >= 1 && 2 * batch < INT32_MAX && d >= 4 && d % 4 == 0 && d <= kMaxD && group >= kMinGroup &&
+           group <= kMaxGroup && group % kTile == 0;
+}
+
+size_t sort_tmp_bytes(int64_t n_ref) { return ((size_t)1 << 20) + mi_align_up((size_t)n_ref * 2, 256); }
+
+struct Workspace {
+    float *u_img, *v_img, *g_slot, *lq, *lse, *term, *reg, *part_head, *part_tail;
+    int32_t *uid, *pid;
+    uint32_t *k0, *k1, *r0, *r1;
+    char* tmp;
+    size_t tmp_cap;
+    bool ok() const {
+        return u_img && v_img && g_slot && lq && lse && term && reg && part_head && part_tail && uid && pid && k0 && k1 &&
+               r0 && r1 && tmp;
+    }
+};
+
+Workspace carve(MiArena& a, int64_t batch, int64_t d) {
+    const size_t b = (size_t)batch, bp = (size_t)mi_ceil_div(batch, kTile) * kTile;   // id and statistic arrays: whole tiles
+    const size_t n_ref = 2 * b, chunks = (size_t)mi_ceil_div((int64_t)n_ref, kRefChunk);
+    Workspace w;
+    w.u_img = a.take<float>(b * d);
+    w.v_img = a.take<float>(b * d);
+    w.g_slot = a.take<float>(n_ref * d);
+    w.uid = a.take<int32_t>(bp);
+    w.pid = a.take<int32_t>(bp);
+    w.lq = a.take<float>(bp);
+    w.lse = a.take<float>(bp);
+    w.term = a.take<float>(bp);
+    w.reg = a.take<float>(bp);
+    w.k0 = a.take<uint32_t>(n_ref);
+    w.k1 = a.take<uint32_t>(n_ref);
+    w.r0 = a.take<uint32_t>(n_ref);
+    w.r1 = a.take<uint32_t>(n_ref);
+    w.tmp_cap = sort_tmp_bytes((int64_t)n_ref);
+    w.tmp = a.take<char>(w.tmp_cap);
+    w.part_head = a.take<float>(chunks * d);
+    w.part_tail = a.take<float>(chunks * d);
+    return w;
+}
+
+template <class F>   // f(std::integral_constant<int, N>), N = 1, 2, 4 or 8 >= n
+void with_pow2(int64_t n, F&& f) {
+    if (n <= 1) f(std::integral_constant<int, 1>{});
+    else if (n <= 2) f(std::integral_constant<int, 2>{});
+    else if (n <= 4) f(std::integral_constant<int, 4>{});
+    else f(std::integral_constant<int, 8>{});
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t mi_inbatch_softmax_workspace_bytes(int64_t batch, int64_t d, int32_t group) {
+    if (!args_in_range(batch, d, group)) return 0;
+    const size_t b = (size_t)batch, bp = (size_t)mi_ceil_div(batch, kTile) * kTile;
+    const size_t n_ref = 2 * b, chunks = (size_t)mi_ceil_div((int64_t)n_ref, kRefChunk);
+    return 2 * mi_align_up(b * d * sizeof(float), 256) + mi_align_up(n_ref * d * sizeof(float), 256) +
+           6 * mi_align_up(bp * sizeof(float), 256) + 4 * mi_align_up(n_ref * sizeof(uint32_t), 256) +
+           mi_align_up(sort_tmp_bytes((int64_t)n_ref), 256) + 2 * mi_align_up(chunks * d * sizeof(float), 256);
+}
+
+int mi_inbatch_softmax_fwd_bwd_f32(int64_t batch, int32_t group, int64_t d, int64_t n_users, const int64_t* users,
+                                   const int64_t* pos, const float* final_emb, int64_t ldf, const float* e0, int64_t lde,
+                                   float lambda, float g_scale, float reg_scale, float* loss_out, float* g_final,
+                                   int64_t ldg, float* reg_w, const int32_t* node_map, const float* logq, void* ws,
+                                   size_t ws_bytes, mi_stream_t stream) {
+    MI_CHECK_ARG(batch >= 1 && d > 0 && n_users >= 0);
+    if (d % 4 != 0 || d > kMaxD) return MI_ERR_UNSUPPORTED;
+    MI_CHECK_ARG(group >= kMinGroup && group <= kMaxGroup && group % kTile == 0);
+    if (!g_final && reg_w) return MI_ERR_UNSUPPORTED;   // the loss-only form has no reference list to count the nodes from
+    if (2 * batch >= INT32_MAX) return MI_ERR_TOO_LARGE;
+    MI_CHECK_ARG(users && pos && final_emb && e0 && loss_out && ws);
+    MI_CHECK_ARG(ldf >= d && lde >= d && ldf % 4 == 0 && lde % 4 == 0 && (!g_final || ldg >= d));
+    MI_CHECK_ARG(mi_aligned16(final_emb) && mi_aligned16(e0) && mi_aligned16(ws));
+    MI_CHECK_ARG(((uintptr_t)users | (uintptr_t)pos) % 8 == 0);
+    MI_CHECK_ARG(((uintptr_t)loss_out | (uintptr_t)g_final | (uintptr_t)reg_w | (uintptr_t)node_map | (uintptr_t)logq) % 4 == 0);
+    if (ws_bytes < mi_inbatch_softmax_workspace_bytes(batch, d, group)) return MI_ERR_WORKSPACE;
+    MiArena arena(ws, ws_bytes);
+    const Workspace w = carve(arena, batch, d);
+    if (!w.ok()) return MI_ERR_WORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t n_ref = 2 * batch, n_chunks = mi_ceil_div(n_ref, kRefChunk), n_tiles = mi_ceil_div(batch, kTile);
+    const int d4 = (int)(d / 4), nq = (d4 + 1) / 2;
+    const size_t lds = (size_t)kTile * (2 * nq + 1) * sizeof(float4);   // 33 280 bytes at d = 256
+    rocprim::double_buffer<uint32_t> keys(w.k0, w.k1), refs(w.r0, w.r1);
+    unsigned bits = 32;   // compact slots are < 2B; node ids need all 32 bits
+    size_t need = 0;
+    if (g_final) {
+        if (node_map) bits = mi_bits_for(n_ref);
+        MI_HIP(rocprim::radix_sort_pairs(nullptr, need, keys, refs, (size_t)n_ref, 0, bits, s));
+        if (need > w.tmp_cap) return MI_ERR_WORKSPACE;
+    }
+    // ---- nothing has been enqueued up to here ----
+    const float4* u_img = reinterpret_cast<const float4*>(w.u_img);
+    const float4* v_img = reinterpret_cast<const float4*>(w.v_img);
+    hipLaunchKernelGGL(inbatch_gather_kernel, dim3((unsigned)mi_ceil_div(batch * MI_WAVE, 256)), dim3(256), 0, s, batch, d4,
+                       n_users, users, pos, reinterpret_cast<const float4*>(final_emb), ldf / 4,
+                       reinterpret_cast<const float4*>(e0), lde / 4, node_map, logq, reinterpret_cast<float4*>(w.u_img),
+                       reinterpret_cast<float4*>(w.v_img), w.uid, w.pid, w.lq, w.reg);
+    hipLaunchKernelGGL(inbatch_stats_kernel, dim3((unsigned)n_tiles), dim3(MI_WAVE), lds, s, batch, (int)group, d4, nq, u_img,
+                       v_img, w.uid, w.pid, w.lq, w.lse, w.term);
+    if (g_final) {
+        const float wgt = g_scale / (float)batch;
+        with_pow2(mi_ceil_div(d, 32), [&](auto nt) {
+            constexpr int NT = decltype(nt)::value;
+            hipLaunchKernelGGL(inbatch_sweep_kernel<NT>, dim3((unsigned)n_tiles, 2), dim3(MI_WAVE), lds, s, batch, (int)group,
+                               (int)d, nq, u_img, v_img, w.uid, w.pid, w.lq, w.lse, wgt, w.g_slot);
+        });
+        hipLaunchKernelGGL(inbatch_refs_kernel, dim3((unsigned)mi_ceil_div(n_ref, 256)), dim3(256), 0, s, batch, n_users, users,
+                           pos, node_map, w.k0, w.r0);
+        MI_HIP(rocprim::radix_sort_pairs(w.tmp, need, keys, refs, (size_t)n_ref, 0, bits, s));
+        const dim3 gc((unsigned)mi_ceil_div(n_chunks * MI_WAVE, kChunkBlock));
+        with_pow2(mi_ceil_div(d, MI_WAVE), [&](auto vpt) {
+            constexpr int V = decltype(vpt)::value < 4 ? decltype(vpt)::value : 4;   // d <= 256
+            hipLaunchKernelGGL(inbatch_chunk_kernel<V>, gc, dim3(kChunkBlock), 0, s, batch, (int)d, n_users, users, pos,
+                               w.g_slot, keys.current(), refs.current(), g_final, ldg, w.part_head, w.part_tail, reg_w,
+                               2.0f * reg_scale * lambda);
+            hipLaunchKernelGGL(inbatch_combine_kernel<V>, gc, dim3(kChunkBlock), 0, s, n_ref, (int)d, keys.current(),
+                               w.part_head, w.part_tail, g_final, ldg);
+        });
+    }
+    hipLaunchKernelGGL(inbatch_finish_kernel, dim3(1), dim3(1024), 0, s, batch, w.term, w.reg, 1.0f / (float)batch, lambda,
+                       loss_out);
+    return mi_launch_status();
+}
+
+}  // extern "C"

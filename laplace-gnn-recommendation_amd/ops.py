@@ -997,6 +997,58 @@ def bpr_fwd_bwd(users: Tensor, pos: Tensor, neg: Tensor, final_emb: Tensor, e0: 
                              g_scale=g_scale, reg_scale=reg_scale, loss_out=loss_out, node_map=node_map, _bpr_entry=True)
 
 
+INBATCH_MAX_D = 256   # kMaxD of csrc/inbatch.hip
+
+
+def check_inbatch_group(group: int) -> int:
+    if not isinstance(group, int) or isinstance(group, bool) or not 32 <= group <= 4096 or group % 32:
+        raise ValueError(f"group must be an integer multiple of 32 in 32..4096, got {group!r}")
+    return group
+
+
+def inbatch_softmax_fwd_bwd(users: Tensor, pos: Tensor, final_emb: Tensor, e0: Tensor, n_users: int, lambda_val: float, *,
+                            group: int = 1024, logq: Optional[Tensor] = None, g_final: Optional[Tensor] = None,
+                            reg_w: Optional[Tensor] = None, g_scale: float = 1.0, reg_scale: float = 1.0,
+                            loss_out: Optional[Tensor] = None, node_map: Optional[Tensor] = None) -> Tensor:
+    """In-batch sampled softmax (include/laplace_hip.h, "In-batch sampled softmax"): the candidates of slot b are the
+    positives of its group of `group` consecutive slots, minus those that name slot b's item or belong to slot b's user;
+    logq (float32, one entry per item of e0, by item id) is subtracted from the logits.  Conventions of rank_loss_fwd_bwd;
+    the loss-only form (no g_final) takes no reg_w."""
+    check_inbatch_group(group)
+    if final_emb.dim() != 2:
+        raise ValueError("final_emb: a 2-D table expected")
+    d = int(final_emb.shape[1])
+    if d < 4 or d % 4 or d > INBATCH_MAX_D:
+        raise ValueError(f"the in-batch softmax needs d % 4 == 0 and d <= {INBATCH_MAX_D}, got d = {d}")
+    batch = users.numel()
+    if batch < 1 or pos.numel() != batch:
+        raise ValueError("users [B], pos [B] expected, B >= 1")
+    if g_final is None and reg_w is not None:
+        raise ValueError("the loss-only form takes no reg_w (pass g_final, or leave reg_w out)")
+    for n, x in (("users", users), ("pos", pos)):
+        _need(x, t.int64, n)
+    ldf = _rows_ok(final_emb, "final_emb")
+    lde = _rows_ok(e0, "e0")
+    ldg = _rows_ok(g_final, "g_final") if g_final is not None else 0
+    if reg_w is not None:
+        _need(reg_w, t.float32, "reg_w")
+    if logq is not None:
+        _need(logq, t.float32, "logq")
+        if logq.dim() != 1 or logq.numel() != e0.shape[0] - n_users:
+            raise ValueError(f"logq: one entry per item expected ({e0.shape[0] - n_users}), got shape {tuple(logq.shape)}")
+    dev = final_emb.device
+    if loss_out is None:
+        loss_out = t.empty(1, dtype=t.float32, device=dev)
+    L = _lib.lib()
+    ws = _ws(L.mi_inbatch_softmax_workspace_bytes(batch, d, group), dev)
+    check(L.mi_inbatch_softmax_fwd_bwd_f32(batch, group, d, n_users, _ptr(users), _ptr(pos), final_emb.data_ptr(), ldf,
+                                           e0.data_ptr(), lde, float(lambda_val), float(g_scale), float(reg_scale),
+                                           loss_out.data_ptr(), _ptr(g_final), ldg, _ptr(reg_w), _ptr(node_map),
+                                           _ptr(logq), ws.data_ptr(), ws.numel(), _stream()),
+          "mi_inbatch_softmax_fwd_bwd_f32")
+    return loss_out
+
+
 def adam_step(p: Tensor, grad: Tensor, m: Tensor, v: Tensor, *, step: int, lr: float, beta1: float = 0.9,
               beta2: float = 0.999, eps: float = 1e-8, reg_w: Optional[Tensor] = None) -> None:
     """a9 — dense Adam (torch.optim.Adam semantics) in one pass."""

@@ -5,7 +5,9 @@ the GPU and no host round trip.
     sample    B edges + structured negatives on device               data/lightgcn_loader.py:95-112
     loss      gathers + BPR forward/backward in one kernel           run_pipeline_lightgcn.py:133-155
               (objective="bpr" / "softmax" and n_neg = M <= 16 negatives per positive: opt-in, SURVEY F9;
-               negatives="popularity": negatives drawn ∝ degree ** neg_power, and with the softmax the logQ correction)
+               negatives="popularity": negatives drawn ∝ degree ** neg_power, and with the softmax the logQ correction;
+               negatives="in_batch": no negative is drawn, the other positives of a slot's group of in_batch_group slots
+               are its negatives, scored on the f32 matrix cores — mi_inbatch_softmax_fwd_bwd_f32)
     backward  K SpMM launches on A^T, G/(K+1) folded in as addend    (autograd of the forward)
     update    dense Adam over the whole table, L2 term folded in     run_pipeline_lightgcn.py:157-159
 
@@ -60,7 +62,7 @@ def _lib_bytes_batch_nodes(n_nodes: int) -> int:
     return int(_lib.lib().mi_batch_nodes_workspace_bytes(n_nodes))
 
 
-NEGATIVES = ("uniform", "popularity")
+NEGATIVES = ("uniform", "popularity", "in_batch")
 
 
 class LightGCNTrainer:
@@ -69,10 +71,16 @@ class LightGCNTrainer:
                  neg_range: Optional[int] = None, reference_sampler_quirks: bool = False,
                  sparse_batch: bool = True, fuse_adam: bool = True, reorder: Optional[bool] = None,
                  objective: str = "reference", n_neg: int = 1, negatives: str = "uniform", neg_power: float = 0.75,
-                 logq_correction: Optional[bool] = None):
+                 logq_correction: Optional[bool] = None, in_batch_group: int = 1024):
         """negatives="popularity": negatives drawn ∝ (training degree) ** neg_power from `neg_table`, built in the id space
         the kernels train in.  logq_correction: the softmax's logits become s - log q(item); None = on iff
-        objective == "softmax" and negatives == "popularity".  The defaults launch the step as it was."""
+        objective == "softmax" and negatives != "uniform".  The defaults launch the step as it was.
+        negatives="in_batch" (objective="softmax", n_neg = 1: nothing is drawn): the candidates of a slot are the positives of
+        its group of in_batch_group consecutive slots (a multiple of 32 in 32..4096), minus those that name the slot's own item
+        or belong to its user; the user's other items in the group are NOT rejected.  The batch is the uniform sampler's edge
+        stream — users and pos at a (seed, step) are the bits a negatives="uniform" trainer draws; the negative it draws as
+        well is ignored.  The logQ correction's proposal is "the item of a uniformly drawn training edge", q ∝ training degree
+        (ops.negative_table(degree, 1.0)); neg_power is not used.  step(batch) takes (users, pos); a third entry is ignored."""
         ops.rank_objective_code(objective)   # ValueError for an unknown name
         ops.check_n_neg(n_neg)
         if negatives not in NEGATIVES:
@@ -80,7 +88,7 @@ class LightGCNTrainer:
         if isinstance(neg_power, bool) or not isinstance(neg_power, (int, float)) or not 0.0 <= neg_power <= 1.0:
             raise ValueError(f"neg_power must be a number in [0, 1], got {neg_power!r}")
         if logq_correction is None:
-            logq_correction = objective == "softmax" and negatives == "popularity"
+            logq_correction = objective == "softmax" and negatives in ("popularity", "in_batch")
         elif logq_correction and objective != "softmax":
             raise ValueError(f"logq_correction corrects the sampled softmax, not objective={objective!r}")
         if negatives == "popularity":
@@ -88,6 +96,18 @@ class LightGCNTrainer:
                 raise ValueError('negatives="popularity" does not combine with reference_sampler_quirks')
             if neg_range is not None and int(neg_range) != model.num_items:
                 raise ValueError(f'negatives="popularity" draws from every item: neg_range {neg_range} != {model.num_items}')
+        if negatives == "in_batch":
+            ops.check_inbatch_group(in_batch_group)
+            if objective != "softmax":
+                raise ValueError(f'negatives="in_batch" is a sampled softmax: objective="softmax" expected, got {objective!r}')
+            if n_neg != 1:
+                raise ValueError(f'negatives="in_batch" draws nothing: n_neg stays 1, got {n_neg}')
+            if reference_sampler_quirks:
+                raise ValueError('negatives="in_batch" does not combine with reference_sampler_quirks')
+            if neg_range is not None and int(neg_range) != model.num_items:
+                raise ValueError(f'negatives="in_batch" takes its negatives from the batch: neg_range {neg_range} != {model.num_items}')
+        self.in_batch = negatives == "in_batch"
+        self.in_batch_group = int(in_batch_group) if self.in_batch else None
         self.objective, self.n_neg = objective, n_neg
         self.negatives, self.neg_power, self.logq_correction = negatives, float(neg_power), bool(logq_correction)
         self.model = model
@@ -156,7 +176,10 @@ class LightGCNTrainer:
         if self.negatives == "popularity":
             degree = t.bincount(self._r.col.long(), minlength=train.num_items)
             self.neg_table = ops.negative_table(degree, self.neg_power, device=dev)
-        if self.logq_correction:   # uniform negatives: q = 1 / neg_range for every item
+        if self.logq_correction and self.in_batch:   # the item of a uniformly drawn training edge: q ∝ degree
+            degree = t.bincount(self._r.col.long(), minlength=train.num_items)
+            self.logq = ops.negative_table(degree, 1.0, device=dev).logq
+        elif self.logq_correction:   # uniform negatives: q = 1 / neg_range for every item
             self.logq = (self.neg_table.logq if self.neg_table is not None
                          else t.full((train.num_items,), -math.log(self.neg_range), dtype=t.float32, device=dev))
 
@@ -176,6 +199,11 @@ class LightGCNTrainer:
     finish = to_original_order
 
     def _ids_to_training(self, batch):
+        if self.in_batch:   # (users, pos); a third entry is ignored, and pos stands in for it (the node set's third column)
+            users, pos = batch[0], batch[1]
+            if self.order is not None:
+                users, pos = self.order.user_new_of_old[users], self.order.item_new_of_old[pos]
+            return users, pos, pos
         users, pos, neg = batch
         if self.n_neg > 1 and (neg.dim() != 2 or neg.shape[1] != self.n_neg):
             raise ValueError(f"batch: neg [B, {self.n_neg}] expected, got {list(neg.shape)}")
@@ -198,8 +226,17 @@ class LightGCNTrainer:
 
     def _loss(self, users, pos, neg, final, **kw) -> None:
         """Loss and its gradient on `final` (self.logq is None without the logQ correction)."""
+        if self.in_batch:
+            ops.inbatch_softmax_fwd_bwd(users, pos, final, self.table, self.model.num_users, self.Lambda,
+                                        group=self.in_batch_group, reg_w=self.reg_w, loss_out=self.loss, logq=self.logq, **kw)
+            return
         ops.rank_loss_fwd_bwd(users, pos, neg, final, self.table, self.model.num_users, self.Lambda,
                               objective=self.objective, reg_w=self.reg_w, loss_out=self.loss, logq=self.logq, **kw)
+
+    def _batch(self) -> Tuple[Tensor, Tensor, Tensor]:
+        """The step's own batch: _sample(), with pos in place of the drawn negatives when they come from the batch."""
+        users, pos, neg = self._sample()
+        return (users, pos, pos) if self.in_batch else (users, pos, neg)
 
     def sample(self) -> Tuple[Tensor, Tensor, Tensor]:
         """(users, pos, neg) of the next step's batch, ORIGINAL ids."""
@@ -216,7 +253,7 @@ class LightGCNTrainer:
             return self._step_sparse(batch)
         K = self.K
         self.forward()
-        users, pos, neg = batch if batch is not None else self._sample()
+        users, pos, neg = batch if batch is not None else self._batch()
         self.gc.zero_()
         self.reg_w.zero_()
         self._loss(users, pos, neg, self.final, g_final=self.gc, g_scale=1.0 / (K + 1))
@@ -228,7 +265,7 @@ class LightGCNTrainer:
 
     def _step_sparse(self, batch: Optional[Tuple[Tensor, Tensor, Tensor]]) -> Tensor:
         K, tab, adj, adj_t = self.K, self.table, self.adj_fwd, self.adj_bwd
-        users, pos, neg = batch if batch is not None else self._sample()
+        users, pos, neg = batch if batch is not None else self._batch()
         if users.numel() != self.batch_size:
             raise ValueError("batch size differs from the trainer's")
         gmap, nodes, cnt2 = ops.batch_nodes(users, pos, neg, self.model.num_users, tab.shape[0], gmap=self.gmap,

@@ -111,6 +111,73 @@ def ranking_loss(users_emb_final: Tensor, users_emb_0: Tensor, pos_items_emb_fin
                                 float(lambda_val), objective, table)
 
 
+class _InBatchSoftmaxFn(t.autograd.Function):
+    """in_batch_softmax_loss over gathered blocks through mi_inbatch_softmax_fwd_bwd_f32.  The entry knows a slot's user
+    and item by the row it reads, so the blocks become one table row per DISTINCT id (the block row of the id's first
+    slot); the gradient of an id comes back whole at that slot and zero at its other slots, which is what the backward of
+    the gather that made the blocks adds up."""
+
+    @staticmethod
+    def forward(ctx, uf, u0, pf, p0, lambda_val: float, uinv, ufirst, iinv, ifirst, logq, group: int):
+        B = uf.shape[0]
+        nu = ufirst.numel()
+        final = t.cat([uf[ufirst], pf[ifirst]]).contiguous()
+        e0 = t.cat([u0[ufirst], p0[ifirst]]).contiguous()
+        table = None if logq is None else logq.detach().reshape(B).to(t.float32)[ifirst].contiguous()
+        g_final = t.zeros_like(final)
+        reg_w = t.zeros(final.shape[0], device=uf.device)
+        loss = ops.inbatch_softmax_fwd_bwd(uinv, iinv, final, e0, nu, lambda_val, group=group, logq=table,
+                                           g_final=g_final, reg_w=reg_w)
+        ctx.save_for_backward(g_final, reg_w, e0, ufirst, ifirst)
+        ctx.B = B
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        g_final, reg_w, e0, ufirst, ifirst = ctx.saved_tensors
+        B, nu = ctx.B, ufirst.numel()
+        gf = g_final * grad_out
+        g0 = (reg_w[:, None] * e0) * grad_out
+        outs = []
+        for g, first in ((gf[:nu], ufirst), (g0[:nu], ufirst), (gf[nu:], ifirst), (g0[nu:], ifirst)):
+            full = g.new_zeros(B, g.shape[1])
+            full[first] = g
+            outs.append(full)
+        return (*outs, None, None, None, None, None, None, None)
+
+
+def _first_slots(ids: Optional[Tensor], B: int, device):
+    """(inverse [B], first [n_distinct]): the distinct-id number of every slot and the first slot of every distinct id."""
+    if ids is None:
+        a = t.arange(B, device=device)
+        return a, a
+    if ids.numel() != B:
+        raise ValueError(f"ids: one per slot expected ({B}), got {ids.numel()}")
+    uniq, inv = t.unique(ids.reshape(B), return_inverse=True)
+    first = t.full((uniq.numel(),), B, dtype=t.int64, device=ids.device)
+    first.scatter_reduce_(0, inv, t.arange(B, device=ids.device), reduce="amin")
+    return inv.contiguous(), first
+
+
+def in_batch_softmax_loss(users_emb_final: Tensor, users_emb_0: Tensor, pos_items_emb_final: Tensor, pos_items_emb_0: Tensor,
+                          lambda_val: float, *, user_ids: Optional[Tensor] = None, item_ids: Optional[Tensor] = None,
+                          logq: Optional[Tensor] = None, group: int = 1024) -> Tensor:
+    """The sampled softmax with in-batch negatives: slot b's candidates are the positives of its group of `group`
+    consecutive slots, with the logit <u_b, p_j> - logq[j]; a candidate with slot b's item id or slot b's user id is left out
+    (ids default to arange: no masks).  The user's other items that happen to be in the group are not rejected — the usual
+    approximation.  logq [B]: log-probability of each slot's positive under the batch's proposal (float32 constants).
+    Slots with equal ids must carry equal rows (blocks gathered from one table)."""
+    ops.check_inbatch_group(group)
+    B = int(users_emb_final.shape[0])
+    if logq is not None and logq.numel() != B:
+        raise ValueError(f"logq: [{B}] expected, got {tuple(logq.shape)}")
+    dev = users_emb_final.device
+    uinv, ufirst = _first_slots(user_ids, B, dev)
+    iinv, ifirst = _first_slots(item_ids, B, dev)
+    return _InBatchSoftmaxFn.apply(users_emb_final, users_emb_0, pos_items_emb_final, pos_items_emb_0, float(lambda_val),
+                                   uinv, ufirst, iinv, ifirst, logq, group)
+
+
 # ----------------------------------------------------------------------------------------------
 # evaluation: batched on device (reference: per-user Python loops on the CPU)
 # ----------------------------------------------------------------------------------------------
