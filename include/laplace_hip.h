@@ -760,6 +760,51 @@ int    mi_topk_prefilter_scores_f32(int64_t n_q, int64_t n_items, int64_t d,
                                     void* ws, size_t ws_bytes, mi_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * K10r  full-catalogue rank of one target item per query row (csrc/rank.hip).
+ * The reference has no such call: it reads every metric off a top-k list (utils/metrics_lightgcn.py:79-122).  This is the
+ * quantity behind MRR, mean rank, AUC, MAP and recall@K at any K: how many admissible items beat the held-out one.
+ * For query row p with user uid[p], target t = target[p] and exclusion row excl(p) (excl_ptr / excl_idx: CSR by position
+ * in uid, K10's contract: ids sorted or not, repeats allowed, ids outside [0, n_items) ignored):
+ *   s_j      = fmaf-chain over d ascending, from 0, of user_emb[uid[p], :] . item_emb[j, :]   (K10's scores, bit for bit)
+ *   key(s)   = score_key of csrc/score_panel.hpp (-0 -> +0, monotone)
+ *   j BEATS t  iff  key(s_j) > key(s_t), or key(s_j) == key(s_t) and j < t                    (K10's order)
+ *   rank[p]  = #{ j in [0, n_items) : j != t, j not in excl(p), j beats t }
+ *   rank[p]  = -1 if t is in excl(p) or t is outside [0, n_items)
+ *   score[p] = s_t (nullable output); 0 when t is outside [0, n_items)
+ *   n_excluded[p] = number of DISTINCT in-range ids of excl(p) (nullable output; AUC's denominator needs it)
+ * Hence for every k <= 1024: t stands in column c of mi_topk_excl_f32's row for the same user and exclusions iff
+ * rank[p] == c < k.  uid may repeat: a user with five held-out items is five rows.  All outputs are integers or single
+ * fma chains: exact, and equal from call to call.  NON-FINITE embeddings are outside the contract, as for K10.
+ * Two paths, chosen by mi_rank_path's function:
+ *   F  fused          d <= 128, d % 4 == 0, ldu % 4 == 0, ldi % 4 == 0, both bases 16-byte aligned (K10's "fused-eligible"
+ *                     without its n_items >= 32 768: any n_items): scores on the f32 MFMA, compared and counted in
+ *                     registers, never written; one integer atomicAdd per row and workgroup
+ *   M  materialised   everything else: the [n_q, n_items] score block through the GEMM of K10's M path, one counting
+ *                     workgroup per row
+ * Exclusions on both paths: every item is counted first; one pass over a row's list then takes back the excluded items
+ * that beat t (first occurrences found with a per-call bitmap in `ws`).
+ * Errors: MI_ERR_BAD_ARG; MI_ERR_TOO_LARGE for n_items >= 2^31 - 1 or n_q > 65 535 * 64 (callers chunk n_q);
+ * MI_ERR_WORKSPACE when ws_bytes < mi_rank_items_workspace_bytes(n_q, n_items): address space for path M's score block
+ * (never touched on path F), n_q * n_items / 8 bytes of bitmap, 8 bytes per row.
+ * ---------------------------------------------------------------------------------- */
+size_t mi_rank_items_workspace_bytes(int64_t n_q, int64_t n_items);
+int    mi_rank_items_f32(int64_t n_q, int64_t n_items, int64_t d,
+                         const int64_t* uid, const int64_t* target /* int64[n_q] */,
+                         const float* user_emb, int64_t ldu,
+                         const float* item_emb, int64_t ldi,
+                         const int32_t* excl_ptr /* nullable */, const int32_t* excl_idx,
+                         int32_t* out_rank /* int32[n_q] */, float* out_score /* nullable */,
+                         int32_t* out_n_excluded /* nullable int32[n_q] */,
+                         void* ws, size_t ws_bytes, mi_stream_t stream);
+/* Which path a call with these tables takes; host-only, enqueues nothing, the dispatcher's own decision function (the
+ * precedent is mi_topk_path).  The pointers are tested for alignment only.  Negative: MI_ERR_BAD_ARG, MI_ERR_TOO_LARGE. */
+#define MI_RANK_PATH_MATERIALISED 0 /* M */
+#define MI_RANK_PATH_FUSED        1 /* F */
+int mi_rank_path(int64_t n_items, int64_t d,
+                 const float* user_emb, int64_t ldu,
+                 const float* item_emb, int64_t ldi);
+
+/* ------------------------------------------------------------------------------------
  * K5  SAGEConv message passing.
  * replaces: SAGEConv.propagate -> torch_scatter.scatter(x_j, index, reduce=aggr) reached from
  *           model/layers.py:11-24 via model/encoder_decoder.py:32,44.

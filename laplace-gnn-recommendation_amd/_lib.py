@@ -60,7 +60,8 @@ MI_TOPK_ITEMS_PREPARED = 1
 MI_RECENT_MAX_SLOTS = 16       # mi_recent_items / mi_pool_recent_f32: slots per user
 MI_TOPK_MERGE_MAX_ENTRIES = 4096   # mi_topk_merge_max_f32: n_lists * k_in
 MI_TOPK_PATH_MATERIALISED, MI_TOPK_PATH_ONE_PASS, MI_TOPK_PATH_FUSED, MI_TOPK_PATH_FUSED_DMA, MI_TOPK_PATH_PREFILTER = range(5)
-MI_RANK_OBJECTIVES = {"reference": 0, "bpr": 1, "softmax": 2}
+MI_RANK_PATH_MATERIALISED, MI_RANK_PATH_FUSED = range(2)
+MI_RANK_OBJECTIVES ={"reference": 0, "bpr": 1, "softmax": 2}
 MI_RANK_MAX_NEG = 16
 MI_COOC_WEIGHTINGS = {"count": 0, "cosine": 1}
 
@@ -310,6 +311,9 @@ _PROTOTYPES = {
     "mi_topk_path": (c_int32, [c_int64, c_int64, c_int64, P, c_int64, P, c_int64]),
     "mi_topk_prefilter_scores_workspace_bytes": (c_size_t, [c_int64, c_int64]),
     "mi_topk_prefilter_scores_f32": (c_int32, [c_int64, c_int64, c_int64, P, P, c_int64, P, c_int64, P, P, P, c_size_t, P]),
+    "mi_rank_items_workspace_bytes": (c_size_t, [c_int64, c_int64]),
+    "mi_rank_items_f32": (c_int32, [c_int64, c_int64, c_int64, P, P, P, c_int64, P, c_int64, P, P, P, P, P, P, c_size_t, P]),
+    "mi_rank_path": (c_int32, [c_int64, c_int64, P, c_int64, P, c_int64]),
     "mi_segment_max_f32": (c_int32, [c_int64, c_int64, P, P, P, c_int64, P, c_int64, P, P]),
     "mi_segment_max_bwd_f32": (c_int32, [c_int64, c_int64, P, P, P, P, c_int64, P, c_int64, P]),
     "mi_embed_concat_f32": (c_int32, [c_int64, c_int32, P, POINTER(c_void_p), POINTER(c_int64), POINTER(c_int32),

@@ -15,6 +15,7 @@
 //      (ties at the threshold resolved towards smaller item ids).  Either way the result is the same.
 // Integer/index work throughout after step 1: results are exact and deterministic.
 #include "gemm.hpp"
+#include "score_panel.hpp"   // score_key / key_score / composite, the tile constants and the panel loaders (shared with rank.hip)
 
 namespace {
 
@@ -32,16 +33,6 @@ constexpr int kMaxK = 1024;
 constexpr int kCand = 4096;     // LDS candidate capacity of the one-pass path (>= kMaxK)
 constexpr int kSample = 4096;   // sampled scores per row: 32 runs of 128 consecutive items
 constexpr int kSampleRun = 128;
-
-__device__ __forceinline__ uint32_t score_key(float x) {
-    x = x + 0.0f;  // -0 -> +0 so that equal scores compare equal
-    uint32_t u = __float_as_uint(x);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);  // monotone: larger float -> larger key
-}
-__device__ __forceinline__ float key_score(uint32_t k) {
-    uint32_t u = (k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k;
-    return __uint_as_float(u);
-}
 
 __global__ void exclude_kernel(int64_t n_q, int64_t n_items, const int32_t* __restrict__ excl_ptr,
                                const int32_t* __restrict__ excl_idx, float* __restrict__ scores) {
@@ -99,10 +90,6 @@ struct SelectShared {
     uint32_t prefix;
     int need, count, eq_total;
 };
-
-__device__ __forceinline__ unsigned long long composite(uint32_t key, uint32_t item) {
-    return ((unsigned long long)key << 32) | (unsigned long long)(0xFFFFFFFFu - item);  // key desc, then id asc
-}
 
 // out row <- the first kk entries of the sorted candidate list; excluded items (-inf) never surface.
 __device__ __forceinline__ void write_row(const unsigned long long* cand, int got, int k, int64_t q,
@@ -565,9 +552,7 @@ __global__ __launch_bounds__(kBlock) void select_kernel(int64_t n_q, int64_t n_i
 //   3. topk_finalize_kernel: sorts a row's candidates and writes the answer; a row whose list came out short or
 //      overflowed (massive ties, nearly everything excluded) recomputes its scores with a scalar fma chain —
 //      the same bits as the MFMA — and takes the exact multi-pass selection.
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-constexpr int FM = 64, FN = 64, FKC = 128, FKPAD = 129;   // query / item panel rows, panel width, padded LDS row
-constexpr int kCap = kCand;                                // candidate slots per query in global memory
+constexpr int kCap = kCand;                               // candidate slots per query in global memory
 
 struct FusedArgs {
     int64_t n_q, n_items;
@@ -638,38 +623,7 @@ __global__ __launch_bounds__(kBlock) void threshold_kernel(int64_t n_q, int64_t 
     }
 }
 
-// 64 x FKC panel rows [row0, row0 + 64) of a K-contiguous operand into registers / LDS (zero beyond n_rows and d).
-__device__ __forceinline__ void fpanel_issue(float4 (&v)[8], const float* __restrict__ base, int64_t ld,
-                                             const int64_t* __restrict__ row_map, int64_t row0, int64_t n_rows, int d,
-                                             int tid) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const int idx = tid + 256 * j;
-        const int r = idx / (FKC / 4), c4 = idx % (FKC / 4);
-        const int64_t gr = row0 + r;
-        v[j] = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (gr < n_rows && c4 * 4 < d) {
-            const int64_t row = row_map ? row_map[gr] : gr;
-            v[j] = *reinterpret_cast<const float4*>(base + row * ld + c4 * 4);
-        }
-    }
-}
-// (A/B, round 1: one float per lane and load -> conflict-free LDS writes but 32 address computations spill;
-// rotating the float4 component by lane / 8 -> 32 distinct banks but the selects cost more than the conflicts:
-// 2.01 -> 1.71 M users/s; 132-float rows with ds_write_b128 / ds_read_b128 (conflict-free both ways, one float4
-// per two MFMAs) plus a float compare against the threshold: 950 -> 1 010 us per chunk.  Stage timings of this
-// kernel per 2 621-query chunk: MFMA loop + barriers alone 586 us (114 TF/s), + panel prefetch / commit 721,
-// + threshold epilogue and staging 950.  A 128-item panel with two accumulators per wavefront (one workgroup per CU):
-// 2.06 -> 1.74 M users/s.  The plain four-word write below stays.)
-__device__ __forceinline__ void fpanel_commit(float (*panel)[FKPAD], const float4 (&v)[8], int tid) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const int idx = tid + 256 * j;
-        const int r = idx / (FKC / 4), c = (idx % (FKC / 4)) * 4;
-        panel[r][c] = v[j].x; panel[r][c + 1] = v[j].y; panel[r][c + 2] = v[j].z; panel[r][c + 3] = v[j].w;
-    }
-}
-
+// (fpanel_issue / fpanel_commit, the loaders of a 64 x FKC panel, and what was measured about them: score_panel.hpp)
 constexpr int kStage = 1024;  // per-workgroup staging slots in LDS
 
 // Staged candidates -> their rows' lists in global memory (exclusion bitmap tested here, off the MFMA path).
@@ -1225,16 +1179,6 @@ __global__ __launch_bounds__(kBlock) void topk_finalize_kernel(FusedArgs a, int 
 #include "topk_prefilter.hpp"
 
 }  // namespace
-
-static int mi_cu_count() {
-    static int n_cu = 0;
-    if (n_cu == 0) {
-        int dev = 0, v = 0;
-        if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) n_cu = v;
-        else n_cu = 256;
-    }
-    return n_cu;
-}
 
 // bf16x3 prefilter (topk_prefilter.hpp): split tables, thresholds, slice-partitioned lists and their counters
 static size_t topk_prefilter_bytes(int64_t n_q, int64_t n_items) {

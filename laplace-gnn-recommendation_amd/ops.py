@@ -1248,6 +1248,74 @@ def topk_path(user_emb: Tensor, item_emb: Tensor, k: int) -> int:
     return rc
 
 
+RANK_WS_BYTES = 2 << 30    # workspace per launch of rank_of_items (path M's score block: 4 n_items bytes per row; exclusion
+                           # bitmap: n_items / 8 bytes per row); rows are processed in chunks that fit
+RANK_MAX_ROWS = 1 << 20    # and never more than this many rows per launch (the entry's limit is 65 535 panels of 64)
+
+
+def rank_of_items(uid: Tensor, target: Tensor, user_emb: Tensor, item_emb: Tensor, excl: Optional[DeviceCSR] = None,
+                  want_scores: bool = False, want_n_excluded: bool = False, chunk: Optional[int] = None,
+                  ws: Optional[Tensor] = None):
+    """K10r — for each query row p: how many items beat target[p] for user uid[p] in top-K's order (score desc, id asc) among
+    the items not in excl row p (a CSR with one row per query position, as topk_excl's).  rank int32 [n_q]: -1 when the target is
+    excluded or outside [0, n_items).  For k <= 1024, target[p] stands in column c of topk_excl's row iff rank[p] == c < k.
+    Returns rank, then (want_scores) the target's score float32 [n_q] and (want_n_excluded) the number of distinct in-range
+    ids of each exclusion row, int32 [n_q].  chunk: rows per launch (default: what fits RANK_WS_BYTES); one stream.
+    ws: a uint8 workspace of the caller's to run in (it is cleared per call as far as the call reads it); too small is an error."""
+    _need(uid, t.int64, "uid")
+    _need(target, t.int64, "target")
+    ldu = _rows_ok(user_emb, "user_emb")
+    ldi = _rows_ok(item_emb, "item_emb")
+    n_q, n_items, d = uid.numel(), item_emb.shape[0], item_emb.shape[1]
+    if user_emb.shape[1] != d:
+        raise ValueError("user and item embeddings differ in width")
+    if target.numel() != n_q:
+        raise ValueError("one target per query row expected")
+    if excl is not None and excl.n_rows != n_q:
+        raise ValueError("exclusion CSR needs one row per query")
+    if chunk is not None and chunk < 1:
+        raise ValueError("chunk must be positive")
+    dev = item_emb.device
+    rank = t.empty(n_q, dtype=t.int32, device=dev)
+    score = t.empty(n_q, dtype=t.float32, device=dev) if want_scores else None
+    n_ex = t.empty(n_q, dtype=t.int32, device=dev) if want_n_excluded else None
+    L = _lib.lib()
+    if chunk is None:
+        chunk = max(1, min(n_q, RANK_MAX_ROWS))
+        while chunk > 64 and int(L.mi_rank_items_workspace_bytes(chunk, n_items)) > RANK_WS_BYTES:
+            chunk = (chunk + 1) // 2
+    chunk = max(1, min(chunk, n_q))
+    if ws is None:
+        ws = _ws(int(L.mi_rank_items_workspace_bytes(chunk, n_items)), dev)
+    else:
+        _need(ws, t.uint8, "ws")
+    for q0 in range(0, n_q, chunk):
+        q1 = min(n_q, q0 + chunk)
+        # rowptr keeps absolute offsets into excl.col, so a chunk is just a slice of rowptr
+        ep = excl.rowptr[q0:q1 + 1] if excl is not None else None
+        ei = excl.col if (excl is not None and excl.nnz) else None
+        check(L.mi_rank_items_f32(q1 - q0, n_items, d, uid[q0:q1].data_ptr(), target[q0:q1].data_ptr(), user_emb.data_ptr(), ldu,
+                                  item_emb.data_ptr(), ldi, _ptr(ep), _ptr(ei), rank[q0:q1].data_ptr(),
+                                  score[q0:q1].data_ptr() if want_scores else None,
+                                  n_ex[q0:q1].data_ptr() if want_n_excluded else None,
+                                  ws.data_ptr(), ws.numel(), _stream()), "mi_rank_items_f32")
+    out = (rank,) + ((score,) if want_scores else ()) + ((n_ex,) if want_n_excluded else ())
+    return out if len(out) > 1 else rank
+
+
+def rank_path(user_emb: Tensor, item_emb: Tensor) -> int:
+    """Which code path rank_of_items takes for these tables (_lib.MI_RANK_PATH_FUSED / _MATERIALISED) — asked of the
+    dispatcher's own decision function; host-only, nothing is enqueued.  It depends on neither the rows nor the chunk."""
+    ldu = _rows_ok(user_emb, "user_emb")
+    ldi = _rows_ok(item_emb, "item_emb")
+    n_items, d = item_emb.shape
+    if user_emb.shape[1] != d:
+        raise ValueError("user and item embeddings differ in width")
+    rc = int(_lib.lib().mi_rank_path(n_items, d, user_emb.data_ptr(), ldu, item_emb.data_ptr(), ldi))
+    check(rc if rc < 0 else 0, "mi_rank_path")
+    return rc
+
+
 def topk_prefilter_scores(uid: Optional[Tensor], user_emb: Tensor, item_emb: Tensor) -> Tuple[Tensor, Tensor]:
     """Diagnostic of the bf16x3 prefilter behind topk_excl (csrc/topk_prefilter.hpp): the approximate scores [n_q, n_items]
     it compares with its thresholds and the per-query bound eps it assumes for |approximate - exact fma chain|."""

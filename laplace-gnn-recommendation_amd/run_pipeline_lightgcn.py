@@ -20,7 +20,7 @@ from .model.lightgcn import LightGCN
 from .reporting.types import Stats
 from .sparse import SparseTensor
 from .trainer import LightGCNTrainer
-from .utils.metrics_lightgcn import get_metrics_lightgcn, topk_for_users
+from .utils.metrics_lightgcn import get_full_rank_metrics_lightgcn, get_metrics_lightgcn, topk_for_users
 
 
 PREDICTORS = ("layer0", "propagated")
@@ -54,10 +54,20 @@ def evaluation(model: LightGCN, edge_index: Tensor, sparse_edge_index: SparseTen
     return float(loss), recall, precision, ndcg
 
 
+def evaluation_full_rank(model: LightGCN, edge_index: Tensor, exclude_edge_indices: List[Tensor], ks=(12,),
+                         embeddings: Optional[Tuple[Tensor, Tensor]] = None, filtered: bool = False) -> dict:
+    """The split's metrics from the full-catalogue rank of every held-out pair (utils.metrics_lightgcn.full_rank_metrics):
+    recall / precision / ndcg / map @ every K of `ks`, mrr, mean_rank, auc.  The float entries only: what a log line or a
+    JSON file holds.  Same tables and exclusions as evaluation()'s ranking metrics, so recall@k is evaluation()'s recall."""
+    m = get_full_rank_metrics_lightgcn(model, edge_index, exclude_edge_indices, ks, embeddings=embeddings, filtered=filtered)
+    return {key: v for key, v in m.items() if not isinstance(v, Tensor)}
+
+
 def train(config: LightGCNConfig = lightgcn_config, *, edge_index: Tensor, num_users: int, num_articles: int,
           compat: str = "reference", device: str = "cuda", seed: int = 0, save_dir: Optional[str] = None,
           verbose: bool = True, objective: str = "reference", n_neg: int = 1, predictor: str = "layer0",
-          negatives: str = "uniform", neg_power: float = 0.75, in_batch_group: int = 1024) -> Stats:
+          negatives: str = "uniform", neg_power: float = 0.75, in_batch_group: int = 1024,
+          full_rank_ks: Optional[Tuple[int, ...]] = None) -> Stats:
     """objective / n_neg: the training loss (trainer.LightGCNTrainer).  predictor="propagated": evaluation,
     the ranking metrics and the saved predictions score with mean_k(A^k E0) of the training adjacency — the scores the
     loss trains — instead of the layer-0 tables.
@@ -66,7 +76,10 @@ def train(config: LightGCNConfig = lightgcn_config, *, edge_index: Tensor, num_u
     sampler and are left out.  negatives="in_batch" (objective="softmax"): the other positives of a slot's group of
     in_batch_group slots are its negatives, logQ-corrected by training degree; likewise without the reference's range and
     quirk.  evaluation() keeps its uniform negatives and uncorrected loss in every case, so
-    validation and test losses stay comparable across samplers."""
+    validation and test losses stay comparable across samplers.
+    full_rank_ks: when given, the test split is also scored by evaluation_full_rank at these K (same predictor, same
+    exclusions); the dict is printed under `verbose` and, with `save_dir`, written as full_rank_metrics.json.  The returned
+    Stats are the same either way."""
     if predictor not in PREDICTORS:
         raise ValueError(f"predictor must be one of {PREDICTORS}, got {predictor!r}")
     if verbose:
@@ -117,6 +130,17 @@ def train(config: LightGCNConfig = lightgcn_config, *, edge_index: Tensor, num_u
     if verbose:
         print(f"[test_loss: {round(test_loss, 5)}, test_recall@{config.k}: {round(test_recall, 5)}, "
               f"test_precision@{config.k}: {round(test_precision, 5)}, test_ndcg@{config.k}: {round(test_ndcg, 5)}")
+    if full_rank_ks is not None:
+        full = evaluation_full_rank(model, test_edges, [train_edges, val_edges], tuple(full_rank_ks),
+                                    embeddings=scoring_tables())
+        if verbose:
+            print("[test full-rank] " + ", ".join(f"{key}: {round(v, 6) if isinstance(v, float) else v}" for key, v in full.items()))
+        if save_dir is not None:
+            import json
+            import os
+            os.makedirs(save_dir, exist_ok=True)
+            with open(os.path.join(save_dir, "full_rank_metrics.json"), "w") as f:
+                json.dump(full, f, indent=1, sort_keys=True)
 
     # predictions for the matcher: top `num_recommendations` unseen items per user, layer-0 scores (F8) by default
     top_items = save_predictions(model, all_edges, config.num_recommendations, save_dir, embeddings=scoring_tables())

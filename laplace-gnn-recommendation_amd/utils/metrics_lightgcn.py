@@ -271,3 +271,130 @@ def get_metrics_lightgcn(model, edge_index: Tensor, exclude_edge_indices: List[T
     r = t.isin(pred_keys, truth_keys) & (top >= 0)
     gt_len = t.bincount(pos_of, minlength=users.numel())
     return rank_metrics(r, gt_len, k)
+
+
+# ----------------------------------------------------------------------------------------------
+# full-catalogue ranks of the held-out items (ops.rank_of_items): MRR, mean rank, AUC, MAP@K and recall@K at any K
+# ----------------------------------------------------------------------------------------------
+def _rows_of_csr(csr: ops.DeviceCSR, rows: Tensor) -> ops.DeviceCSR:
+    """The CSR whose row p is row rows[p] of `csr` (ops.rank_of_items wants one exclusion row per query row, and a
+    user's pairs share the user's row)."""
+    ptr = csr.rowptr.to(t.int64)
+    lens = (ptr[1:] - ptr[:-1])[rows]
+    new_ptr = t.zeros(rows.numel() + 1, dtype=t.int64, device=rows.device)
+    new_ptr[1:] = lens.cumsum(0)
+    total = int(new_ptr[-1])
+    if total >= 2 ** 31:
+        raise ValueError("exclusion lists of the pairs exceed int32 indexing: rank the edges in several calls")
+    src = t.repeat_interleave(ptr[:-1][rows] - new_ptr[:-1], lens) + t.arange(total, device=rows.device)
+    return ops.DeviceCSR(rows.numel(), csr.n_cols, new_ptr.to(t.int32), csr.col[src].contiguous())
+
+
+def ranks_for_edges(user_embedding: Tensor, item_embedding: Tensor, edge_index: Tensor,
+                    exclude_edges: Optional[Tensor]) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """(users, pos_of, items, ranks, n_excluded) over the DISTINCT (user, item) pairs of `edge_index`, sorted by user (then
+    item): users = the sorted distinct users, pos_of[p] = the position of pair p's user in `users`, items[p] its item,
+    ranks[p] (int32) = how many items that `exclude_edges` does not list for the user score above it in top-K's order
+    (-1: the pair itself is listed), n_excluded[p] (int32) = the user's distinct excluded items."""
+    dev = item_embedding.device
+    edge_index = edge_index.to(dev)
+    n_items = item_embedding.shape[0]
+    users = edge_index[0].unique()
+    keys = t.unique(t.searchsorted(users, edge_index[0]) * n_items + edge_index[1])
+    pos_of, items = keys // n_items, keys % n_items
+    excl = _exclusion_csr(users, exclude_edges, n_items)
+    if excl is not None:
+        excl = _rows_of_csr(excl, pos_of)
+    ranks, n_excluded = ops.rank_of_items(users[pos_of].contiguous(), items.contiguous(), user_embedding, item_embedding,
+                                          excl, want_n_excluded=True)
+    return users, pos_of, items, ranks, n_excluded
+
+
+def full_rank_metrics(pos_of: Tensor, ranks: Tensor, n_items: int, n_excluded: Tensor, gt_len: Tensor, ks=(12,),
+                      filtered: bool = False) -> dict:
+    """Ranking metrics from one exact integer per held-out pair; pure torch (device or host), floats in float64.
+    pos_of / ranks / n_excluded: per pair, as ranks_for_edges returns them (a user's pairs are DISTINCT items, so their
+    ranks differ).  gt_len [n_users]: |GT| per user by get_metrics_lightgcn's rule, bincount over the split's edges, which
+    counts a repeated edge every time it occurs.  Pairs with rank -1 are left out of everything ("excluded_pairs" says how
+    many); m_u below is the number of a user's pairs that are left.
+      recall@K, precision@K, ndcg@K   for any K <= n_items, over every user of gt_len: rank_metrics on the hit matrix of
+                                      a top-K list (equal to it wherever K <= 1024 lets one be made)
+      hits@K                          int64 [n_users]: the user's pairs with rank < K
+      map@K                           per user 1 / min(K, m_u) * sum over pairs with rank < K of h / (rank + 1), h the
+                                      1-based position of the pair among the user's own pairs by rank; mean over the users
+                                      with m_u > 0
+      mrr                             mean over those users of 1 / (best rank + 1)
+      mean_rank                       mean over pairs of the rank (0-based)
+      auc                             mean over pairs of 1 - r_f / (n_items - n_excluded - m_u), r_f the filtered rank; pairs
+                                      whose denominator is 0 are left out (nan when none is left)
+      filtered_rank                   int64 per pair (-1: left out): r_f = rank - (h - 1), the pair's rank against the
+                                      items that are not the user's own positives
+    filtered=True: every metric above takes r_f in the place of rank (h stays the position by rank).  Integer
+    post-processing of the same ranks: nothing is scored again."""
+    dev = ranks.device
+    n_users = int(gt_len.numel())
+    pos_of = pos_of.to(t.int64)
+    rk = ranks.to(t.int64)
+    valid = rk >= 0
+    vp, vr = pos_of[valid], rk[valid]
+    n_valid = int(vp.numel())
+    m_u = t.bincount(vp, minlength=n_users)
+    # position of every pair among its user's pairs by rank
+    order = t.argsort(vp * (int(n_items) + 1) + vr)
+    start = t.cumsum(m_u, 0) - m_u
+    h0_sorted = t.arange(n_valid, device=dev) - start[vp[order]]
+    h0 = t.empty_like(h0_sorted)
+    h0[order] = h0_sorted
+    r_f = vr - h0
+    use = r_f if filtered else vr
+    out = {"excluded_pairs": int((~valid).sum()), "pairs": n_valid}
+    fr = t.full_like(rk, -1)
+    fr[valid] = r_f
+    out["filtered_rank"] = fr
+    gt = gt_len.to(t.float64)
+    has = m_u > 0
+    n_has = max(int(has.sum()), 1)
+    for k in ks:
+        k = int(k)
+        if not 1 <= k <= max(int(n_items), 1):
+            raise ValueError(f"K must be in [1, n_items], got {k}")
+        inside = use < k
+        hits = t.bincount(vp[inside], minlength=n_users)
+        out[f"hits@{k}"] = hits
+        out[f"recall@{k}"] = float((hits.to(t.float64) / gt).mean()) if n_users else float("nan")
+        out[f"precision@{k}"] = float(hits.to(t.float64).mean() / k) if n_users else float("nan")
+        disc = 1.0 / t.log2(t.arange(2, k + 2, device=dev, dtype=t.float64))
+        cum = t.cat([t.zeros(1, dtype=t.float64, device=dev), disc.cumsum(0)])
+        idcg = cum[gt_len.to(t.int64).clamp(min=0, max=k)]
+        idcg = t.where(idcg == 0.0, t.ones_like(idcg), idcg)
+        dcg = t.zeros(n_users, dtype=t.float64, device=dev).index_add_(0, vp[inside], disc[use[inside]])
+        out[f"ndcg@{k}"] = float((dcg / idcg).mean()) if n_users else float("nan")
+        ap = t.zeros(n_users, dtype=t.float64, device=dev).index_add_(
+            0, vp[inside], (h0[inside] + 1).to(t.float64) / (use[inside] + 1).to(t.float64))
+        ap = ap / m_u.clamp(min=1, max=k).to(t.float64)
+        out[f"map@{k}"] = float(ap[has].sum() / n_has) if n_valid else float("nan")
+    best = t.full((n_users,), int(n_items), dtype=t.int64, device=dev).scatter_reduce_(0, vp, use, reduce="amin")
+    out["mrr"] = float((1.0 / (best[has] + 1).to(t.float64)).sum() / n_has) if n_valid else float("nan")
+    out["mean_rank"] = float(use.to(t.float64).mean()) if n_valid else float("nan")
+    den = int(n_items) - n_excluded.to(t.int64)[valid] - m_u[vp]
+    ok = den > 0
+    out["auc"] = float((1.0 - r_f[ok].to(t.float64) / den[ok].to(t.float64)).mean()) if int(ok.sum()) else float("nan")
+    return out
+
+
+def get_full_rank_metrics_lightgcn(model, edge_index: Tensor, exclude_edge_indices: List[Tensor], ks=(12,),
+                                   embeddings: Optional[Tuple[Tensor, Tensor]] = None, filtered: bool = False) -> dict:
+    """full_rank_metrics of the layer-0 embeddings (or of `embeddings` = (users, items)) on the distinct pairs of
+    `edge_index`, never ranking against items in `exclude_edge_indices`: the counterpart of get_metrics_lightgcn with the
+    whole catalogue in view instead of the first k places.  Its recall / precision / ndcg @ K are get_metrics_lightgcn's."""
+    if embeddings is not None:
+        ue, ie = embeddings[0].detach(), embeddings[1].detach()
+    else:
+        ue = model.users_emb.weight.detach()
+        ie = model.items_emb.weight.detach()
+    dev = ie.device
+    edge_index = edge_index.to(dev)
+    excl = t.cat([e.to(dev) for e in exclude_edge_indices], dim=1) if len(exclude_edge_indices) else None
+    users, pos_of, _, ranks, n_excluded = ranks_for_edges(ue, ie, edge_index, excl)
+    gt_len = t.bincount(t.searchsorted(users, edge_index[0]), minlength=users.numel())
+    return full_rank_metrics(pos_of, ranks, ie.shape[0], n_excluded, gt_len, ks=ks, filtered=filtered)
