@@ -13,22 +13,19 @@
 //                      gradient product as it stands (the sum runs over the accumulator's row index), no transpose, no LDS.
 //                      One wavefront owns its 32 output rows for the whole sweep: one writer per slot row.
 //   4. refs / sort / chunk / combine   the 2B slot rows become rows of g_final: the sorted-reference segmented sum of
-//                      train.hip (bpr_chunk_kernel), with a slot row as each reference's only term; reg_w from the run lengths
-//   5. finish_kernel   loss = sum(term) / B + lambda * sum(reg), one block, fixed order
+//                      refsum.hpp, with a slot row as each reference's only term; reg_w from the run lengths
+//   5. refsum::finish_kernel   loss = sum(term) / B + lambda * sum(reg), one block, fixed order
 // No float atomics; every order of summation is a function of (B, G, d) and the ids: two calls give equal bits.
 // k order of a score: lane half h takes the float4 chunks 2q + h of a row, q ascending, the four floats in order, and the
 // instruction adds half 0's product before half 1's.  The three passes share it, so they see the same score bits.
-#include "common.hpp"
+#include "refsum.hpp"
 #include <cmath>
-#include <rocprim/rocprim.hpp>
 
 namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int kTile = 32;        // slots per tile: the rows and the columns of the matrix instruction
-constexpr int kChunkBlock = 256;
-constexpr int kRefChunk = 64;    // references per chunk of the segmented sum
 constexpr int kMaxD = 256;
 constexpr int kMinGroup = 32, kMaxGroup = 4096;
 
@@ -253,149 +250,31 @@ __global__ void inbatch_refs_kernel(int64_t batch, int64_t n_users, const int64_
     refs[r] = (uint32_t)r;
 }
 
-// bpr_chunk_kernel (train.hip) with one term per reference, the slot row itself: one wavefront per chunk of 64 sorted
-// references; a run of equal keys inside the chunk is summed in order and stored by this wavefront alone, a run that crosses
-// chunk borders leaves a head / tail partial for combine_kernel.
+// The chunk pass of refsum.hpp with one term per reference, the slot row itself, unweighted.
+struct SlotRow {
+    static constexpr int kTerms = 1;
+    int64_t src = 0;   // row of g_slot
+    __device__ __forceinline__ int64_t row(int, int q) const { return __shfl(src, q, MI_WAVE); }
+    __device__ __forceinline__ float weight(int, int) const { return 1.f; }
+};
+
 template <int VPT>  // floats of a row per lane: ceil(d / 64)
-__global__ __launch_bounds__(kChunkBlock) void inbatch_chunk_kernel(
-    int64_t batch, int d, int64_t n_users, const int64_t* __restrict__ users, const int64_t* __restrict__ pos,
-    const float* __restrict__ g_slot, const uint32_t* __restrict__ keys, const uint32_t* __restrict__ refs,
-    float* __restrict__ g_final, int64_t ldg, float* __restrict__ part_head, float* __restrict__ part_tail,
+__global__ __launch_bounds__(refsum::kBlock) void inbatch_chunk_kernel(
+    int64_t batch, int64_t n_users, const int64_t* __restrict__ users, const int64_t* __restrict__ pos,
+    const float* __restrict__ g_slot, const uint32_t* __restrict__ keys, const uint32_t* __restrict__ refs, refsum::Dest to,
     float* __restrict__ reg_w, float reg_unit /* 2 * lambda * reg_scale: one reference's share */) {
     const int64_t n_ref = 2 * batch;
-    const int64_t chunk = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / MI_WAVE;
-    const int64_t j0 = chunk * kRefChunk;
-    if (j0 >= n_ref) return;
-    const int lane = mi_lane();
-    const int n_here = (int)min((int64_t)kRefChunk, n_ref - j0);
-    uint32_t my_key = 0xFFFFFFFFu;
-    int64_t my_src = 0;
-    if (lane < n_here) {
-        my_key = keys[j0 + lane];
-        my_src = refs[j0 + lane];
-        // the reference that opens the node's run finds the run's end by bisection and is the entry's only writer
+    const refsum::Chunk c = refsum::open_chunk(keys, n_ref);
+    if (c.n_here == 0) return;
+    SlotRow term;
+    if (c.lane < c.n_here) {
+        term.src = refs[c.j0 + c.lane];
         if (reg_w) {
-            const int64_t j = j0 + lane;
-            if (j == 0 || keys[j - 1] != my_key) {
-                int64_t lo = j + 1, hi = n_ref;   // first position in (j, n_ref] whose key differs
-                while (lo < hi) {
-                    const int64_t mid = (lo + hi) >> 1;
-                    if (keys[mid] == my_key) lo = mid + 1; else hi = mid;
-                }
-                const int64_t node = my_src < batch ? users[my_src] : n_users + pos[my_src - batch];
-                reg_w[node] = (float)(lo - j) * reg_unit;
-            }
+            const int64_t len = refsum::run_length(keys, c.j0 + c.lane, n_ref);
+            if (len) reg_w[term.src < batch ? users[term.src] : n_users + pos[term.src - batch]] = (float)len * reg_unit;
         }
     }
-    const bool head_open = j0 > 0 && keys[j0 - 1] == __shfl(my_key, 0, MI_WAVE);
-    const bool next_same = (j0 + n_here < n_ref) && keys[j0 + n_here] == __shfl(my_key, n_here - 1, MI_WAVE);
-    float acc[VPT];
-#pragma unroll
-    for (int v = 0; v < VPT; ++v) acc[v] = 0.f;
-    int run_start = 0;
-    constexpr int U = 8;  // references whose rows are in flight together
-    for (int q0 = 0; q0 < n_here; q0 += U) {
-        float x[U][VPT];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int q = min(q0 + u, n_here - 1);
-            const bool live = q0 + u < n_here;
-            const float* row = g_slot + __shfl(my_src, q, MI_WAVE) * d;
-#pragma unroll
-            for (int v = 0; v < VPT; ++v) {
-                const int k = lane + v * MI_WAVE;
-                x[u][v] = (live && k < d) ? row[k] : 0.f;
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int q = q0 + u;
-            if (q >= n_here) break;
-            const uint32_t kq = __shfl(my_key, q, MI_WAVE);
-#pragma unroll
-            for (int v = 0; v < VPT; ++v) acc[v] += x[u][v];
-            const bool last_of_run = (q + 1 == n_here) || __shfl(my_key, q + 1, MI_WAVE) != kq;
-            if (!last_of_run) continue;
-            const bool from_prev = run_start == 0 && head_open;
-            const bool into_next = (q + 1 == n_here) && next_same;
-            float* dst;
-            if (from_prev) dst = part_head + chunk * d;          // finished by the chunk where the run starts
-            else if (into_next) dst = part_tail + chunk * d;     // this chunk starts the run; the combine finishes it
-            else dst = g_final + (int64_t)kq * ldg;              // the run lies inside this chunk: the row's only writer
-#pragma unroll
-            for (int v = 0; v < VPT; ++v) {
-                const int k = lane + v * MI_WAVE;
-                if (k < d) dst[k] = acc[v];   // g_final is zero on entry (header contract): a store
-                acc[v] = 0.f;
-            }
-            run_start = q + 1;
-        }
-    }
-}
-
-// One wavefront per chunk whose trailing run starts in it and runs on: tail partial + the head partials of the following
-// chunks, in chunk order (bpr_combine_kernel of train.hip).
-template <int VPT>
-__global__ __launch_bounds__(kChunkBlock) void inbatch_combine_kernel(int64_t n_ref, int d, const uint32_t* __restrict__ keys,
-                                                                      const float* __restrict__ part_head,
-                                                                      const float* __restrict__ part_tail,
-                                                                      float* __restrict__ g_final, int64_t ldg) {
-    const int64_t chunk = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / MI_WAVE;
-    const int64_t j0 = chunk * kRefChunk;
-    if (j0 >= n_ref) return;
-    const int64_t j_last = min(j0 + kRefChunk, n_ref) - 1;
-    if (j_last + 1 >= n_ref) return;                       // nothing after this chunk
-    const uint32_t row = keys[j_last];
-    if (keys[j_last + 1] != row) return;                   // the trailing run ends here
-    if (keys[j0] == row && j0 > 0 && keys[j0 - 1] == row) return;  // the run started in an earlier chunk: not the owner
-    const int lane = mi_lane();
-    float acc[VPT];
-#pragma unroll
-    for (int v = 0; v < VPT; ++v) {
-        const int k = lane + v * MI_WAVE;
-        acc[v] = k < d ? part_tail[chunk * d + k] : 0.f;
-    }
-    for (int64_t nb = chunk + 1; nb * kRefChunk < n_ref && keys[nb * kRefChunk] == row; ++nb) {
-#pragma unroll
-        for (int v = 0; v < VPT; ++v) {
-            const int k = lane + v * MI_WAVE;
-            if (k < d) acc[v] += part_head[nb * d + k];
-        }
-        if (keys[min((nb + 1) * kRefChunk, n_ref) - 1] != row) break;   // the run ends inside chunk nb
-    }
-    float* dst = g_final + (int64_t)row * ldg;
-#pragma unroll
-    for (int v = 0; v < VPT; ++v) {
-        const int k = lane + v * MI_WAVE;
-        if (k < d) dst[k] = acc[v];
-    }
-}
-
-// ------------------------------------------------------------------ 5. loss ------------------------------------------------
-// Single block, fixed order (bpr_finish_kernel's scheme): loss = sum(term) / B + lambda * sum(reg).
-__global__ __launch_bounds__(1024) void inbatch_finish_kernel(int64_t batch, const float* __restrict__ term_v,
-                                                              const float* __restrict__ reg_v, float inv_batch, float lambda,
-                                                              float* __restrict__ loss_out) {
-    __shared__ float sh_a[1024];
-    __shared__ float sh_b[1024];
-    const int t = threadIdx.x;
-    float a = 0.f, r = 0.f;
-#pragma unroll 4
-    for (int64_t i = t; i < batch; i += 1024) {
-        a += term_v[i];
-        r += reg_v[i];
-    }
-    sh_a[t] = a;
-    sh_b[t] = r;
-    __syncthreads();
-    for (int s = 512; s > 0; s >>= 1) {
-        if (t < s) {
-            sh_a[t] += sh_a[t + s];
-            sh_b[t] += sh_b[t + s];
-        }
-        __syncthreads();
-    }
-    if (t == 0) loss_out[0] = sh_a[0] * inv_batch + lambda * sh_b[0];
+    refsum::walk_references<VPT>(c, term, g_slot, to.d, to);
 }
 
 // ------------------------------------------------------------------ host ---------------------------------------------------
@@ -404,23 +283,16 @@ bool args_in_range(int64_t batch, int64_t d, int32_t group) {
            group <= kMaxGroup && group % kTile == 0;
 }
 
-size_t sort_tmp_bytes(int64_t n_ref) { return ((size_t)1 << 20) + mi_align_up((size_t)n_ref * 2, 256); }
-
 struct Workspace {
-    float *u_img, *v_img, *g_slot, *lq, *lse, *term, *reg, *part_head, *part_tail;
+    float *u_img, *v_img, *g_slot, *lq, *lse, *term, *reg;
     int32_t *uid, *pid;
-    uint32_t *k0, *k1, *r0, *r1;
-    char* tmp;
-    size_t tmp_cap;
-    bool ok() const {
-        return u_img && v_img && g_slot && lq && lse && term && reg && part_head && part_tail && uid && pid && k0 && k1 &&
-               r0 && r1 && tmp;
-    }
+    refsum::Buffers sum;   // partial rows of d floats: this entry knows its d
+    bool ok() const { return u_img && v_img && g_slot && lq && lse && term && reg && uid && pid && sum.ok(); }
 };
 
 Workspace carve(MiArena& a, int64_t batch, int64_t d) {
     const size_t b = (size_t)batch, bp = (size_t)mi_ceil_div(batch, kTile) * kTile;   // id and statistic arrays: whole tiles
-    const size_t n_ref = 2 * b, chunks = (size_t)mi_ceil_div((int64_t)n_ref, kRefChunk);
+    const size_t n_ref = 2 * b;
     Workspace w;
     w.u_img = a.take<float>(b * d);
     w.v_img = a.take<float>(b * d);
@@ -431,23 +303,8 @@ Workspace carve(MiArena& a, int64_t batch, int64_t d) {
     w.lse = a.take<float>(bp);
     w.term = a.take<float>(bp);
     w.reg = a.take<float>(bp);
-    w.k0 = a.take<uint32_t>(n_ref);
-    w.k1 = a.take<uint32_t>(n_ref);
-    w.r0 = a.take<uint32_t>(n_ref);
-    w.r1 = a.take<uint32_t>(n_ref);
-    w.tmp_cap = sort_tmp_bytes((int64_t)n_ref);
-    w.tmp = a.take<char>(w.tmp_cap);
-    w.part_head = a.take<float>(chunks * d);
-    w.part_tail = a.take<float>(chunks * d);
+    w.sum = refsum::take(a, (int64_t)n_ref, d);
     return w;
-}
-
-template <class F>   // f(std::integral_constant<int, N>), N = 1, 2, 4 or 8 >= n
-void with_pow2(int64_t n, F&& f) {
-    if (n <= 1) f(std::integral_constant<int, 1>{});
-    else if (n <= 2) f(std::integral_constant<int, 2>{});
-    else if (n <= 4) f(std::integral_constant<int, 4>{});
-    else f(std::integral_constant<int, 8>{});
 }
 
 }  // namespace
@@ -457,10 +314,9 @@ extern "C" {
 size_t mi_inbatch_softmax_workspace_bytes(int64_t batch, int64_t d, int32_t group) {
     if (!args_in_range(batch, d, group)) return 0;
     const size_t b = (size_t)batch, bp = (size_t)mi_ceil_div(batch, kTile) * kTile;
-    const size_t n_ref = 2 * b, chunks = (size_t)mi_ceil_div((int64_t)n_ref, kRefChunk);
+    const size_t n_ref = 2 * b;
     return 2 * mi_align_up(b * d * sizeof(float), 256) + mi_align_up(n_ref * d * sizeof(float), 256) +
-           6 * mi_align_up(bp * sizeof(float), 256) + 4 * mi_align_up(n_ref * sizeof(uint32_t), 256) +
-           mi_align_up(sort_tmp_bytes((int64_t)n_ref), 256) + 2 * mi_align_up(chunks * d * sizeof(float), 256);
+           6 * mi_align_up(bp * sizeof(float), 256) + refsum::workspace_bytes((int64_t)n_ref, d);
 }
 
 int mi_inbatch_softmax_fwd_bwd_f32(int64_t batch, int32_t group, int64_t d, int64_t n_users, const int64_t* users,
@@ -483,16 +339,13 @@ int mi_inbatch_softmax_fwd_bwd_f32(int64_t batch, int32_t group, int64_t d, int6
     const Workspace w = carve(arena, batch, d);
     if (!w.ok()) return MI_ERR_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
-    const int64_t n_ref = 2 * batch, n_chunks = mi_ceil_div(n_ref, kRefChunk), n_tiles = mi_ceil_div(batch, kTile);
+    const int64_t n_ref = 2 * batch, n_tiles = mi_ceil_div(batch, kTile);
     const int d4 = (int)(d / 4), nq = (d4 + 1) / 2;
     const size_t lds = (size_t)kTile * (2 * nq + 1) * sizeof(float4);   // 33 280 bytes at d = 256
-    rocprim::double_buffer<uint32_t> keys(w.k0, w.k1), refs(w.r0, w.r1);
-    unsigned bits = 32;   // compact slots are < 2B; node ids need all 32 bits
-    size_t need = 0;
+    refsum::Sort sorted;
     if (g_final) {
-        if (node_map) bits = mi_bits_for(n_ref);
-        MI_HIP(rocprim::radix_sort_pairs(nullptr, need, keys, refs, (size_t)n_ref, 0, bits, s));
-        if (need > w.tmp_cap) return MI_ERR_WORKSPACE;
+        const int rc = refsum::plan_sort(w.sum, n_ref, node_map != nullptr, s, sorted);
+        if (rc) return rc;
     }
     // ---- nothing has been enqueued up to here ----
     const float4* u_img = reinterpret_cast<const float4*>(w.u_img);
@@ -505,26 +358,25 @@ int mi_inbatch_softmax_fwd_bwd_f32(int64_t batch, int32_t group, int64_t d, int6
                        v_img, w.uid, w.pid, w.lq, w.lse, w.term);
     if (g_final) {
         const float wgt = g_scale / (float)batch;
-        with_pow2(mi_ceil_div(d, 32), [&](auto nt) {
+        refsum::with_vpt(mi_ceil_div(d, 32), [&](auto nt) {
             constexpr int NT = decltype(nt)::value;
             hipLaunchKernelGGL(inbatch_sweep_kernel<NT>, dim3((unsigned)n_tiles, 2), dim3(MI_WAVE), lds, s, batch, (int)group,
                                (int)d, nq, u_img, v_img, w.uid, w.pid, w.lq, w.lse, wgt, w.g_slot);
         });
         hipLaunchKernelGGL(inbatch_refs_kernel, dim3((unsigned)mi_ceil_div(n_ref, 256)), dim3(256), 0, s, batch, n_users, users,
-                           pos, node_map, w.k0, w.r0);
-        MI_HIP(rocprim::radix_sort_pairs(w.tmp, need, keys, refs, (size_t)n_ref, 0, bits, s));
-        const dim3 gc((unsigned)mi_ceil_div(n_chunks * MI_WAVE, kChunkBlock));
-        with_pow2(mi_ceil_div(d, MI_WAVE), [&](auto vpt) {
+                           pos, node_map, w.sum.k0, w.sum.r0);
+        const int rc = refsum::sort(w.sum, n_ref, s, sorted);
+        if (rc) return rc;
+        const refsum::Dest to{g_final, ldg, w.sum.part_head, w.sum.part_tail, (int)d};
+        refsum::with_vpt(mi_ceil_div(d, MI_WAVE), [&](auto vpt) {
             constexpr int V = decltype(vpt)::value < 4 ? decltype(vpt)::value : 4;   // d <= 256
-            hipLaunchKernelGGL(inbatch_chunk_kernel<V>, gc, dim3(kChunkBlock), 0, s, batch, (int)d, n_users, users, pos,
-                               w.g_slot, keys.current(), refs.current(), g_final, ldg, w.part_head, w.part_tail, reg_w,
-                               2.0f * reg_scale * lambda);
-            hipLaunchKernelGGL(inbatch_combine_kernel<V>, gc, dim3(kChunkBlock), 0, s, n_ref, (int)d, keys.current(),
-                               w.part_head, w.part_tail, g_final, ldg);
+            hipLaunchKernelGGL(inbatch_chunk_kernel<V>, refsum::chunk_grid(n_ref), dim3(refsum::kBlock), 0, s, batch, n_users,
+                               users, pos, (const float*)w.g_slot, (const uint32_t*)sorted.keys.current(),
+                               (const uint32_t*)sorted.refs.current(), to, reg_w, 2.0f * reg_scale * lambda);
+            refsum::launch_combine<V>(sorted, n_ref, to, s);
         });
     }
-    hipLaunchKernelGGL(inbatch_finish_kernel, dim3(1), dim3(1024), 0, s, batch, w.term, w.reg, 1.0f / (float)batch, lambda,
-                       loss_out);
+    refsum::launch_finish(batch, w.term, w.reg, 1.0f / (float)batch, lambda, loss_out, s);
     return mi_launch_status();
 }
 

@@ -15,7 +15,7 @@
 //      its run of equal keys hands the finished row to the caller's per-row operation — the lazy Adam update of
 //      lazy_adam.hpp.  After the combine, because a run that crosses chunk borders is not complete before it.
 // One writer per row and a fixed association that does not depend on scheduling: equal bits on every call
-// (tests/segsum_emulation.py restates it).  The scheme of bpr_chunk_kernel / bpr_combine_kernel (train.hip), with float4 lanes.
+// (tests/segsum_emulation.py restates it).  The scheme of refsum.hpp (the LightGCN trainer's loss paths), with float4 lanes.
 // The reference count is the host's n_ref, or min(*count, n_ref) read on the device when the caller counts its references
 // there (slots past the count hold a key that sorts last and are never read).
 #pragma once

@@ -7,9 +7,8 @@
 // The reference's entries are the (MI_RANK_REFERENCE, one negative) case of the general ones and launch what those launch
 // at n_neg = 1: one sampler kernel, one marking kernel, one loss host path (rank_loss_run).  That case alone keeps two loss
 // kernels of its own, bpr_slot_kernel and bpr_chunk_kernel, because they are faster there.
-#include "common.hpp"
+#include "refsum.hpp"
 #include <cmath>
-#include <rocprim/rocprim.hpp>
 
 namespace {
 
@@ -171,177 +170,46 @@ __global__ __launch_bounds__(kBlock) void bpr_slot_kernel(
 // ---- gradient of the final embeddings, without float atomics -------------------------------------------------
 // A batch touches (2 + M) B rows with repeats (the most popular item is the positive of hundreds of samples).  The
 // (2 + M) B references (sample b, role) are keyed by the row they touch — its compact slot under node_map, its node id
-// otherwise — by rank_refs_kernel and sorted (stable radix sort: the references of a row stay in (role, b) order).  The
-// sorted list is cut into chunks
-// of 64 references, one wavefront each: a run of equal keys that lies inside a chunk is summed in order and added to its
-// row by that wavefront alone; a run that crosses chunk borders leaves one partial row per chunk, and the wavefront of
-// the chunk where the run starts adds those up in chunk order.  One writer per row, fixed orders throughout: the whole
-// train step is bitwise reproducible.
-constexpr int kRefChunk = 64;
+// otherwise — by rank_refs_kernel, sorted (stable: the references of a row stay in (role, b) order) and summed row by row
+// by the wave-per-chunk scheme of refsum.hpp.  The two chunk kernels below say what a reference adds.
 constexpr int kMaxDPerLane = 8;  // d <= 512
 
 // The chunk pass of (reference, M = 1, no logq), 3B references: a reference has at most two terms (the user's row takes
 // p - n), so the lane that holds a reference holds its terms and the in-order pass needs no term numbering.
+struct BprTerms {
+    static constexpr int kTerms = 2;
+    int64_t srcA = 0, srcB = 0;   // rows of final
+    float wA = 0.f, wB = 0.f;     // wB == 0: one term
+    __device__ __forceinline__ int64_t row(int t, int q) const { return __shfl(t == 0 ? srcA : srcB, q, MI_WAVE); }
+    __device__ __forceinline__ float weight(int t, int q) const { return __shfl(t == 0 ? wA : wB, q, MI_WAVE); }
+};
+
 template <int VPT>  // floats of a row per lane: ceil(d / 64)
 __global__ __launch_bounds__(kBlock) void bpr_chunk_kernel(
-    int64_t batch, int d, int64_t n_users, const int64_t* __restrict__ users, const int64_t* __restrict__ pos,
+    int64_t batch, int64_t n_users, const int64_t* __restrict__ users, const int64_t* __restrict__ pos,
     const int64_t* __restrict__ neg, const float* __restrict__ fin, int64_t ldf, const float* __restrict__ coef,
     const uint32_t* __restrict__ keys, const uint32_t* __restrict__ refs, const int32_t* __restrict__ node_map,
-    float* __restrict__ g_final, int64_t ldg, float* __restrict__ part_head, float* __restrict__ part_tail,
-    float* __restrict__ reg_w, float reg_unit /* 2 * lambda * reg_scale: one reference's share */) {
+    refsum::Dest to, float* __restrict__ reg_w, float reg_unit /* 2 * lambda * reg_scale: one reference's share */) {
     const int64_t n_ref = 3 * batch;
-    const int64_t chunk = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / MI_WAVE;
-    const int64_t j0 = chunk * kRefChunk;
-    if (j0 >= n_ref) return;
-    const int lane = mi_lane();
-    const int n_here = (int)min((int64_t)kRefChunk, n_ref - j0);
-    // this lane's reference: destination key, up to two (source row, weight) terms
-    uint32_t my_key = 0xFFFFFFFFu;
-    int64_t srcA = 0, srcB = 0;
-    float wA = 0.f, wB = 0.f;
-    if (lane < n_here) {
-        my_key = keys[j0 + lane];
-        const uint32_t r = refs[j0 + lane];
+    const refsum::Chunk c = refsum::open_chunk(keys, n_ref);
+    if (c.n_here == 0) return;
+    BprTerms term;
+    if (c.lane < c.n_here) {
+        const uint32_t r = refs[c.j0 + c.lane];
         const int role = (int)(r / batch);
         const int64_t b = r - (int64_t)role * batch;
-        const float c = coef[b];
+        const float cf = coef[b];
         const int64_t u = users[b], p = n_users + pos[b], n = n_users + neg[b];
         const int64_t fu = node_map ? node_map[u] : u, fp = node_map ? node_map[p] : p, fn = node_map ? node_map[n] : n;
-        if (role == 0) { srcA = fp; wA = c; srcB = fn; wB = -c; }   // d x / d u = p - n
-        else if (role == 1) { srcA = fu; wA = c; }
-        else { srcA = fu; wA = -c; }
-        // L2 weight of the node: (its references in the batch) x reg_unit.  The reference that opens the node's run in the
-        // sorted list finds the run's end by bisection and is the entry's only writer (reg_w is zero on entry).
+        if (role == 0) { term.srcA = fp; term.wA = cf; term.srcB = fn; term.wB = -cf; }   // d x / d u = p - n
+        else if (role == 1) { term.srcA = fu; term.wA = cf; }
+        else { term.srcA = fu; term.wA = -cf; }
         if (reg_w) {
-            const int64_t j = j0 + lane;
-            if (j == 0 || keys[j - 1] != my_key) {
-                int64_t lo = j + 1, hi = n_ref;        // first position in (j, n_ref] whose key differs
-                while (lo < hi) {
-                    const int64_t mid = (lo + hi) >> 1;
-                    if (keys[mid] == my_key) lo = mid + 1; else hi = mid;
-                }
-                const int64_t node = role == 0 ? u : (role == 1 ? p : n);
-                reg_w[node] = (float)(lo - j) * reg_unit;
-            }
+            const int64_t len = refsum::run_length(keys, c.j0 + c.lane, n_ref);
+            if (len) reg_w[role == 0 ? u : (role == 1 ? p : n)] = (float)len * reg_unit;
         }
     }
-    const bool head_open = j0 > 0 && keys[j0 - 1] == __shfl(my_key, 0, MI_WAVE);
-    const bool next_same = (j0 + n_here < n_ref) && keys[j0 + n_here] == __shfl(my_key, n_here - 1, MI_WAVE);
-    float acc[VPT];
-#pragma unroll
-    for (int v = 0; v < VPT; ++v) acc[v] = 0.f;
-    int run_start = 0;
-    constexpr int U = 8;  // references whose source rows are in flight together
-    for (int q0 = 0; q0 < n_here; q0 += U) {
-        float xa[U][VPT], xb[U][VPT], wa[U], wb[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int q = min(q0 + u, n_here - 1);
-            const bool live = q0 + u < n_here;
-            wa[u] = live ? __shfl(wA, q, MI_WAVE) : 0.f;
-            wb[u] = live ? __shfl(wB, q, MI_WAVE) : 0.f;
-            const float* ra = fin + __shfl(srcA, q, MI_WAVE) * ldf;
-            const float* rb = fin + __shfl(srcB, q, MI_WAVE) * ldf;
-#pragma unroll
-            for (int v = 0; v < VPT; ++v) {
-                const int k = lane + v * MI_WAVE;
-                xa[u][v] = (live && k < d) ? ra[k] : 0.f;
-                xb[u][v] = (wb[u] != 0.f && k < d) ? rb[k] : 0.f;   // wave-uniform condition
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int q = q0 + u;
-            if (q >= n_here) break;
-            const uint32_t kq = __shfl(my_key, q, MI_WAVE);
-#pragma unroll
-            for (int v = 0; v < VPT; ++v) {
-                acc[v] = fmaf(wa[u], xa[u][v], acc[v]);
-                if (wb[u] != 0.f) acc[v] = fmaf(wb[u], xb[u][v], acc[v]);
-            }
-            const bool last_of_run = (q + 1 == n_here) || __shfl(my_key, q + 1, MI_WAVE) != kq;
-            if (!last_of_run) continue;
-            const bool from_prev = run_start == 0 && head_open;
-            const bool into_next = (q + 1 == n_here) && next_same;
-            float* dst;
-            if (from_prev) dst = part_head + chunk * d;          // finished by the chunk where the run starts
-            else if (into_next) dst = part_tail + chunk * d;     // this chunk starts the run and finishes it below
-            else dst = g_final + (int64_t)kq * ldg;              // the run lies inside this chunk: the row's only writer
-#pragma unroll
-            for (int v = 0; v < VPT; ++v) {
-                const int k = lane + v * MI_WAVE;
-                if (k < d) dst[k] = acc[v];   // g_final is zero on entry (header contract): a store, not a read-modify-write
-                acc[v] = 0.f;
-            }
-            run_start = q + 1;
-        }
-    }
-}
-
-// One wavefront per chunk whose trailing run starts in it and runs on: tail partial + the head partials of the following
-// chunks, in chunk order, added to the row.
-template <int VPT>
-__global__ __launch_bounds__(kBlock) void bpr_combine_kernel(int64_t n_ref, int d, const uint32_t* __restrict__ keys,
-                                                             const float* __restrict__ part_head,
-                                                             const float* __restrict__ part_tail,
-                                                             float* __restrict__ g_final, int64_t ldg) {
-    const int64_t chunk = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / MI_WAVE;
-    const int64_t j0 = chunk * kRefChunk;
-    if (j0 >= n_ref) return;
-    const int64_t j_last = min(j0 + kRefChunk, n_ref) - 1;
-    if (j_last + 1 >= n_ref) return;                       // nothing after this chunk
-    const uint32_t row = keys[j_last];
-    if (keys[j_last + 1] != row) return;                   // the trailing run ends here
-    if (keys[j0] == row && j0 > 0 && keys[j0 - 1] == row) return;  // the run started in an earlier chunk: not the owner
-    const int lane = mi_lane();
-    float acc[VPT];
-#pragma unroll
-    for (int v = 0; v < VPT; ++v) {
-        const int k = lane + v * MI_WAVE;
-        acc[v] = k < d ? part_tail[chunk * d + k] : 0.f;
-    }
-    for (int64_t nb = chunk + 1; nb * kRefChunk < n_ref && keys[nb * kRefChunk] == row; ++nb) {
-#pragma unroll
-        for (int v = 0; v < VPT; ++v) {
-            const int k = lane + v * MI_WAVE;
-            if (k < d) acc[v] += part_head[nb * d + k];
-        }
-        if (keys[min((nb + 1) * kRefChunk, n_ref) - 1] != row) break;   // the run ends inside chunk nb
-    }
-    float* dst = g_final + (int64_t)row * ldg;
-#pragma unroll
-    for (int v = 0; v < VPT; ++v) {
-        const int k = lane + v * MI_WAVE;
-        if (k < d) dst[k] = acc[v];
-    }
-}
-
-// Single block, fixed order: loss = -sum(softplus)/B + lambda*sum(reg).
-__global__ __launch_bounds__(1024) void bpr_finish_kernel(int64_t batch,
-                                                          const float* __restrict__ softplus_v,
-                                                          const float* __restrict__ reg_v,
-                                                          float inv_batch, float lambda,
-                                                          float* __restrict__ loss_out) {
-    __shared__ float sh_a[1024];
-    __shared__ float sh_b[1024];
-    const int t = threadIdx.x;
-    float a = 0.f, r = 0.f;
-#pragma unroll 4
-    for (int64_t i = t; i < batch; i += 1024) {   // coalesced, independent loads (a contiguous slice per thread was a chain
-        a += softplus_v[i];                        // of 16 strided loads: 17 us at B = 16 384); fixed order all the same
-        r += reg_v[i];
-    }
-    sh_a[t] = a;
-    sh_b[t] = r;
-    __syncthreads();
-    for (int s = 512; s > 0; s >>= 1) {
-        if (t < s) {
-            sh_a[t] += sh_a[t + s];
-            sh_b[t] += sh_b[t + s];
-        }
-        __syncthreads();
-    }
-    if (t == 0) loss_out[0] = -sh_a[0] * inv_batch + lambda * sh_b[0];
+    refsum::walk_references<VPT>(c, term, fin, ldf, to);
 }
 
 // ------------------------------------------------------------------ ranking objectives, M negatives ------------
@@ -484,35 +352,25 @@ __global__ void rank_refs_kernel(int64_t batch, int n_neg, int64_t n_users, cons
 // in flight whatever the mix of roles.
 template <int VPT>
 __global__ __launch_bounds__(kBlock) void rank_chunk_kernel(
-    int64_t batch, int n_neg, int d, int64_t n_users, const int64_t* __restrict__ users,
+    int64_t batch, int n_neg, int64_t n_users, const int64_t* __restrict__ users,
     const int64_t* __restrict__ pos, const int64_t* __restrict__ neg, const float* __restrict__ fin, int64_t ldf,
     const float* __restrict__ coef, const uint32_t* __restrict__ keys, const uint32_t* __restrict__ refs,
-    const int32_t* __restrict__ node_map, float* __restrict__ g_final, int64_t ldg, float* __restrict__ part_head,
-    float* __restrict__ part_tail, float* __restrict__ reg_w, float reg_unit) {
+    const int32_t* __restrict__ node_map, refsum::Dest to, float* __restrict__ reg_w, float reg_unit) {
     const int64_t n_ref = (2 + n_neg) * batch;
-    const int64_t chunk = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / MI_WAVE;
-    const int64_t j0 = chunk * kRefChunk;
-    if (j0 >= n_ref) return;
-    const int lane = mi_lane();
-    const int n_here = (int)min((int64_t)kRefChunk, n_ref - j0);
-    uint32_t my_key = 0xFFFFFFFFu;
+    const refsum::Chunk c = refsum::open_chunk(keys, n_ref);
+    if (c.n_here == 0) return;
+    const int lane = c.lane, n_here = c.n_here;
     int my_role = 1, my_b = 0, my_terms = 0;
     if (lane < n_here) {
-        my_key = keys[j0 + lane];
-        const uint32_t r = refs[j0 + lane];
+        const uint32_t r = refs[c.j0 + lane];
         my_role = (int)(r / batch);
         my_b = (int)(r - (int64_t)my_role * batch);
         my_terms = my_role == 0 ? 1 + n_neg : 1;
-        if (reg_w) {   // the reference that opens the node's run is the entry's only writer (see bpr_chunk_kernel)
-            const int64_t j = j0 + lane;
-            if (j == 0 || keys[j - 1] != my_key) {
-                int64_t lo = j + 1, hi = n_ref;
-                while (lo < hi) {
-                    const int64_t mid = (lo + hi) >> 1;
-                    if (keys[mid] == my_key) lo = mid + 1; else hi = mid;
-                }
+        if (reg_w) {
+            const int64_t len = refsum::run_length(keys, c.j0 + lane, n_ref);
+            if (len) {
                 const int64_t node = my_role == 0 ? users[my_b] : n_users + (my_role == 1 ? pos[my_b] : neg[(int64_t)my_b * n_neg + (my_role - 2)]);
-                reg_w[node] = (float)(lo - j) * reg_unit;
+                reg_w[node] = (float)len * reg_unit;
             }
         }
     }
@@ -524,13 +382,8 @@ __global__ __launch_bounds__(kBlock) void rank_chunk_kernel(
     }
     const int total = __shfl(incl, MI_WAVE - 1, MI_WAVE);
     const int excl = incl - my_terms;
-    const bool head_open = j0 > 0 && keys[j0 - 1] == __shfl(my_key, 0, MI_WAVE);
-    const bool next_same = (j0 + n_here < n_ref) && keys[j0 + n_here] == __shfl(my_key, n_here - 1, MI_WAVE);
-    float acc[VPT];
-#pragma unroll
-    for (int v = 0; v < VPT; ++v) acc[v] = 0.f;
-    int run_start = 0;
-    constexpr int U = 8;  // terms whose source rows are in flight together
+    refsum::RunWriter<VPT> run;
+    constexpr int U = refsum::kInFlight;  // terms whose source rows are in flight together
     for (int r0 = 0; r0 < total; r0 += MI_WAVE) {
         // a round of up to 64 terms, one per lane: owner by bisection over the prefix sums, then this lane's own chain of
         // loads (ids -> slot -> weight), so that the in-order pass below only shuffles
@@ -572,33 +425,16 @@ __global__ __launch_bounds__(kBlock) void rank_chunk_kernel(
 #pragma unroll
                 for (int v = 0; v < VPT; ++v) {
                     const int k = lane + v * MI_WAVE;
-                    x[i][v] = (live && k < d) ? row[k] : 0.f;
+                    x[i][v] = (live && k < to.d) ? row[k] : 0.f;
                 }
             }
 #pragma unroll
             for (int i = 0; i < U; ++i) {
                 const int sl = q0 + i;
                 if (sl >= n_round) break;
-#pragma unroll
-                for (int v = 0; v < VPT; ++v) acc[v] = fmaf(w[i], x[i][v], acc[v]);
+                run.add(w[i], x[i]);
                 if (!__shfl(t_closes, sl, MI_WAVE)) continue;   // more terms of this reference follow
-                const int q = __shfl(t_owner, sl, MI_WAVE);
-                const uint32_t kq = __shfl(my_key, q, MI_WAVE);
-                const bool last_of_run = (q + 1 == n_here) || __shfl(my_key, q + 1, MI_WAVE) != kq;
-                if (!last_of_run) continue;
-                const bool from_prev = run_start == 0 && head_open;
-                const bool into_next = (q + 1 == n_here) && next_same;
-                float* dst;
-                if (from_prev) dst = part_head + chunk * d;
-                else if (into_next) dst = part_tail + chunk * d;
-                else dst = g_final + (int64_t)kq * ldg;
-#pragma unroll
-                for (int v = 0; v < VPT; ++v) {
-                    const int k = lane + v * MI_WAVE;
-                    if (k < d) dst[k] = acc[v];
-                    acc[v] = 0.f;
-                }
-                run_start = q + 1;
+                run.close(c, __shfl(t_owner, sl, MI_WAVE), to);
             }
         }
     }
@@ -705,15 +541,6 @@ int sample_batch_launch(int64_t batch, int n_neg, int64_t nnz, const int32_t* ro
                        (hipStream_t)stream, batch, n_neg, nnz, rowptr, col, row_of_edge, draw, edges_in_order, seed, step,
                        users, pos, neg);
     return mi_launch_status();
-}
-
-// f(std::integral_constant<int, VPT>), VPT = the floats of a d-wide row per lane, ceil(d / 64) rounded up to 1, 2, 4 or 8
-template <class F>
-void with_vpt(int64_t d, F&& f) {
-    if (d <= 64) f(std::integral_constant<int, 1>{});
-    else if (d <= 128) f(std::integral_constant<int, 2>{});
-    else if (d <= 256) f(std::integral_constant<int, 4>{});
-    else f(std::integral_constant<int, 8>{});
 }
 
 }  // namespace
@@ -827,17 +654,13 @@ int mi_scatter_rows_f32(int64_t n_max, const int32_t* n_dev, const int32_t* begi
     return mi_launch_status();
 }
 
-static size_t bpr_sort_tmp_bytes(int64_t n_ref) { return ((size_t)1 << 20) + mi_align_up((size_t)n_ref * 2, 256); }
-
 size_t mi_rank_loss_workspace_bytes(int64_t batch, int32_t n_neg) {
     const size_t b = (size_t)(batch > 0 ? batch : 1);
     const size_t m = (size_t)(n_neg >= 1 && n_neg <= kMaxNeg ? n_neg : 1);
-    const size_t n_ref = (2 + m) * b, chunks = (n_ref + 63) / 64;
-    // loss term, reg per slot; 1 + M coefficients per slot; (key, reference) double buffers; rocPRIM scratch; head / tail
-    // partial rows per 64-reference chunk (d <= 512)
+    // loss term, reg per slot; 1 + M coefficients per slot; the segmented sum's buffers.  This function is not told d, so the
+    // partial rows are sized for the widest row the kernels take (d <= 512); the kernels address them d floats apart.
     return 2 * mi_align_up(b * sizeof(float), 256) + mi_align_up((1 + m) * b * sizeof(float), 256) +
-           4 * mi_align_up(n_ref * sizeof(uint32_t), 256) + bpr_sort_tmp_bytes((int64_t)n_ref) +
-           2 * mi_align_up(chunks * 512 * sizeof(float), 256);
+           refsum::workspace_bytes((int64_t)((2 + m) * b), MI_WAVE * kMaxDPerLane);
 }
 
 // all three loss entries; logq == nullptr launches what mi_rank_loss_fwd_bwd_f32 always launched
@@ -857,21 +680,20 @@ static int rank_loss_run(int64_t batch, int32_t n_neg, int32_t objective, int64_
     if ((2 + (int64_t)n_neg) * batch >= INT32_MAX) return MI_ERR_TOO_LARGE;
     if (d > MI_WAVE * kMaxDPerLane) return MI_ERR_UNSUPPORTED;
     if (ws_bytes < mi_rank_loss_workspace_bytes(batch, n_neg)) return MI_ERR_WORKSPACE;
-    const int64_t n_ref = (2 + (int64_t)n_neg) * batch, n_chunks = mi_ceil_div(n_ref, kRefChunk);
+    const int64_t n_ref = (2 + (int64_t)n_neg) * batch;
     MiArena arena(ws, ws_bytes);
     float* termv = arena.take<float>(batch);
     float* rgv = arena.take<float>(batch);
     float* coef = arena.take<float>((size_t)(1 + n_neg) * batch);
-    uint32_t* k0 = arena.take<uint32_t>(n_ref);
-    uint32_t* k1 = arena.take<uint32_t>(n_ref);
-    uint32_t* r0 = arena.take<uint32_t>(n_ref);
-    uint32_t* r1 = arena.take<uint32_t>(n_ref);
-    const size_t tmp_cap = bpr_sort_tmp_bytes(n_ref);
-    char* tmp = arena.take<char>(tmp_cap);
-    float* part_head = arena.take<float>((size_t)n_chunks * 512);
-    float* part_tail = arena.take<float>((size_t)n_chunks * 512);
-    if (!termv || !rgv || !coef || !k0 || !k1 || !r0 || !r1 || !tmp || !part_head || !part_tail) return MI_ERR_WORKSPACE;
+    const refsum::Buffers sum = refsum::take(arena, n_ref, MI_WAVE * kMaxDPerLane);
+    if (!termv || !rgv || !coef || !sum.ok()) return MI_ERR_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
+    refsum::Sort sorted;
+    if (g_final) {
+        const int rc = refsum::plan_sort(sum, n_ref, node_map != nullptr, s, sorted);
+        if (rc) return rc;
+    }
+    // ---- nothing has been enqueued up to here ----
     // the mean runs over the B*M pairs, or over the B slots for the softmax
     const float inv_count = 1.0f / (float)(objective == kRankSoftmax ? batch : batch * n_neg);
     const float reg_coef = reg_scale * lambda;
@@ -880,12 +702,13 @@ static int rank_loss_run(int64_t batch, int32_t n_neg, int32_t objective, int64_
     const dim3 g((unsigned)mi_ceil_div(batch * MI_WAVE, kBlock));
     float* const coef_out = g_final ? coef : nullptr;
     float* const slot_reg_w = g_final ? nullptr : reg_w;
+    const int64_t vpt = mi_ceil_div(d, MI_WAVE);
     if (bpr_form)
         hipLaunchKernelGGL(bpr_slot_kernel, g, dim3(kBlock), 0, s, batch, (int)d, n_users, users, pos, neg, final_emb, ldf,
                            e0, lde, inv_count, g_scale, reg_coef, termv, rgv, coef_out, slot_reg_w, node_map);
     else
-        with_vpt(d, [&](auto vpt) {
-            constexpr int V = decltype(vpt)::value;
+        refsum::with_vpt(vpt, [&](auto v) {
+            constexpr int V = decltype(v)::value;
             auto slot = logq ? rank_slot_kernel<V, true> : rank_slot_kernel<V, false>;
             hipLaunchKernelGGL(slot, g, dim3(kBlock), 0, s, batch, (int)n_neg, (int)objective, (int)d, n_users, users, pos,
                                neg, final_emb, ldf, e0, lde, inv_count, g_scale, reg_coef, termv, rgv, coef_out, slot_reg_w,
@@ -893,34 +716,25 @@ static int rank_loss_run(int64_t batch, int32_t n_neg, int32_t objective, int64_
         });
     if (g_final) {
         hipLaunchKernelGGL(rank_refs_kernel, dim3((unsigned)mi_ceil_div(n_ref, 256)), dim3(256), 0, s, batch, (int)n_neg,
-                           n_users, users, pos, neg, node_map, k0, r0);
-        unsigned bits = 32;   // compact slots are < (2 + M) B; node ids need all 32 bits
-        if (node_map) {
-            bits = 1;
-            while (((int64_t)1 << bits) < n_ref) ++bits;
-        }
-        rocprim::double_buffer<uint32_t> keys(k0, k1), refs(r0, r1);
-        size_t need = 0;
-        MI_HIP(rocprim::radix_sort_pairs(nullptr, need, keys, refs, (size_t)n_ref, 0, bits, s));
-        if (need > tmp_cap) return MI_ERR_WORKSPACE;
-        MI_HIP(rocprim::radix_sort_pairs(tmp, need, keys, refs, (size_t)n_ref, 0, bits, s));
-        const dim3 gc((unsigned)mi_ceil_div(n_chunks * MI_WAVE, kBlock));
-        with_vpt(d, [&](auto vpt) {
-            constexpr int V = decltype(vpt)::value;
+                           n_users, users, pos, neg, node_map, sum.k0, sum.r0);
+        const int rc = refsum::sort(sum, n_ref, s, sorted);
+        if (rc) return rc;
+        const uint32_t *keys = sorted.keys.current(), *refs = sorted.refs.current();
+        const refsum::Dest to{g_final, ldg, sum.part_head, sum.part_tail, (int)d};
+        const dim3 gc = refsum::chunk_grid(n_ref);
+        refsum::with_vpt(vpt, [&](auto v) {
+            constexpr int V = decltype(v)::value;
             if (bpr_form)
-                hipLaunchKernelGGL(bpr_chunk_kernel<V>, gc, dim3(kBlock), 0, s, batch, (int)d, n_users, users, pos, neg,
-                                   final_emb, ldf, coef, keys.current(), refs.current(), node_map, g_final, ldg, part_head,
-                                   part_tail, reg_w, 2.0f * reg_coef);
+                hipLaunchKernelGGL(bpr_chunk_kernel<V>, gc, dim3(kBlock), 0, s, batch, n_users, users, pos, neg, final_emb,
+                                   ldf, coef, keys, refs, node_map, to, reg_w, 2.0f * reg_coef);
             else
-                hipLaunchKernelGGL(rank_chunk_kernel<V>, gc, dim3(kBlock), 0, s, batch, (int)n_neg, (int)d, n_users, users,
-                                   pos, neg, final_emb, ldf, coef, keys.current(), refs.current(), node_map, g_final, ldg,
-                                   part_head, part_tail, reg_w, 2.0f * reg_coef);
-            hipLaunchKernelGGL(bpr_combine_kernel<V>, gc, dim3(kBlock), 0, s, n_ref, (int)d, keys.current(), part_head,
-                               part_tail, g_final, ldg);
+                hipLaunchKernelGGL(rank_chunk_kernel<V>, gc, dim3(kBlock), 0, s, batch, (int)n_neg, n_users, users, pos, neg,
+                                   final_emb, ldf, coef, keys, refs, node_map, to, reg_w, 2.0f * reg_coef);
+            refsum::launch_combine<V>(sorted, n_ref, to, s);
         });
     }
     // the slot terms are stored negated, so every objective closes with loss = -sum(term) / count + lambda * sum(reg)
-    hipLaunchKernelGGL(bpr_finish_kernel, dim3(1), dim3(1024), 0, s, batch, termv, rgv, inv_count, lambda, loss_out);
+    refsum::launch_finish(batch, termv, rgv, -inv_count, lambda, loss_out, s);
     return mi_launch_status();
 }
 

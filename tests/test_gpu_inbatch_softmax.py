@@ -6,6 +6,7 @@ Tolerances are the project's (tests/test_gpu_lightgcn.py): loss 1e-6 * max(1, |l
 trained embeddings <= 1e-4.
 
 Measured maxima on an MI355X are in profiles/inbatch_softmax.md, section (e)."""
+import json
 import os
 import sys
 
@@ -132,6 +133,28 @@ def test_loss_only_form_and_second_call_give_equal_bits(i, with_map):
     only = _device_call(c, 1e-2, c["logq"], with_map, want_grad=False)
     assert t.equal(only[0], a[0])
     assert float(a[1].abs().max()) > 0.0
+
+
+def _loss_bits_tool():
+    """tools/record_loss_bits.py: the cases of tests/golden/loss_path_bits.json and the function that records one."""
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import record_loss_bits
+    return record_loss_bits
+
+
+@pytest.mark.parametrize("i", range(len(T.SHAPES) + 2))
+def test_every_shape_gives_its_recorded_bits(i):
+    """Loss, g_final, reg_w and the loss-only form's loss of every shape of the twin, and of B = 32 and B = 33 at G = 32 (64
+    sorted references: one full chunk; and one reference more), over lam in LAMS, logq off and on, node map off and on,
+    against the bits recorded at the commit tests/golden/loss_path_bits.json names.  The cases and the recording are the
+    tool's: neither side changes alone."""
+    tool = _loss_bits_tool()
+    assert tool.INBATCH_LAMS == LAMS and tool.inbatch_shapes() == len(T.SHAPES) + 2
+    with open(os.path.join(ROOT, "tests", "golden", "loss_path_bits.json")) as f:
+        rec = json.load(f)["in_batch"]
+    assert len(rec) == 8 * tool.inbatch_shapes()
+    for c in tool.inbatch_cases(i):
+        assert tool.inbatch_record(c) == rec[c["key"]], c["key"]
 
 
 # ---------------------------------------------------------------------------- 4: against the M-negative kernel

@@ -188,6 +188,33 @@ def test_reference_objective_one_negative_is_bitwise_the_bpr_entry(D, with_map):
         assert _bits(la) == want["loss_bits"] and _bits(lb) == want["loss_bits"]
 
 
+def _loss_bits_tool():
+    """tools/record_loss_bits.py: the cases of tests/golden/loss_path_bits.json and the function that records one."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
+    import record_loss_bits
+    return record_loss_bits
+
+
+def _recorded_paths():
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "loss_path_bits.json")) as f:
+        return json.load(f)
+
+
+@pytest.mark.parametrize("objective", ["reference", "bpr", "softmax", "softmax+logq"])
+@pytest.mark.parametrize("kind", ["dense", "sparse", "one_chunk", "chunk_plus_one"])
+def test_every_rank_loss_path_gives_its_recorded_bits(kind, objective):
+    """Loss, g_final, reg_w and the loss-only form's loss of every objective, M in {1, 4, 16}, D in {32, 100, 200, 512} (1, 2, 4
+    and 8 floats of a row per lane), without and with node map, against the bits recorded at the commit the file names: on
+    11 nodes (every run crosses chunk borders, some chunks lie wholly inside a run), on 7000 nodes (runs of one, a ragged
+    last chunk), and at 64 and 65 references.  The batches and the recording are the tool's: neither side changes alone."""
+    tool = _loss_bits_tool()
+    rec = _recorded_paths()["rank"]
+    cases = tool.rank_cases(kind, objective)
+    assert len(cases) == (24 if kind in ("dense", "sparse") else 8)
+    for c in cases:
+        assert tool.rank_record(c) == rec[c["key"]], c["key"]
+
+
 @pytest.mark.parametrize("D", [32, 128])
 def test_softmax_with_one_negative_is_bpr(D):
     ops = _ops()

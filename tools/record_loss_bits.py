@@ -5,7 +5,13 @@ tests/test_gpu_objectives.py compares both loss entries and the default step wit
 recorded at the commit it names, the last one whose one-negative entry had a host body of its own; a run on a later tree
 records that tree and is worth a diff against the committed file, nothing else.  The batches below are the test's
 (_small_batch, _model_and_graph, _run): change neither side alone.
-    python3 tools/record_loss_bits.py --commit <short hash of the tree that runs> [--out tests/golden/bpr_entry_bits.json]"""
+
+It also writes tests/golden/loss_path_bits.json: the same for every other loss path (ops.rank_loss_fwd_bwd over objectives, M,
+D and node map on four kinds of batch; ops.inbatch_softmax_fwd_bwd over the twin's shapes and two more), recorded at the
+commit that file names, before the paths shared csrc/refsum.hpp.  Both GPU test files take these cases and their records
+from the functions below.
+    python3 tools/record_loss_bits.py --commit <short hash of the tree that runs> [--out tests/golden/bpr_entry_bits.json]
+                                      [--paths-out tests/golden/loss_path_bits.json]"""
 import argparse
 import hashlib
 import json
@@ -14,6 +20,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))   # the batches and shapes of the tests
 import torch as t
 from laplace_amd import ops
 from laplace_amd.interactions import Interactions
@@ -84,19 +91,128 @@ def default_trainer():
     return {"loss_bits": losses, "table_sha256": digest(tr.table)}
 
 
+# ---- every loss path against its own past: tests/golden/loss_path_bits.json --------------------------------------------------
+# The M-negative entries (ops.rank_loss_fwd_bwd, logq included) and the in-batch softmax, whose gradient passes all end in
+# the sorted-reference segmented sum of csrc/refsum.hpp.  tests/test_gpu_objectives.py and tests/test_gpu_inbatch_softmax.py
+# take the cases and the records from the functions below, so the file and the tests cannot drift apart.
+RANK_OBJECTIVES = ("reference", "bpr", "softmax", "softmax+logq")
+RANK_NEGS = (1, 4, 16)
+RANK_DIMS = (32, 100, 200, 512)          # 1, 2, 4, 8 floats of a row per lane, with ragged tails
+# batch kind -> (B, U, I, the M it is run at); n_ref = (2 + M) B
+RANK_BATCHES = {"dense": (300, 5, 6, RANK_NEGS),      # 11 nodes: every run crosses chunk borders, chunks lie wholly inside runs
+                "sparse": (96, 4000, 3000, RANK_NEGS),  # runs mostly of one; 288 references at M = 1: a ragged last chunk
+                "one_chunk": (16, 5, 6, (2,)),        # n_ref = 64: one full chunk
+                "chunk_plus_one": (13, 5, 6, (3,))}   # n_ref = 65: one chunk and one reference
+INBATCH_LAMS = (0.0, 1e-2)               # LAMS of tests/test_gpu_inbatch_softmax.py
+# (B, G, d, users, items) beside inbatch_softmax_twin.SHAPES: 2B = 64, one full chunk, and one reference more; the smallest group
+INBATCH_EXTRA_SHAPES = ((32, 32, 16, 5, 6), (33, 32, 16, 5, 6))
+
+
+def rank_cases(kind, objective):
+    """The cases of one batch kind and objective: dicts of kind, objective, M, D, with_map and their key in the file."""
+    return [dict(kind=kind, objective=objective, M=M, D=D, with_map=with_map,
+                 key=f"{kind}_{objective}_M{M}_D{D}_map{int(with_map)}")
+            for M in RANK_BATCHES[kind][3] for D in RANK_DIMS for with_map in (False, True)]
+
+
+def rank_record(c):
+    """Loss bits, digests of g_final and reg_w, and the loss bits of the loss-only form (no g_final, no reg_w) of case c."""
+    from test_gpu_objectives import _small_batch
+    B, U, I, _ = RANK_BATCHES[c["kind"]]
+    M, D = c["M"], c["D"]
+    _, _, final, e0, users, pos, neg = _small_batch(B, M, D, seed=1000 * M + D, U=U, I=I)
+    objective, logq = c["objective"], None
+    if objective == "softmax+logq":
+        objective = "softmax"
+        logq = t.log(0.1 * t.rand(I, generator=t.Generator().manual_seed(D + M)) + 1e-4).to(DEV)
+    ud, pd, nd, e0d = users.to(DEV), pos.to(DEV), neg.to(DEV), e0.to(DEV)
+    src, gmap, rows_n = final.to(DEV), None, U + I
+    if c["with_map"]:
+        gmap, nodes, cnt = ops.batch_nodes(ud, pd, nd, U, U + I)
+        rows_n = (2 + M) * B
+        src = t.zeros(rows_n, D, device=DEV)
+        src[: int(cnt[0])] = final.to(DEV)[nodes[: int(cnt[0])].long()]
+    gf, rw = t.zeros(rows_n, D, device=DEV), t.zeros(U + I, device=DEV)
+    kw = dict(objective=objective, node_map=gmap, logq=logq)
+    loss = ops.rank_loss_fwd_bwd(ud, pd, nd, src, e0d, U, 1e-3, g_final=gf, reg_w=rw, g_scale=1.0 / 3, **kw)
+    only = ops.rank_loss_fwd_bwd(ud, pd, nd, src, e0d, U, 1e-3, **kw)
+    return {"loss_bits": bits(loss), "g_final_sha256": digest(gf), "reg_w_sha256": digest(rw), "loss_only_bits": bits(only)}
+
+
+def inbatch_shapes():
+    import inbatch_softmax_twin as T
+    return len(T.SHAPES) + len(INBATCH_EXTRA_SHAPES)
+
+
+def _inbatch_inputs(i):
+    """Case i of inbatch_softmax_twin.cases(), or the extra shape that follows them (skewed ids: long runs)."""
+    import inbatch_softmax_twin as T
+    if i < len(T.SHAPES):
+        return T.cases()[i]
+    B, G, d, U, I = INBATCH_EXTRA_SHAPES[i - len(T.SHAPES)]
+    g = t.Generator().manual_seed(2000 + i)
+    final, e0 = 0.3 * t.randn(U + I, d, generator=g), t.randn(U + I, d, generator=g)
+    logq = t.log(0.1 * t.rand(I, generator=g) + 1e-4)
+    users, pos = t.randint(0, U, (B,), generator=g), t.randint(0, I, (B,), generator=g)
+    return dict(B=B, G=G, d=d, U=U, I=I, final=final, e0=e0, logq=logq, users=users, pos=pos)
+
+
+def inbatch_cases(i):
+    return [dict(i=i, lam=lam, with_logq=with_logq, with_map=with_map,
+                 key=f"shape{i}_lam{li}_logq{int(with_logq)}_map{int(with_map)}")
+            for li, lam in enumerate(INBATCH_LAMS) for with_logq in (False, True) for with_map in (False, True)]
+
+
+def inbatch_record(c):
+    s = _inbatch_inputs(c["i"])
+    U, I, d, B = s["U"], s["I"], s["d"], s["B"]
+    ud, pd, e0d = s["users"].to(DEV), s["pos"].to(DEV), s["e0"].to(DEV)
+    src, gmap, rows_n = s["final"].to(DEV), None, U + I
+    if c["with_map"]:
+        gmap, nodes, cnt = ops.batch_nodes(ud, pd, pd, U, U + I)   # the node set of (users, pos): neg aliased to pos
+        rows_n = 2 * B
+        src = t.zeros(rows_n, d, device=DEV)
+        src[: int(cnt[0])] = s["final"].to(DEV)[nodes[: int(cnt[0])].long()]
+    gf, rw = t.zeros(rows_n, d, device=DEV), t.zeros(U + I, device=DEV)
+    kw = dict(group=s["G"], logq=s["logq"].to(DEV) if c["with_logq"] else None, node_map=gmap)
+    loss = ops.inbatch_softmax_fwd_bwd(ud, pd, src, e0d, U, c["lam"], g_final=gf, reg_w=rw, g_scale=1.0 / 3, **kw)
+    only = ops.inbatch_softmax_fwd_bwd(ud, pd, src, e0d, U, c["lam"], **kw)
+    return {"loss_bits": bits(loss), "g_final_sha256": digest(gf), "reg_w_sha256": digest(rw), "loss_only_bits": bits(only)}
+
+
+def loss_paths():
+    rank = {c["key"]: rank_record(c) for kind in RANK_BATCHES for o in RANK_OBJECTIVES for c in rank_cases(kind, o)}
+    inb = {c["key"]: inbatch_record(c) for i in range(inbatch_shapes()) for c in inbatch_cases(i)}
+    return rank, inb
+
+
+def write_json(path, out):
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "w") as f:
+        json.dump(out, f, indent=1, sort_keys=True)
+        f.write("\n")
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--commit", required=True, help="short hash of the tree that runs; written into the file")
     ap.add_argument("--out", default=os.path.join(ROOT, "tests", "golden", "bpr_entry_bits.json"))
+    ap.add_argument("--paths-out", default=os.path.join(ROOT, "tests", "golden", "loss_path_bits.json"))
     args = ap.parse_args()
+    rank, inb = loss_paths()
+    write_json(args.paths_out, {
+        "recorded_at_commit": args.commit,
+        "what": "ops.rank_loss_fwd_bwd (rank: batch kind, objective, M, D, node map; lam 1e-3, g_scale 1/3) and "
+                "ops.inbatch_softmax_fwd_bwd (in_batch: shape, lam, logq, node map; g_scale 1/3) on the cases of "
+                "tools/record_loss_bits.py.  fp32 bit patterns in hex (loss, and the loss of the loss-only form), SHA-256 "
+                "of the bytes of g_final and reg_w.",
+        "rank": rank, "in_batch": inb})
+    print(f"{len(rank)} rank and {len(inb)} in-batch cases -> {args.paths_out}")
     full, loss_only = entry_cases()
     out = {"recorded_at_commit": args.commit,
            "what": "ops.bpr_fwd_bwd on _small_batch(300, 1, D, seed=D, U=40, I=25), lam 1e-3, g_scale 1 and 1/3 "
                    "(gscale0 / gscale1), without and with node map; its loss-only form; three default trainer steps of "
                    "_run('reference', 1, steps=3).  fp32 bit patterns in hex, SHA-256 of the arrays' bytes.",
            "entry": full, "entry_loss_only": loss_only, "default_trainer": default_trainer()}
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        json.dump(out, f, indent=1, sort_keys=True)
-        f.write("\n")
+    write_json(args.out, out)
     print(f"{len(full)} + {len(loss_only)} entry cases and the default trainer's three steps -> {args.out}")
