@@ -13,6 +13,9 @@ Faithful quirks: the categorical embedding tables live in a plain dict (not para
 state_dict, frozen) — here they are at least moved by .to(device).  BatchNorm (K8) and the decoder's
 gather + concat run on csrc/norm.hip behind torch's own BatchNorm1d modules (parameters, running statistics and
 state_dict keys unchanged); dropout stays torch's (its mask is torch's RNG stream, as in the reference).
+
+The batch's relation graphs (HeteroGNNEncoder.relation_graphs) and the bookkeeping of a BatchNorm call (bn_call_args) are
+stated here once; ranker_step.FusedRankerStep calls the same two.
 """
 from __future__ import annotations
 
@@ -27,7 +30,7 @@ from torch.nn import BatchNorm1d, ModuleDict, ModuleList
 
 from .. import ops
 from ..utils.constants import Constants
-from .layers import BipartiteGraph, hetero_sage_layer
+from .layers import BipartiteGraph, hetero_sage_layer, relations_arriving
 
 
 def _key(edge_type: Tuple[str, str, str]) -> str:
@@ -89,15 +92,23 @@ def batch_norm(bn: BatchNorm1d, x: Tensor) -> Tensor:
     hand-written kernels.  They hold a channel's scale and shift in LDS for up to ops.BATCHNORM_MAX_CHANNELS channels; the
     reference's BatchNorm1d takes any width, so a wider layer runs torch's own batch_norm (and its autograd backward) on the
     same buffers, with num_batches_tracked and the momentum handled here exactly as for the kernel path."""
+    training, momentum, rm, rv = bn_call_args(bn)
+    if x.shape[-1] > ops.BATCHNORM_MAX_CHANNELS:
+        return F.batch_norm(x, rm, rv, bn.weight, bn.bias, training, momentum, float(bn.eps))
+    return _BatchNormFn.apply(x, bn.weight, bn.bias, rm, rv, momentum, float(bn.eps), training)
+
+
+def bn_call_args(bn: BatchNorm1d) -> Tuple[bool, float, Optional[Tensor], Optional[Tensor]]:
+    """(training, momentum, running_mean, running_var) of one call of a torch BatchNorm1d module, with the bookkeeping
+    torch's own forward does before it: num_batches_tracked counts the call, and momentum=None means the cumulative
+    average 1 / num_batches_tracked."""
     training = bn.training or not bn.track_running_stats
     momentum = 0.0
     if training and bn.track_running_stats:
         bn.num_batches_tracked.add_(1)
         momentum = bn.momentum if bn.momentum is not None else 1.0 / float(bn.num_batches_tracked)
     rm, rv = (bn.running_mean, bn.running_var) if bn.track_running_stats else (None, None)
-    if x.shape[-1] > ops.BATCHNORM_MAX_CHANNELS:
-        return F.batch_norm(x, rm, rv, bn.weight, bn.bias, training, float(momentum), float(bn.eps))
-    return _BatchNormFn.apply(x, bn.weight, bn.bias, rm, rv, float(momentum), float(bn.eps), training)
+    return training, float(momentum), rm, rv
 
 
 class _GatherCatFn(t.autograd.Function):
@@ -141,7 +152,9 @@ class HeteroGNNEncoder(nn.Module):
             per_layer.append(ModuleDict(convs))
         self.layers = ModuleList(per_layer)
 
-    def forward(self, x_dict: Dict[str, Tensor], edge_index_dict: Dict[Tuple[str, str, str], Tensor]):
+    def relation_graphs(self, x_dict: Dict[str, Tensor], edge_index_dict: dict) -> Dict[Tuple[str, str, str], BipartiteGraph]:
+        """{edge type: BipartiteGraph} of a batch, for the edge types this encoder has layers for.  A relation whose
+        edge index is declared another one's reverse (`_reverse_of`, the device sampler) shares that one's sorted CSRs."""
         graphs = {}
         built = {}  # id(edge_index tensor) -> its graph, for relations declared to be another one reversed
         for et, ei in edge_index_dict.items():
@@ -155,6 +168,10 @@ class HeteroGNNEncoder(nn.Module):
                 else:
                     graphs[et] = BipartiteGraph.of(ei, x_dict[et[0]].shape[0], x_dict[et[2]].shape[0])
                     built[id(ei)] = graphs[et]
+        return graphs
+
+    def forward(self, x_dict: Dict[str, Tensor], edge_index_dict: Dict[Tuple[str, str, str], Tensor]):
+        graphs = self.relation_graphs(x_dict, edge_index_dict)
         n_layers = len(self.layers)
         for index, convs in enumerate(self.layers):
             last = index == n_layers - 1
@@ -164,9 +181,7 @@ class HeteroGNNEncoder(nn.Module):
             if fused is not None:  # one autograd node, grouped GEMM launches (model/layers.py)
                 x_dict = fused
                 continue
-            arriving: Dict[str, int] = {}
-            for et in graphs:
-                arriving[et[2]] = arriving.get(et[2], 0) + 1
+            arriving = relations_arriving(graphs)
             by_dst: Dict[str, List[Tensor]] = {}
             for et, graph in graphs.items():
                 # one relation into this destination (the default metadata): the relu rides in the conv's GEMM epilogue

@@ -7,6 +7,10 @@ with lazily sized weights.  Aggregation runs on the HIP SpMM (add / mean) or seg
 over a CSR sorted by destination — no [E, C] message tensor, no atomics in the forward; the two
 Linear products run on the f32-MFMA GEMM.  Both are torch.autograd.Functions whose backward calls
 the same kernels (transposed CSR; dX = dY W, dW = dY^T X).
+
+Stages every path of the ranker iteration shares are stated here once: the aggregate and its backward
+(BipartiteGraph.aggregate / aggregate_backward), the two sorted CSRs of a relation (sorted_csr_pair), and
+the count of relations arriving at a destination type (relations_arriving).
 """
 from __future__ import annotations
 
@@ -84,29 +88,33 @@ class Linear(nn.Module):
 # ------------------------------------------------------------------------------------------------
 # message passing on a destination-sorted CSR
 # ------------------------------------------------------------------------------------------------
+def sorted_csr_pair(edge_index: Tensor, n_src: int, n_dst: int, reuse: bool = True):
+    """(by source, by destination): the two sorted CSRs of a relation.  When the producer of `edge_index` already holds them
+    (the device sampler attaches them as `_sorted_csr`) and their shapes fit, they are taken as they are; a batch from a
+    host loader gets the two sorts the device sampler would have done."""
+    pre = getattr(edge_index, "_sorted_csr", None) if reuse else None
+    if pre is not None and pre[0].n_rows == int(n_src) and pre[1].n_rows == int(n_dst):
+        return pre
+    src, dst = edge_index[0].contiguous(), edge_index[1].contiguous()
+    return (ops.coo_to_csr(src, dst, int(n_src), int(n_dst), want_perm=False),
+            ops.coo_to_csr(dst, src, int(n_dst), int(n_src), want_perm=False))
+
+
 class BipartiteGraph:
     """One relation of a batch: edges src -> dst as two sorted CSRs (by dst for the forward aggregate,
-    by src for its backward), built once per batch on device and shared by all layers."""
+    by src for its backward), built once per batch on device and shared by all layers.  aggregate() and
+    aggregate_backward() are the one statement of the layer's message passing: every path of the ranker calls them."""
 
-    def __init__(self, edge_index: Optional[Tensor], n_src: int, n_dst: int):
+    def __init__(self, edge_index: Optional[Tensor], n_src: int, n_dst: int, reuse: bool = False):
         self.n_src, self.n_dst = int(n_src), int(n_dst)
         self._vals = {}
-        if edge_index is None:  # filled by reversed()
-            return
-        src, dst = edge_index[0].contiguous(), edge_index[1].contiguous()
-        self.by_dst = ops.coo_to_csr(dst, src, self.n_dst, self.n_src, want_perm=False)
-        self.by_src = ops.coo_to_csr(src, dst, self.n_src, self.n_dst, want_perm=False)
+        if edge_index is not None:  # None: filled by reversed()
+            self.by_src, self.by_dst = sorted_csr_pair(edge_index, n_src, n_dst, reuse)
 
     @classmethod
     def of(cls, edge_index: Tensor, n_src: int, n_dst: int) -> "BipartiteGraph":
-        """The relation of `edge_index`; when its producer already holds the two sorted CSRs (the device sampler
-        attaches them as `_sorted_csr` = (by source, by destination)) they are taken as they are."""
-        pre = getattr(edge_index, "_sorted_csr", None)
-        if pre is None or pre[0].n_rows != int(n_src) or pre[1].n_rows != int(n_dst):
-            return cls(edge_index, n_src, n_dst)
-        g = cls(None, n_src, n_dst)
-        g.by_src, g.by_dst = pre
-        return g
+        """The relation of `edge_index`, on its producer's own sorted CSRs when it carries them (sorted_csr_pair)."""
+        return cls(edge_index, n_src, n_dst, reuse=True)
 
     def reversed(self) -> "BipartiteGraph":
         """The relation with every edge turned round (the reference's `rev_*` relation is `edge_index.flip(0)`,
@@ -129,45 +137,40 @@ class BipartiteGraph:
                 raise ValueError(aggr)
         return self._vals[aggr]
 
-
-def _pad4(x: Tensor) -> Tensor:
-    pad = (-x.shape[1]) % 4
-    x = x if x.stride(-1) == 1 else x.contiguous()
-    return F.pad(x, (0, pad)) if pad else x
-
-
-class _AggregateFn(t.autograd.Function):
     @staticmethod
-    def forward(ctx, x_src: Tensor, graph: BipartiteGraph, aggr: str):
-        d = x_src.shape[1]
-        ctx.graph, ctx.aggr, ctx.d = graph, aggr, d
-        if aggr == "max":
-            y, arg = ops.segment_max(graph.by_dst, x_src if x_src.stride(-1) == 1 else x_src.contiguous())
-            ctx.save_for_backward(arg)
-            return y
-        xp = _pad4(x_src)
-        v_dst, _ = graph.weights(aggr)
-        a = ops.DeviceCSR(graph.by_dst.n_rows, graph.by_dst.n_cols, graph.by_dst.rowptr, graph.by_dst.col, v_dst, None,
-                          graph.by_dst.plan)
-        y = t.empty(graph.n_dst, xp.shape[1], device=x_src.device)
-        ops.spmm(a, xp, Y=y)
-        graph.by_dst.plan = a.plan
-        return y[:, :d] if xp.shape[1] != d else y
+    def _weighted_sum(csr, vals: Tensor, x: Tensor, into: Optional[Tensor] = None) -> Tensor:
+        """A x on the SpMM, A = `csr` with `vals`: the width padded to a multiple of 4 for the kernel and sliced off again,
+        the launch plan the call built kept on `csr`.  into: a tensor the product is added to — in the SpMM's epilogue, in
+        place, when no padding was needed."""
+        d = x.shape[1]
+        x = x if x.stride(-1) == 1 else x.contiguous()
+        xp = F.pad(x, (0, (-d) % 4)) if d % 4 else x
+        a = ops.DeviceCSR(csr.n_rows, csr.n_cols, csr.rowptr, csr.col, vals, None, csr.plan)
+        if into is not None and xp.shape[1] == d:
+            ops.spmm(a, xp, addend=into, S=into)
+            y = into
+        else:
+            y = t.empty(csr.n_rows, xp.shape[1], device=x.device)
+            ops.spmm(a, xp, Y=y)
+            if xp.shape[1] != d:
+                y = y[:, :d]
+            if into is not None:
+                y = into + y
+        csr.plan = a.plan
+        return y
 
-    @staticmethod
-    def backward(ctx, dy: Tensor):
-        graph, aggr, d = ctx.graph, ctx.aggr, ctx.d
+    def aggregate(self, x_src: Tensor, aggr: str) -> Tuple[Tensor, Optional[Tensor]]:
+        """(AGG_{j -> i} x_src[j] as [n_dst, C], the winning source rows of "max" for its backward — None otherwise)."""
         if aggr == "max":
-            (arg,) = ctx.saved_tensors
-            return ops.segment_max_bwd(graph.by_src, arg, dy.contiguous()), None, None
-        dyp = _pad4(dy)
-        _, v_src = graph.weights(aggr)
-        a = ops.DeviceCSR(graph.by_src.n_rows, graph.by_src.n_cols, graph.by_src.rowptr, graph.by_src.col, v_src, None,
-                          graph.by_src.plan)
-        dx = t.empty(graph.n_src, dyp.shape[1], device=dy.device)
-        ops.spmm(a, dyp, Y=dx)
-        graph.by_src.plan = a.plan
-        return (dx[:, :d] if dyp.shape[1] != d else dx), None, None
+            return ops.segment_max(self.by_dst, x_src if x_src.stride(-1) == 1 else x_src.contiguous())
+        return self._weighted_sum(self.by_dst, self.weights(aggr)[0], x_src), None
+
+    def aggregate_backward(self, d_agg: Tensor, aggr: str, arg: Optional[Tensor], into: Optional[Tensor] = None) -> Tensor:
+        """dX_src [n_src, C] of aggregate() from dAgg [n_dst, C] (+ `into`, a gradient of x_src that is already there)."""
+        if aggr == "max":
+            g = ops.segment_max_bwd(self.by_src, arg, d_agg)
+            return g if into is None else into + g
+        return self._weighted_sum(self.by_src, self.weights(aggr)[1], d_agg, into)
 
 
 class _SAGEConvFn(t.autograd.Function):
@@ -182,33 +185,20 @@ class _SAGEConvFn(t.autograd.Function):
     @staticmethod
     def forward(ctx, x_src: Tensor, x_dst: Optional[Tensor], w_l: Tensor, b_l: Optional[Tensor], w_r: Optional[Tensor],
                 graph: BipartiteGraph, aggr: str, relu: bool):
-        d = x_src.shape[1]
-        arg = None
-        if aggr == "max":
-            agg, arg = ops.segment_max(graph.by_dst, x_src if x_src.stride(-1) == 1 else x_src.contiguous())
-        else:
-            xp = _pad4(x_src)
-            v_dst, _ = graph.weights(aggr)
-            a = ops.DeviceCSR(graph.by_dst.n_rows, graph.by_dst.n_cols, graph.by_dst.rowptr, graph.by_dst.col, v_dst, None,
-                              graph.by_dst.plan)
-            agg = t.empty(graph.n_dst, xp.shape[1], device=x_src.device)
-            ops.spmm(a, xp, Y=agg)
-            graph.by_dst.plan = a.plan
-            if xp.shape[1] != d:
-                agg = agg[:, :d]
+        agg, arg = graph.aggregate(x_src, aggr)
         root = w_r is not None and x_dst is not None
         out = ops.gemm(agg, w_l, trans_b=True, bias=b_l, relu=relu and not root)
         if root:
             x_dst = x_dst if x_dst.stride(-1) == 1 else x_dst.contiguous()
             ops.gemm(x_dst, w_r, trans_b=True, out=out, accumulate=True, relu=relu)
         ctx.save_for_backward(agg, x_dst if root else None, w_l, w_r if root else None, arg, out if relu else None)
-        ctx.graph, ctx.aggr, ctx.d, ctx.root, ctx.has_bias = graph, aggr, d, root, b_l is not None
+        ctx.graph, ctx.aggr, ctx.root, ctx.has_bias = graph, aggr, root, b_l is not None
         return out
 
     @staticmethod
     def backward(ctx, dy: Tensor):
         agg, x_dst, w_l, w_r, arg, out = ctx.saved_tensors
-        graph, aggr, d = ctx.graph, ctx.aggr, ctx.d
+        graph, aggr = ctx.graph, ctx.aggr
         need = ctx.needs_input_grad
         dy = dy.contiguous()
         if out is not None:
@@ -216,18 +206,7 @@ class _SAGEConvFn(t.autograd.Function):
         dx_src = dx_dst = dw_l = db = dw_r = None
         if need[0]:
             d_agg = ops.gemm(dy, w_l, trans_b=False)                       # [n_dst, C_src]
-            if aggr == "max":
-                dx_src = ops.segment_max_bwd(graph.by_src, arg, d_agg)
-            else:
-                dp = _pad4(d_agg)
-                _, v_src = graph.weights(aggr)
-                a = ops.DeviceCSR(graph.by_src.n_rows, graph.by_src.n_cols, graph.by_src.rowptr, graph.by_src.col, v_src,
-                                  None, graph.by_src.plan)
-                dx_src = t.empty(graph.n_src, dp.shape[1], device=dy.device)
-                ops.spmm(a, dp, Y=dx_src)
-                graph.by_src.plan = a.plan
-                if dp.shape[1] != d:
-                    dx_src = dx_src[:, :d]
+            dx_src = graph.aggregate_backward(d_agg, aggr, arg)
         if ctx.root and need[1]:
             dx_dst = ops.gemm(dy, w_r, trans_b=False)
         if need[2]:
@@ -325,20 +304,7 @@ def hetero_layer_forward(rels, relu: bool, xs, wts):
     for i, (si, di, graph, aggr) in enumerate(rels):
         w_l, b_l, w_r = wts[3 * i: 3 * i + 3]
         x_src, x_dst = xs[si], xs[di]
-        d = x_src.shape[1]
-        arg = None
-        if aggr == "max":
-            agg, arg = ops.segment_max(graph.by_dst, x_src)
-        else:
-            xp = _pad4(x_src)
-            v_dst, _ = graph.weights(aggr)
-            a = ops.DeviceCSR(graph.by_dst.n_rows, graph.by_dst.n_cols, graph.by_dst.rowptr, graph.by_dst.col, v_dst, None,
-                              graph.by_dst.plan)
-            agg = t.empty(graph.n_dst, xp.shape[1], device=x_src.device)
-            ops.spmm(a, xp, Y=agg)
-            graph.by_dst.plan = a.plan
-            if xp.shape[1] != d:
-                agg = agg[:, :d]
+        agg, arg = graph.aggregate(x_src, aggr)
         out = t.empty(graph.n_dst, w_l.shape[0], device=x_src.device)
         specs.append(dict(A=agg, B=w_l, out=out, A2=x_dst, B2=w_r, bias=b_l, relu=relu))
         aggs.append(agg); args.append(arg); outs.append(out)
@@ -378,24 +344,7 @@ def hetero_layer_backward(rels, xs, wts, aggs, args, outs, dys, need):
     for i, (si, di, graph, aggr) in enumerate(rels):
         if d_aggs[i] is None:
             continue
-        d = xs[si].shape[1]
-        if aggr == "max":
-            g_src = ops.segment_max_bwd(graph.by_src, args[i], d_aggs[i])
-            dx[si] = g_src if dx[si] is None else dx[si] + g_src
-        else:
-            dp = _pad4(d_aggs[i])
-            _, v_src = graph.weights(aggr)
-            a = ops.DeviceCSR(graph.by_src.n_rows, graph.by_src.n_cols, graph.by_src.rowptr, graph.by_src.col, v_src,
-                              None, graph.by_src.plan)
-            if dx[si] is not None and dp.shape[1] == d:   # A^T dAgg + the dX_dst already there, in the epilogue
-                ops.spmm(a, dp, addend=dx[si], S=dx[si])
-            else:
-                g_src = t.empty(graph.n_src, dp.shape[1], device=dev)
-                ops.spmm(a, dp, Y=g_src)
-                if dp.shape[1] != d:
-                    g_src = g_src[:, :d]
-                dx[si] = g_src if dx[si] is None else dx[si] + g_src
-            graph.by_src.plan = a.plan
+        dx[si] = graph.aggregate_backward(d_aggs[i], aggr, args[i], into=dx[si])   # A^T dAgg + the dX_dst already there
     # ---- dW half: dW_l = dY^T agg, dW_r = dY^T x_dst, db = dY^T 1 for every relation in one split-K launch
     grads_w = [None] * (3 * n_rel)
     # (round 3) every relation's three transposed products as one launch of the LDS-free kernel (csrc/wgrad.hip) when all
@@ -440,27 +389,26 @@ def hetero_sage_layer(convs: dict, graphs: dict, x_dict: dict, relu: bool) -> Op
     """x_dict after one hetero layer, through _HeteroSAGELayerFn — or None when the layer is not of the fused form
     (several relations into one destination type, normalize=True, no root weight): the caller then runs the relations
     one by one.  convs: {edge type: SAGEConv}; graphs: {edge type: BipartiteGraph}."""
-    types = list(x_dict)
-    arriving = {}
-    for et in graphs:
-        arriving[et[2]] = arriving.get(et[2], 0) + 1
-    if not graphs or any(v != 1 for v in arriving.values()):
-        return None
     col = hetero_layer_relations(convs, graphs, x_dict)
     if col is None:
         return None
     rels, wts = col
-    outs = _HeteroSAGELayerFn.apply(tuple(rels), relu, len(types), *[x_dict[k] for k in types], *wts)
+    outs = _HeteroSAGELayerFn.apply(tuple(rels), relu, len(x_dict), *x_dict.values(), *wts)
     return {et[2]: o for et, o in zip(graphs, outs)}
+
+
+def relations_arriving(edge_types) -> dict:
+    """{destination type: how many of `edge_types` arrive at it}.  The fused form of a layer needs exactly one each."""
+    arriving = {}
+    for et in edge_types:
+        arriving[et[2]] = arriving.get(et[2], 0) + 1
+    return arriving
 
 
 def hetero_layer_relations(convs: dict, graphs: dict, x_dict: dict):
     """(rels, wts) of a layer in the fused form, or None (see hetero_sage_layer); sizes lazy weights from x_dict."""
     types = list(x_dict)
-    arriving = {}
-    for et in graphs:
-        arriving[et[2]] = arriving.get(et[2], 0) + 1
-    if not graphs or any(v != 1 for v in arriving.values()):
+    if not graphs or any(v != 1 for v in relations_arriving(graphs).values()):
         return None
     rels, wts = [], []
     for et, graph in graphs.items():

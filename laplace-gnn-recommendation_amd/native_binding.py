@@ -1,6 +1,7 @@
 """What the one-C-call executors' host sides share (ranker_native.NativeRankerStep / NativeRankerForward,
 pinsage.native.NativePinSAGEStep, pinsage.model.ItemProjector): torch.optim.Adam's state as the executors read and write it, the
-flat gradient buffer, the test for a stale raw-pointer descriptor, and the collective accept / decline of a data-parallel step.
+flat gradient buffer, the workspace growth rule (grown_workspace), the test for a stale raw-pointer descriptor, and the collective
+accept / decline of a data-parallel step.
 """
 from __future__ import annotations
 
@@ -62,6 +63,15 @@ def flat_grad_views(params: Sequence[Tensor], flat: Optional[Tensor], *, keep_va
             view.copy_(p.grad)
         p.grad = view
     return flat
+
+
+# ---- the executors' workspace -------------------------------------------------------------------------------------------------
+def grown_workspace(current: Optional[Tensor], need: int, device) -> Tensor:
+    """`current` when it holds `need` bytes; else a new one of `need` + 25 % + 1 MiB, so that the next, slightly larger batch
+    does not allocate again.  current=None always allocates."""
+    if current is not None and current.numel() >= need:
+        return current
+    return t.empty(int(need * 1.25) + (1 << 20), dtype=t.uint8, device=device)
 
 
 # ---- stale descriptors ----------------------------------------------------------------------------------------------------------

@@ -29,8 +29,8 @@ iteration walks a lazy table: `p.grad` of a lazy table stays None (the id-only m
 featured model's summed rows pass through a zero-kept buffer the step owns), and sparse_optimizer.state[p] keeps torch's layout
 (`step` a Python int, dense exp_avg / exp_avg_sq), so its state_dict() loads into a fresh SparseAdam and the reverse.
 
-The host side shared with the ranker's executor — Adam's state, the flat gradient buffer, the stale-descriptor test, the
-collective decline — is native_binding.py.
+The host side shared with the ranker's executor — Adam's state, the flat gradient buffer, the workspace growth rule, the
+stale-descriptor test, the collective decline — is native_binding.py.
 """
 from __future__ import annotations
 
@@ -44,7 +44,7 @@ from .. import _lib
 from .._lib import PinsageModel, PinsageStepBatch
 from ..model.layers import _ones4
 from ..native_binding import (PEER_DECLINED, PointerSnapshot, adam_unsupported_reason, all_ranks_take_it, bind_param,
-                              bump_adam_steps, collective_prepare, ensure_adam_state, flat_grad_views)
+                              bump_adam_steps, collective_prepare, ensure_adam_state, flat_grad_views, grown_workspace)
 from .model import PinSAGEModel
 
 
@@ -349,8 +349,7 @@ class NativePinSAGEStep:
             b.rows_out, b.bias_out = rows[1].data_ptr(), rows[2].data_ptr()
         L = _lib.lib()
         need = int(L.mi_pinsage_step_workspace_bytes(ctypes.byref(d), ctypes.byref(b)))
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = t.empty(int(need * 1.25) + (1 << 20), dtype=t.uint8, device=seeds.device)
+        self._ws = grown_workspace(self._ws, need, seeds.device)
         if self._world() > 1:      # the validation pass on its own only where the ranks must agree before anything is enqueued
             rc = L.mi_pinsage_step_check(ctypes.byref(d), ctypes.byref(b), self._ws.data_ptr(), self._ws.numel())
             if rc == _lib.MI_ERR_UNSUPPORTED:

@@ -11,9 +11,10 @@ The model, its parameters / buffers / state_dict and the optimizer object stay t
 `param.grad`, Adam's moments in `optimizer.state[p]["exp_avg" / "exp_avg_sq"]`, its step count in `state[p]["step"]`.
 Shapes the executor does not take (MI_ERR_UNSUPPORTED, nothing enqueued) fall to FusedRankerStep / autograd.
 
-The training step and NativeRankerForward fill the model half of the descriptor with one function (_fill_model); what this host
-side shares with PinSAGE's executor (Adam's state, the flat gradient buffer, the stale-descriptor test, the collective decline) is
-native_binding.py.
+The training step and NativeRankerForward fill the model half of the descriptor with one function (_fill_model) and the half of
+the batch descriptor they share with another (_fill_batch; the relation's two sorted CSRs are model/layers.sorted_csr_pair);
+what this host side shares with PinSAGE's executor (Adam's state, the flat gradient buffer, the workspace growth rule, the
+stale-descriptor test, the collective decline) is native_binding.py.
 """
 from __future__ import annotations
 
@@ -27,9 +28,9 @@ from torch import Tensor
 from . import _lib, ops
 from ._lib import RankerBatch, RankerModel
 from .model.encoder_decoder import Encoder_Decoder_Model, _key
-from .model.layers import Linear, SAGEConv, _ones4
+from .model.layers import Linear, SAGEConv, _ones4, sorted_csr_pair
 from .native_binding import (PEER_DECLINED, PointerSnapshot, adam_unsupported_reason, all_ranks_take_it, bind_param,
-                             bump_adam_steps, collective_prepare, ensure_adam_state, flat_grad_views)
+                             bump_adam_steps, collective_prepare, ensure_adam_state, flat_grad_views, grown_workspace)
 from .utils.constants import Constants
 
 _NODES = (Constants.node_user, Constants.node_item)
@@ -86,6 +87,57 @@ def _fill_model(d: RankerModel, model: Encoder_Decoder_Model, grad_of=None) -> N
             if layer.bias is not None:
                 ln.gb = grad_of(layer.bias)
         ln.out, ln.in_ = (int(x) for x in layer.weight.shape)
+
+
+def _fill_batch(owner, x_dict: Dict[str, Tensor], edge_index_dict: dict, edge_label_index: Tensor, why, labels: Optional[Tensor] = None):
+    """The half of a mi_ranker_batch the training step and the forward share: the buys relation as the two sorted CSRs
+    (model/layers.sorted_csr_pair), the feature columns, the label edges — with `labels`, their labels in the field of their
+    dtype — and the ones of the bias gradients in the model descriptor.  Returns (d, b, the tensors b points into), or None
+    with owner.declined set to the caller's words for the failed check: why = (buys relation / label index, labels, features,
+    batch not on the GPU — None where the caller does not ask), checked in that order.  owner._descriptor() is asked for the
+    model descriptor once the batch is accepted."""
+    ei = None
+    for k, v in edge_index_dict.items():
+        if tuple(k) == tuple(Constants.edge_key):
+            ei = v
+    if ei is None or edge_label_index.dtype != t.int64:
+        owner.declined = why[0]
+        return None
+    if labels is not None and labels.dtype not in (t.int64, t.float32):
+        owner.declined = why[1]
+        return None
+    xc, xa = x_dict[Constants.node_user], x_dict[Constants.node_item]
+    if xc.dtype != t.int64 or xa.dtype != t.int64:
+        owner.declined = why[2]
+        return None
+    if why[3] is not None and not xc.is_cuda:
+        owner.declined = why[3]
+        return None
+    n_c, n_a = int(xc.shape[0]), int(xa.shape[0])
+    by_c, by_a = sorted_csr_pair(ei, n_c, n_a)
+    d = owner._descriptor()
+    xc, xa = xc.contiguous(), xa.contiguous()
+    row, col = edge_label_index[0].contiguous(), edge_label_index[1].contiguous()
+    n_lab = int((row if labels is None else labels).numel())
+    ones = _ones4(max(n_c, n_a, n_lab), xc.device)
+    d.ones4, d.n_ones = ones.data_ptr(), int(ones.shape[0])
+    b = RankerBatch()
+    b.n_nodes[0], b.n_nodes[1] = n_c, n_a
+    b.x[0], b.x[1] = xc.data_ptr(), xa.data_ptr()
+    # the column pointer of an edgeless CSR: its tensor has no storage, and the executor wants an address
+    b.by_customer_ptr, b.by_customer_col = by_c.rowptr.data_ptr(), (by_c.col.data_ptr() if by_c.nnz else by_c.rowptr.data_ptr())
+    b.by_article_ptr, b.by_article_col = by_a.rowptr.data_ptr(), (by_a.col.data_ptr() if by_a.nnz else by_a.rowptr.data_ptr())
+    b.nnz, b.n_label = by_c.nnz, n_lab
+    b.label_row, b.label_col = row.data_ptr(), col.data_ptr()
+    keep = [xc, xa, row, col, ones, by_c, by_a]
+    if labels is not None:
+        labels = labels.contiguous()
+        if labels.dtype == t.int64:     # the sampler's edge_label as it is: cast inside the executor
+            b.label = labels.data_ptr()
+        else:
+            b.label_f32 = labels.data_ptr()
+        keep.append(labels)
+    return d, b, keep
 
 
 class NativeRankerStep:
@@ -227,6 +279,12 @@ class NativeRankerStep:
             return out
         return PointerSnapshot([others], optimizer=self.optimizer)
 
+    def _descriptor(self) -> RankerModel:
+        if self._desc is None or not self._snapshot.current():
+            self._desc = self._build()
+            self._snapshot = self._snapshot_now()
+        return self._desc
+
     # ------------------------------------------------------------------------------------------
     def _prepare(self, x_dict: Dict[str, Tensor], edge_index_dict: dict, edge_label_index: Tensor, labels: Tensor):
         """Everything up to (not including) the launch: descriptors built, workspace sized, the executor's own validation
@@ -239,32 +297,12 @@ class NativeRankerStep:
         if model.batch_normalize and not (model.encoder_layer_norm_customer.training and model.encoder_layer_norm_article.training):
             self.declined = "BatchNorm layers in eval mode"
             return None
-        ei = None
-        for k, v in edge_index_dict.items():
-            if tuple(k) == tuple(Constants.edge_key):
-                ei = v
-        if ei is None or edge_label_index.dtype != t.int64:
-            self.declined = "no buys relation / label index not int64"
+        half = _fill_batch(self, x_dict, edge_index_dict, edge_label_index,
+                           ("no buys relation / label index not int64", "labels are neither int64 nor float32",
+                            "features are not int64 categorical columns", None), labels)
+        if half is None:
             return None
-        if labels.dtype not in (t.int64, t.float32):
-            self.declined = "labels are neither int64 nor float32"
-            return None
-        xc, xa = x_dict[Constants.node_user], x_dict[Constants.node_item]
-        if xc.dtype != t.int64 or xa.dtype != t.int64:
-            self.declined = "features are not int64 categorical columns"
-            return None
-        n_c, n_a = int(xc.shape[0]), int(xa.shape[0])
-        pre = getattr(ei, "_sorted_csr", None)
-        if pre is not None and pre[0].n_rows == n_c and pre[1].n_rows == n_a:
-            by_c, by_a = pre
-        else:  # a batch from a host loader: the two sorts the device sampler would have done
-            src, dst = ei[0].contiguous(), ei[1].contiguous()
-            by_c = ops.coo_to_csr(src, dst, n_c, n_a, want_perm=False)
-            by_a = ops.coo_to_csr(dst, src, n_a, n_c, want_perm=False)
-        if self._desc is None or not self._snapshot.current():
-            self._desc = self._build()
-            self._snapshot = self._snapshot_now()
-        d = self._desc
+        d, b, keep = half
         p = model.encoder.p_dropout_features
         d.p_dropout = float(p) if p else 0.0
         group = self.optimizer.param_groups[0]
@@ -272,30 +310,14 @@ class NativeRankerStep:
         d.apply_adam = 0 if (self.before_step is not None or self.data_parallel) else 1
         steps = [self.optimizer.state[q]["step"] for q in group["params"]]
         d.step = self._adam_step + 1
-        xc, xa = xc.contiguous(), xa.contiguous()
-        row, col = edge_label_index[0].contiguous(), edge_label_index[1].contiguous()
-        labels = labels.contiguous()
-        n_lab = int(labels.numel())
-        ones = _ones4(max(n_c, n_a, n_lab), xc.device)
-        d.ones4, d.n_ones = ones.data_ptr(), int(ones.shape[0])
-        b = RankerBatch()
-        b.n_nodes[0], b.n_nodes[1] = n_c, n_a
-        b.x[0], b.x[1] = xc.data_ptr(), xa.data_ptr()
-        b.by_customer_ptr, b.by_customer_col = by_c.rowptr.data_ptr(), (by_c.col.data_ptr() if by_c.nnz else by_c.rowptr.data_ptr())
-        b.by_article_ptr, b.by_article_col = by_a.rowptr.data_ptr(), (by_a.col.data_ptr() if by_a.nnz else by_a.rowptr.data_ptr())
-        b.nnz, b.n_label = by_c.nnz, n_lab
-        b.label_row, b.label_col = row.data_ptr(), col.data_ptr()
-        if labels.dtype == t.int64:     # the sampler's edge_label as it is: cast inside the executor
-            b.label = labels.data_ptr()
-        else:
-            b.label_f32 = labels.data_ptr()
+        dev = keep[0].device
         b.seed, b.step = self.seed, self.iteration
-        loss = t.empty(1, dtype=t.float32, device=xc.device)
+        loss = t.empty(1, dtype=t.float32, device=dev)
         b.loss = loss.data_ptr()
         if self._aux is not None:
             b.aux_stream, b.ev_fork, b.ev_join = self._aux[0].cuda_stream, self._aux[1].cuda_event, self._aux[2].cuda_event
         L = _lib.lib()
-        dims = (n_c, n_a, int(by_c.nnz), n_lab, d.p_dropout > 0.0)
+        dims = (b.n_nodes[0], b.n_nodes[1], int(b.nnz), int(b.n_label), d.p_dropout > 0.0)
         sized = self._ws_dims      # (dims of the largest batch the counting pass has seen, its byte count)
         if self._ws is None or sized is None or dims[4] != sized[0][4] or any(x > y for x, y in zip(dims[:4], sized[0][:4])):
             # The counting pass (a host walk of the whole iteration) is skipped for a batch no larger in ANY of these four counts
@@ -307,8 +329,7 @@ class NativeRankerStep:
             # executor's validation pass answers MI_ERR_WORKSPACE before anything is
             # enqueued and the pass is run after all (_recount_workspace: here under data parallelism, in step() otherwise).
             need = int(L.mi_ranker_step_workspace_bytes(ctypes.byref(d), ctypes.byref(b)))
-            if self._ws is None or self._ws.numel() < need:
-                self._ws = t.empty(int(need * 1.25) + (1 << 20), dtype=t.uint8, device=xc.device)
+            self._ws = grown_workspace(self._ws, need, dev)
             if sized is None or dims[4] != sized[0][4] or need >= sized[1]:
                 self._ws_dims = (dims, need)
         if self._world() > 1:    # the validation pass on its own only where the ranks must agree BEFORE anything is enqueued;
@@ -321,13 +342,13 @@ class NativeRankerStep:
                 self.declined = "mi_ranker_step_f32: MI_ERR_UNSUPPORTED (shape outside the executor's)"
                 return None
             _lib.check(rc, "mi_ranker_step_check")
-        return d, b, loss, steps, (xc, xa, row, col, labels, ones, by_c, by_a)
+        return d, b, loss, steps, keep
 
     def _recount_workspace(self, d: RankerModel, b: RankerBatch) -> None:
         """MI_ERR_WORKSPACE from the validation pass (nothing enqueued): this batch needs more than the larger one the
         workspace was sized on.  Count it, allocate, and forget the remembered dims so that the next batch is counted too."""
         need = int(_lib.lib().mi_ranker_step_workspace_bytes(ctypes.byref(d), ctypes.byref(b)))
-        self._ws = t.empty(int(need * 1.25) + (1 << 20), dtype=t.uint8, device=self._ws.device)
+        self._ws = grown_workspace(None, need, self._ws.device)
         self._ws_dims = None
 
     def _world(self) -> int:
@@ -433,45 +454,25 @@ class NativeRankerForward:
         d.p_dropout = 0.0
         return d
 
-    def logits(self, x_dict: Dict[str, Tensor], edge_index_dict: dict, edge_label_index: Tensor) -> Optional[Tensor]:
-        self.declined = None
-        ei = None
-        for k, v in edge_index_dict.items():
-            if tuple(k) == tuple(Constants.edge_key):
-                ei = v
-        xc, xa = x_dict.get(Constants.node_user), x_dict.get(Constants.node_item)
-        if ei is None or xc is None or xa is None or edge_label_index.dtype != t.int64 or xc.dtype != t.int64 or xa.dtype != t.int64:
-            self.declined = "no buys relation, or features / label index not int64"
-            return None
-        if not xc.is_cuda:
-            self.declined = "batch not on the GPU"
-            return None
+    def _descriptor(self) -> RankerModel:
         if self._desc is None or not self._snapshot.current():     # a table / weight / buffer was replaced (load_state_dict keeps storages; .to() does not)
             self._desc, self._snapshot = self._build(), PointerSnapshot([self._tensors])
-        d = self._desc
-        n_c, n_a = int(xc.shape[0]), int(xa.shape[0])
-        pre = getattr(ei, "_sorted_csr", None)
-        if pre is not None and pre[0].n_rows == n_c and pre[1].n_rows == n_a:
-            by_c, by_a = pre
-        else:
-            src, dst = ei[0].contiguous(), ei[1].contiguous()
-            by_c = ops.coo_to_csr(src, dst, n_c, n_a, want_perm=False)
-            by_a = ops.coo_to_csr(dst, src, n_a, n_c, want_perm=False)
-        xc, xa = xc.contiguous(), xa.contiguous()
-        row, col = edge_label_index[0].contiguous(), edge_label_index[1].contiguous()
-        n_lab = int(row.numel())
-        if n_lab == 0:
-            return t.empty(0, dtype=t.float32, device=xc.device)
-        ones = _ones4(max(n_c, n_a, n_lab), xc.device)
-        d.ones4, d.n_ones = ones.data_ptr(), int(ones.shape[0])
-        out = t.empty(n_lab, dtype=t.float32, device=xc.device)
-        b = RankerBatch()
-        b.n_nodes[0], b.n_nodes[1] = n_c, n_a
-        b.x[0], b.x[1] = xc.data_ptr(), xa.data_ptr()
-        b.by_customer_ptr, b.by_customer_col = by_c.rowptr.data_ptr(), (by_c.col.data_ptr() if by_c.nnz else by_c.rowptr.data_ptr())
-        b.by_article_ptr, b.by_article_col = by_a.rowptr.data_ptr(), (by_a.col.data_ptr() if by_a.nnz else by_a.rowptr.data_ptr())
-        b.nnz, b.n_label = by_c.nnz, n_lab
-        b.label_row, b.label_col = row.data_ptr(), col.data_ptr()
+        return self._desc
+
+    def logits(self, x_dict: Dict[str, Tensor], edge_index_dict: dict, edge_label_index: Tensor) -> Optional[Tensor]:
+        self.declined = None
+        why = "no buys relation, or features / label index not int64"
+        if x_dict.get(Constants.node_user) is None or x_dict.get(Constants.node_item) is None:
+            self.declined = why
+            return None
+        half = _fill_batch(self, x_dict, edge_index_dict, edge_label_index, (why, None, why, "batch not on the GPU"))
+        if half is None:
+            return None
+        d, b, keep = half
+        dev = keep[0].device
+        if b.n_label == 0:
+            return t.empty(0, dtype=t.float32, device=dev)
+        out = t.empty(b.n_label, dtype=t.float32, device=dev)
         b.logits = out.data_ptr()
         L = _lib.lib()
         for attempt in (0, 1):
@@ -480,7 +481,7 @@ class NativeRankerForward:
                 if need == 0:
                     self.declined = "mi_ranker_step_f32: shape outside the executor's"
                     return None
-                self._ws = t.empty(int(need * 1.25) + (1 << 20), dtype=t.uint8, device=xc.device)
+                self._ws = grown_workspace(None, need, dev)
             rc = L.mi_ranker_step_f32(ctypes.byref(d), ctypes.byref(b), self._ws.data_ptr(), self._ws.numel(), _lib.current_stream())
             if rc != _lib.MI_ERR_WORKSPACE:
                 break
@@ -488,5 +489,5 @@ class NativeRankerForward:
             self.declined = "mi_ranker_step_f32: MI_ERR_UNSUPPORTED (shape outside the executor's)"
             return None
         _lib.check(rc, "mi_ranker_step_f32 (inference)")
-        self._keep = (xc, xa, row, col, ones, by_c, by_a)   # until the next call: the launches may still be reading them
+        self._keep = keep   # until the next call: the launches may still be reading them
         return out

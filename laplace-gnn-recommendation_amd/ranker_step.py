@@ -6,8 +6,9 @@ runs for 5-40 us, so the iteration is bound by launches and — on the host — 
 module dispatch, autograd-node construction, the engine's walk of the graph (measured, tools/prof_host_ranker.py:
 1.35 ms of Python per iteration against 1.07 ms of kernels).  `FusedRankerStep` runs the SAME arithmetic — the same
 C-ABI launches in the same order as `Encoder_Decoder_Model.forward` + autograd would issue — as straight-line code:
-forward, hand-derived backward (the functions the autograd nodes of model/layers.py and model/encoder_decoder.py call),
-gradients written to `param.grad`, then the caller's `optimizer.step()`.  The model object, its parameters, buffers,
+forward, hand-derived backward (the functions the autograd nodes of model/layers.py and model/encoder_decoder.py call: the
+batch's graphs are HeteroGNNEncoder.relation_graphs, a layer is hetero_layer_forward / hetero_layer_backward over
+BipartiteGraph.aggregate, a BatchNorm call's bookkeeping is bn_call_args), gradients written to `param.grad`, then the caller's `optimizer.step()`.  The model object, its parameters, buffers,
 state_dict and the optimizer stay torch's own; `training.train_with_dataloader` switches to this step when the model
 has the shape it supports (`supports(model)`) and falls back to autograd otherwise.
 
@@ -21,9 +22,8 @@ import torch as t
 from torch import Tensor
 
 from . import ops
-from .model.encoder_decoder import Encoder_Decoder_Model, _key
-from .model.layers import BipartiteGraph, Linear, _run_products, _ones4, hetero_layer_backward, hetero_layer_forward, \
-    hetero_layer_relations
+from .model.encoder_decoder import Encoder_Decoder_Model, _key, bn_call_args
+from .model.layers import Linear, _run_products, _ones4, hetero_layer_backward, hetero_layer_forward, hetero_layer_relations
 from .utils.constants import Constants
 
 
@@ -67,19 +67,7 @@ class FusedRankerStep:
         if model.embedding:
             x_dict = model._embed(dict(x_dict))
         types = list(x_dict)
-        # ---- graphs (as HeteroGNNEncoder.forward builds them)
-        graphs, built = {}, {}
-        for et, ei in edge_index_dict.items():
-            et = tuple(et)
-            if _key(et) in enc.layers[0]:
-                fwd = getattr(ei, "_reverse_of", None)
-                if isinstance(ei, BipartiteGraph):
-                    graphs[et] = ei
-                elif fwd is not None and id(fwd) in built:
-                    graphs[et] = built[id(fwd)].reversed()
-                else:
-                    graphs[et] = BipartiteGraph.of(ei, x_dict[et[0]].shape[0], x_dict[et[2]].shape[0])
-                    built[id(ei)] = graphs[et]
+        graphs = enc.relation_graphs(x_dict, edge_index_dict)
         # ---- encoder forward
         n_layers = len(enc.layers)
         saved = []
@@ -111,13 +99,8 @@ class FusedRankerStep:
             bn_saved = []
             z = []
             for bn, x in ((model.encoder_layer_norm_customer, zu), (model.encoder_layer_norm_article, zi)):
-                train_bn = bn.training or not bn.track_running_stats
-                momentum = 0.0
-                if train_bn and bn.track_running_stats:
-                    bn.num_batches_tracked.add_(1)
-                    momentum = bn.momentum if bn.momentum is not None else 1.0 / float(bn.num_batches_tracked)
-                rm, rv = (bn.running_mean, bn.running_var) if bn.track_running_stats else (None, None)
-                y, mean, invstd = ops.batchnorm_fwd(x, bn.weight, bn.bias, rm, rv, float(momentum), float(bn.eps), train_bn)
+                train_bn, momentum, rm, rv = bn_call_args(bn)
+                y, mean, invstd = ops.batchnorm_fwd(x, bn.weight, bn.bias, rm, rv, momentum, float(bn.eps), train_bn)
                 bn_saved.append((bn, x, mean, invstd))
                 z.append(y)
             zu, zi = z

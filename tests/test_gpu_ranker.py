@@ -629,3 +629,40 @@ def test_linear1_bwd_matches_torch_linear_backward(n, k):
     assert t.equal(gw, gw2) and t.equal(gb, gb2)
     _, gw3, _ = ops.linear1_bwd(dy.reshape(-1), w.detach(), x, need_dx=False)
     assert t.equal(gw, gw3)
+
+
+# ---- every host path of the iteration against its own past: tests/golden/ranker_path_bits.json ------------------------------
+
+def _ranker_bits_tool():
+    """tools/record_ranker_bits.py: the cases of tests/golden/ranker_path_bits.json and the function that records one."""
+    import sys
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
+    import record_ranker_bits
+    return record_ranker_bits
+
+
+def _differences(got, want, at=""):
+    """Where two records differ: the paths of the leaves, so that a failure names the tensor and the iteration."""
+    if isinstance(want, dict) and isinstance(got, dict):
+        return [d for k in sorted(set(want) | set(got)) for d in
+                (_differences(got[k], want[k], f"{at}/{k}") if k in got and k in want else [f"{at}/{k} on one side only"])]
+    if isinstance(want, list) and isinstance(got, list) and len(got) == len(want):
+        return [d for i, (g, w) in enumerate(zip(got, want)) for d in _differences(g, w, f"{at}[{i}]")]
+    return [] if got == want else [f"{at}: {got!r}, recorded {want!r}"]
+
+
+@pytest.mark.parametrize("key", [c["key"] for c in _ranker_bits_tool().cases()])
+def test_ranker_host_paths_give_the_recorded_bits(key):
+    """The iteration through autograd, FusedRankerStep and NativeRankerStep, and NativeRankerForward, on the cases of
+    tools/record_ranker_bits.py: loss bits, the digest of every gradient, BatchNorm buffer, updated parameter and of the
+    logits, the workspace sizes, and what each path does with a batch without edges — all equal to what the commit named in
+    tests/golden/ranker_path_bits.json produced, when each path still wrote out its stages for itself.  The cases and the
+    recording are the tool's: neither side changes alone."""
+    import json
+    tool = _ranker_bits_tool()
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ranker_path_bits.json")) as f:
+        recorded = json.load(f)["cases"]
+    assert sorted(recorded) == sorted(c["key"] for c in tool.cases())       # nothing in the file is left out
+    case = next(c for c in tool.cases() if c["key"] == key)
+    got = json.loads(json.dumps(tool.record(case)))                        # as the file holds it
+    assert not _differences(got, recorded[key])
