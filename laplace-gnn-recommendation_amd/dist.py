@@ -22,6 +22,9 @@ int degree vector at set-up.
 xGMI is point-to-point, 7 links per GPU: the payload per collective is small (I*D*4 bytes), so
 what matters is that the collective runs beside the user-row SpMM of the same layer (independent
 work) rather than peak bus bandwidth; RCCL picks the algorithm.
+
+The host logic that does not depend on the partition — hyper-parameters, the locality order's bookkeeping, per-batch and
+optimizer state, sample() — is trainer._LightGCNTrainerBase's, shared with the single-device trainer.
 """
 from __future__ import annotations
 
@@ -34,12 +37,13 @@ from torch import Tensor
 from . import ops as hip_ops
 from .interactions import Interactions
 from .model.lightgcn import LightGCN
+from .trainer import _LightGCNTrainerBase
 
 
 REORDER_MIN_EDGES_PER_RANK = 1 << 20   # default locality order: on when the JOB holds this many edges per rank
 
 
-class ShardedLightGCNTrainer:
+class ShardedLightGCNTrainer(_LightGCNTrainerBase):
     def __init__(self, model: LightGCN, train: Interactions, *, lr: float, Lambda: float, batch_size: int,
                  betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8, seed: int = 0,
                  neg_range: Optional[int] = None, group=None, ops_impl=None, sparse_batch: bool = True,
@@ -47,22 +51,16 @@ class ShardedLightGCNTrainer:
         """model: LightGCN(num_users = this rank's users, num_items = all items).  `train` holds this
         rank's edges with LOCAL user ids.  ops_impl: the kernel provider (default: the HIP ops;
         the CPU gloo tests inject an oracle-backed one — the product never does).
-        reorder (default: on from 1M edges per rank, decided on the all-reduced total): train under the locality order of trainer.LightGCNTrainer — the
+        reorder (default: on from 1M edges per rank, decided on the all-reduced total): train under the locality order (trainer.py) — the
         replicated items are ranked by their GLOBAL degree, so every rank numbers them alike; users are local anyway.
-        objective / n_neg: as trainer.LightGCNTrainer (the same on every rank); anything but the default needs a provider
+        objective / n_neg: the single-device trainer's (the same on every rank); anything but the default needs a provider
         with rank_loss_fwd_bwd, sample_bpr_batch(n_neg=) and batch_nodes over neg [B, M]."""
-        hip_ops.rank_objective_code(objective)   # ValueError for an unknown name
-        hip_ops.check_n_neg(n_neg)
-        self.objective, self.n_neg = objective, n_neg
-        self.ops = ops_impl if ops_impl is not None else hip_ops
+        super().__init__(model, ops_impl if ops_impl is not None else hip_ops, lr=lr, Lambda=Lambda, batch_size=batch_size,
+                         betas=betas, eps=eps, seed=seed, sparse_batch=sparse_batch, objective=objective, n_neg=n_neg)
         self.group = group
         self.world = dist.get_world_size(group) if dist.is_initialized() else 1
-        self.model, self.train = model, train
-        self.table = model.table()
+        self.train = train
         self.U, self.I = model.num_users, model.num_items
-        self.K = model.num_iterations
-        self.lr, self.Lambda, self.batch_size = float(lr), float(Lambda), int(batch_size)
-        self.betas, self.eps, self.seed = betas, float(eps), int(seed)
         self.neg_range = int(neg_range) if neg_range is not None else self.I
         n, d = self.table.shape
         dev = self.table.device
@@ -89,16 +87,10 @@ class ShardedLightGCNTrainer:
             raise ValueError("ShardedLightGCNTrainer: the `reorder` argument differs across ranks")
         if reorder is None:
             reorder = bool(int(lo[2])) and int(votes[0]) >= REORDER_MIN_EDGES_PER_RANK * self.world
-        self.order, self.in_training_order = None, True
         if reorder:
             gdeg = t.bincount(train.edge_index[1], minlength=I)
             self._allreduce(gdeg)                       # the same ranking of the items on every rank
-            self.order = train.locality_order(item_degree=gdeg)
-            self._new_of_old, self._old_of_new = self.order.node_new_of_old(), self.order.node_old_of_new()
-            train = train.permuted(self.order)
-            self.train = train
-            self.in_training_order = False
-            self.to_training_order()
+            self.train = train = self._reorder(train, item_degree=gdeg)
 
         # local symmetric bipartite CSR, globally-normalised edge weights
         u, i = train.edge_index[0], train.edge_index[1]
@@ -119,57 +111,16 @@ class ShardedLightGCNTrainer:
         self.a_users.plan = self.ops.build_spmm_plan(self.a_users)
         self.a_items.plan = self.ops.build_spmm_plan(self.a_items)
 
-        self.sparse_batch = bool(sparse_batch)
-        self.final = t.empty(n, d, device=dev)
-        self.bufs = (t.empty(n, d, device=dev), t.empty(n, d, device=dev))
-        if self.sparse_batch:  # compact per-batch tables (see trainer.py) + dense item-side exchange buffers
-            nb = (2 + self.n_neg) * self.batch_size
-            self.gc = None
-            self.gmap = t.empty(n, dtype=t.int32, device=dev)
-            self.nodes = t.zeros(nb, dtype=t.int32, device=dev)
-            self.n_nodes = t.zeros(2, dtype=t.int32, device=dev)
-            self.sum_c = t.empty(nb, d, device=dev)
-            self.gc_c = t.zeros(nb, d, device=dev)
+        self._alloc_state()
+        if self.sparse_batch:  # the dense item-side exchange buffers beside the compact per-batch tables
             self.items_y = t.empty(I, d, device=dev)
             self.items_g = t.zeros(I, d, device=dev)
             self.imap = t.full((n,), -1, dtype=t.int32, device=dev)
             self._item_ids = t.arange(I, dtype=t.int32, device=dev)
-        else:
-            self.gc = t.zeros(n, d, device=dev)
-        self.reg_w = t.zeros(n, device=dev)
-        self.m = t.zeros(n, d, device=dev)
-        self.v = t.zeros(n, d, device=dev)
-        self.loss = t.zeros(1, device=dev)
-        self.batch_idx = (t.empty(self.batch_size, dtype=t.int64, device=dev),
-                          t.empty(self.batch_size, dtype=t.int64, device=dev),
-                          t.empty(self.batch_size if n_neg == 1 else (self.batch_size, n_neg), dtype=t.int64, device=dev))
-        self.step_count = 0
         self._r = train.csr() if ops_impl is None else self.ops.coo_to_csr(u.contiguous(), i.contiguous(), U, I,
                                                                              want_perm=False)
         self._row_of_edge = self.ops.expand_rows(self._r)
-
-    # -- locality order (see trainer.LightGCNTrainer) -------------------------------------------------
-    def to_training_order(self) -> None:
-        if self.order is not None and not self.in_training_order:
-            self.table.copy_(self.table[self._old_of_new])
-            self.in_training_order = True
-
-    def to_original_order(self) -> None:
-        if self.order is not None and self.in_training_order:
-            self.table.copy_(self.table[self._new_of_old])
-            self.in_training_order = False
-
-    finish = to_original_order
-
-    def _ids_to_training(self, batch):
-        if batch is None:
-            return batch
-        users, pos, neg = batch
-        if self.n_neg > 1 and (neg.dim() != 2 or neg.shape[1] != self.n_neg):
-            raise ValueError(f"batch: neg [B, {self.n_neg}] expected, got {list(neg.shape)}")
-        if self.order is None:
-            return batch
-        return self.order.user_new_of_old[users], self.order.item_new_of_old[pos], self.order.item_new_of_old[neg]
+        self._sample_kw = {} if self.n_neg == 1 else {"n_neg": self.n_neg}   # one negative: the provider's plain call
 
     # -- collectives ---------------------------------------------------------------------------
     def _allreduce(self, x: Tensor, async_op: bool = False):
@@ -219,11 +170,6 @@ class ShardedLightGCNTrainer:
             x = out
         return S
 
-    def _sample(self):
-        more = {} if self.n_neg == 1 else {"n_neg": self.n_neg}
-        return self.ops.sample_bpr_batch(self._r, self._row_of_edge, self.batch_size, self.neg_range, self.seed,
-                                         self.step_count, out=self.batch_idx, **more)
-
     def _loss(self, users, pos, neg, final, **kw) -> None:
         """This rank's loss term and gradient; the default objective keeps the one-negative call of the provider."""
         if self.objective == "reference" and self.n_neg == 1:
@@ -232,13 +178,6 @@ class ShardedLightGCNTrainer:
         else:
             self.ops.rank_loss_fwd_bwd(users, pos, neg, final, self.table, self.U, self.Lambda,
                                        objective=self.objective, reg_w=self.reg_w, loss_out=self.loss, **kw)
-
-    def sample(self):
-        """(users, pos, neg) of the next step's batch, ORIGINAL (local) ids."""
-        users, pos, neg = self._sample()
-        if self.order is None:
-            return users, pos, neg
-        return self.order.user_old_of_new[users], self.order.item_old_of_new[pos], self.order.item_old_of_new[neg]
 
     def step(self, batch=None) -> Tensor:
         """One training iteration over the GLOBAL batch (world * batch_size positive edges); returns this
@@ -265,12 +204,11 @@ class ShardedLightGCNTrainer:
             nxt[U:].add_(self.gc[U:])
             g = nxt
         self.step_count += 1
-        self.ops.adam_step(self.table, g, self.m, self.v, step=self.step_count, lr=self.lr, beta1=self.betas[0],
-                           beta2=self.betas[1], eps=self.eps, reg_w=self.reg_w)
+        self.ops.adam_step(self.table, g, self.m, self.v, reg_w=self.reg_w, **self._adam_kw(self.step_count))
         return self.loss
 
     def _step_sparse(self, batch) -> Tensor:
-        """The byte-saving form of trainer.LightGCNTrainer._step_sparse, sharded.  User rows get the
+        """The byte-saving form of the single-device sparse step, sharded.  User rows get the
         row_list / x_map / compact-addend treatment; item rows stay dense because their partial sums
         are exchanged: forward layer K still needs every rank's users, and the item gradient is the
         sum of every rank's batch."""
@@ -340,9 +278,9 @@ class ShardedLightGCNTrainer:
                 cur[U:].add_(self.items_g)                                  # previous layer's item rows, now complete
                 work = self._allreduce(nxt[U:], async_op=True)
                 if i == K - 1:  # user rows are local: their gradient goes straight into Adam (mi_adam_args)
-                    hyp = dict(step=self.step_count + 1, lr=self.lr, beta1=self.betas[0], beta2=self.betas[1], eps=self.eps)
                     ops.spmm(self.a_users, cur, addend=self.gc_c, addend_map=gmap_u,
-                             adam=dict(p=tab[:U], m=self.m[:U], v=self.v[:U], reg_w=self.reg_w[:U], **hyp))
+                             adam=dict(p=tab[:U], m=self.m[:U], v=self.v[:U], reg_w=self.reg_w[:U],
+                                       **self._adam_kw(self.step_count + 1)))
                     users_done = True
                 else:
                     ops.spmm(self.a_users, cur, addend=self.gc_c, S=nxt[:U], addend_map=gmap_u)
@@ -356,9 +294,5 @@ class ShardedLightGCNTrainer:
                 w.wait()
         self.step_count += 1
         lo = U if users_done else 0  # item rows (summed over ranks above), and the user rows unless already updated
-        ops.adam_step(tab[lo:], cur[lo:], self.m[lo:], self.v[lo:], step=self.step_count, lr=self.lr,
-                      beta1=self.betas[0], beta2=self.betas[1], eps=self.eps, reg_w=self.reg_w[lo:])
+        ops.adam_step(tab[lo:], cur[lo:], self.m[lo:], self.v[lo:], reg_w=self.reg_w[lo:], **self._adam_kw(self.step_count))
         return self.loss
-
-    def decay_lr(self, gamma: float = 0.95) -> None:
-        self.lr *= gamma

@@ -42,6 +42,10 @@ and `to_original_order()` / `to_training_order()` put the table's rows back / fo
 `finish()` = to_original_order).  Batches passed to `step()` and returned by `sample()` are in ORIGINAL ids.  The
 result is the same training run up to the summation order inside a row (entries are summed in column order, and
 columns are renamed): equal to rounding, and still bitwise reproducible run to run.
+
+_LightGCNTrainerBase, below, holds what this trainer shares with the user-sharded one (dist.ShardedLightGCNTrainer): the
+hyper-parameters and their checks, the locality order's bookkeeping, the per-batch and optimizer state, sample() and the Adam
+keywords.  The steps themselves differ in their launches and stay with each class.
 """
 from __future__ import annotations
 
@@ -65,7 +69,113 @@ def _lib_bytes_batch_nodes(n_nodes: int) -> int:
 NEGATIVES = ("uniform", "popularity", "in_batch")
 
 
-class LightGCNTrainer:
+class _LightGCNTrainerBase:
+    """What LightGCNTrainer and dist.ShardedLightGCNTrainer share, once: the objective and hyper-parameter checks and
+    assignments, the locality order's bookkeeping, the per-batch and optimizer state, sample() and the Adam keywords.
+    `self.ops` is the kernel provider (this package's HIP `ops`; the sharded trainer's CPU tests inject another).  A subclass
+    sets up its adjacency, `_r`, `_row_of_edge`, `neg_range` and `_sample_kw`, and writes its own steps."""
+    in_batch = False   # negatives come from the batch itself: (users, pos) batches
+
+    def __init__(self, model: LightGCN, kernels, *, lr: float, Lambda: float, batch_size: int, betas: Tuple[float, float],
+                 eps: float, seed: int, sparse_batch: bool, objective: str, n_neg: int):
+        ops.rank_objective_code(objective)   # ValueError for an unknown name
+        ops.check_n_neg(n_neg)
+        self.objective, self.n_neg = objective, n_neg
+        self.ops = kernels
+        self.model = model
+        self.table = model.table()
+        self.K = model.num_iterations
+        self.lr, self.Lambda, self.batch_size = float(lr), float(Lambda), int(batch_size)
+        self.betas, self.eps, self.seed = betas, float(eps), int(seed)
+        self.sparse_batch = bool(sparse_batch)
+        self.order, self.in_training_order = None, True
+        self.step_count = 0
+
+    def _alloc_state(self) -> None:
+        """`final`, the two ping-pong buffers of the propagates, the per-batch tables (sparse_batch: compact [(2 + n_neg) B, D]
+        ones and the node map instead of the dense gradient buffer) and the optimizer state."""
+        n, d = self.table.shape
+        dev = self.table.device
+        self.final = t.empty(n, d, device=dev)
+        self.bufs = (t.empty(n, d, device=dev), t.empty(n, d, device=dev))
+        if self.sparse_batch:
+            nb = (2 + self.n_neg) * self.batch_size
+            self.gc = None
+            self.gmap = t.empty(n, dtype=t.int32, device=dev)
+            self.nodes = t.zeros(nb, dtype=t.int32, device=dev)
+            self.n_nodes = t.zeros(2, dtype=t.int32, device=dev)
+            self.sum_c = t.empty(nb, d, device=dev)
+            self.gc_c = t.zeros(nb, d, device=dev)
+        else:
+            self.gc = t.zeros(n, d, device=dev)
+        self.reg_w = t.zeros(n, device=dev)
+        self.m = t.zeros(n, d, device=dev)
+        self.v = t.zeros(n, d, device=dev)
+        self.loss = t.zeros(1, device=dev)
+        self.batch_idx = (t.empty(self.batch_size, dtype=t.int64, device=dev),
+                          t.empty(self.batch_size, dtype=t.int64, device=dev),
+                          t.empty(self.batch_size if self.n_neg == 1 else (self.batch_size, self.n_neg), dtype=t.int64, device=dev))
+
+    # -- locality order --------------------------------------------------------------------------
+    def _reorder(self, train: Interactions, item_degree: Optional[Tensor] = None) -> Interactions:
+        """Take up train's locality order: the table's rows go into it, and `train` comes back relabelled."""
+        self.order = train.locality_order(item_degree=item_degree)
+        self._new_of_old = self.order.node_new_of_old()
+        self._old_of_new = self.order.node_old_of_new()
+        self.in_training_order = False
+        self.to_training_order()
+        return train.permuted(self.order)
+
+    def to_training_order(self) -> None:
+        """Rows of the model's table into the order the kernels train in (no-op without reorder)."""
+        if self.order is not None and not self.in_training_order:
+            self.table.copy_(self.table[self._old_of_new])  # new row r = old row old_of_new[r]
+            self.in_training_order = True
+
+    def to_original_order(self) -> None:
+        """Rows of the model's table back under their original ids (evaluation, top-K, saving)."""
+        if self.order is not None and self.in_training_order:
+            self.table.copy_(self.table[self._new_of_old])
+            self.in_training_order = False
+
+    finish = to_original_order
+
+    def _ids_to_training(self, batch):
+        if batch is None:
+            return batch
+        if self.in_batch:   # (users, pos); a third entry is ignored, and pos stands in for it (the node set's third column)
+            users, pos = batch[0], batch[1]
+            if self.order is not None:
+                users, pos = self.order.user_new_of_old[users], self.order.item_new_of_old[pos]
+            return users, pos, pos
+        users, pos, neg = batch
+        if self.n_neg > 1 and (neg.dim() != 2 or neg.shape[1] != self.n_neg):
+            raise ValueError(f"batch: neg [B, {self.n_neg}] expected, got {list(neg.shape)}")
+        if self.order is None:
+            return batch
+        return self.order.user_new_of_old[users], self.order.item_new_of_old[pos], self.order.item_new_of_old[neg]
+
+    # -- the batch and the optimizer's keywords ----------------------------------------------------
+    def _sample(self) -> Tuple[Tensor, Tensor, Tensor]:
+        return self.ops.sample_bpr_batch(self._r, self._row_of_edge, self.batch_size, self.neg_range, self.seed,
+                                         self.step_count, out=self.batch_idx, **self._sample_kw)
+
+    def sample(self) -> Tuple[Tensor, Tensor, Tensor]:
+        """(users, pos, neg) of the next step's batch, ORIGINAL ids (the sharded trainer's: local ones)."""
+        users, pos, neg = self._sample()
+        if self.order is None:
+            return users, pos, neg
+        return self.order.user_old_of_new[users], self.order.item_old_of_new[pos], self.order.item_old_of_new[neg]
+
+    def _adam_kw(self, step: int) -> dict:
+        return dict(step=step, lr=self.lr, beta1=self.betas[0], beta2=self.betas[1], eps=self.eps)
+
+    def decay_lr(self, gamma: float = 0.95) -> None:
+        """ExponentialLR(gamma).step() (run_pipeline_lightgcn.py:104,178-179)."""
+        self.lr *= gamma
+
+
+class LightGCNTrainer(_LightGCNTrainerBase):
     def __init__(self, model: LightGCN, adj: SparseTensor, train: Interactions, *, lr: float, Lambda: float,
                  batch_size: int, betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8, seed: int = 0,
                  neg_range: Optional[int] = None, reference_sampler_quirks: bool = False,
@@ -81,8 +191,8 @@ class LightGCNTrainer:
         stream — users and pos at a (seed, step) are the bits a negatives="uniform" trainer draws; the negative it draws as
         well is ignored.  The logQ correction's proposal is "the item of a uniformly drawn training edge", q ∝ training degree
         (ops.negative_table(degree, 1.0)); neg_power is not used.  step(batch) takes (users, pos); a third entry is ignored."""
-        ops.rank_objective_code(objective)   # ValueError for an unknown name
-        ops.check_n_neg(n_neg)
+        super().__init__(model, ops, lr=lr, Lambda=Lambda, batch_size=batch_size, betas=betas, eps=eps, seed=seed,
+                         sparse_batch=sparse_batch, objective=objective, n_neg=n_neg)
         if negatives not in NEGATIVES:
             raise ValueError(f"negatives must be one of {NEGATIVES}, got {negatives!r}")
         if isinstance(neg_power, bool) or not isinstance(neg_power, (int, float)) or not 0.0 <= neg_power <= 1.0:
@@ -108,15 +218,9 @@ class LightGCNTrainer:
                 raise ValueError(f'negatives="in_batch" takes its negatives from the batch: neg_range {neg_range} != {model.num_items}')
         self.in_batch = negatives == "in_batch"
         self.in_batch_group = int(in_batch_group) if self.in_batch else None
-        self.objective, self.n_neg = objective, n_neg
         self.negatives, self.neg_power, self.logq_correction = negatives, float(neg_power), bool(logq_correction)
-        self.model = model
-        self.table = model.table()
         if not self.table.is_cuda:
             raise RuntimeError("LightGCNTrainer needs the model on the GPU (model.to('cuda')); no CPU fallback")
-        self.K = model.num_iterations
-        self.lr, self.Lambda, self.batch_size = float(lr), float(Lambda), int(batch_size)
-        self.betas, self.eps, self.seed = betas, float(eps), int(seed)
         # reference: num_nodes = max(train item id)  => negatives in [0, max_item_id)  (Appendix A.3)
         self.neg_range = int(neg_range) if neg_range is not None else train.num_items
         self.quirk = bool(reference_sampler_quirks)
@@ -126,49 +230,22 @@ class LightGCNTrainer:
             reorder = can_reorder and adj.nnz() >= ops.PLAN_MIN_NNZ
         elif reorder and not can_reorder:
             raise ValueError("reorder=True needs neg_range == num_items and no reference sampler quirks")
-        self.order = None
-        self.in_training_order = True
         if reorder:
-            self.order = train.locality_order()
-            self._new_of_old = self.order.node_new_of_old()
-            self._old_of_new = self.order.node_old_of_new()
-            train = train.permuted(self.order)
+            train = self._reorder(train)
             adj = adj.permuted(self._new_of_old)
-            self.in_training_order = False
-            self.to_training_order()
         self.adj_fwd, self.adj_bwd = adj.gcn_normalized(model.add_self_loops)
         if self.order is not None:
             # items are numbered by popularity: their first rows take half of all user-row gathers — dense launches keep
             # them in LDS (ops.spmm, `hot`; a speed hint, results unchanged)
             self.adj_fwd.hot = self.adj_bwd.hot = ops.hot_item_rows(model.num_users, model.num_items)
         self.train = train
-        n, d = self.table.shape
-        dev = self.table.device
-        self.sparse_batch = bool(sparse_batch)
         self.fuse_adam = bool(fuse_adam)
-        self.final = t.empty(n, d, device=dev)
-        self.buf_a = t.empty(n, d, device=dev)
-        self.buf_b = t.empty(n, d, device=dev)
-        nb = (2 + self.n_neg) * self.batch_size
-        if self.sparse_batch:  # compact per-batch tables instead of the dense gradient buffer
-            self.gc = None
-            self.gmap = t.empty(n, dtype=t.int32, device=dev)
-            self.nodes = t.zeros(nb, dtype=t.int32, device=dev)
-            self.n_nodes = t.zeros(2, dtype=t.int32, device=dev)
-            self.sum_c = t.empty(nb, d, device=dev)
-            self.final_c = t.empty(nb, d, device=dev)
-            self.gc_c = t.zeros(nb, d, device=dev)
-            self._nodes_ws = t.empty(_lib_bytes_batch_nodes(n), dtype=t.uint8, device=dev)
-        else:
-            self.gc = t.zeros(n, d, device=dev)
-        self.reg_w = t.zeros(n, device=dev)
-        self.m = t.zeros(n, d, device=dev)
-        self.v = t.zeros(n, d, device=dev)
-        self.loss = t.zeros(1, device=dev)
-        self.batch_idx = (t.empty(self.batch_size, dtype=t.int64, device=dev),
-                          t.empty(self.batch_size, dtype=t.int64, device=dev),
-                          t.empty(self.batch_size if n_neg == 1 else (self.batch_size, n_neg), dtype=t.int64, device=dev))
-        self.step_count = 0
+        self._alloc_state()
+        self.buf_a, self.buf_b = self.bufs
+        dev = self.table.device
+        if self.sparse_batch:
+            self.final_c = t.empty(self.sum_c.shape, device=dev)
+            self._nodes_ws = t.empty(_lib_bytes_batch_nodes(self.table.shape[0]), dtype=t.uint8, device=dev)
         self._r = train.csr()
         self._row_of_edge = train.row_of_edge()
         # the proposal of the negatives and its log, by TRAINING id (`train` is already relabelled here)
@@ -182,47 +259,14 @@ class LightGCNTrainer:
         elif self.logq_correction:   # uniform negatives: q = 1 / neg_range for every item
             self.logq = (self.neg_table.logq if self.neg_table is not None
                          else t.full((train.num_items,), -math.log(self.neg_range), dtype=t.float32, device=dev))
-
-    # -- locality order --------------------------------------------------------------------------
-    def to_training_order(self) -> None:
-        """Rows of the model's table into the order the kernels train in (no-op without reorder)."""
-        if self.order is not None and not self.in_training_order:
-            self.table.copy_(self.table[self._old_of_new])  # new row r = old row old_of_new[r]
-            self.in_training_order = True
-
-    def to_original_order(self) -> None:
-        """Rows of the model's table back under their original ids (evaluation, top-K, saving)."""
-        if self.order is not None and self.in_training_order:
-            self.table.copy_(self.table[self._new_of_old])
-            self.in_training_order = False
-
-    finish = to_original_order
-
-    def _ids_to_training(self, batch):
-        if self.in_batch:   # (users, pos); a third entry is ignored, and pos stands in for it (the node set's third column)
-            users, pos = batch[0], batch[1]
-            if self.order is not None:
-                users, pos = self.order.user_new_of_old[users], self.order.item_new_of_old[pos]
-            return users, pos, pos
-        users, pos, neg = batch
-        if self.n_neg > 1 and (neg.dim() != 2 or neg.shape[1] != self.n_neg):
-            raise ValueError(f"batch: neg [B, {self.n_neg}] expected, got {list(neg.shape)}")
-        if self.order is None:
-            return batch
-        return self.order.user_new_of_old[users], self.order.item_new_of_old[pos], self.order.item_new_of_old[neg]
+        self._sample_kw = (dict(n_neg=self.n_neg, table=self.neg_table) if self.neg_table is not None
+                           else dict(quirk=self.quirk, n_neg=self.n_neg))
 
     # -- pieces (also used one by one in tests) ------------------------------------------------
     def forward(self) -> Tensor:
         """mean_k(A^k E0) over the whole table; rows in TRAINING order (index with order.node_new_of_old())."""
         self.to_training_order()
         return propagate_mean(self.adj_fwd, self.table, self.K, out=self.final, scratch=(self.buf_a, self.buf_b))
-
-    def _sample(self) -> Tuple[Tensor, Tensor, Tensor]:
-        if self.neg_table is not None:
-            return ops.sample_bpr_batch(self._r, self._row_of_edge, self.batch_size, self.neg_range, self.seed,
-                                        self.step_count, out=self.batch_idx, n_neg=self.n_neg, table=self.neg_table)
-        return ops.sample_bpr_batch(self._r, self._row_of_edge, self.batch_size, self.neg_range, self.seed,
-                                    self.step_count, quirk=self.quirk, out=self.batch_idx, n_neg=self.n_neg)
 
     def _loss(self, users, pos, neg, final, **kw) -> None:
         """Loss and its gradient on `final` (self.logq is None without the logQ correction)."""
@@ -238,17 +282,10 @@ class LightGCNTrainer:
         users, pos, neg = self._sample()
         return (users, pos, pos) if self.in_batch else (users, pos, neg)
 
-    def sample(self) -> Tuple[Tensor, Tensor, Tensor]:
-        """(users, pos, neg) of the next step's batch, ORIGINAL ids."""
-        users, pos, neg = self._sample()
-        if self.order is None:
-            return users, pos, neg
-        return self.order.user_old_of_new[users], self.order.item_old_of_new[pos], self.order.item_old_of_new[neg]
-
     def step(self, batch: Optional[Tuple[Tensor, Tensor, Tensor]] = None) -> Tensor:
         """One training iteration; returns the loss as a 1-element device tensor (no sync).  batch: original ids."""
         self.to_training_order()
-        batch = self._ids_to_training(batch) if batch is not None else None
+        batch = self._ids_to_training(batch)
         if self.sparse_batch:
             return self._step_sparse(batch)
         K = self.K
@@ -259,8 +296,7 @@ class LightGCNTrainer:
         self._loss(users, pos, neg, self.final, g_final=self.gc, g_scale=1.0 / (K + 1))
         g0 = propagate_mean_backward(self.adj_bwd, self.gc, K, scratch=(self.buf_a, self.buf_b), pre_scaled=True)
         self.step_count += 1
-        ops.adam_step(self.table, g0, self.m, self.v, step=self.step_count, lr=self.lr, beta1=self.betas[0],
-                      beta2=self.betas[1], eps=self.eps, reg_w=self.reg_w)
+        ops.adam_step(self.table, g0, self.m, self.v, reg_w=self.reg_w, **self._adam_kw(self.step_count))
         return self.loss
 
     def _step_sparse(self, batch: Optional[Tuple[Tensor, Tensor, Tensor]]) -> Tensor:
@@ -302,8 +338,7 @@ class LightGCNTrainer:
                 # the last product's output is the parameter gradient: Adam consumes it in the epilogue
                 opt = None
                 if i == K - 1 and self.fuse_adam:
-                    opt = dict(p=tab, m=self.m, v=self.v, step=self.step_count + 1, lr=self.lr, beta1=self.betas[0],
-                               beta2=self.betas[1], eps=self.eps, reg_w=self.reg_w)
+                    opt = dict(p=tab, m=self.m, v=self.v, reg_w=self.reg_w, **self._adam_kw(self.step_count + 1))
                 out = None if opt is not None else nxt
                 if i == 0:   # input = the compact gradient itself: skip its all-zero rows
                     # (the split rows are the hub ITEMS': their columns are users, of which the batch names few)
@@ -315,10 +350,5 @@ class LightGCNTrainer:
             g0 = cur
         self.step_count += 1
         if K == 0 or not self.fuse_adam:
-            ops.adam_step(tab, g0, self.m, self.v, step=self.step_count, lr=self.lr, beta1=self.betas[0],
-                          beta2=self.betas[1], eps=self.eps, reg_w=self.reg_w)
+            ops.adam_step(tab, g0, self.m, self.v, reg_w=self.reg_w, **self._adam_kw(self.step_count))
         return self.loss
-
-    def decay_lr(self, gamma: float = 0.95) -> None:
-        """ExponentialLR(gamma).step() (run_pipeline_lightgcn.py:104,178-179)."""
-        self.lr *= gamma

@@ -1409,3 +1409,47 @@ def test_c1_movielens_shaped_parity(compat):
     for k in (12, 256):
         got = topk_for_users(ue, ie, users, train_e.to(DEV), k).cpu()
         assert t.equal(got, R.topk_excl_exact(scores, excl, k))
+
+
+# ---- both trainers against their own past: tests/golden/trainer_path_bits.json ----------------------------------------------
+def _trainer_bits_tool():
+    """tools/record_trainer_bits.py: the cases of tests/golden/trainer_path_bits.json and the function that records one."""
+    import sys
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
+    import record_trainer_bits
+    return record_trainer_bits
+
+
+def _trainer_cases_give_the_recorded_bits(kind, monkeypatch):
+    import json
+    tool = _trainer_bits_tool()
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "trainer_path_bits.json")) as f:
+        recorded = tool.unpack(json.load(f))
+    assert sorted(recorded) == sorted(c["key"] for c in tool.cases())       # nothing in the file is left out
+    mine = [c for c in tool.cases() if c["kind"] == kind]
+    assert mine
+    calls = tool.Calls(monkeypatch.setattr)
+    wrong = []
+    for c in mine:
+        got, want = tool.record(c, calls), recorded[c["key"]]
+        assert sorted(got) == sorted(want)
+        for field in sorted(want):
+            if got[field] != want[field]:
+                wrong.append(f"{c['key']}/{field}: {got[field]!r}, recorded {want[field]!r}")
+    assert not wrong, "\n".join(wrong)
+
+
+def test_trainer_gives_the_recorded_bits_and_calls(monkeypatch):
+    """LightGCNTrainer on the single-device cases of tools/record_trainer_bits.py (both step forms, K = 0, 1, 3, with and
+    without the locality order, the unfused Adam, every objective and kind of negatives, the sampler's quirks, a narrower
+    negative range, batches fed in original ids): the loss bits of four steps, the digest of table, m and v after finish(),
+    the digest of sample(), and the laplace_amd.ops calls of the first two steps in order — all equal to what the commit named
+    in tests/golden/trainer_path_bits.json produced, when each trainer still carried its own copy of the shared host logic.
+    The cases and the recording are the tool's: neither side changes alone."""
+    _trainer_cases_give_the_recorded_bits("single", monkeypatch)
+
+
+def test_sharded_trainer_gives_the_recorded_bits_and_calls(monkeypatch):
+    """The same for dist.ShardedLightGCNTrainer at world 1, through the HIP ops: both step forms, K = 0, 1, 3, with and without
+    the locality order, M negatives under two objectives, and batches fed in original ids."""
+    _trainer_cases_give_the_recorded_bits("sharded", monkeypatch)
