@@ -564,6 +564,47 @@ int    mi_inbatch_softmax_fwd_bwd_f32(int64_t batch, int32_t group, int64_t d, i
                                       void* ws, size_t ws_bytes, mi_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * Full-catalogue softmax (behind a flag): the objective the sampled softmaxes above estimate, computed exactly.  Every item
+ * is a candidate of every slot; nothing is drawn, nothing is masked, nothing is corrected.
+ *
+ * A batch is users[B], pos[B] (int64); no neg.  f is a row of final_emb, whose user rows are [0, n_users) and whose item
+ * rows are [n_users, n_users + n_items):
+ *   l[b,i]  = <f[users_b], f[n_users + i]>                  for every i in [0, n_items)  — no mask, no logq
+ *   loss    = (1/B) sum_b [ logsumexp_i l[b,i] - l[b,pos_b] ]
+ *             + lambda * sum_b (|e0[users_b]|^2 + |e0[n_users + pos_b]|^2)
+ *   with the maximum subtracted before the exponentials; n_items == 1 gives a main term of exactly 0 and zero gradients.
+ *   c[b,i]  = g_scale/B * (softmax_b[i] - [i == pos_b])
+ *   dL/df[users_b]      += sum_i c[b,i] f[n_users + i]
+ *   dL/df[n_users + i]   = sum_b c[b,i] f[users_b]
+ * g_final all zero on entry; on return EVERY item row holds its sum, the user rows the batch names hold theirs, other user
+ * rows stay zero.  There is no node_map: this gradient is dense over the items, so the compact tables of a sparse batch do
+ * not apply.  reg_w (zero on entry), g_scale, reg_scale and loss_out behave as in mi_inbatch_softmax_fwd_bwd_f32:
+ * reg_w[row] = (occurrences among the 2B references) * 2*lambda*reg_scale; reg_scale does not scale the loss VALUE.  The
+ * loss-only form is g_final == NULL and needs reg_w == NULL (MI_ERR_UNSUPPORTED otherwise).
+ * d % 4 == 0 and 4 <= d <= 256 (MI_ERR_UNSUPPORTED otherwise); batch >= 1, 2 * batch < 2^31, 1 <= n_items < 2^31
+ * (MI_ERR_TOO_LARGE past 2^31).  final_emb, e0 and ws 16-byte aligned, ldf and lde multiples of 4.  Every check is made
+ * before anything is enqueued.
+ * The scores never reach memory: the row statistics, the user-gradient sweep and the item-gradient sweep each recompute their
+ * 32 x 32 score tiles through one routine in one k order, so all see the same bits.  No float atomics: an item row has one
+ * writer for the whole pass over the batch; the per-slot user rows are summed per user by the sorted-reference segmented
+ * sum of the other losses.  The catalogue is cut into item chunks whose (max, sum) pairs and partial user rows are merged in
+ * ascending chunk order; the cut and every order of summation are functions of (B, n_items, d) and the ids only, not of the
+ * device's size or of timing: two calls give equal bits, on any gfx950.  The workspace holds row images and per-chunk
+ * partials, never anything of size B x n_items.
+ * mi_full_softmax_workspace_bytes: 0 for arguments outside these limits.
+ * ---------------------------------------------------------------------------------- */
+size_t mi_full_softmax_workspace_bytes(int64_t batch, int64_t d, int64_t n_items);
+int    mi_full_softmax_fwd_bwd_f32(int64_t batch, int64_t d, int64_t n_users, int64_t n_items,
+                                   const int64_t* users, const int64_t* pos,
+                                   const float* final_emb, int64_t ldf,
+                                   const float* e0, int64_t lde,
+                                   float lambda, float g_scale, float reg_scale,
+                                   float* loss_out,
+                                   float* g_final, int64_t ldg,
+                                   float* reg_w,
+                                   void* ws, size_t ws_bytes, mi_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * a9  dense Adam step (torch.optim.Adam semantics, no weight decay, no amsgrad).
  * replaces: optimizer.step() at run_pipeline_lightgcn.py:159.
  *   g   = grad[i] + (reg_w ? reg_w[row(i)] * p[i] : 0)

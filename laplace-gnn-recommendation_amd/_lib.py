@@ -295,6 +295,9 @@ _PROTOTYPES = {
     "mi_inbatch_softmax_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int32]),
     "mi_inbatch_softmax_fwd_bwd_f32": (c_int32, [c_int64, c_int32, c_int64, c_int64, P, P, P, c_int64, P, c_int64,
                                                  c_float, c_float, c_float, P, P, c_int64, P, P, P, P, c_size_t, P]),
+    "mi_full_softmax_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64]),
+    "mi_full_softmax_fwd_bwd_f32": (c_int32, [c_int64, c_int64, c_int64, c_int64, P, P, P, c_int64, P, c_int64,
+                                              c_float, c_float, c_float, P, P, c_int64, P, P, c_size_t, P]),
     "mi_gemm_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64]),
     "mi_gemm_f32": (c_int32, [c_int32, c_int32, c_int64, c_int64, c_int64, P, c_int64, P, c_int64, P, P, c_int64,
                               c_int32, c_int32, P, c_size_t, P]),

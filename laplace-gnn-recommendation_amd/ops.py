@@ -1049,6 +1049,50 @@ def inbatch_softmax_fwd_bwd(users: Tensor, pos: Tensor, final_emb: Tensor, e0: T
     return loss_out
 
 
+def full_softmax_fwd_bwd(users: Tensor, pos: Tensor, final_emb: Tensor, e0: Tensor, n_users: int, lambda_val: float, *,
+                         g_final: Optional[Tensor] = None, reg_w: Optional[Tensor] = None, g_scale: float = 1.0,
+                         reg_scale: float = 1.0, loss_out: Optional[Tensor] = None) -> Tensor:
+    """Exact softmax over the whole catalogue (include/laplace_hip.h, "Full-catalogue softmax"): the candidates of slot b
+    are all n_items = final_emb.shape[0] - n_users item rows of final_emb, with no mask and no logq.  g_final (all zero on
+    entry) comes back with every item row written and the user rows the batch names; there is no node_map.  Conventions of
+    inbatch_softmax_fwd_bwd; the loss-only form (no g_final) takes no reg_w."""
+    if final_emb.dim() != 2:
+        raise ValueError("final_emb: a 2-D table expected")
+    d = int(final_emb.shape[1])
+    if d < 4 or d % 4 or d > INBATCH_MAX_D:
+        raise ValueError(f"the full softmax needs d % 4 == 0 and d <= {INBATCH_MAX_D}, got d = {d}")
+    batch = users.numel()
+    if batch < 1 or pos.numel() != batch:
+        raise ValueError("users [B], pos [B] expected, B >= 1")
+    n_items = int(final_emb.shape[0]) - int(n_users)
+    if n_users < 0 or n_items < 1:
+        raise ValueError(f"final_emb: {n_users} user rows and at least one item row expected, got {final_emb.shape[0]} rows")
+    if g_final is None and reg_w is not None:
+        raise ValueError("the loss-only form takes no reg_w (pass g_final, or leave reg_w out)")
+    for n, x in (("users", users), ("pos", pos)):
+        _need(x, t.int64, n)
+    ldf = _rows_ok(final_emb, "final_emb")
+    lde = _rows_ok(e0, "e0")
+    ldg = _rows_ok(g_final, "g_final") if g_final is not None else 0
+    if g_final is not None and g_final.shape[0] < final_emb.shape[0]:
+        raise ValueError(f"g_final: {final_emb.shape[0]} rows expected (every item row is written), got {g_final.shape[0]}")
+    if reg_w is not None:
+        _need(reg_w, t.float32, "reg_w")
+        if reg_w.numel() < final_emb.shape[0]:
+            raise ValueError(f"reg_w: {final_emb.shape[0]} entries expected, got {reg_w.numel()}")
+    dev = final_emb.device
+    if loss_out is None:
+        loss_out = t.empty(1, dtype=t.float32, device=dev)
+    L = _lib.lib()
+    ws = _ws(L.mi_full_softmax_workspace_bytes(batch, d, n_items), dev)
+    check(L.mi_full_softmax_fwd_bwd_f32(batch, d, n_users, n_items, _ptr(users), _ptr(pos), final_emb.data_ptr(), ldf,
+                                        e0.data_ptr(), lde, float(lambda_val), float(g_scale), float(reg_scale),
+                                        loss_out.data_ptr(), _ptr(g_final), ldg, _ptr(reg_w), ws.data_ptr(), ws.numel(),
+                                        _stream()),
+          "mi_full_softmax_fwd_bwd_f32")
+    return loss_out
+
+
 def adam_step(p: Tensor, grad: Tensor, m: Tensor, v: Tensor, *, step: int, lr: float, beta1: float = 0.9,
               beta2: float = 0.999, eps: float = 1e-8, reg_w: Optional[Tensor] = None) -> None:
     """a9 — dense Adam (torch.optim.Adam semantics) in one pass."""

@@ -67,7 +67,7 @@ def train(config: LightGCNConfig = lightgcn_config, *, edge_index: Tensor, num_u
           compat: str = "reference", device: str = "cuda", seed: int = 0, save_dir: Optional[str] = None,
           verbose: bool = True, objective: str = "reference", n_neg: int = 1, predictor: str = "layer0",
           negatives: str = "uniform", neg_power: float = 0.75, in_batch_group: int = 1024,
-          full_rank_ks: Optional[Tuple[int, ...]] = None) -> Stats:
+          full_rank_ks: Optional[Tuple[int, ...]] = None, full_softmax: bool = False) -> Stats:
     """objective / n_neg: the training loss (trainer.LightGCNTrainer).  predictor="propagated": evaluation,
     the ranking metrics and the saved predictions score with mean_k(A^k E0) of the training adjacency — the scores the
     loss trains — instead of the layer-0 tables.
@@ -75,7 +75,9 @@ def train(config: LightGCNConfig = lightgcn_config, *, edge_index: Tensor, num_u
     correction when objective == "softmax"; the reference's negative range and sampler quirk do not apply to that
     sampler and are left out.  negatives="in_batch" (objective="softmax"): the other positives of a slot's group of
     in_batch_group slots are its negatives, logQ-corrected by training degree; likewise without the reference's range and
-    quirk.  evaluation() keeps its uniform negatives and uncorrected loss in every case, so
+    quirk.  full_softmax=True (objective="softmax", negatives="uniform"): the exact softmax over every item, in the dense
+    step form (sparse_batch=False is chosen here), also without the range and the quirk.
+    evaluation() keeps its uniform negatives and uncorrected loss in every case, so
     validation and test losses stay comparable across samplers.
     full_rank_ks: when given, the test split is also scored by evaluation_full_rank at these K (same predictor, same
     exclusions); the dict is printed under `verbose` and, with `save_dir`, written as full_rank_metrics.json.  The returned
@@ -93,12 +95,15 @@ def train(config: LightGCNConfig = lightgcn_config, *, edge_index: Tensor, num_u
     model.train()
     train_inter = Interactions(train_edges, num_users, num_articles)
     # reference sampler: negatives from [0, max train item id) with its key-collision quirk
-    popular = negatives in ("popularity", "in_batch")   # samplers over every item, without the reference's quirk
+    # samplers over every item (or no sampler at all), without the reference's quirk
+    popular = negatives in ("popularity", "in_batch") or full_softmax
+    exact = dict(full_softmax=True, sparse_batch=False) if full_softmax else {}
     trainer = LightGCNTrainer(model, train_sparse, train_inter, lr=config.learning_rate, Lambda=config.Lambda,
                               batch_size=config.batch_size, seed=seed,
                               neg_range=None if popular else int(train_edges[1].max()),
                               reference_sampler_quirks=(compat == "reference" and not popular), objective=objective,
-                              n_neg=n_neg, negatives=negatives, neg_power=neg_power, in_batch_group=in_batch_group)
+                              n_neg=n_neg, negatives=negatives, neg_power=neg_power, in_batch_group=in_batch_group,
+                              **exact)
 
     def scoring_tables():
         return propagated_embeddings(model, train_sparse) if predictor == "propagated" else None

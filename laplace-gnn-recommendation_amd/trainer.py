@@ -7,7 +7,9 @@ the GPU and no host round trip.
               (objective="bpr" / "softmax" and n_neg = M <= 16 negatives per positive: opt-in, SURVEY F9;
                negatives="popularity": negatives drawn ∝ degree ** neg_power, and with the softmax the logQ correction;
                negatives="in_batch": no negative is drawn, the other positives of a slot's group of in_batch_group slots
-               are its negatives, scored on the f32 matrix cores — mi_inbatch_softmax_fwd_bwd_f32)
+               are its negatives, scored on the f32 matrix cores — mi_inbatch_softmax_fwd_bwd_f32;
+               full_softmax=True: the exact softmax over every item of the catalogue, the objective the sampled ones
+               estimate — mi_full_softmax_fwd_bwd_f32; its gradient is dense over the item rows, so sparse_batch=False)
     backward  K SpMM launches on A^T, G/(K+1) folded in as addend    (autograd of the forward)
     update    dense Adam over the whole table, L2 term folded in     run_pipeline_lightgcn.py:157-159
 
@@ -74,7 +76,8 @@ class _LightGCNTrainerBase:
     assignments, the locality order's bookkeeping, the per-batch and optimizer state, sample() and the Adam keywords.
     `self.ops` is the kernel provider (this package's HIP `ops`; the sharded trainer's CPU tests inject another).  A subclass
     sets up its adjacency, `_r`, `_row_of_edge`, `neg_range` and `_sample_kw`, and writes its own steps."""
-    in_batch = False   # negatives come from the batch itself: (users, pos) batches
+    in_batch = False   # no negative is drawn: (users, pos) batches (in-batch negatives, or the whole catalogue)
+    full_softmax = False   # every item is a candidate (LightGCNTrainer, full_softmax=True); implies in_batch
 
     def __init__(self, model: LightGCN, kernels, *, lr: float, Lambda: float, batch_size: int, betas: Tuple[float, float],
                  eps: float, seed: int, sparse_batch: bool, objective: str, n_neg: int):
@@ -181,7 +184,7 @@ class LightGCNTrainer(_LightGCNTrainerBase):
                  neg_range: Optional[int] = None, reference_sampler_quirks: bool = False,
                  sparse_batch: bool = True, fuse_adam: bool = True, reorder: Optional[bool] = None,
                  objective: str = "reference", n_neg: int = 1, negatives: str = "uniform", neg_power: float = 0.75,
-                 logq_correction: Optional[bool] = None, in_batch_group: int = 1024):
+                 logq_correction: Optional[bool] = None, in_batch_group: int = 1024, full_softmax: bool = False):
         """negatives="popularity": negatives drawn ∝ (training degree) ** neg_power from `neg_table`, built in the id space
         the kernels train in.  logq_correction: the softmax's logits become s - log q(item); None = on iff
         objective == "softmax" and negatives != "uniform".  The defaults launch the step as it was.
@@ -190,7 +193,11 @@ class LightGCNTrainer(_LightGCNTrainerBase):
         or belong to its user; the user's other items in the group are NOT rejected.  The batch is the uniform sampler's edge
         stream — users and pos at a (seed, step) are the bits a negatives="uniform" trainer draws; the negative it draws as
         well is ignored.  The logQ correction's proposal is "the item of a uniformly drawn training edge", q ∝ training degree
-        (ops.negative_table(degree, 1.0)); neg_power is not used.  step(batch) takes (users, pos); a third entry is ignored."""
+        (ops.negative_table(degree, 1.0)); neg_power is not used.  step(batch) takes (users, pos); a third entry is ignored.
+        full_softmax=True (objective="softmax", negatives="uniform", n_neg = 1, sparse_batch=False passed explicitly, no
+        logq_correction, no reference_sampler_quirks, neg_range None or num_items): the exact softmax over all num_items items,
+        nothing drawn and nothing corrected.  Batches are the uniform sampler's users and pos at the same (seed, step), as for
+        negatives="in_batch"; the step is the dense one, whose gradient buffer the loss fills at every item row."""
         super().__init__(model, ops, lr=lr, Lambda=Lambda, batch_size=batch_size, betas=betas, eps=eps, seed=seed,
                          sparse_batch=sparse_batch, objective=objective, n_neg=n_neg)
         if negatives not in NEGATIVES:
@@ -216,8 +223,24 @@ class LightGCNTrainer(_LightGCNTrainerBase):
                 raise ValueError('negatives="in_batch" does not combine with reference_sampler_quirks')
             if neg_range is not None and int(neg_range) != model.num_items:
                 raise ValueError(f'negatives="in_batch" takes its negatives from the batch: neg_range {neg_range} != {model.num_items}')
-        self.in_batch = negatives == "in_batch"
-        self.in_batch_group = int(in_batch_group) if self.in_batch else None
+        if full_softmax:
+            if objective != "softmax":
+                raise ValueError(f'full_softmax is the exact softmax: objective="softmax" expected, got {objective!r}')
+            if negatives != "uniform":
+                raise ValueError(f'full_softmax draws nothing: negatives stays "uniform", got {negatives!r}')
+            if n_neg != 1:
+                raise ValueError(f"full_softmax draws nothing: n_neg stays 1, got {n_neg}")
+            if reference_sampler_quirks:
+                raise ValueError("full_softmax does not combine with reference_sampler_quirks")
+            if neg_range is not None and int(neg_range) != model.num_items:
+                raise ValueError(f"full_softmax scores every item: neg_range {neg_range} != {model.num_items}")
+            if logq_correction:
+                raise ValueError("full_softmax samples nothing: logq_correction has nothing to correct")
+            if sparse_batch:
+                raise ValueError("full_softmax has a gradient at every item row: pass sparse_batch=False")
+            self.full_softmax = True
+        self.in_batch = negatives == "in_batch" or self.full_softmax
+        self.in_batch_group = int(in_batch_group) if negatives == "in_batch" else None
         self.negatives, self.neg_power, self.logq_correction = negatives, float(neg_power), bool(logq_correction)
         if not self.table.is_cuda:
             raise RuntimeError("LightGCNTrainer needs the model on the GPU (model.to('cuda')); no CPU fallback")
@@ -271,6 +294,10 @@ class LightGCNTrainer(_LightGCNTrainerBase):
     def _loss(self, users, pos, neg, final, **kw) -> None:
         """Loss and its gradient on `final` (self.logq is None without the logQ correction)."""
         if self.in_batch:
+            if self.full_softmax:
+                ops.full_softmax_fwd_bwd(users, pos, final, self.table, self.model.num_users, self.Lambda, reg_w=self.reg_w,
+                                         loss_out=self.loss, **kw)
+                return
             ops.inbatch_softmax_fwd_bwd(users, pos, final, self.table, self.model.num_users, self.Lambda,
                                         group=self.in_batch_group, reg_w=self.reg_w, loss_out=self.loss, logq=self.logq, **kw)
             return

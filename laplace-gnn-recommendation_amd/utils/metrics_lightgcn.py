@@ -178,6 +178,46 @@ def in_batch_softmax_loss(users_emb_final: Tensor, users_emb_0: Tensor, pos_item
                                    uinv, ufirst, iinv, ifirst, logq, group)
 
 
+class _FullSoftmaxFn(t.autograd.Function):
+    """full_softmax_loss through mi_full_softmax_fwd_bwd_f32: the user block and the item table become one table whose user
+    rows are the B slots (slot b is user b), and the positives' layer-0 rows go to their items' rows of a layer-0 table."""
+
+    @staticmethod
+    def forward(ctx, uf, itf, pos, u0, p0, lambda_val: float):
+        B, n_items = uf.shape[0], itf.shape[0]
+        final = t.cat([uf, itf]).contiguous()
+        e0 = t.cat([u0, u0.new_zeros(n_items, u0.shape[1])])
+        e0[B + pos] = p0                     # slots with equal ids carry equal rows
+        g_final = t.zeros_like(final)
+        loss = ops.full_softmax_fwd_bwd(t.arange(B, device=uf.device), pos, final, e0, B, lambda_val, g_final=g_final)
+        ctx.save_for_backward(g_final, u0, p0)
+        ctx.B, ctx.lam = B, lambda_val
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        g_final, u0, p0 = ctx.saved_tensors
+        gf = g_final * grad_out
+        w = 2.0 * ctx.lam * grad_out         # every slot adds lambda |row|^2 for its user row and for its positive's row
+        return gf[:ctx.B], gf[ctx.B:], None, w * u0, w * p0, None
+
+
+def full_softmax_loss(users_emb_final: Tensor, items_emb_final: Tensor, pos: Tensor, users_emb_0: Tensor,
+                      pos_items_emb_0: Tensor, lambda_val: float) -> Tensor:
+    """The exact softmax over the whole catalogue, the objective in_batch_softmax_loss and the sampled softmax of
+    ranking_loss estimate: slot b's candidates are all rows of items_emb_final [I, D] with the logit <u_b, item_i>, no
+    mask and no logq; pos [B] (int64) names each slot's positive.  users_emb_final and users_emb_0 are gathered blocks
+    [B, D], pos_items_emb_0 [B, D] the positives' layer-0 rows (slots with equal ids must carry equal rows).  Gradients go
+    to users_emb_final, items_emb_final (dense: every item row), users_emb_0 and pos_items_emb_0."""
+    B = int(users_emb_final.shape[0])
+    if pos.numel() != B or users_emb_0.shape != users_emb_final.shape or pos_items_emb_0.shape != users_emb_final.shape:
+        raise ValueError(f"pos [{B}] and layer-0 blocks of shape {tuple(users_emb_final.shape)} expected")
+    if items_emb_final.dim() != 2 or items_emb_final.shape[1] != users_emb_final.shape[1] or items_emb_final.shape[0] < 1:
+        raise ValueError(f"items_emb_final: [I, {users_emb_final.shape[1]}] with I >= 1 expected")
+    return _FullSoftmaxFn.apply(users_emb_final, items_emb_final, pos.reshape(B), users_emb_0, pos_items_emb_0,
+                                float(lambda_val))
+
+
 # ----------------------------------------------------------------------------------------------
 # evaluation: batched on device (reference: per-user Python loops on the CPU)
 # ----------------------------------------------------------------------------------------------
