@@ -605,6 +605,63 @@ int    mi_full_softmax_fwd_bwd_f32(int64_t batch, int64_t d, int64_t n_users, in
                                    void* ws, size_t ws_bytes, mi_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * Noise-view contrastive term (behind a flag; XSimGCL, Yu et al., TKDE 2023, on the LightGCN backbone): every propagated
+ * layer of ONE forward pass is perturbed by a small random vector, and the final read-out of a node is contrasted with the
+ * same node's layer-l* embedding.  The perturbation is an additive constant (sign has zero derivative), so the backward is
+ * the A^T chain of the unperturbed step with one more addend at layer l*.
+ *
+ * Perturbed propagate, for layer k = 1..K, Y_k = A X_{k-1} (X_0 = E0, the table):
+ *   w       = Philox4x32-10( counter (id, c / 4, k, 0x58434C31), key (lo32(s), hi32(s)) ), s = seed + 0x9E3779B97F4A7C15 * step
+ *             mod 2^64; id = the low 32 bits of the row's ORIGINAL id (row_ids[r], or r itself when row_ids is NULL); word
+ *             c % 4 of the block belongs to column c
+ *   u[r,c]  = (w >> 8) * 2^-24                        exact in fp32, in [0, 1)
+ *   n[r,:]  = u[r,:] / max(|u[r,:]|_2, 1e-12)         the summation order of the norm is the kernel's own
+ *   X_k[r,c] = Y_k[r,c] + eps * sign(Y_k[r,c]) * n[r,c]      sign(+-0) = 0: an all-zero row stays zero
+ *   F = (1 / (K+1)) * sum_{k=0..K} X_k                (layer 0 is not perturbed)
+ * A row's noise depends on (seed, step, k, id, c) only: not on n_rows, not on the leading dimension, not on the order of
+ * the rows.  mi_perturb_rows_f32 perturbs x [n_rows, d] in place and, when S is given, also writes
+ * S = (addend + X) * scale (addend nullable: zero; S may alias addend when lda == lds; neither may alias x), the running
+ * layer sum of mi_spmm_csr_f32's epilogue.  d % 4 == 0 and 4 <= d <= 256 (MI_ERR_UNSUPPORTED otherwise); x, addend, S 16-byte
+ * aligned, leading dimensions multiples of 4; eps >= 0, layer >= 0; n_rows == 0 is a no-op.  Every check is made before
+ * anything is enqueued.  No atomics, one writer per element: two calls give equal bits.
+ *
+ * Contrast (mi_contrastive_fwd_bwd_f32), over ids[B] (int64 rows of BOTH tables a and b; the trainer calls it once with the
+ * batch's users and once with its positives' node ids, a = F, b = X_{l*}), in groups of G consecutive slots as the in-batch
+ * softmax cuts them (G a multiple of 32 in 32..4096, the last group may be partial):
+ *   p_b = a[id_b] / max(|a[id_b]|, 1e-12)       q_b = b[id_b] / max(|b[id_b]|, 1e-12)
+ *   l[b,j] = <p_b, q_j> * inv_tau               j in b's group; j != b is MASKED when id_j == id_b (the same node again)
+ *   loss = (1/B) sum_b [ logsumexp_{j unmasked, incl. j = b} l[b,j] - l[b,b] ]
+ * with the maximum subtracted before the exponentials; a slot alone in its group adds 0.  The contrast runs over slots, not
+ * over distinct nodes: a node named m times weighs m times and its copies are masked as candidates of each other.
+ *   g_a[id_b] += g_scale_a * dloss/da[id_b],  g_b[id_b] += g_scale_b * dloss/db[id_b], through the normalisation,
+ *   dp/df = (I - p p^T) / |f| (a row under the 1e-12 floor: I / 1e-12).  The call ADDS to what the rows hold (it runs after
+ *   the main loss, whose kernels demand zeros); rows that ids does not name are not touched.  The loss-only form is
+ *   g_a == g_b == NULL; exactly one of them NULL is MI_ERR_UNSUPPORTED.  loss_out is written, not added to.
+ * Limits and checks of mi_inbatch_softmax_fwd_bwd_f32: d % 4 == 0 and d <= 256 (MI_ERR_UNSUPPORTED), batch >= 1,
+ * 2 * batch < 2^31 (MI_ERR_TOO_LARGE), ids < 2^31, inv_tau > 0 and finite, a, b and ws 16-byte aligned, lda and ldb multiples
+ * of 4; all made before anything is enqueued.
+ * The step (LightGCNTrainer, cl_weight > 0): loss = main loss + cl_weight * (L_user + L_item), L_user over id_b = users_b,
+ * L_item over id_b = n_users + pos_b.  With gc = dL/dF / (K+1) (both terms) and G = cl_weight * dL_cl/dX_{l*}:
+ *   h_K = gc (+ G if l* == K);   h_k = gc + A^T h_{k+1} (+ G if k == l*), k = K-1..1;   h_0 = gc + A^T h_1 = dL/dE0.
+ * The call is the in-batch softmax's tile routine, row statistics and gradient sweeps on two normalised [B, d] images (p / tau
+ * and q); the per-slot gradient rows go through the normalisation and are summed per id, in slot order, by the
+ * sorted-reference segmented sum: one writer per row, no float atomics, two calls give equal bits.
+ * mi_contrastive_workspace_bytes: 0 for arguments outside these limits.
+ * ---------------------------------------------------------------------------------- */
+int    mi_perturb_rows_f32(int64_t n_rows, int64_t d, float* x, int64_t ldx,
+                           const int64_t* row_ids /* [n_rows], nullable */,
+                           float eps, int32_t layer, uint64_t seed, uint64_t step,
+                           const float* addend, int64_t lda, float* S, int64_t lds, float scale,
+                           mi_stream_t stream);
+size_t mi_contrastive_workspace_bytes(int64_t batch, int64_t d, int32_t group);
+int    mi_contrastive_fwd_bwd_f32(int64_t batch, int32_t group, int64_t d, const int64_t* ids,
+                                  const float* a, int64_t lda, const float* b, int64_t ldb,
+                                  float inv_tau, float* loss_out,
+                                  float* g_a, int64_t ldga, float g_scale_a,
+                                  float* g_b, int64_t ldgb, float g_scale_b,
+                                  void* ws, size_t ws_bytes, mi_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * a9  dense Adam step (torch.optim.Adam semantics, no weight decay, no amsgrad).
  * replaces: optimizer.step() at run_pipeline_lightgcn.py:159.
  *   g   = grad[i] + (reg_w ? reg_w[row(i)] * p[i] : 0)

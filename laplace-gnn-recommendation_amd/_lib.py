@@ -298,6 +298,11 @@ _PROTOTYPES = {
     "mi_full_softmax_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64]),
     "mi_full_softmax_fwd_bwd_f32": (c_int32, [c_int64, c_int64, c_int64, c_int64, P, P, P, c_int64, P, c_int64,
                                               c_float, c_float, c_float, P, P, c_int64, P, P, c_size_t, P]),
+    "mi_perturb_rows_f32": (c_int32, [c_int64, c_int64, P, c_int64, P, c_float, c_int32, c_uint64, c_uint64, P, c_int64,
+                                      P, c_int64, c_float, P]),
+    "mi_contrastive_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int32]),
+    "mi_contrastive_fwd_bwd_f32": (c_int32, [c_int64, c_int32, c_int64, P, P, c_int64, P, c_int64, c_float, P,
+                                             P, c_int64, c_float, P, c_int64, c_float, P, c_size_t, P]),
     "mi_gemm_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64]),
     "mi_gemm_f32": (c_int32, [c_int32, c_int32, c_int64, c_int64, c_int64, P, c_int64, P, c_int64, P, P, c_int64,
                               c_int32, c_int32, P, c_size_t, P]),

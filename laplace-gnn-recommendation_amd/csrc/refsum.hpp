@@ -81,6 +81,7 @@ struct Dest {   // where the sums go: rows of g_final, and one head and one tail
     float* __restrict__ part_head;
     float* __restrict__ part_tail;
     int d;
+    bool add = false;   // the finished rows are ADDED to what g_final holds (still one writer per row) instead of stored
 };
 
 // The sum of the run a wavefront is in, and where it goes when the run closes.
@@ -100,7 +101,8 @@ struct RunWriter {
     // came in from the previous chunk goes to part_head[chunk], also when it runs on into the next one: a chunk that lies
     // wholly inside a run is a head partial, from_prev wins over into_next, and the combine walks head partials until a
     // chunk's last key differs.  A run that starts here and runs on goes to part_tail[chunk]; a run inside the chunk goes
-    // to its row of g_final, whose only writer this wavefront is (g_final is zero on entry: a store, no read-modify-write).
+    // to its row of g_final, whose only writer this wavefront is (g_final is zero on entry: a store, no read-modify-write;
+    // with Dest::add the row is added to what g_final holds instead, for a caller whose table another loss has filled).
     __device__ __forceinline__ void close(const Chunk& c, int q, const Dest& to) {
         const uint32_t kq = __shfl(c.key, q, MI_WAVE);
         const bool last_of_run = (q + 1 == c.n_here) || __shfl(c.key, q + 1, MI_WAVE) != kq;
@@ -111,10 +113,11 @@ struct RunWriter {
         if (from_prev) dst = to.part_head + c.id * to.d;         // finished by the chunk where the run starts
         else if (into_next) dst = to.part_tail + c.id * to.d;    // this chunk starts the run; combine_kernel finishes it
         else dst = to.g_final + (int64_t)kq * to.ldg;
+        const bool add = to.add && !from_prev && !into_next;   // partial rows are always stored
 #pragma unroll
         for (int v = 0; v < VPT; ++v) {
             const int k = c.lane + v * MI_WAVE;
-            if (k < to.d) dst[k] = acc[v];
+            if (k < to.d) dst[k] = add ? dst[k] + acc[v] : acc[v];
             acc[v] = 0.f;
         }
         run_start = q + 1;
@@ -167,7 +170,7 @@ template <int VPT>
 static __global__ __launch_bounds__(kBlock) void combine_kernel(int64_t n_ref, int d, const uint32_t* __restrict__ keys,
                                                                 const float* __restrict__ part_head,
                                                                 const float* __restrict__ part_tail,
-                                                                float* __restrict__ g_final, int64_t ldg) {
+                                                                float* __restrict__ g_final, int64_t ldg, bool add) {
     const int64_t chunk = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / MI_WAVE;
     const int64_t j0 = chunk * kChunk;
     if (j0 >= n_ref) return;
@@ -195,7 +198,7 @@ static __global__ __launch_bounds__(kBlock) void combine_kernel(int64_t n_ref, i
 #pragma unroll
     for (int v = 0; v < VPT; ++v) {
         const int k = lane + v * MI_WAVE;
-        if (k < d) dst[k] = acc[v];
+        if (k < d) dst[k] = add ? dst[k] + acc[v] : acc[v];
     }
 }
 
@@ -290,7 +293,7 @@ inline dim3 chunk_grid(int64_t n_ref) { return dim3((unsigned)mi_ceil_div(mi_cei
 template <int VPT>
 void launch_combine(const Sort& plan, int64_t n_ref, const Dest& to, hipStream_t s) {
     hipLaunchKernelGGL(combine_kernel<VPT>, chunk_grid(n_ref), dim3(kBlock), 0, s, n_ref, to.d, (const uint32_t*)plan.keys.current(),
-                       (const float*)to.part_head, (const float*)to.part_tail, to.g_final, to.ldg);
+                       (const float*)to.part_head, (const float*)to.part_tail, to.g_final, to.ldg, to.add);
 }
 
 inline void launch_finish(int64_t batch, const float* term_v, const float* reg_v, float mean_scale, float lambda,

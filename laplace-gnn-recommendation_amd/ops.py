@@ -7,6 +7,7 @@ from __future__ import annotations
 
 import ctypes
 import itertools
+import math
 import os
 from os import environ as _os_environ
 from dataclasses import dataclass, field
@@ -1090,6 +1091,83 @@ def full_softmax_fwd_bwd(users: Tensor, pos: Tensor, final_emb: Tensor, e0: Tens
                                         loss_out.data_ptr(), _ptr(g_final), ldg, _ptr(reg_w), ws.data_ptr(), ws.numel(),
                                         _stream()),
           "mi_full_softmax_fwd_bwd_f32")
+    return loss_out
+
+
+def check_contrastive(d: int, *, eps: float = 0.0, tau: float = 1.0, group: int = 32) -> None:
+    """The limits of perturb_rows / contrastive_fwd_bwd, each refusal naming its argument."""
+    if d < 4 or d % 4 or d > INBATCH_MAX_D:
+        raise ValueError(f"the contrastive term needs d % 4 == 0 and d <= {INBATCH_MAX_D}, got d = {d}")
+    if isinstance(eps, bool) or not isinstance(eps, (int, float)) or not 0.0 <= eps < math.inf:
+        raise ValueError(f"eps must be a finite number >= 0, got {eps!r}")
+    if isinstance(tau, bool) or not isinstance(tau, (int, float)) or not 0.0 < tau < math.inf:
+        raise ValueError(f"tau must be a finite number > 0, got {tau!r}")
+    check_inbatch_group(group)
+
+
+def perturb_rows(x: Tensor, *, eps: float, layer: int, seed: int, step: int, row_ids: Optional[Tensor] = None,
+                 addend: Optional[Tensor] = None, S: Optional[Tensor] = None, scale: float = 1.0) -> Tensor:
+    """x[r, :] += eps * sign(x[r, :]) * n[r, :] in place, n the unit noise vector of (seed, step, layer, the row's original
+    id = row_ids[r], or r) — include/laplace_hip.h, "Noise-view contrastive term".  With S also S = (addend + x) * scale in
+    the same pass (addend None: zero; S may be addend itself)."""
+    if x.dim() != 2:
+        raise ValueError("x: a 2-D table expected")
+    n, d = int(x.shape[0]), int(x.shape[1])
+    check_contrastive(d, eps=eps)
+    if isinstance(layer, bool) or not isinstance(layer, int) or layer < 0:
+        raise ValueError(f"layer must be an integer >= 0, got {layer!r}")
+    ldx = _rows_ok(x, "x")
+    if addend is not None and S is None:
+        raise ValueError("addend without S: the sum has nowhere to go")
+    if row_ids is not None:
+        _need(row_ids, t.int64, "row_ids")
+        if row_ids.numel() != n:
+            raise ValueError(f"row_ids: one id per row expected ({n}), got {row_ids.numel()}")
+    lda = lds = 0
+    for name, y in (("addend", addend), ("S", S)):
+        if y is not None and tuple(y.shape) != (n, d):
+            raise ValueError(f"{name}: shape {(n, d)} expected, got {tuple(y.shape)}")
+    if addend is not None:
+        lda = _rows_ok(addend, "addend")
+    if S is not None:
+        lds = _rows_ok(S, "S")
+    check(_lib.lib().mi_perturb_rows_f32(n, d, x.data_ptr(), ldx, _ptr(row_ids), float(eps), layer,
+                                         int(seed) & (2 ** 64 - 1), int(step) & (2 ** 64 - 1), _ptr(addend), lda, _ptr(S),
+                                         lds, float(scale), _stream()), "mi_perturb_rows_f32")
+    return x
+
+
+def contrastive_fwd_bwd(ids: Tensor, a: Tensor, b: Tensor, *, tau: float, group: int = 1024, g_a: Optional[Tensor] = None,
+                        g_b: Optional[Tensor] = None, g_scale_a: float = 1.0, g_scale_b: float = 1.0,
+                        loss_out: Optional[Tensor] = None) -> Tensor:
+    """InfoNCE between the normalised rows a[ids] and b[ids] over groups of `group` consecutive slots (include/laplace_hip.h,
+    "Noise-view contrastive term"): slot b's candidates are the b-rows of its group, minus other slots that name its own id.
+    g_a / g_b: the call ADDS g_scale_a * dloss/da and g_scale_b * dloss/db to the rows `ids` names; both or neither (the
+    loss-only form).  Returns the loss as a 1-element device tensor."""
+    if a.dim() != 2 or b.dim() != 2 or a.shape[1] != b.shape[1]:
+        raise ValueError("a, b: two 2-D tables of one width expected")
+    d = int(a.shape[1])
+    check_contrastive(d, tau=tau, group=group)
+    batch = ids.numel()
+    if batch < 1 or ids.dim() != 1:
+        raise ValueError("ids [B] expected, B >= 1")
+    if (g_a is None) != (g_b is None):
+        raise ValueError("g_a and g_b: both, or neither for the loss-only form")
+    _need(ids, t.int64, "ids")
+    lda, ldb = _rows_ok(a, "a"), _rows_ok(b, "b")
+    ldga = ldgb = 0
+    if g_a is not None:
+        ldga, ldgb = _rows_ok(g_a, "g_a"), _rows_ok(g_b, "g_b")
+        if g_a.shape != a.shape or g_b.shape != b.shape:
+            raise ValueError("g_a, g_b: the shapes of a and b expected")
+    dev = a.device
+    if loss_out is None:
+        loss_out = t.empty(1, dtype=t.float32, device=dev)
+    L = _lib.lib()
+    ws = _ws(L.mi_contrastive_workspace_bytes(batch, d, group), dev)
+    check(L.mi_contrastive_fwd_bwd_f32(batch, group, d, ids.data_ptr(), a.data_ptr(), lda, b.data_ptr(), ldb, 1.0 / float(tau),
+                                       loss_out.data_ptr(), _ptr(g_a), ldga, float(g_scale_a), _ptr(g_b), ldgb,
+                                       float(g_scale_b), ws.data_ptr(), ws.numel(), _stream()), "mi_contrastive_fwd_bwd_f32")
     return loss_out
 
 

@@ -67,7 +67,8 @@ def train(config: LightGCNConfig = lightgcn_config, *, edge_index: Tensor, num_u
           compat: str = "reference", device: str = "cuda", seed: int = 0, save_dir: Optional[str] = None,
           verbose: bool = True, objective: str = "reference", n_neg: int = 1, predictor: str = "layer0",
           negatives: str = "uniform", neg_power: float = 0.75, in_batch_group: int = 1024,
-          full_rank_ks: Optional[Tuple[int, ...]] = None, full_softmax: bool = False) -> Stats:
+          full_rank_ks: Optional[Tuple[int, ...]] = None, full_softmax: bool = False, cl_weight: float = 0.0,
+          cl_eps: float = 0.2, cl_tau: float = 0.15, cl_layer: int = 1, cl_group: int = 1024) -> Stats:
     """objective / n_neg: the training loss (trainer.LightGCNTrainer).  predictor="propagated": evaluation,
     the ranking metrics and the saved predictions score with mean_k(A^k E0) of the training adjacency — the scores the
     loss trains — instead of the layer-0 tables.
@@ -77,6 +78,8 @@ def train(config: LightGCNConfig = lightgcn_config, *, edge_index: Tensor, num_u
     in_batch_group slots are its negatives, logQ-corrected by training degree; likewise without the reference's range and
     quirk.  full_softmax=True (objective="softmax", negatives="uniform"): the exact softmax over every item, in the dense
     step form (sparse_batch=False is chosen here), also without the range and the quirk.
+    cl_weight > 0: the noise-view contrastive term (LightGCNTrainer's cl_* keywords, passed through) is added to the training
+    loss, in the dense step form (chosen here as well).
     evaluation() keeps its uniform negatives and uncorrected loss in every case, so
     validation and test losses stay comparable across samplers.
     full_rank_ks: when given, the test split is also scored by evaluation_full_rank at these K (same predictor, same
@@ -98,6 +101,8 @@ def train(config: LightGCNConfig = lightgcn_config, *, edge_index: Tensor, num_u
     # samplers over every item (or no sampler at all), without the reference's quirk
     popular = negatives in ("popularity", "in_batch") or full_softmax
     exact = dict(full_softmax=True, sparse_batch=False) if full_softmax else {}
+    if cl_weight:
+        exact.update(sparse_batch=False, cl_weight=cl_weight, cl_eps=cl_eps, cl_tau=cl_tau, cl_layer=cl_layer, cl_group=cl_group)
     trainer = LightGCNTrainer(model, train_sparse, train_inter, lr=config.learning_rate, Lambda=config.Lambda,
                               batch_size=config.batch_size, seed=seed,
                               neg_range=None if popular else int(train_edges[1].max()),

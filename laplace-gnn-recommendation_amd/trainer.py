@@ -10,6 +10,9 @@ the GPU and no host round trip.
                are its negatives, scored on the f32 matrix cores — mi_inbatch_softmax_fwd_bwd_f32;
                full_softmax=True: the exact softmax over every item of the catalogue, the objective the sampled ones
                estimate — mi_full_softmax_fwd_bwd_f32; its gradient is dense over the item rows, so sparse_batch=False)
+              (cl_weight > 0, sparse_batch=False: the noise-view contrastive term of XSimGCL on top of any of these — every
+               layer of the step's forward perturbed by mi_perturb_rows_f32, the batch's users and positives contrasted,
+               final read-out against layer cl_layer, by mi_contrastive_fwd_bwd_f32; _step_contrastive)
     backward  K SpMM launches on A^T, G/(K+1) folded in as addend    (autograd of the forward)
     update    dense Adam over the whole table, L2 term folded in     run_pipeline_lightgcn.py:157-159
 
@@ -184,7 +187,8 @@ class LightGCNTrainer(_LightGCNTrainerBase):
                  neg_range: Optional[int] = None, reference_sampler_quirks: bool = False,
                  sparse_batch: bool = True, fuse_adam: bool = True, reorder: Optional[bool] = None,
                  objective: str = "reference", n_neg: int = 1, negatives: str = "uniform", neg_power: float = 0.75,
-                 logq_correction: Optional[bool] = None, in_batch_group: int = 1024, full_softmax: bool = False):
+                 logq_correction: Optional[bool] = None, in_batch_group: int = 1024, full_softmax: bool = False,
+                 cl_weight: float = 0.0, cl_eps: float = 0.2, cl_tau: float = 0.15, cl_layer: int = 1, cl_group: int = 1024):
         """negatives="popularity": negatives drawn ∝ (training degree) ** neg_power from `neg_table`, built in the id space
         the kernels train in.  logq_correction: the softmax's logits become s - log q(item); None = on iff
         objective == "softmax" and negatives != "uniform".  The defaults launch the step as it was.
@@ -197,7 +201,14 @@ class LightGCNTrainer(_LightGCNTrainerBase):
         full_softmax=True (objective="softmax", negatives="uniform", n_neg = 1, sparse_batch=False passed explicitly, no
         logq_correction, no reference_sampler_quirks, neg_range None or num_items): the exact softmax over all num_items items,
         nothing drawn and nothing corrected.  Batches are the uniform sampler's users and pos at the same (seed, step), as for
-        negatives="in_batch"; the step is the dense one, whose gradient buffer the loss fills at every item row."""
+        negatives="in_batch"; the step is the dense one, whose gradient buffer the loss fills at every item row.
+        cl_weight > 0 (sparse_batch=False passed explicitly, K >= 1): the noise-view contrastive term of XSimGCL is added to
+        whatever main loss the other keywords choose — loss + cl_weight * (L_user + L_item).  Every propagated layer of the
+        step's forward is perturbed by cl_eps * sign(x) * (unit noise keyed on (seed, step, layer, ORIGINAL node id)), and the
+        batch's user nodes and positive item nodes are each contrasted, final read-out against layer cl_layer (1..K), at
+        temperature cl_tau in groups of cl_group consecutive slots (a multiple of 32 in 32..4096).  The rule is in
+        include/laplace_hip.h, "Noise-view contrastive term".  forward(), evaluation and serving stay unperturbed; cl_weight = 0
+        (the default) launches the step as it was."""
         super().__init__(model, ops, lr=lr, Lambda=Lambda, batch_size=batch_size, betas=betas, eps=eps, seed=seed,
                          sparse_batch=sparse_batch, objective=objective, n_neg=n_neg)
         if negatives not in NEGATIVES:
@@ -240,6 +251,18 @@ class LightGCNTrainer(_LightGCNTrainerBase):
                 raise ValueError("full_softmax has a gradient at every item row: pass sparse_batch=False")
             self.full_softmax = True
         self.in_batch = negatives == "in_batch" or self.full_softmax
+        if isinstance(cl_weight, bool) or not isinstance(cl_weight, (int, float)) or not 0.0 <= cl_weight < math.inf:
+            raise ValueError(f"cl_weight must be a finite number >= 0, got {cl_weight!r}")
+        self.cl_weight = float(cl_weight)
+        if self.cl_weight > 0.0:
+            ops.check_contrastive(model.embedding_dim, eps=cl_eps, tau=cl_tau, group=cl_group)
+            if self.K == 0:
+                raise ValueError("cl_weight > 0 contrasts a propagated layer: num_iterations >= 1 expected, got K = 0")
+            if isinstance(cl_layer, bool) or not isinstance(cl_layer, int) or not 1 <= cl_layer <= self.K:
+                raise ValueError(f"cl_layer must be an integer in 1..{self.K}, got {cl_layer!r}")
+            if sparse_batch:
+                raise ValueError("cl_weight > 0 perturbs whole layers, the dense step: pass sparse_batch=False")
+            self.cl_eps, self.cl_tau, self.cl_layer, self.cl_group = float(cl_eps), float(cl_tau), cl_layer, cl_group
         self.in_batch_group = int(in_batch_group) if negatives == "in_batch" else None
         self.negatives, self.neg_power, self.logq_correction = negatives, float(neg_power), bool(logq_correction)
         if not self.table.is_cuda:
@@ -284,6 +307,12 @@ class LightGCNTrainer(_LightGCNTrainerBase):
                          else t.full((train.num_items,), -math.log(self.neg_range), dtype=t.float32, device=dev))
         self._sample_kw = (dict(n_neg=self.n_neg, table=self.neg_table) if self.neg_table is not None
                            else dict(quirk=self.quirk, n_neg=self.n_neg))
+        if self.cl_weight > 0.0:
+            # layer cl_layer of the perturbed forward (the backward's h_K when cl_layer == K); dL_cl/dX_{cl_layer}, all zero
+            # between steps: a step writes the batch's rows and zeroes them again; the two sides' losses
+            self.x_cl = t.empty_like(self.final)
+            self.g_cl = t.zeros_like(self.final)
+            self.cl_loss = t.zeros(2, device=dev)
 
     # -- pieces (also used one by one in tests) ------------------------------------------------
     def forward(self) -> Tensor:
@@ -315,6 +344,8 @@ class LightGCNTrainer(_LightGCNTrainerBase):
         batch = self._ids_to_training(batch)
         if self.sparse_batch:
             return self._step_sparse(batch)
+        if self.cl_weight > 0.0:
+            return self._step_contrastive(batch)
         K = self.K
         self.forward()
         users, pos, neg = batch if batch is not None else self._batch()
@@ -324,6 +355,47 @@ class LightGCNTrainer(_LightGCNTrainerBase):
         g0 = propagate_mean_backward(self.adj_bwd, self.gc, K, scratch=(self.buf_a, self.buf_b), pre_scaled=True)
         self.step_count += 1
         ops.adam_step(self.table, g0, self.m, self.v, reg_w=self.reg_w, **self._adam_kw(self.step_count))
+        return self.loss
+
+    def _step_contrastive(self, batch: Optional[Tuple[Tensor, Tensor, Tensor]]) -> Tensor:
+        """The dense step with the noise-view contrastive term: K products each followed by ops.perturb_rows (which also
+        folds the layer into `final`), the main loss as it is, the two contrast calls adding to its gradient buffer, and the
+        backward h_k = gc + A^T h_{k+1} with cl_weight * dL_cl/dX_l added at layer l = cl_layer."""
+        K, l, tab, c, w = self.K, self.cl_layer, self.table, 1.0 / (self.K + 1), self.cl_weight
+        users, pos, neg = batch if batch is not None else self._batch()
+        row_ids = self._old_of_new if self.order is not None else None
+        x = tab
+        for k in range(1, K + 1):
+            y = self.x_cl if k == l else self.bufs[k % 2]
+            ops.spmm(self.adj_fwd, x, Y=y)
+            ops.perturb_rows(y, eps=self.cl_eps, layer=k, seed=self.seed, step=self.step_count, row_ids=row_ids,
+                             addend=tab if k == 1 else self.final, S=self.final, scale=c if k == K else 1.0)
+            x = y
+        self.gc.zero_()
+        self.reg_w.zero_()
+        self._loss(users, pos, neg, self.final, g_final=self.gc, g_scale=c)
+        nodes = t.cat([users, pos + self.model.num_users])
+        B = users.numel()
+        for side in range(2):
+            ops.contrastive_fwd_bwd(nodes[side * B:(side + 1) * B], self.final, self.x_cl, tau=self.cl_tau, group=self.cl_group,
+                                    g_a=self.gc, g_b=self.g_cl, g_scale_a=w * c, g_scale_b=w, loss_out=self.cl_loss[side:side + 1])
+        self.loss.add_(self.cl_loss.sum(), alpha=w)
+
+        def add_layer_gradient(h):   # h[node] += g_cl[node] at the batch's nodes; a node named twice writes one value twice
+            h[nodes] = h[nodes] + self.g_cl[nodes]
+            self.g_cl[nodes] = 0.0
+        cur = self.gc
+        if l == K:                   # x_cl is free again: it holds h_K = gc + G
+            cur = self.x_cl.copy_(self.gc)
+            add_layer_gradient(cur)
+        for k in range(K - 1, -1, -1):
+            nxt = self.bufs[k % 2]
+            ops.spmm(self.adj_bwd, cur, addend=self.gc, S=nxt)
+            if k == l:
+                add_layer_gradient(nxt)
+            cur = nxt
+        self.step_count += 1
+        ops.adam_step(tab, cur, self.m, self.v, reg_w=self.reg_w, **self._adam_kw(self.step_count))
         return self.loss
 
     def _step_sparse(self, batch: Optional[Tuple[Tensor, Tensor, Tensor]]) -> Tensor:

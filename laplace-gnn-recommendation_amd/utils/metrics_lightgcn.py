@@ -178,6 +178,44 @@ def in_batch_softmax_loss(users_emb_final: Tensor, users_emb_0: Tensor, pos_item
                                    uinv, ufirst, iinv, ifirst, logq, group)
 
 
+class _ContrastiveFn(t.autograd.Function):
+    """contrastive_loss over gathered blocks through mi_contrastive_fwd_bwd_f32.  The entry knows a slot's node by the row
+    it reads, so the blocks become one table row per DISTINCT id, as in _InBatchSoftmaxFn: the gradient of an id comes back
+    whole at its first slot and zero at its other slots."""
+
+    @staticmethod
+    def forward(ctx, f_rows, x_rows, inv, first, tau: float, group: int):
+        a, b = f_rows[first].contiguous(), x_rows[first].contiguous()
+        g_a, g_b = t.zeros_like(a), t.zeros_like(b)
+        loss = ops.contrastive_fwd_bwd(inv, a, b, tau=tau, group=group, g_a=g_a, g_b=g_b)
+        ctx.save_for_backward(g_a, g_b, first)
+        ctx.B = f_rows.shape[0]
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        g_a, g_b, first = ctx.saved_tensors
+        outs = []
+        for g in (g_a, g_b):
+            full = g.new_zeros(ctx.B, g.shape[1])
+            full[first] = g * grad_out
+            outs.append(full)
+        return (*outs, None, None, None, None)
+
+
+def contrastive_loss(f_rows: Tensor, x_rows: Tensor, ids: Optional[Tensor], tau: float, group: int = 1024) -> Tensor:
+    """The noise-view contrastive term over gathered blocks: InfoNCE between the normalised rows f_rows[b] (the final
+    read-out of slot b's node) and x_rows[j] (layer l* of slot j's node) over groups of `group` consecutive slots at
+    temperature tau; another slot with slot b's id is left out of b's candidates (ids None: arange, no masks).  Slots with
+    equal ids must carry equal rows (blocks gathered from one table).  The rule is in include/laplace_hip.h."""
+    B = int(f_rows.shape[0])
+    if x_rows.shape != f_rows.shape:
+        raise ValueError(f"x_rows: shape {tuple(f_rows.shape)} expected, got {tuple(x_rows.shape)}")
+    ops.check_contrastive(int(f_rows.shape[1]), tau=tau, group=group)
+    inv, first = _first_slots(ids, B, f_rows.device)
+    return _ContrastiveFn.apply(f_rows, x_rows, inv, first, float(tau), group)
+
+
 class _FullSoftmaxFn(t.autograd.Function):
     """full_softmax_loss through mi_full_softmax_fwd_bwd_f32: the user block and the item table become one table whose user
     rows are the B slots (slot b is user b), and the positives' layer-0 rows go to their items' rows of a layer-0 table."""
