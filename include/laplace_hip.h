@@ -18,7 +18,8 @@
  *  - node / edge indices inside the library are int32 (n, nnz < 2^31 is checked);
  *    edge lists coming from the reference's tensors are int64 and converted once
  *    in mi_coo_to_csr_i32;
- *  - floating point is fp32 end to end (the reference's dtype); no reduced precision.
+ *  - floating point is fp32 end to end (the reference's dtype); no reduced precision.  (Opt-in exceptions, each with a
+ *    stated rule: top-K's bf16 prefilter, and the bf16 layer tables of the LightGCN forward at the end of this file.)
  */
 #ifndef LAPLACE_HIP_H
 #define LAPLACE_HIP_H
@@ -1706,6 +1707,63 @@ int    mi_pool_recent_f32(int64_t n_users, int32_t n_recent, int64_t d, const in
                           const float* w, const float* table, int64_t ld, float* q_out, int64_t ldq, mi_stream_t stream);
 int    mi_topk_merge_max_f32(int64_t n_q, int32_t n_lists, int32_t k_in, int32_t k_out, const int64_t* ids, const float* scores,
                              const int32_t* n_slots, const float* w, int64_t* out_ids, float* out_scores, mi_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
+ * bf16 layer tables of the LightGCN forward (opt-in: LightGCNTrainer(layer_dtype="bf16"); csrc/spmm_bf16.hip).
+ * LightGCN is linear: its backward never reads a forward activation.  A step may therefore keep the LAYERS of its forward in
+ * bf16 — every gathered row is then 2 d bytes instead of 4 d — and change nothing else: f32 master table, f32 read-out and
+ * loss, the f32 backward products, the f32 Adam.
+ *
+ * The rule.  rn = round to nearest even, f32 -> bf16.  K layers, c = 1 / (K + 1):
+ *   X_0      = rn(E0)                                                bf16 image of the f32 table, made once per step
+ *   acc_k[r] = sum over the entries p of row r of val[p] * float(X_{k-1}[col[p]])          f32, k = 1..K
+ *   X_k      = rn(acc_k)                                             stored in bf16 for k = 1..K-1 only; X_K is never stored
+ *   final    = c * (E0 + float(X_1) + ... + float(X_{K-1}) + acc_K)  f32, added in this order
+ * The read-out adds the STORED (rounded) layers and the unrounded last one, so that the dense step and the sparse-batch step,
+ * which can only re-read what was stored, compute the same value.
+ * Sums.  A short row (no plan, or at most plan->chunk entries) is ONE f32 chain acc = fmaf(val, x, acc) per output element, in
+ * list order, from 0.  A split row is one such chain per work item of the plan; the partial f32 rows go to the workspace and a
+ * fix-up adds them in a fixed order that depends on the row's slots alone (as in mi_spmm_csr_f32).  No float atomic anywhere;
+ * two runs give equal bits; the row-list form gives the dense form's bits on the listed rows (up to the sign of zero).
+ * Gradient.  The backward of a step that runs this forward is today's f32 one, that of the UNROUNDED linear map: the rounding is
+ * treated as the identity (straight-through).
+ *
+ * mi_rows_f32_to_bf16: dst[r, :] = rn(src[r, :]), one pass with the hardware's packed conversion.  d % 8 == 0; src / dst
+ *   16-byte aligned, ld_src a multiple of 4 floats, ld_dst a multiple of 8 elements, both >= d.  +-0 and +-inf map to
+ *   themselves, a finite value beyond the largest bf16 rounds to inf; NaN is outside the contract.
+ * mi_spmm_csr_bf16: the product above.  X and the optional Y are bf16 rows (uint16 bit patterns), val, addend and S f32:
+ *     if (Y) Y[r, :] = rn(acc)
+ *     if (S) S[r, :] = scale * ((addend ? addend[r, :] : 0) + (Y ? float(rn(acc)) : acc))
+ *   d % 8 == 0 and d <= 256; ldx / ldy multiples of 8 elements, lda / lds of 4 floats, all >= d; rows 16-byte aligned.  S may
+ *   alias addend; Y and S must not alias X.  A row is a sub-group of max(4, the power of two >= d / 8) lanes, a lane loads 16
+ *   bytes = 8 elements of a row and keeps 8 f32 sums: at d = 128 one wave-instruction fetches four neighbour rows.
+ *   row_list / n_list_dev / n_list: as in mi_spmm_ex (Y, S and addend compact by list position; needs plan->long_index when
+ *   the plan has split rows); rows at and beyond *n_list_dev are not written.  parts: 0 = the whole product, or a mask of
+ *   MI_SPMM_SHORT_ROWS / MI_SPMM_SPLIT_ROWS (disjoint output rows: the halves may run on two streams).
+ *   plan: null, or a WORK-ITEM plan as mi_spmm_plan_fill writes it (items in launch order, negative slots = padding, long_rows,
+ *   item_ptr, long_index).  epos / ecol / eval are not read: val comes from the CSR arrays for every entry, so a re-weighted
+ *   adjacency needs no copy refreshed.  ws: mi_spmm_workspace_bytes(plan, d).  The sweep form, thin rows and the hot, sliced
+ *   and persistent short-row launches do not exist here: do not pass a plan counted with thin rows or laid out as a sweep.
+ * mi_gather_rows_bf16_f32: dst[i, :] = (accumulate ? dst[i, :] : 0) + float(src[rows[i], :]) for i < min(n_max, n_dev ? *n_dev
+ *   : n_max) — the running layer sum at the batch's rows.  d % 8 == 0, alignments as above.
+ * Returned before anything is enqueued: MI_ERR_BAD_ARG (a width that is no multiple of 8, a null or misaligned pointer, a bad
+ *   leading dimension, Y or S on X, an unknown bit in parts, a plan with work items but without its arrays),
+ *   MI_ERR_UNSUPPORTED (mi_spmm_csr_bf16 with d > 256), MI_ERR_WORKSPACE (ws null or short), MI_ERR_TOO_LARGE (2^31 rows).
+ * ---------------------------------------------------------------------------------- */
+int mi_rows_f32_to_bf16(int64_t n_rows, int64_t d, const float* src, int64_t ld_src, uint16_t* dst, int64_t ld_dst,
+                        mi_stream_t stream);
+int mi_spmm_csr_bf16(int64_t n_rows, int64_t d,
+                     const int32_t* rowptr, const int32_t* col, const float* val,
+                     const uint16_t* X, int64_t ldx,
+                     uint16_t* Y, int64_t ldy,
+                     const float* addend, int64_t lda,
+                     float* S, int64_t lds, float scale,
+                     const mi_spmm_plan* plan,
+                     const int32_t* row_list, const int32_t* n_list_dev, int64_t n_list, int32_t parts,
+                     void* ws, size_t ws_bytes, mi_stream_t stream);
+int mi_gather_rows_bf16_f32(int64_t n_max, const int32_t* n_dev, int64_t d, const int32_t* rows,
+                            const uint16_t* src, int64_t ld_src, float* dst, int64_t ld_dst, int32_t accumulate,
+                            mi_stream_t stream);
 
 #ifdef __cplusplus
 }

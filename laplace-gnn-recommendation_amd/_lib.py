@@ -404,6 +404,10 @@ _PROTOTYPES = {
     "mi_recent_items": (c_int32, [c_int64, P, P, c_int32, P, P, P]),
     "mi_pool_recent_f32": (c_int32, [c_int64, c_int32, c_int64, P, P, P, P, c_int64, P, c_int64, P]),
     "mi_topk_merge_max_f32": (c_int32, [c_int64, c_int32, c_int32, c_int32, P, P, P, P, P, P, P]),
+    "mi_rows_f32_to_bf16": (c_int32, [c_int64, c_int64, P, c_int64, P, c_int64, P]),
+    "mi_spmm_csr_bf16": (c_int32, [c_int64, c_int64, P, P, P, P, c_int64, P, c_int64, P, c_int64, P, c_int64, c_float,
+                                   POINTER(SpmmPlanStruct), P, P, c_int64, c_int32, P, c_size_t, P]),
+    "mi_gather_rows_bf16_f32": (c_int32, [c_int64, P, c_int64, P, P, c_int64, P, c_int64, c_int32, P]),
 }
 
 _LIB = None

@@ -47,14 +47,18 @@ class ShardedLightGCNTrainer(_LightGCNTrainerBase):
     def __init__(self, model: LightGCN, train: Interactions, *, lr: float, Lambda: float, batch_size: int,
                  betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8, seed: int = 0,
                  neg_range: Optional[int] = None, group=None, ops_impl=None, sparse_batch: bool = True,
-                 reorder: Optional[bool] = None, objective: str = "reference", n_neg: int = 1):
+                 reorder: Optional[bool] = None, objective: str = "reference", n_neg: int = 1, layer_dtype: str = "f32"):
         """model: LightGCN(num_users = this rank's users, num_items = all items).  `train` holds this
         rank's edges with LOCAL user ids.  ops_impl: the kernel provider (default: the HIP ops;
         the CPU gloo tests inject an oracle-backed one — the product never does).
         reorder (default: on from 1M edges per rank, decided on the all-reduced total): train under the locality order (trainer.py) — the
         replicated items are ranked by their GLOBAL degree, so every rank numbers them alike; users are local anyway.
         objective / n_neg: the single-device trainer's (the same on every rank); anything but the default needs a provider
-        with rank_loss_fwd_bwd, sample_bpr_batch(n_neg=) and batch_nodes over neg [B, M]."""
+        with rank_loss_fwd_bwd, sample_bpr_batch(n_neg=) and batch_nodes over neg [B, M].
+        layer_dtype: "f32" only; the bf16 layer tables are the single-device trainer's."""
+        if layer_dtype != "f32":
+            raise ValueError(f'ShardedLightGCNTrainer keeps its layers in f32: layer_dtype={layer_dtype!r} is '
+                             "LightGCNTrainer's (single device)")
         super().__init__(model, ops_impl if ops_impl is not None else hip_ops, lr=lr, Lambda=Lambda, batch_size=batch_size,
                          betas=betas, eps=eps, seed=seed, sparse_batch=sparse_batch, objective=objective, n_neg=n_neg)
         self.group = group

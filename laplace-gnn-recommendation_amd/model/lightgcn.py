@@ -28,18 +28,59 @@ def _joint_view(a: Tensor, b: Tensor) -> Optional[Tensor]:
     return None
 
 
+LAYER_DTYPES = ("f32", "bf16")
+
+
+def check_layer_dtype(layer_dtype: str, d: int) -> None:
+    """ValueError for a name outside LAYER_DTYPES, and for a width bf16 layer tables do not take."""
+    if layer_dtype not in LAYER_DTYPES:
+        raise ValueError(f"layer_dtype must be one of {LAYER_DTYPES}, got {layer_dtype!r}")
+    if layer_dtype == "bf16":
+        ops.check_bf16_width(d)
+
+
+def _propagate_mean_bf16(adj: ops.DeviceCSR, e0: Tensor, K: int, final: Tensor, scratch) -> Tensor:
+    """The bf16-layer rule of include/laplace_hip.h: X_0 = rn(e0); X_k = rn(A X_{k-1}) stored for k < K; final =
+    c * (e0 + X_1 + ... + X_{K-1} + A X_{K-1}), the last product unrounded.  scratch: the bf16 tables (X_0, ping, pong);
+    K = 1 needs X_0 only."""
+    n, d = e0.shape
+    scale = 1.0 / (K + 1)
+
+    def table(i):
+        if scratch is not None and i < len(scratch) and scratch[i] is not None:
+            return scratch[i]
+        return t.empty(n, d, dtype=t.bfloat16, device=e0.device)
+    x = ops.rows_to_bf16(e0, out=table(0))
+    if K == 1:
+        ops.spmm_bf16(adj, x, addend=e0, S=final, scale=scale)
+        return final
+    pair = (table(1), table(2) if K > 2 else None)
+    for k in range(1, K):   # layers 1..K-1: X_k = rn(A X_{k-1}); S += float(X_k)
+        y = pair[(k - 1) % 2]
+        ops.spmm_bf16(adj, x, Y=y, addend=e0 if k == 1 else final, S=final, scale=1.0)
+        x = y
+    ops.spmm_bf16(adj, x, addend=final, S=final, scale=scale)   # layer K: no Y, its sum joins unrounded
+    return final
+
+
 def propagate_mean(adj: ops.DeviceCSR, e0: Tensor, num_iterations: int, out: Optional[Tensor] = None,
-                   scratch: Optional[Tuple[Tensor, Tensor]] = None) -> Tensor:
+                   scratch: Optional[Tuple[Tensor, ...]] = None, layer_dtype: str = "f32") -> Tensor:
     """final = mean_k(A^k e0), k = 0..K (model/lightgcn.py:58-68), K fused SpMM launches.
 
     The layer sum rides in the SpMM epilogue: no [N, K+1, D] stack, no separate mean pass.
+    layer_dtype="bf16" (opt-in): the layers are kept in bf16 under the rule of include/laplace_hip.h ("bf16 layer tables");
+    scratch is then up to three bf16 tables (X_0 and a ping-pong pair).  The default is the f32 path as it was.
     """
     K = int(num_iterations)
     n, d = e0.shape
+    if layer_dtype != "f32":
+        check_layer_dtype(layer_dtype, d)
     final = out if out is not None else t.empty_like(e0)
     if K == 0:
         final.copy_(e0)
         return final
+    if layer_dtype == "bf16":
+        return _propagate_mean_bf16(adj, e0, K, final, scratch)
     scale = 1.0 / (K + 1)
     if K == 1:
         ops.spmm(adj, e0, addend=e0, S=final, scale=scale)

@@ -184,6 +184,7 @@ class DeviceCSR:
     perm: Optional[Tensor] = None
     plan: Optional[SpmmPlan] = None
     hot: Optional[Tuple[int, int]] = None   # (first row, rows) of X worth an LDS cache in dense launches: see spmm()
+    plan_bf16: Optional[SpmmPlan] = None    # spmm_bf16's own work-item plan: `plan` and the f32 launches are untouched by it
 
     # Value generation: 0 for an adjacency whose `val` is the one it was built with, a process-wide fresh number after every
     # later assignment of `val` and every invalidate_values().  With the identity and _version of the tensor itself it is
@@ -790,6 +791,114 @@ def spmm(a: DeviceCSR, X: Tensor, *, Y: Optional[Tensor] = None, addend: Optiona
         ev[1].record()
         kind = "sparse" if (x_map is not None or row_list is not None) else ("dense_adam" if adam is not None else "dense")
         SPMM_EVENTS.append((ev[0], ev[1], kind, None, a.n_rows, a))
+
+
+BF16_MAX_D = 256   # mi_spmm_csr_bf16: a row is at most 32 lanes of 8 elements
+
+
+def check_bf16_width(d: int) -> None:
+    """ValueError unless rows of d elements can be bf16 layer tables (mi_spmm_csr_bf16: d % 8 == 0, d <= 256)."""
+    if d % 8 != 0:
+        raise ValueError(f"bf16 layer tables need a width that is a multiple of 8 (16-byte row pieces), got d = {d}")
+    if d > BF16_MAX_D:
+        raise ValueError(f"bf16 layer tables stop at d = {BF16_MAX_D}, got d = {d}")
+
+
+def _rows_ok_bf16(x: Tensor, name: str) -> int:
+    """Checks a 2-D bf16 row-major matrix with unit inner stride; returns its leading dimension in elements."""
+    _need(x, t.bfloat16, name, contiguous=False)
+    if x.dim() != 2 or (x.shape[1] > 1 and x.stride(1) != 1):
+        raise ValueError(f"{name}: expected a row-major 2-D matrix, got shape {tuple(x.shape)} strides {x.stride()}")
+    return x.stride(0) if x.shape[0] > 1 else max(x.shape[1], x.stride(0))
+
+
+def rows_to_bf16(src: Tensor, out: Optional[Tensor] = None) -> Tensor:
+    """The bf16 image of an f32 table, round to nearest even (mi_rows_f32_to_bf16); returns a torch.bfloat16 tensor."""
+    lds_ = _rows_ok(src, "src")
+    n, d = src.shape
+    if out is None:
+        out = t.empty(n, d, dtype=t.bfloat16, device=src.device)
+    ldo = _rows_ok_bf16(out, "out")
+    if tuple(out.shape) != (n, d):
+        raise ValueError(f"out must be [{n}, {d}], got {tuple(out.shape)}")
+    check(_lib.lib().mi_rows_f32_to_bf16(n, d, _ptr(src), lds_, _ptr(out), ldo, _stream()), "mi_rows_f32_to_bf16")
+    return out
+
+
+def spmm_bf16(a: DeviceCSR, X: Tensor, *, Y: Optional[Tensor] = None, addend: Optional[Tensor] = None,
+              S: Optional[Tensor] = None, scale: float = 1.0, row_list: Optional[Tensor] = None,
+              n_list_dev: Optional[Tensor] = None, plan: Optional[SpmmPlan] = None) -> None:
+    """acc = A @ float(X) in f32 from a bf16 operand (mi_spmm_csr_bf16; the rule is in include/laplace_hip.h, "bf16 layer
+    tables"): Y = rn(acc) in bf16 (optional); S = scale * (addend + (Y is given ? float(rn(acc)) : acc)) in f32 (optional).
+    row_list int32[n] (+ n_list_dev, device int32[1]): only these rows, Y / S / addend compact by list position.
+
+    plan=None uses a.plan_bf16, a slot of its own beside a.plan, built on first need under spmm's rule (nnz >= PLAN_MIN_NNZ
+    or a row list) as build_spmm_plan(a, sweep=False, thin_max=0): work items only, since this product has neither the sweep
+    form nor thin rows.  The f32 plan and its launches are untouched.  An explicit plan= (a work-item plan) overrides it.
+
+    SPMM_TWO_STREAMS: the short rows run on the side stream beside the work items and the fix-up, as in spmm; equal bits
+    either way.
+
+    Re-weighting: val is read from the CSR arrays for every entry (a packed plan's copies are not used), so a re-weighted
+    adjacency needs no _sync_plan_values here."""
+    if a.val is None:
+        raise ValueError("spmm_bf16 needs edge values (run gcn_norm or set val)")
+    _need(a.val, t.float32, "val")
+    ldx = _rows_ok_bf16(X, "X")
+    d = X.shape[1]
+    check_bf16_width(d)
+    if X.shape[0] != a.n_cols:
+        raise ValueError(f"X has {X.shape[0]} rows, adjacency has {a.n_cols} columns")
+    if row_list is not None:
+        _need(row_list, t.int32, "row_list")
+    if n_list_dev is not None:
+        _need(n_list_dev, t.int32, "n_list_dev")
+        if row_list is None:
+            raise ValueError("n_list_dev counts a row_list")
+    n_out = row_list.numel() if row_list is not None else a.n_rows
+    for name, m in (("Y", Y), ("S", S), ("addend", addend)):
+        if m is not None and (m.dim() != 2 or m.shape[0] != n_out or m.shape[1] != d):
+            raise ValueError(f"{name} must be [{n_out}, {d}], got {tuple(m.shape)}")
+    if Y is None and S is None:
+        raise ValueError("spmm_bf16 needs an output (Y and/or S)")
+    ldy = _rows_ok_bf16(Y, "Y") if Y is not None else 0
+    lda = _rows_ok(addend, "addend") if addend is not None else 0
+    lds = _rows_ok(S, "S") if S is not None else 0
+    if a.n_rows == 0 or n_out == 0:
+        return
+    if plan is None:
+        if a.plan_bf16 is None and (a.nnz >= PLAN_MIN_NNZ or row_list is not None):
+            a.plan_bf16 = build_spmm_plan(a, sweep=False, thin_max=0)
+            st = a.plan_bf16.struct   # the packed (col, val) copies are never read here: give their memory back
+            st.epos = st.ecol = st.eval = None
+            a.plan_bf16.packed, a.plan_bf16.values_of = (), ()
+        plan = a.plan_bf16
+    if plan is not None and (plan.sweep is not None or plan.n_thin_rows):
+        raise ValueError("spmm_bf16 takes a work-item plan: no sweep form, no thin rows")
+    L = _lib.lib()
+    ws_ptr, ws_bytes = None, 0
+    if plan is not None and plan.n_items > 0:
+        if d not in plan.partial:
+            plan.partial[d] = _ws(L.mi_spmm_workspace_bytes(ctypes.byref(plan.struct), d), a.device)
+        ws_ptr, ws_bytes = plan.partial[d].data_ptr(), plan.partial[d].numel()
+    col_ptr = _ptr(a.col) if a.nnz else a.rowptr.data_ptr()
+    val_ptr = _ptr(a.val) if a.nnz else a.rowptr.data_ptr()
+
+    def launch(parts: int, stream: int) -> None:
+        check(L.mi_spmm_csr_bf16(a.n_rows, d, _ptr(a.rowptr), col_ptr, val_ptr, X.data_ptr(), ldx, _ptr(Y), ldy,
+                                 _ptr(addend), lda, _ptr(S), lds, float(scale),
+                                 ctypes.byref(plan.struct) if plan is not None else None, _ptr(row_list), _ptr(n_list_dev),
+                                 n_out if row_list is not None else 0, parts, ws_ptr, ws_bytes, stream), "mi_spmm_csr_bf16")
+
+    if SPMM_TWO_STREAMS and plan is not None and plan.n_items > 0:
+        cur = t.cuda.current_stream()
+        side = _side_stream(a.device)
+        side.wait_stream(cur)
+        launch(_lib.MI_SPMM_SHORT_ROWS, side.cuda_stream)
+        launch(_lib.MI_SPMM_SPLIT_ROWS, cur.cuda_stream)
+        cur.wait_stream(side)
+    else:
+        launch(0, _stream())
 
 
 def expand_rows(a: DeviceCSR) -> Tensor:
@@ -1845,8 +1954,22 @@ def batch_nodes(users: Tensor, pos: Tensor, neg: Tensor, n_users: int, n_nodes: 
 
 def gather_rows(dst: Tensor, src: Tensor, rows: Tensor, n_dev: Optional[Tensor] = None, accumulate: bool = False,
                 scale: float = 1.0, begin_dev: Optional[Tensor] = None, row_offset: int = 0) -> None:
-    """dst[i] = scale * ((accumulate ? dst[i] : 0) + src[rows[i] - row_offset]) for i in [*begin_dev, *n_dev)."""
+    """dst[i] = scale * ((accumulate ? dst[i] : 0) + src[rows[i] - row_offset]) for i in [*begin_dev, *n_dev).
+    A bf16 src (a stored layer of the bf16 forward) is widened on the way: dst[i] = (accumulate ? dst[i] : 0) + float(src[rows[i]]),
+    mi_gather_rows_bf16_f32; scale, begin_dev and row_offset keep their defaults there."""
     _need(rows, t.int32, "rows")
+    if isinstance(src, Tensor) and src.dtype is t.bfloat16:
+        if scale != 1.0 or begin_dev is not None or row_offset != 0:
+            raise ValueError("gather_rows from a bf16 table takes no scale, begin_dev or row_offset")
+        lds_, ldd = _rows_ok_bf16(src, "src"), _rows_ok(dst, "dst")
+        if dst.shape[0] < rows.numel() or dst.shape[1] != src.shape[1]:
+            raise ValueError("dst must be [len(rows), d]")
+        if n_dev is not None:
+            _need(n_dev, t.int32, "n_dev")
+        check(_lib.lib().mi_gather_rows_bf16_f32(rows.numel(), _ptr(n_dev), src.shape[1], _ptr(rows), src.data_ptr(), lds_,
+                                                 dst.data_ptr(), ldd, 1 if accumulate else 0, _stream()),
+              "mi_gather_rows_bf16_f32")
+        return
     lds_, ldd = _rows_ok(src, "src"), _rows_ok(dst, "dst")
     if dst.shape[0] < rows.numel() or dst.shape[1] != src.shape[1]:
         raise ValueError("dst must be [len(rows), d]")

@@ -68,7 +68,8 @@ def train(config: LightGCNConfig = lightgcn_config, *, edge_index: Tensor, num_u
           verbose: bool = True, objective: str = "reference", n_neg: int = 1, predictor: str = "layer0",
           negatives: str = "uniform", neg_power: float = 0.75, in_batch_group: int = 1024,
           full_rank_ks: Optional[Tuple[int, ...]] = None, full_softmax: bool = False, cl_weight: float = 0.0,
-          cl_eps: float = 0.2, cl_tau: float = 0.15, cl_layer: int = 1, cl_group: int = 1024) -> Stats:
+          cl_eps: float = 0.2, cl_tau: float = 0.15, cl_layer: int = 1, cl_group: int = 1024,
+          layer_dtype: str = "f32") -> Stats:
     """objective / n_neg: the training loss (trainer.LightGCNTrainer).  predictor="propagated": evaluation,
     the ranking metrics and the saved predictions score with mean_k(A^k E0) of the training adjacency — the scores the
     loss trains — instead of the layer-0 tables.
@@ -80,6 +81,8 @@ def train(config: LightGCNConfig = lightgcn_config, *, edge_index: Tensor, num_u
     step form (sparse_batch=False is chosen here), also without the range and the quirk.
     cl_weight > 0: the noise-view contrastive term (LightGCNTrainer's cl_* keywords, passed through) is added to the training
     loss, in the dense step form (chosen here as well).
+    layer_dtype="bf16": the training step keeps the layers of its forward in bf16 (LightGCNTrainer's keyword, passed through);
+    evaluation and the saved predictions keep the f32 forward.
     evaluation() keeps its uniform negatives and uncorrected loss in every case, so
     validation and test losses stay comparable across samplers.
     full_rank_ks: when given, the test split is also scored by evaluation_full_rank at these K (same predictor, same
@@ -108,7 +111,7 @@ def train(config: LightGCNConfig = lightgcn_config, *, edge_index: Tensor, num_u
                               neg_range=None if popular else int(train_edges[1].max()),
                               reference_sampler_quirks=(compat == "reference" and not popular), objective=objective,
                               n_neg=n_neg, negatives=negatives, neg_power=neg_power, in_batch_group=in_batch_group,
-                              **exact)
+                              layer_dtype=layer_dtype, **exact)
 
     def scoring_tables():
         return propagated_embeddings(model, train_sparse) if predictor == "propagated" else None

@@ -62,7 +62,7 @@ from torch import Tensor
 
 from . import ops
 from .interactions import Interactions
-from .model.lightgcn import LightGCN, propagate_mean, propagate_mean_backward
+from .model.lightgcn import LightGCN, check_layer_dtype, propagate_mean, propagate_mean_backward
 from .sparse import SparseTensor
 
 
@@ -188,7 +188,8 @@ class LightGCNTrainer(_LightGCNTrainerBase):
                  sparse_batch: bool = True, fuse_adam: bool = True, reorder: Optional[bool] = None,
                  objective: str = "reference", n_neg: int = 1, negatives: str = "uniform", neg_power: float = 0.75,
                  logq_correction: Optional[bool] = None, in_batch_group: int = 1024, full_softmax: bool = False,
-                 cl_weight: float = 0.0, cl_eps: float = 0.2, cl_tau: float = 0.15, cl_layer: int = 1, cl_group: int = 1024):
+                 cl_weight: float = 0.0, cl_eps: float = 0.2, cl_tau: float = 0.15, cl_layer: int = 1, cl_group: int = 1024,
+                 layer_dtype: str = "f32"):
         """negatives="popularity": negatives drawn ∝ (training degree) ** neg_power from `neg_table`, built in the id space
         the kernels train in.  logq_correction: the softmax's logits become s - log q(item); None = on iff
         objective == "softmax" and negatives != "uniform".  The defaults launch the step as it was.
@@ -208,7 +209,14 @@ class LightGCNTrainer(_LightGCNTrainerBase):
         batch's user nodes and positive item nodes are each contrasted, final read-out against layer cl_layer (1..K), at
         temperature cl_tau in groups of cl_group consecutive slots (a multiple of 32 in 32..4096).  The rule is in
         include/laplace_hip.h, "Noise-view contrastive term".  forward(), evaluation and serving stay unperturbed; cl_weight = 0
-        (the default) launches the step as it was."""
+        (the default) launches the step as it was.
+        layer_dtype="bf16" (opt-in mixed precision; d % 8 == 0, d <= 256, cl_weight = 0): the layers of the step's forward are
+        kept in bf16 under the rule of include/laplace_hip.h, "bf16 layer tables" — X_0 = rn(table), X_k = rn(A X_{k-1}) for
+        k < K, read-out c * (E0 + X_1 + ... + X_{K-1} + A X_{K-1}) in f32.  The master table, the loss, the backward products
+        (those of the unrounded linear map: the rounding is treated as the identity) and Adam stay f32.  Both step forms, every
+        objective, n_neg, negatives, full_softmax and reorder.  forward() keeps returning the f32 forward, so evaluation and
+        serving do not change; forward(layer_dtype="bf16") returns what the step trains on.  "f32" (the default) launches the
+        step as it was."""
         super().__init__(model, ops, lr=lr, Lambda=Lambda, batch_size=batch_size, betas=betas, eps=eps, seed=seed,
                          sparse_batch=sparse_batch, objective=objective, n_neg=n_neg)
         if negatives not in NEGATIVES:
@@ -263,6 +271,10 @@ class LightGCNTrainer(_LightGCNTrainerBase):
             if sparse_batch:
                 raise ValueError("cl_weight > 0 perturbs whole layers, the dense step: pass sparse_batch=False")
             self.cl_eps, self.cl_tau, self.cl_layer, self.cl_group = float(cl_eps), float(cl_tau), cl_layer, cl_group
+        check_layer_dtype(layer_dtype, model.embedding_dim)
+        if layer_dtype == "bf16" and self.cl_weight > 0.0:
+            raise ValueError('layer_dtype="bf16" does not combine with cl_weight > 0: the perturbation kernel is f32')
+        self.layer_dtype = layer_dtype
         self.in_batch_group = int(in_batch_group) if negatives == "in_batch" else None
         self.negatives, self.neg_power, self.logq_correction = negatives, float(neg_power), bool(logq_correction)
         if not self.table.is_cuda:
@@ -313,11 +325,21 @@ class LightGCNTrainer(_LightGCNTrainerBase):
             self.x_cl = t.empty_like(self.final)
             self.g_cl = t.zeros_like(self.final)
             self.cl_loss = t.zeros(2, device=dev)
+        # bf16 layer tables beside the f32 buffers the backward keeps: X_0 and a ping-pong pair; K <= 1 stores no layer
+        self.x_bf16 = ()
+        if self.layer_dtype == "bf16":
+            n_tab = 0 if self.K == 0 else min(self.K, 3)
+            self.x_bf16 = tuple(t.empty(self.table.shape, dtype=t.bfloat16, device=dev) for _ in range(n_tab))
 
     # -- pieces (also used one by one in tests) ------------------------------------------------
-    def forward(self) -> Tensor:
-        """mean_k(A^k E0) over the whole table; rows in TRAINING order (index with order.node_new_of_old())."""
+    def forward(self, layer_dtype: str = "f32") -> Tensor:
+        """mean_k(A^k E0) over the whole table; rows in TRAINING order (index with order.node_new_of_old()).  The f32 forward
+        whatever the trainer's layer_dtype (evaluation, serving); layer_dtype="bf16" = the forward a bf16 step trains on."""
         self.to_training_order()
+        if layer_dtype != "f32":
+            check_layer_dtype(layer_dtype, self.table.shape[1])
+            return propagate_mean(self.adj_fwd, self.table, self.K, out=self.final, scratch=self.x_bf16 or None,
+                                  layer_dtype=layer_dtype)
         return propagate_mean(self.adj_fwd, self.table, self.K, out=self.final, scratch=(self.buf_a, self.buf_b))
 
     def _loss(self, users, pos, neg, final, **kw) -> None:
@@ -347,7 +369,7 @@ class LightGCNTrainer(_LightGCNTrainerBase):
         if self.cl_weight > 0.0:
             return self._step_contrastive(batch)
         K = self.K
-        self.forward()
+        self.forward(self.layer_dtype)
         users, pos, neg = batch if batch is not None else self._batch()
         self.gc.zero_()
         self.reg_w.zero_()
@@ -411,13 +433,17 @@ class LightGCNTrainer(_LightGCNTrainerBase):
         ops.gather_rows(self.sum_c, tab, nodes, cnt)                      # S_c = E0[batch rows]
         x = tab
         bufs = (self.buf_a, self.buf_b)
+        bf16 = self.layer_dtype == "bf16" and K >= 1
+        spmm = ops.spmm_bf16 if bf16 else ops.spmm
+        if bf16:                                                          # X_0 = rn(E0); the layers ping-pong in bf16
+            x = ops.rows_to_bf16(tab, out=self.x_bf16[0])
         for k in range(1, K):                                             # layers 1..K-1: plain products
-            y = bufs[(k - 1) % 2]
-            ops.spmm(adj, x, Y=y)
+            y = self.x_bf16[1 + (k - 1) % 2] if bf16 else bufs[(k - 1) % 2]
+            spmm(adj, x, Y=y)
             ops.gather_rows(self.sum_c, y, nodes, cnt, accumulate=True)   # S_c += X_k[batch rows]
             x = y
         if K >= 1:                                                        # layer K at the batch rows only
-            ops.spmm(adj, x, addend=self.sum_c, S=self.final_c, scale=c, row_list=nodes, n_list_dev=cnt)
+            spmm(adj, x, addend=self.sum_c, S=self.final_c, scale=c, row_list=nodes, n_list_dev=cnt)
             final_c = self.final_c
         else:
             final_c = self.sum_c
