@@ -1193,6 +1193,59 @@ int    mi_match_cooc_i32(int64_t n_queries, const int64_t* query_users,
                          void* ws, size_t ws_bytes, mi_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
+ * N3c random-walk matcher: Pixie-style candidates for a user, by walking from the items they hold
+ *      (additive to ABI 14; csrc/walk_match.hip).
+ * replaces: nothing.  The reference's two walks keep the first k entries of an unscored expansion;
+ *           mi_pinsage_neighbors / mi_pinsage_hard_negatives walk from ONE item.  This walks from a
+ *           user's recent items, counts where the walks end and ranks by the counts.  It needs no
+ *           training and no table: an edge counts the moment it is in the two CSRs.
+ * Inputs: iu_ptr / iu_idx (item -> users) and ui_ptr / ui_idx (user -> items) as int32 CSR on device,
+ * transposes of one another, user rows in transaction order.  ui_sorted: a copy of ui_idx with every
+ * row sorted by item id (read only with exclude_seen; null otherwise).
+ *
+ * The rule for query user u at (seed, step), restated in numpy by tests/random_walk_matcher_emulation.py:
+ *   slots     the history rule of the recent-items recommender (N5 below): the last min(len, 64)
+ *             entries of row u, most recent first, an entry dropped when a more recent position holds
+ *             its item; the first n_recent survivors are slots 0 .. R - 1, 1 <= n_recent <=
+ *             MI_RECENT_MAX_SLOTS.  An empty row (or an id outside [0, n_users)) has R = 0 and gets no
+ *             proposal: ids -1, scores 0, count 0.  That is not an error.
+ *   walks     num_walks walks; walk w starts at the item of slot w % R and makes at most walk_length
+ *             item -> user -> item traversals under mi_pinsage_neighbors' law.  Traversal t of walk w
+ *             draws x = Philox(purpose 17, a = w * walk_length + t, b = 0, c = u, seed, step) in the
+ *             PinSAGE counter layout.  Before every traversal but the first the walk ends if
+ *             x.c[2] < (uint32)(restart_prob * 2^32); otherwise the hop takes user
+ *             iu[item][x.c[0] % len] and item ui[user][x.c[1] % len]; a walk that meets an item
+ *             without users ends.  The draws are keyed on the user id, not on the query position: a
+ *             user's answer does not depend on who else is queried, or in which order.
+ *   counts    c[r][i] = number of traversal ends at item i among the walks of slot r.
+ *   eligible  exclude_seen != 0 drops every item of u's WHOLE row (not only the slots); 0 drops nothing.
+ *   score     MI_WALK_BOOST_SUM: s(i) = sum_r c[r][i], an integer <= 4096, exact in float.
+ *             MI_WALK_BOOST_MULTI_HIT (Pixie's booster): s(i) = (sum_r sqrt(c[r][i]))^2 in float over
+ *             the slots with c > 0 in ascending r: every root the correctly rounded float root, every
+ *             addition (from 0) and the final multiply rounded once, no contraction.
+ *   answer    the k best eligible items with s > 0 by (s descending, id ascending).  out_ids
+ *             int32[n, k], -1 padded; out_scores float[n, k] (nullable), 0 padded; out_count int32[n]
+ *             (nullable): the distinct eligible items visited, before the cut to k.
+ * One workgroup per query; visits are sorted in LDS: num_walks * walk_length <=
+ * MI_WALK_MATCH_MAX_VISITS, beyond that MI_ERR_UNSUPPORTED.  n_items < 2^31 - 1 (MI_ERR_TOO_LARGE).
+ * MI_ERR_BAD_ARG: num_walks, walk_length or k <= 0, restart_prob outside [0, 1), n_recent outside
+ * 1 .. MI_RECENT_MAX_SLOTS, an unknown boost, a negative count, a null or misaligned pointer.  All of
+ * these are returned before anything is enqueued; zero queries return 0 with nothing enqueued.
+ * query_users int64[n] (null = users 0 .. n - 1; any order, repeats allowed).  No float atomics, no
+ * global scratch, one writer per output: two calls give equal bits.
+ * ---------------------------------------------------------------------------------- */
+#define MI_WALK_BOOST_SUM        0
+#define MI_WALK_BOOST_MULTI_HIT  1
+#define MI_WALK_MATCH_MAX_VISITS 4096
+int    mi_match_random_walks_i32(int64_t n_queries, const int64_t* query_users, int64_t n_users, int64_t n_items,
+                                 const int32_t* iu_ptr, const int32_t* iu_idx,
+                                 const int32_t* ui_ptr, const int32_t* ui_idx, const int32_t* ui_sorted,
+                                 int32_t k, int32_t num_walks, int32_t walk_length, double restart_prob,
+                                 int32_t n_recent, int32_t boost, int32_t exclude_seen,
+                                 uint64_t seed, uint64_t step,
+                                 int32_t* out_ids, float* out_scores, int32_t* out_count, mi_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
  * N1  on-device N-hop subgraph sampler for the ranker.
  * replaces: GraphDataset.__getitem__ + helpers (data/dataset.py:39-309, train mode) for a whole
  *           batch of seed users, and the PyG collate of the resulting HeteroData items

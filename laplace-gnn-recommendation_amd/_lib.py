@@ -64,6 +64,8 @@ MI_RANK_PATH_MATERIALISED, MI_RANK_PATH_FUSED = range(2)
 MI_RANK_OBJECTIVES ={"reference": 0, "bpr": 1, "softmax": 2}
 MI_RANK_MAX_NEG = 16
 MI_COOC_WEIGHTINGS = {"count": 0, "cosine": 1}
+MI_WALK_BOOSTS = {"sum": 0, "multi_hit": 1}   # mi_match_random_walks_i32: MI_WALK_BOOST_*
+MI_WALK_MATCH_MAX_VISITS = 4096              # mi_match_random_walks_i32: num_walks * walk_length
 
 
 class GemmProblem(Structure):
@@ -351,6 +353,8 @@ _PROTOTYPES = {
     "mi_cooc_items_topt": (c_int32, [c_int64, c_int64, c_int64, P, P, P, P, c_int32, c_int32, P, P, P, P, c_size_t, P]),
     "mi_match_cooc_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int32]),
     "mi_match_cooc_i32": (c_int32, [c_int64, P, P, P, c_int64, c_int32, P, P, c_int32, c_int32, c_int32, P, P, P, P, c_size_t, P]),
+    "mi_match_random_walks_i32": (c_int32, [c_int64, P, c_int64, c_int64, P, P, P, P, P, c_int32, c_int32, c_int32, c_double,
+                                            c_int32, c_int32, c_int32, c_uint64, c_uint64, P, P, P, P]),
     "mi_sampler_workspace_bytes": (c_size_t, [POINTER(SamplerDesc)]),
     "mi_sampler_count": (c_int32, [POINTER(SamplerDesc), P, c_uint64, c_uint64, P, c_size_t, POINTER(c_int64), P]),
     "mi_sampler_count_async": (c_int32, [POINTER(SamplerDesc), P, c_uint64, c_uint64, P, c_size_t, P, P]),

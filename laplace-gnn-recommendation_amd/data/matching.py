@@ -21,6 +21,15 @@ the reference materialises every article of every co-purchasing user and then ke
                                (csrc/cooccurrence.hip); the host get_matches restates the definitions in NumPy and is the
                                checker (tests/test_cooccurrence_cpu.py, tests/test_gpu_cooccurrence.py)
 
+  RandomWalkMatcher            NO reference counterpart — Pixie-style candidates: walks of item -> user -> item traversals
+                               from the user's last n_recent distinct items (PinSAGE's walk law and Philox draws, keyed on
+                               the user id), visit counts per start slot, score = their sum or Pixie's multi-hit boost
+                               (sum_r sqrt(c_r))^2, the k best by (score desc, id asc), optionally without the items the
+                               user already has.  No training and no table: an edge counts the moment it is in the
+                               adjacency.  Device only: mi_match_random_walks_i32 (csrc/walk_match.hip); the checker is the
+                               numpy mirror tests/random_walk_matcher_emulation.py (tests/test_random_walk_matcher_cpu.py,
+                               tests/test_gpu_random_walk_matcher.py)
+
 The first four are pinned against the reference's own classes: tests/golden/matchers.pt (tests/make_golden.py runs them on
 small dict-of-list files) — host forms in tests/test_oracle_golden.py, device forms in tests/test_gpu_matching.py.
 
@@ -267,6 +276,68 @@ class ItemCooccurrenceMatcher(Matcher):
                                                  query_users=query_users, n_recent=self.n_recent,
                                                  exclude_seen=self.exclude_seen, max_list_len=longest)
         return (out.to(t.int64), score, cnt) if with_scores else out.to(t.int64)
+
+
+class RandomWalkMatcher(Matcher):
+    """Random-walk (Pixie-style) candidates (include/laplace_hip.h, N3c, states the rule): num_walks walks of at most
+    walk_length item -> user -> item traversals start at the user's last n_recent distinct items, an item's score is its
+    visit count ("sum") or Pixie's multi-hit boost (sum_r sqrt(c_r))^2 over the start slots r ("multi_hit"), the k best by
+    (score desc, id asc) are the proposals.  Nothing is trained and no table is built: the walks read the two adjacency
+    lists, so an edge counts the moment it is in them, and the answer is a pure function of (graph, user, seed).
+
+    The defaults are NOT tuned: they are the middle of the settings a numpy rehearsal tried, not the result of a search.
+    Not in get_matchers: the reference has no such matcher, callers add it to their list themselves.
+
+    There is no host form: the product may not import the test mirror (tests/random_walk_matcher_emulation.py), so
+    get_matches and matches_for_all run the device call (get_matches for ONE query user, on the current GPU)."""
+
+    def __init__(self, users_adj, articles_adj, k: int, *, num_walks: int = 256, walk_length: int = 4, restart_prob: float = 0.5,
+                 n_recent: int = 8, boost: str = "multi_hit", exclude_seen: bool = False, seed: int = 0):
+        from .. import ops
+        ops.check_random_walks(k, num_walks, walk_length, restart_prob, n_recent, boost)
+        if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 2 ** 64:
+            raise ValueError(f"seed must be an integer in [0, 2^64), got {seed!r}")
+        self.users = users_adj if isinstance(users_adj, AdjList) else AdjList(users_adj)
+        self.articles = articles_adj if isinstance(articles_adj, AdjList) else AdjList(articles_adj)
+        self.k, self.num_walks, self.walk_length = int(k), int(num_walks), int(walk_length)
+        self.restart_prob, self.n_recent, self.boost = float(restart_prob), int(n_recent), boost
+        self.exclude_seen, self.seed = bool(exclude_seen), int(seed)
+        self._dev = None      # (articles_ptr, articles_idx, users_ptr, users_idx) on one device
+        self._sorted = None   # the users' rows sorted by item id, on that device (exclude_seen only)
+
+    def _on(self, device):
+        from .. import ops
+        dev = t.device(device)
+        if dev.type == "cuda" and dev.index is None:       # "cuda" and "cuda:0" are the same place: compare normalised devices
+            dev = t.device("cuda", t.cuda.current_device())
+        if self._dev is None or self._dev[0].device != dev:
+            to32 = lambda a: t.from_numpy(np.ascontiguousarray(a.astype(np.int32))).to(dev)
+            self._dev = (to32(self.articles.ptr), to32(self.articles.idx), to32(self.users.ptr), to32(self.users.idx))
+            self._sorted = ops.sort_csr_rows(self._dev[2], self._dev[3]) if self.exclude_seen else None
+        return self._dev, self._sorted
+
+    def matches_for_all_device(self, num_users: int, device, query_users=None, with_scores: bool = False):
+        """int64 [n, k] with -1 pads for users 0 .. num_users - 1, or for query_users (ids, any order, repeats allowed) when
+        given; with_scores: (ids, scores float32 [n, k] with 0 pads, counts int32 [n])."""
+        from .. import ops
+        if not 0 <= int(num_users) <= len(self.users):
+            raise ValueError(f"num_users = {num_users} query users but the purchase lists cover {len(self.users)}")
+        dev, ui_sorted = self._on(device)
+        out, score, cnt = ops.match_random_walks(*dev, self.k, num_walks=self.num_walks, walk_length=self.walk_length,
+                                                 restart_prob=self.restart_prob, n_recent=self.n_recent, boost=self.boost,
+                                                 exclude_seen=self.exclude_seen, seed=self.seed, n_queries=int(num_users),
+                                                 query_users=query_users, ui_sorted=ui_sorted)
+        return (out.to(t.int64), score, cnt) if with_scores else out.to(t.int64)
+
+    def matches_for_all(self, num_users: int):
+        return self.matches_for_all_device(num_users, "cuda").cpu().numpy()
+
+    def get_matches(self, user_id: int) -> Tensor:
+        """The device call for this one user (there is no host form, see the class): needs a GPU."""
+        if isinstance(user_id, bool) or not isinstance(user_id, (int, np.integer)) or not 0 <= int(user_id) < len(self.users):
+            raise ValueError(f"user_id must be an integer in [0, {len(self.users)}), got {user_id!r}")
+        row = self.matches_for_all_device(1, "cuda", query_users=[int(user_id)])[0].cpu()
+        return row[row >= 0]
 
 
 def get_matchers(dataset_type: str, users_adj, articles_adj, candidate_pool_size: int) -> List[Matcher]:

@@ -8,6 +8,7 @@ from __future__ import annotations
 import ctypes
 import itertools
 import math
+import numbers
 import os
 from os import environ as _os_environ
 from dataclasses import dataclass, field
@@ -1786,6 +1787,89 @@ def match_cooccurrence(users_ptr: Tensor, users_idx: Tensor, nbr_id: Tensor, nbr
                               _ptr(nbr_id), _ptr(nbr_score), k, int(n_recent or 0), int(bool(exclude_seen)),
                               _ptr(out), _ptr(score), _ptr(cnt), ws.data_ptr(), ws.numel(), _stream()), "mi_match_cooc_i32")
     return out, score, cnt
+
+
+def check_random_walks(k, num_walks, walk_length, restart_prob, n_recent, boost) -> None:
+    """The argument rules of the random-walk matcher (include/laplace_hip.h, N3c): ValueError naming the argument.  Needs no
+    device; ops.match_random_walks, data.matching.RandomWalkMatcher and pinsage.evaluation.RandomWalkRecommender share it."""
+    for name, v in (("k", k), ("num_walks", num_walks), ("walk_length", walk_length)):
+        if isinstance(v, bool) or not isinstance(v, numbers.Integral) or v <= 0:
+            raise ValueError(f"{name} must be a positive integer, got {v!r}")
+    if isinstance(n_recent, bool) or not isinstance(n_recent, numbers.Integral) or not 1 <= n_recent <= _lib.MI_RECENT_MAX_SLOTS:
+        raise ValueError(f"n_recent must be an integer in 1 .. {_lib.MI_RECENT_MAX_SLOTS}, got {n_recent!r}")
+    try:
+        ok = 0.0 <= float(restart_prob) < 1.0     # NaN fails both comparisons
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f"restart_prob must be in [0, 1), got {restart_prob!r}")
+    if boost not in _lib.MI_WALK_BOOSTS:
+        raise ValueError(f"boost must be one of {sorted(_lib.MI_WALK_BOOSTS)}, got {boost!r}")
+    if num_walks * walk_length > _lib.MI_WALK_MATCH_MAX_VISITS:
+        raise ValueError(f"num_walks * walk_length = {num_walks * walk_length} is above the {_lib.MI_WALK_MATCH_MAX_VISITS} "
+                         "visits one workgroup sorts")
+
+
+def sort_csr_rows(ptr: Tensor, idx: Tensor) -> Tensor:
+    """A copy of idx with every row of the int32 CSR (ptr, idx) sorted ascending: the table in which the random-walk matcher
+    looks an item up with exclude_seen.  Built once per graph by its callers; row order itself stays the recency order."""
+    _need(ptr, t.int32, "ptr")
+    _need(idx, t.int32, "idx")
+    rows = t.repeat_interleave(t.arange(ptr.numel() - 1, device=ptr.device), (ptr[1:] - ptr[:-1]).long())
+    return (t.sort((rows << 31) | idx.long())[0] & 0x7FFFFFFF).to(t.int32)
+
+
+def match_random_walks(iu_ptr: Tensor, iu_idx: Tensor, ui_ptr: Tensor, ui_idx: Tensor, k: int, *, num_walks: int, walk_length: int,
+                       restart_prob: float, n_recent: int, boost: str, exclude_seen: bool, seed: int, step: int = 0,
+                       n_queries: Optional[int] = None, query_users=None, ui_sorted: Optional[Tensor] = None):
+    """N3c — random-walk (Pixie-style) candidates for many users at once: (ids int32[n, k] with -1 pads, scores float32[n, k]
+    with 0 pads, counts int32[n] = distinct eligible items visited).  iu_*: item -> users, ui_*: user -> items in transaction
+    order.  The rule is stated in include/laplace_hip.h; the draws are keyed on the user id, so a user's row is the same
+    whoever else is queried.  query_users: int64 ids, any order, repeats allowed — a device tensor is taken as it is (an id
+    outside the graph gets no proposal), ids on the host (list, array, CPU tensor) are checked and refused with ValueError.
+    ui_sorted: ops.sort_csr_rows(ui_ptr, ui_idx), built here when exclude_seen needs it and the caller keeps none."""
+    check_random_walks(k, num_walks, walk_length, restart_prob, n_recent, boost)
+    if not 0 <= int(seed) < 2 ** 64 or not 0 <= int(step) < 2 ** 64:
+        raise ValueError(f"seed and step must fit 64 unsigned bits, got {seed!r}, {step!r}")
+    n_users = ui_ptr.numel() - 1
+    if n_users < 0 or iu_ptr.numel() < 1:
+        raise ValueError("ui_ptr and iu_ptr need n + 1 entries")
+    if query_users is not None and not (isinstance(query_users, Tensor) and query_users.is_cuda):
+        q = t.as_tensor(query_users).reshape(-1).to(t.int64)
+        if q.numel() and (int(q.min()) < 0 or int(q.max()) >= n_users):
+            raise ValueError(f"query_users must lie in [0, {n_users}), got ids from {int(q.min())} to {int(q.max())}")
+        query_users = q.to(ui_ptr.device)
+    if query_users is not None:
+        n_queries = query_users.numel()
+    elif n_queries is None:
+        n_queries = n_users
+    elif not 0 <= int(n_queries) <= n_users:
+        raise ValueError(f"n_queries must lie in 0 .. {n_users}, got {n_queries!r}")
+    for n, x in (("iu_ptr", iu_ptr), ("iu_idx", iu_idx), ("ui_ptr", ui_ptr), ("ui_idx", ui_idx)):
+        _need(x, t.int32, n)
+    if query_users is not None:
+        _need(query_users, t.int64, "query_users")
+    if iu_idx.numel() != ui_idx.numel():
+        raise ValueError("iu_idx and ui_idx must list the same edges")
+    if exclude_seen and ui_sorted is None:
+        ui_sorted = sort_csr_rows(ui_ptr, ui_idx)
+    if exclude_seen:
+        _need(ui_sorted, t.int32, "ui_sorted")
+        if ui_sorted.numel() != ui_idx.numel():
+            raise ValueError("ui_sorted must be ui_idx with every row sorted")
+    n_queries, k, dev = int(n_queries), int(k), ui_ptr.device
+    ids = t.empty(n_queries, k, dtype=t.int32, device=dev)
+    scores = t.empty(n_queries, k, dtype=t.float32, device=dev)
+    counts = t.empty(n_queries, dtype=t.int32, device=dev)
+    if n_queries and ui_idx.numel() == 0:   # nobody holds anything: nothing to propose
+        return ids.fill_(-1), scores.zero_(), counts.zero_()
+    check(_lib.lib().mi_match_random_walks_i32(n_queries, _ptr(query_users), n_users, iu_ptr.numel() - 1, iu_ptr.data_ptr(),
+                                               _ptr(iu_idx), ui_ptr.data_ptr(), _ptr(ui_idx),
+                                               _ptr(ui_sorted) if exclude_seen else None, k, int(num_walks), int(walk_length),
+                                               float(restart_prob), int(n_recent), _lib.MI_WALK_BOOSTS[boost],
+                                               int(bool(exclude_seen)), int(seed), int(step), _ptr(ids), _ptr(scores),
+                                               _ptr(counts), _stream()), "mi_match_random_walks_i32")
+    return ids, scores, counts
 
 
 _BN_WS = {}

@@ -1,7 +1,8 @@
 """PinSAGE evaluation — reference: pinsage/evaluation.py (LatestNNRecommender, prec, evaluate_nn) and the evaluation half of
 pinsage/model.py:120-134.  The graph is the port's user -> item CSR (an AdjList, a PinSAGESampler's ui_ptr / ui_idx, or a
 (ptr, idx) pair) instead of a DGL graph; the scoring is K10 (ops.topk_excl: exact top-K with per-user exclusion).
-RecentItemsRecommender is the port's own: a user's last few distinct items instead of the latest one."""
+RecentItemsRecommender is the port's own: a user's last few distinct items instead of the latest one.  RandomWalkRecommender,
+also the port's own, ignores the embeddings and recommends from random walks over the graph: the graph-only yardstick."""
 from __future__ import annotations
 
 from typing import Optional, Tuple
@@ -144,6 +145,54 @@ class RecentItemsRecommender:
             out_ids = t.cat([o[0] for o in outs]) if outs else t.empty(0, K, dtype=t.int64, device=h.device)
             out_sc = t.cat([o[1] for o in outs]) if outs else t.empty(0, K, dtype=t.float32, device=h.device)
         return (out_ids, out_sc) if want_scores else out_ids
+
+
+class RandomWalkRecommender:
+    """The graph-only yardstick of evaluate_nn: recommendations from random walks over the interaction graph alone (the
+    random-walk matcher of include/laplace_hip.h, N3c, with the user's row excluded), behind LatestNNRecommender's contract.
+    The embeddings are IGNORED — h_item only says how many items there are and where to compute — so
+    evaluate_nn(..., recommender=RandomWalkRecommender(...)) is the hits@K a trained model has to beat on the same graph.
+
+    The arguments are data.matching.RandomWalkMatcher's, with the same untuned defaults.  A graph that carries its item ->
+    user lists (a PinSAGESampler: iu_ptr / iu_idx) is walked over them as they are; for any other form (AdjList, scipy,
+    (ptr, idx)) they are derived here, the users of an item in (user id, row position) order.  Which user a draw picks
+    depends on that order, so the two forms are two equally valid answers, each reproducible bit for bit."""
+
+    def __init__(self, num_walks: int = 256, walk_length: int = 4, restart_prob: float = 0.5, n_recent: int = 8,
+                 boost: str = "multi_hit", seed: int = 0):
+        ops.check_random_walks(1, num_walks, walk_length, restart_prob, n_recent, boost)
+        if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 2 ** 64:
+            raise ValueError(f"seed must be an integer in [0, 2^64), got {seed!r}")
+        self.num_walks, self.walk_length, self.restart_prob = int(num_walks), int(walk_length), float(restart_prob)
+        self.n_recent, self.boost, self.seed = int(n_recent), boost, int(seed)
+
+    def recommend(self, graph, K: int, h_user: Optional[Tensor], h_item: Tensor) -> Tensor:
+        """LongTensor [n_users, K] of item ids by (walk score desc, id asc), the user's row excluded, -1 pads.  h_user and the
+        values of h_item are unused.  A user without any interaction raises ValueError."""
+        ops.check_random_walks(K, self.num_walks, self.walk_length, self.restart_prob, self.n_recent, self.boost)
+        if not isinstance(h_item, Tensor) or h_item.dim() != 2:
+            raise ValueError("h_item must be a [n_items, d] tensor (its rows count the items, its device is where the walks run)")
+        n_items, dev = int(h_item.shape[0]), h_item.device
+        ptr, idx = _csr(graph, dev)
+        if bool((ptr[1:] == ptr[:-1]).any()):
+            raise ValueError("every user needs at least one interaction (a user's recent items start their walks)")
+        if hasattr(graph, "iu_ptr") and hasattr(graph, "iu_idx"):
+            iu_ptr = t.as_tensor(graph.iu_ptr).to(device=dev, dtype=t.int32).contiguous()
+            iu_idx = t.as_tensor(graph.iu_idx).to(device=dev, dtype=t.int32).contiguous()
+            if iu_ptr.numel() != n_items + 1:
+                raise ValueError(f"graph has {iu_ptr.numel() - 1} item rows, h_item {n_items}")
+        else:
+            if idx.numel() and int(idx.max()) >= n_items:
+                raise ValueError(f"graph names item {int(idx.max())} but h_item has {n_items} rows")
+            users = t.repeat_interleave(t.arange(ptr.numel() - 1, device=dev, dtype=t.int32), (ptr[1:] - ptr[:-1]).long())
+            iu_idx = users[t.sort(idx.long(), stable=True)[1]].contiguous()
+            iu_ptr = t.zeros(n_items + 1, dtype=t.int64, device=dev)
+            t.cumsum(t.bincount(idx.long(), minlength=n_items), dim=0, out=iu_ptr[1:])
+            iu_ptr = iu_ptr.to(t.int32)
+        ids, _, _ = ops.match_random_walks(iu_ptr, iu_idx, ptr, idx, int(K), num_walks=self.num_walks,
+                                           walk_length=self.walk_length, restart_prob=self.restart_prob, n_recent=self.n_recent,
+                                           boost=self.boost, exclude_seen=True, seed=self.seed)
+        return ids.to(t.int64)
 
 
 def _latest(ptr: Tensor, idx: Tensor) -> Tensor:
