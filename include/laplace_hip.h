@@ -1818,6 +1818,52 @@ int mi_gather_rows_bf16_f32(int64_t n_max, const int32_t* n_dev, int64_t d, cons
                             const uint16_t* src, int64_t ld_src, float* dst, int64_t ld_dst, int32_t accumulate,
                             mi_stream_t stream);
 
+/* ------------------------------------------------------------------------------------
+ * iALS  implicit-feedback ALS row solves (additive to ABI 14; csrc/als.hip).
+ * replaces: nothing in the reference.  Implicit-feedback matrix factorisation by alternating least squares (Hu, Koren and
+ *           Volinsky, ICDM 2008; Rendle et al., RecSys 2022) is the trained baseline a LightGCN figure is read against: with
+ *           one table fixed, every row of the other is the solution of one d x d system built from the row's entries.  This
+ *           entry is that half-sweep, and — on any other CSR over the same table — the fold-in of rows the model never saw.
+ * Inputs.  A CSR (ptr int32 [n_rows + 1], idx int32 [nnz]) over a factor table Y [n_cols, d] (f32, leading dimension ldy >= d),
+ *   G [d, d] (f32, contiguous, symmetric: only G[j][k] with k <= j is read; the trainer passes Y^T Y), alpha >= 0, reg > 0.
+ * The rule, per row r with entries e_0 .. e_{n-1} in CSR order (y_e = Y[idx[e], :]), restated in float64 by
+ * tests/als_emulation.py:
+ *   chunks    Chunk c is entries [c L, (c + 1) L) of the row, L = mi_als_chunk(d): a compile-time constant of d alone (not of
+ *             the device, the grid or the other rows).
+ *   per chunk S_c[j][k] = sum_e y_e[j] * y_e[k], ONE chain acc = fmaf(y_e[j], y_e[k], acc) from 0 in entry order;
+ *             s_c[j] = sum_e y_e[j], acc = acc + y_e[j] from 0 in entry order.
+ *   across    S = ((S_0 + S_1) + S_2) ... in ascending c, one f32 addition each; s likewise.
+ *   system    A[j][k] = fmaf(alpha, S[j][k], G[j][k]), then reg added on the diagonal (A[j][j] = fmaf(..) + reg);
+ *             b[j] = (1.0f + alpha) * s[j].
+ *   solve     x_r solves A x = b by an f32 Cholesky factorisation (A = L L^T, forward then backward substitution).  The order of
+ *             the additions inside the factorisation and the substitutions is the kernel's and NOT part of the rule; the tests
+ *             bound the residual instead (tests/als_emulation.py: residual_bound).
+ *   empty row x_r = 0.
+ *   pivot     A pivot that is not a positive finite number: x_r = 0 and *n_failed is incremented by one (an int32 device
+ *             counter the CALLER zeroes; an integer atomic).  Nothing is read or written out of bounds on that path.
+ * Duplicates.  For duplicate-free rows this is exactly iALS with confidence 1 + alpha on the observed pairs and 1 on all
+ *   others.  A repeated entry is summed as written, i.e. counts once per occurrence in S and in s.
+ * No float atomics anywhere: two calls give equal bits, and a row's answer is a pure function of (its entries in order, Y, G,
+ *   alpha, reg) whatever else is in the call — alone, in a batch, through row_list.
+ * row_list / n_list: null, or n_list int32 row ids (any order; distinct); X is then COMPACT by list position (X[i, :] belongs to
+ *   row row_list[i]).  An id outside [0, n_rows) gives a zero row.  Without a list X[r, :] belongs to row r.  X: f32, leading
+ *   dimension ldx >= d.
+ * Guards.  idx[e] outside [0, n_cols) contributes a zero row y_e.  A rowptr that runs past nnz, or a long row that found no
+ *   workspace slot (possible only when row_list names a row twice), is treated as a failed pivot: zero row, counted.
+ * Workspace: mi_als_solve_rows_workspace_bytes(n_work, nnz, d), n_work = n_list with a list and n_rows without:
+ *   (d * d + d) * 4 bytes for each of at most nnz / L + nnz / (L + 1) chunks of rows longer than L, and 8 bytes per row.
+ * Returned before anything is enqueued: MI_ERR_BAD_ARG (d % 4 != 0 — rows are read as float4 —, d < 4 or d > 128, 2^31 or
+ *   more rows, columns or entries, a negative count, alpha < 0 or not finite, reg <= 0 or not finite, a null pointer, Y not
+ *   16-byte aligned, ldy % 4 != 0, ldy < d or ldx < d), MI_ERR_WORKSPACE (ws null or short).  Zero rows: 0, nothing enqueued.
+ * mi_als_chunk: L of a width, 0 for a width the entry refuses.
+ * ---------------------------------------------------------------------------------- */
+int32_t mi_als_chunk(int64_t d);
+size_t  mi_als_solve_rows_workspace_bytes(int64_t n_work, int64_t nnz, int64_t d);
+int     mi_als_solve_rows_f32(int64_t n_rows, int64_t d, const int32_t* ptr, const int32_t* idx, int64_t nnz, int64_t n_cols,
+                              const float* Y, int64_t ldy, const float* G, float alpha, float reg, float* X, int64_t ldx,
+                              const int32_t* row_list, int64_t n_list, int32_t* n_failed, void* ws, size_t ws_bytes,
+                              mi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

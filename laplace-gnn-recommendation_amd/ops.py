@@ -1872,6 +1872,74 @@ def match_random_walks(iu_ptr: Tensor, iu_idx: Tensor, ui_ptr: Tensor, ui_idx: T
     return ids, scores, counts
 
 
+ALS_MAX_DIM = 128
+
+
+def check_als(d, alpha, reg) -> None:
+    """The argument rules of the implicit-ALS row solves (include/laplace_hip.h, iALS): ValueError naming the constraint.
+    Needs no device; ops.als_solve_rows and als.ImplicitALS share it."""
+    if isinstance(d, bool) or not isinstance(d, numbers.Integral):
+        raise ValueError(f"dim must be an integer, got {d!r}")
+    if d % 4 != 0:
+        raise ValueError(f"dim must be a multiple of 4 (factor rows are read as float4), got {d}")
+    if not 4 <= d <= ALS_MAX_DIM:
+        raise ValueError(f"dim must lie in 4 .. {ALS_MAX_DIM} (one d x d system per workgroup, in LDS), got {d}")
+    for name, v, strict in (("alpha", alpha, False), ("reg", reg, True)):
+        try:
+            v = float(v)
+            ok = math.isfinite(v) and (v > 0.0 if strict else v >= 0.0)
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise ValueError(f"{name} must be a finite number {'> 0' if strict else '>= 0'}, got {v!r}")
+
+
+def als_chunk(d: int) -> int:
+    """L of the iALS rule for width d: entries per chunk of a row's rank-n update (mi_als_chunk)."""
+    return int(_lib.lib().mi_als_chunk(int(d)))
+
+
+def als_solve_rows(a: DeviceCSR, Y: Tensor, G: Tensor, *, alpha: float, reg: float, out: Optional[Tensor] = None,
+                   row_list: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+    """iALS — for every row r of `a` (a CSR over the rows of Y [n_cols, d]) the solution of
+    (G + alpha * sum_e y_e y_e^T + reg I) x = (1 + alpha) * sum_e y_e, f32 Cholesky, one workgroup per row; the rule is stated in
+    include/laplace_hip.h.  G [d, d] is the caller's (the trainer passes gemm(Y, Y, trans_a=True, trans_b=False)).  Returns
+    (X, n_failed): X [n_rows, d], or [len(row_list), d] compact by list position; n_failed an int32 device scalar counting the
+    rows whose factorisation met a non-positive or non-finite pivot (those rows are zero).  Empty rows are zero and not counted."""
+    _need(a.rowptr, t.int32, "a.rowptr")
+    _need(a.col, t.int32, "a.col")
+    ldy = _rows_ok(Y, "Y")
+    _need(G, t.float32, "G")
+    if Y.shape[0] != a.n_cols:
+        raise ValueError(f"Y must have one row per column of a: {a.n_cols}, got {Y.shape[0]}")
+    d = int(Y.shape[1])
+    check_als(d, alpha, reg)
+    if tuple(G.shape) != (d, d):
+        raise ValueError(f"G must be [{d}, {d}], got {tuple(G.shape)}")
+    if a.rowptr.numel() != a.n_rows + 1:
+        raise ValueError("a.rowptr needs n_rows + 1 entries")
+    if row_list is not None:
+        _need(row_list, t.int32, "row_list")
+    n_work = int(row_list.numel()) if row_list is not None else a.n_rows
+    if out is None:
+        out = t.empty(n_work, d, dtype=t.float32, device=Y.device)
+    ldx = _rows_ok(out, "out")
+    if tuple(out.shape) != (n_work, d):
+        raise ValueError(f"out must be [{n_work}, {d}], got {tuple(out.shape)}")
+    n_failed = t.zeros(1, dtype=t.int32, device=Y.device)
+    if n_work == 0 or a.nnz == 0:   # nothing to solve: every row is empty
+        return out.zero_(), n_failed
+    L = _lib.lib()
+    ws_bytes = L.mi_als_solve_rows_workspace_bytes(n_work, a.nnz, d)
+    ws = _ws_reused(ws_bytes, Y.device)
+    # a pointer that is never dereferenced where the tensor is empty (no entries, no listed rows) keeps the null check simple
+    check(L.mi_als_solve_rows_f32(a.n_rows, d, a.rowptr.data_ptr(), _ptr(a.col), a.nnz, a.n_cols, Y.data_ptr(), ldy,
+                                  G.data_ptr(), float(alpha), float(reg), out.data_ptr() if n_work else None, ldx,
+                                  row_list.data_ptr() if row_list is not None else None, n_work if row_list is not None else 0,
+                                  n_failed.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "mi_als_solve_rows_f32")
+    return out, n_failed
+
+
 _BN_WS = {}
 BATCHNORM_MAX_CHANNELS = 512   # kBnMaxC of csrc/norm.hip: mi_batchnorm_*_f32 return MI_ERR_UNSUPPORTED beyond it
 
