@@ -4,16 +4,19 @@
 //                               A sub-group of LPR lanes per row (LPR the power of two >= d / 4), one float4 and one Philox
 //                               block per lane, the norm by xor shuffles inside the sub-group.  No atomics, one writer per row.
 //   mi_contrastive_fwd_bwd_f32  InfoNCE between p_b = a[id_b] / |a[id_b]| and q_j = b[id_j] / |b[id_j]| over the groups of G
-//                               slots of the in-batch softmax, whose tile routine, row statistics and gradient sweeps
-//                               (inbatch_tiles.hpp) it runs on two normalised [B, d] images: u_img = p / tau, v_img = q, both
-//                               mask ids = id, no logit offset.
+//                               slots of the in-batch softmax, whose row statistics and gradient sweeps (inbatch_tiles.hpp,
+//                               on the score tiles of loss_tiles.hpp) it runs on two normalised [B, d] images: u_img = p / tau,
+//                               v_img = q, both mask ids = id, no logit offset.
 //     1. normalise_kernel   one wavefront per slot: the two rows, their norms, the images, the slot's sort key
 //     2. inbatch_stats_kernel, 3. inbatch_sweep_kernel   as in inbatch.hip: lse and loss term per slot; dL/du_img, dL/dv_img
 //     4. norm_bwd_kernel    one wavefront per slot row: through the normalisation, (I - p p^T) / |f|, times its side's scale
 //     5. sort / chunk / combine   the slot rows of each side are summed per id by refsum.hpp and ADDED to g_a / g_b
 //     6. refsum::finish_kernel    loss = sum(term) / B
 // Every order of summation is a function of (B, G, d) and the ids: two calls give equal bits.
+// This file owns the noise, the normalisation and its backward, and the host entries; the lane map, k order and rescale order
+// of the scores are written in loss_tiles.hpp.
 #include "inbatch_tiles.hpp"
+#include "refsum.hpp"
 
 namespace {
 
@@ -121,17 +124,12 @@ __global__ __launch_bounds__(refsum::kBlock) void contrast_chunk_kernel(int64_t 
                                                                         const uint32_t* __restrict__ refs, refsum::Dest to) {
     const refsum::Chunk c = refsum::open_chunk(keys, batch);
     if (c.n_here == 0) return;
-    SlotRow term;
+    refsum::SlotRow term;
     if (c.lane < c.n_here) term.src = refs[c.j0 + c.lane];
     refsum::walk_references<VPT>(c, term, g_side, to.d, to);
 }
 
 // ------------------------------------------------------------------ host ---------------------------------------------------
-bool contrast_args_in_range(int64_t batch, int64_t d, int32_t group) {
-    return batch >= 1 && 2 * batch < INT32_MAX && d >= 4 && d % 4 == 0 && d <= kMaxD && group >= kMinGroup &&
-           group <= kMaxGroup && group % kTile == 0;
-}
-
 struct ContrastWs {
     float *u_img, *v_img, *g_slot, *lq, *lse, *term, *na, *nb;
     int32_t* id32;
@@ -194,7 +192,7 @@ int mi_perturb_rows_f32(int64_t n_rows, int64_t d, float* x, int64_t ldx, const 
 }
 
 size_t mi_contrastive_workspace_bytes(int64_t batch, int64_t d, int32_t group) {
-    if (!contrast_args_in_range(batch, d, group)) return 0;
+    if (!args_in_range(batch, d, group)) return 0;
     const size_t b = (size_t)batch, bp = (size_t)mi_ceil_div(batch, kTile) * kTile;
     return 2 * mi_align_up(b * d * sizeof(float), 256) + mi_align_up(2 * b * d * sizeof(float), 256) +
            6 * mi_align_up(bp * sizeof(float), 256) + refsum::workspace_bytes(batch, d);
@@ -220,7 +218,7 @@ int mi_contrastive_fwd_bwd_f32(int64_t batch, int32_t group, int64_t d, const in
     if (!w.ok()) return MI_ERR_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     const int64_t n_tiles = mi_ceil_div(batch, kTile);
-    const int d4 = (int)(d / 4), nq = (d4 + 1) / 2;
+    const int d4 = (int)(d / 4), nq = (int)mi_align_up((size_t)(d4 + 1) / 2, kLoadGroup);   // k steps: whole groups
     const size_t lds = (size_t)kTile * (2 * nq + 1) * sizeof(float4);
     refsum::Sort sorted;
     if (g_a) {

@@ -1,17 +1,14 @@
 // Exact full-catalogue softmax for the LightGCN trainer (mi_full_softmax_fwd_bwd_f32; the rule is in the header): every item
-// of the catalogue is a candidate of every slot.  The B x I scores are products of 32 x 32 tiles on the exact-f32 matrix
-// instruction (v_mfma_f32_32x32x2_f32: bit for bit a k-ordered fmaf chain) and never leave the registers; every pass that
-// needs them computes them again through score_tile, the pattern of inbatch.hip against the whole item table.
+// of the catalogue is a candidate of every slot.  The B x I scores are 32 x 32 score tiles (loss_tiles.hpp: the lane map, the
+// k order and the rescale order that its passes share, so they see the same score bits) against the whole item table.
 //   1. gather_kernel   the B user rows of final_emb become one contiguous [B, d] image; pos as int32 and the slot's L2 term
 //                      beside it.  The item rows are read where they lie: rows [n_users, n_users + I) of final_emb.
 //   2. stats_kernel    one wavefront per (32 user slots, item chunk): their scores against every 32-item tile of the chunk, a
 //                      running maximum and sum per lane -> one (max, sum) pair per slot and chunk; the chunk that holds pos_b
 //                      also leaves l[b, pos_b].
 //      merge_kernel    one thread per slot: the pairs in ascending chunk order -> lse[b] and the slot's loss term
-//   3. sweep_kernel    one wavefront per 32 OWNED rows, which sit on the lane (the B operand, staged once in LDS) while the other
-//                      side's rows stream past as the A operand: the coefficient tile is then the A operand of the gradient
-//                      product as it stands, no transpose, no LDS (inbatch.hip, sweep_kernel).
-//        users own     grid (user tiles, item chunks): a partial row of dL/df[users_b] per slot and chunk, then
+//   3. sweep_kernel    one wavefront per 32 OWNED rows, the other side's rows streaming past
+//        users own    grid (user tiles, item chunks): a partial row of dL/df[users_b] per slot and chunk, then
 //                      chunk_sum_kernel adds a slot's partial rows in ascending chunk order -> the slot row
 //        items own     grid (item tiles): the wavefront owns its 32 item rows for the whole pass over the B users and stores
 //                      them straight into g_final (item rows are unique: one writer per row); it also counts the slots that
@@ -21,8 +18,8 @@
 //   5. refsum::finish_kernel   loss = sum(term) / B + lambda * sum(reg), one block, fixed order
 // No float atomics; every order of summation is a function of (B, I, d) and the ids — split_catalogue never asks the device
 // for its size — so two calls give equal bits, here and on any other gfx950.
-// k order of a score: lane half h takes the float4 chunks 2q + h of a row, q ascending, the four floats in order, and the
-// instruction adds half 0's product before half 1's.  The passes share it, so they see the same score bits.
+// This file owns the cut of the catalogue (split_catalogue), the masks and chunking of its kernels, the two chunk merges and
+// the host entry.
 //
 // Decomposition.  A user tile streams I / 32 item tiles (3 125 at I = 100 000) and B / 32 = 512 wavefronts at B = 16 384 do
 // not fill the chip's 1 024 SIMDs, where one resident wavefront hides no load behind its 64-cycle matrix instructions.  The
@@ -34,21 +31,16 @@
 //   512 (one chunk) 35.96 / 65.50    1 024  23.70 / 50.88    2 048  18.65 / 37.28    4 096  16.26 / 36.88
 //   8 192  16.11 / 35.01    16 384  15.86 / 33.86, whose 32 chunks of partial rows (256 MiB at d = 128) buy 3 %: 8 192 it is.
 //   (The first two were taken before score_tile loaded its operand in groups, which moved the others by 0 to 5 %.)
+#include "loss_tiles.hpp"
 #include "refsum.hpp"
-#include <cmath>
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using namespace loss_tiles;
 
-constexpr int kTile = 32;        // rows per tile: the rows and the columns of the matrix instruction
-constexpr int kMaxD = 256;
-constexpr int kGroup = 4;        // k steps (float4 chunk pairs) of a score tile whose operand loads travel together
+constexpr int kLoadGroup = 4;    // k steps of a score tile whose A chunks are loaded together, a group ahead
 constexpr int64_t kWaveTarget = 8192;   // wavefronts the chunked passes aim for
 constexpr int64_t kMaxChunks = 32;
-
-// row of the 32 x 32 accumulator that register `reg` of lane half h holds (the column is lane & 31)
-__device__ __forceinline__ int acc_row(int reg, int h) { return (reg & 3) + 8 * (reg >> 2) + 4 * h; }
 
 // The cut of the catalogue into item chunks: a function of (B, I) alone.
 struct Split {
@@ -81,9 +73,7 @@ __global__ __launch_bounds__(256) void full_gather_kernel(
     float rg = 0.f;
     for (int e = lane; e < d4; e += MI_WAVE) {
         u_img[b * d4 + e] = uf[e];
-        const float4 x = u0[e], y = p0[e];
-        rg = fmaf(x.x, x.x, rg); rg = fmaf(x.y, x.y, rg); rg = fmaf(x.z, x.z, rg); rg = fmaf(x.w, x.w, rg);
-        rg = fmaf(y.x, y.x, rg); rg = fmaf(y.y, y.y, rg); rg = fmaf(y.z, y.z, rg); rg = fmaf(y.w, y.w, rg);
+        rg = add_squares(rg, u0[e], p0[e]);
     }
     rg = mi_wave_sum(rg);
     if (lane == 0) {
@@ -92,71 +82,9 @@ __global__ __launch_bounds__(256) void full_gather_kernel(
     }
 }
 
-// ------------------------------------------------------------------ score tiles --------------------------------------------
-// A side of the score block: n rows of d4 float4 chunks, ld4 float4 apart (the user image, or the item rows of final_emb).
-struct Rows {
-    const float4* __restrict__ p;
-    int64_t ld4, n;
-};
-
-// The owned tile in LDS: 32 rows of 2 nq float4 chunks (zero beyond the row's d4 chunks and beyond the side's rows), rows
-// 2 nq + 1 float4 apart so that the 16-byte reads of a half wavefront spread over the banks.
-__device__ __forceinline__ void load_owned_tile(float4* __restrict__ tile, const Rows& own, int64_t row0, int d4, int nq) {
-    const int per_row = 2 * nq, stride = per_row + 1;
-    for (int i = mi_lane(); i < kTile * per_row; i += MI_WAVE) {
-        const int r = i / per_row, ch = i - r * per_row;
-        const bool in = row0 + r < own.n && ch < d4;
-        tile[r * stride + ch] = in ? own.p[(row0 + r) * own.ld4 + ch] : mi_f4_zero();
-    }
-}
-
-// acc[reg] = <streamed row row0 + acc_row(reg, h), owned row of lane & 31>.  The streamed rows are the A operand, read from
-// memory (a row past the side's end reads as zero), the owned rows the B operand from LDS.  A product of two floats does not
-// depend on which side owns, so the statistics and both sweeps get the same bits for a (user, item) pair.
-__device__ __forceinline__ f32x16 score_tile(const Rows& str, int64_t row0, int d4, int nq, const float4* __restrict__ tile) {
-    const int lane = mi_lane(), c = lane & 31, h = lane >> 5;
-    const bool live = row0 + c < str.n;
-    const float4* ap = str.p + (live ? row0 + c : str.n - 1) * str.ld4;
-    const float4* bp = tile + c * (2 * nq + 1);
-    f32x16 acc;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-    // kGroup steps' A chunks are loaded together (one 128-byte line of a row over the two halves), the next group's while this
-    // group's 16 matrix instructions run: a load per step would put its latency in front of every four of them.
-    float4 cur[kGroup], nxt[kGroup];
-#pragma unroll
-    for (int u = 0; u < kGroup; ++u) {
-        const int ch = 2 * u + h;
-        cur[u] = (live && ch < d4) ? ap[ch] : mi_f4_zero();
-        nxt[u] = mi_f4_zero();
-    }
-    for (int q0 = 0; q0 < nq; q0 += kGroup) {   // nq is a multiple of kGroup; the chunks past d4 are zero on both sides
-        if (q0 + kGroup < nq) {
-#pragma unroll
-            for (int u = 0; u < kGroup; ++u) {
-                const int ch = 2 * (q0 + kGroup + u) + h;
-                nxt[u] = (live && ch < d4) ? ap[ch] : mi_f4_zero();
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < kGroup; ++u) {
-            const float4 a = cur[u];
-            const float4 b = bp[2 * (q0 + u) + h];
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b.x, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, b.y, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, b.z, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, b.w, acc, 0, 0, 0);
-        }
-#pragma unroll
-        for (int u = 0; u < kGroup; ++u) cur[u] = nxt[u];
-    }
-    return acc;
-}
-
 // ------------------------------------------------------------------ 2. row statistics --------------------------------------
-// One wavefront per (32 user slots, item chunk): blockIdx.x the user tile, blockIdx.y the chunk.  Lane (c, h) keeps the
-// running maximum and sum of user b0 + c over the items its half sees (rows 4h..4h+3 of every 8 of each item tile, tiles
-// ascending); the halves are merged at the end, half 0 first.  Items past the catalogue count as -inf.
+// One wavefront per (32 user slots, item chunk): blockIdx.x the user tile, blockIdx.y the chunk; their (max, sum) over the
+// chunk's item tiles, tiles ascending.  Items past the catalogue count as -inf.
 __global__ __launch_bounds__(MI_WAVE) void full_stats_kernel(
     Rows users, Rows items, int d4, int nq, int64_t tiles_per_chunk, int64_t bp /* slots, whole tiles */,
     const int32_t* __restrict__ pid, float* __restrict__ part_max, float* __restrict__ part_sum,
@@ -170,34 +98,27 @@ __global__ __launch_bounds__(MI_WAVE) void full_stats_kernel(
     const int64_t my_p = pid[min(b, users.n - 1)];
     const int64_t t0 = chunk * tiles_per_chunk, t1 = min(t0 + tiles_per_chunk, (items.n + kTile - 1) / kTile);
     const float ninf = -INFINITY;
-    float m = ninf, s = 0.f, diag = ninf;
+    MaxSum run;
+    float diag = ninf;
     for (int64_t t = t0; t < t1; ++t) {
         const int64_t j0 = t * kTile;
-        const f32x16 acc = score_tile(items, j0, d4, nq, tile);
+        const f32x16 acc = score_tile<kLoadGroup>(items, j0, d4, nq, tile);
         float x[16];
-        float tmax = ninf;
 #pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            const int64_t j = j0 + acc_row(i, h);
-            x[i] = j < items.n ? acc[i] : ninf;
-            tmax = fmaxf(tmax, x[i]);
-            if (j == my_p) diag = acc[i];
-        }
-        if (tmax > ninf) {
-            const float mn = fmaxf(m, tmax);
-            s *= expf(m - mn);             // m = -inf: s is 0 and stays 0
+        for (int q4 = 0; q4 < 4; ++q4)   // registers 4 q4 + i: rows 8 q4 + 4 h + i of the tile (the lane map)
 #pragma unroll
-            for (int i = 0; i < 16; ++i) s += expf(x[i] - mn);   // an item past the catalogue adds exp(-inf) = 0
-            m = mn;
-        }
+            for (int i = 0; i < 4; ++i) {
+                const int64_t j = j0 + 8 * q4 + 4 * h + i;
+                x[4 * q4 + i] = j < items.n ? acc[4 * q4 + i] : ninf;
+                if (j == my_p) diag = acc[4 * q4 + i];
+            }
+        lse_add_tile(run, x);
     }
-    const float mo = __shfl_xor(m, 32, MI_WAVE), so = __shfl_xor(s, 32, MI_WAVE);
-    const float m_lo = h ? mo : m, m_hi = h ? m : mo, s_lo = h ? so : s, s_hi = h ? s : so;
+    const MaxSum all = lse_fold_halves(run, h);
     diag = fmaxf(diag, __shfl_xor(diag, 32, MI_WAVE));
     if (b < users.n && h == 0) {   // item 0 of the chunk's first tile is a row of half 0: the maximum is finite
-        const float mx = fmaxf(m_lo, m_hi);
-        part_max[chunk * bp + b] = mx;
-        part_sum[chunk * bp + b] = s_lo * expf(m_lo - mx) + s_hi * expf(m_hi - mx);
+        part_max[chunk * bp + b] = all.m;
+        part_sum[chunk * bp + b] = all.s;
         if (diag > ninf) diag_out[b] = diag;   // pos_b lies in exactly one chunk: one writer
     }
 }
@@ -234,9 +155,7 @@ struct SweepArgs {
 
 // kOwnUsers: the owned rows are user slots (dL/df[users_b] = sum_i c[b,i] f[n_users + i], streamed rows = the chunk's items);
 // otherwise they are items (dL/df[n_users + i] = sum_b c[b,i] f[users_b], streamed rows = all B user slots).
-// The coefficient tile cf has the streamed row in its registers and the owned row on its lane; step s of the gradient product
-// takes register s as the A operand (k = lane half h <-> streamed row acc_row(s, h)) and, as the B operand, 32 columns of
-// that streamed row: out[n][reg] += cf * row.  NT = the 32-column tiles of a row.
+// NT = the 32-column tiles of a row.
 template <int NT, bool kOwnUsers>
 __global__ __launch_bounds__(MI_WAVE) void full_sweep_kernel(SweepArgs a) {
     extern __shared__ float4 tile[];
@@ -257,15 +176,10 @@ __global__ __launch_bounds__(MI_WAVE) void full_sweep_kernel(SweepArgs a) {
     const int64_t my_p = kOwnUsers ? (int64_t)a.pid[o] : 0;
     int named = 0;   // items own: the slots that name item o, over this lane half's rows
     f32x16 out[NT];
-#pragma unroll
-    for (int n = 0; n < NT; ++n)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) out[n][i] = 0.f;
-    const float* strf = reinterpret_cast<const float*>(str.p);
-    const int64_t str_ld = str.ld4 * 4;
+    grad_zero(out);
     for (int64_t t = t0; t < t1; ++t) {
         const int64_t r0 = t * kTile;
-        const f32x16 acc = score_tile(str, r0, d4, nq, tile);
+        const f32x16 acc = score_tile<kLoadGroup>(str, r0, d4, nq, tile);
         f32x16 cf;
 #pragma unroll
         for (int q4 = 0; q4 < 4; ++q4) {
@@ -289,29 +203,9 @@ __global__ __launch_bounds__(MI_WAVE) void full_sweep_kernel(SweepArgs a) {
                 if (!kOwnUsers) named += (!outside && hit) ? 1 : 0;
             }
         }
-#pragma unroll
-        for (int s = 0; s < 16; ++s) {
-            const int64_t r = r0 + acc_row(s, h);
-            const bool live = r < str.n;
-            const float* row = strf + (live ? r : str.n - 1) * str_ld;
-#pragma unroll
-            for (int n = 0; n < NT; ++n) {
-                const int k = n * 32 + c;
-                const float x = (live && k < d) ? row[k] : 0.f;
-                out[n] = __builtin_amdgcn_mfma_f32_32x32x2f32(cf[s], x, out[n], 0, 0, 0);
-            }
-        }
+        grad_add_tile(out, cf, str, r0, d);
     }
-    float* dst = a.dst + (kOwnUsers ? (int64_t)blockIdx.y * own.n * a.ldd : 0);
-#pragma unroll
-    for (int n = 0; n < NT; ++n) {
-        const int k = n * 32 + c;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            const int64_t orow = o0 + acc_row(i, h);
-            if (orow < own.n && k < d) dst[orow * a.ldd + k] = out[n][i];
-        }
-    }
+    grad_store(out, a.dst + (kOwnUsers ? (int64_t)blockIdx.y * own.n * a.ldd : 0), a.ldd, o0, own.n, d);
     if (!kOwnUsers) {
         named += __shfl_xor(named, 32, MI_WAVE);
         if (a.reg_w && h == 0 && o_live && named) a.reg_w[o] = (float)named * a.reg_unit;   // reg_w is zero on entry
@@ -337,21 +231,13 @@ __global__ void full_refs_kernel(int64_t batch, const int64_t* __restrict__ user
     refs[b] = (uint32_t)b;
 }
 
-// The chunk pass of refsum.hpp with one term per reference, the slot row itself, unweighted.
-struct SlotRow {
-    static constexpr int kTerms = 1;
-    int64_t src = 0;   // row of g_slot
-    __device__ __forceinline__ int64_t row(int, int q) const { return __shfl(src, q, MI_WAVE); }
-    __device__ __forceinline__ float weight(int, int) const { return 1.f; }
-};
-
 template <int VPT>  // floats of a row per lane: ceil(d / 64)
 __global__ __launch_bounds__(refsum::kBlock) void full_chunk_kernel(
     int64_t batch, const float* __restrict__ g_slot, const uint32_t* __restrict__ keys, const uint32_t* __restrict__ refs,
     refsum::Dest to, float* __restrict__ reg_w, float reg_unit) {
     const refsum::Chunk c = refsum::open_chunk(keys, batch);
     if (c.n_here == 0) return;
-    SlotRow term;
+    refsum::SlotRow term;
     if (c.lane < c.n_here) {
         term.src = refs[c.j0 + c.lane];
         if (reg_w) {
@@ -425,7 +311,7 @@ int mi_full_softmax_fwd_bwd_f32(int64_t batch, int64_t d, int64_t n_users, int64
     hipStream_t s = (hipStream_t)stream;
     const int64_t user_tiles = mi_ceil_div(batch, kTile), item_tiles = mi_ceil_div(n_items, kTile);
     const int64_t bp = user_tiles * kTile;
-    const int d4 = (int)(d / 4), nq = (int)mi_align_up((size_t)(d4 + 1) / 2, kGroup);   // k steps: whole groups
+    const int d4 = (int)(d / 4), nq = (int)mi_align_up((size_t)(d4 + 1) / 2, kLoadGroup);   // k steps: whole groups
     const size_t lds = (size_t)kTile * (2 * nq + 1) * sizeof(float4);   // 33 280 bytes at d = 256
     refsum::Sort sorted;
     if (g_final) {

@@ -1,25 +1,20 @@
 // In-batch sampled softmax for the LightGCN trainer (mi_inbatch_softmax_fwd_bwd_f32; the rule is in the header): the other
-// positives of a slot's group of G slots are its negatives.  The G x G scores of a group are products of 32 x 32 tiles on
-// the exact-f32 matrix instruction (v_mfma_f32_32x32x2_f32: bit for bit a k-ordered fmaf chain) and never leave the
-// registers; every pass that needs them computes them again.
+// positives of a slot's group of G slots are its negatives.  The G x G scores of a group are 32 x 32 score tiles
+// (loss_tiles.hpp: the lane map, the k order and the rescale order that its passes share, so they see the same score bits).
 //   1. gather_kernel   the B user rows and B positive rows of final_emb become two contiguous [B, d] images (through
 //                      node_map when given); ids as int32, logq[pos_b] and the slot's L2 term beside them
 //   2. stats_kernel    one wavefront per 32 user slots: their scores against every 32-candidate tile of the group, masks
 //                      and - logq in registers, a running maximum and sum per lane -> lse[b] and the slot's loss term
 //   3. sweep_kernel    one wavefront per 32 OWNED slots, twice: the user rows of a tile (dL/df[users_b]) and the positive
-//                      rows of a tile (dL/df[pos_j]).  The owned rows sit on the lane (the B operand, staged once in LDS),
-//                      the other side's rows stream past as the A operand, so the score tile has the streamed row in its
-//                      16 registers and the owned slot on its lane: the coefficient tile is then the A operand of the
-//                      gradient product as it stands (the sum runs over the accumulator's row index), no transpose, no LDS.
-//                      One wavefront owns its 32 output rows for the whole sweep: one writer per slot row.
+//                      rows of a tile (dL/df[pos_j]), the other side's rows streaming past.  One wavefront owns its 32
+//                      output rows for the whole sweep: one writer per slot row.
 //   4. refs / sort / chunk / combine   the 2B slot rows become rows of g_final: the sorted-reference segmented sum of
 //                      refsum.hpp, with a slot row as each reference's only term; reg_w from the run lengths
 //   5. refsum::finish_kernel   loss = sum(term) / B + lambda * sum(reg), one block, fixed order
 // No float atomics; every order of summation is a function of (B, G, d) and the ids: two calls give equal bits.
-// k order of a score: lane half h takes the float4 chunks 2q + h of a row, q ascending, the four floats in order, and the
-// instruction adds half 0's product before half 1's.  The three passes share it, so they see the same score bits.
-// Passes 2 and 3 and the tile routine are in inbatch_tiles.hpp, which contrastive.hip uses too.
+// This file owns passes 1 and 4 and the host entry; passes 2 and 3 are in inbatch_tiles.hpp, which contrastive.hip runs too.
 #include "inbatch_tiles.hpp"
+#include "refsum.hpp"
 
 namespace {
 
@@ -45,9 +40,7 @@ __global__ __launch_bounds__(256) void inbatch_gather_kernel(
     for (int e = lane; e < d4; e += MI_WAVE) {
         u_img[b * d4 + e] = uf[e];
         v_img[b * d4 + e] = pf[e];
-        const float4 x = u0[e], y = p0[e];
-        rg = fmaf(x.x, x.x, rg); rg = fmaf(x.y, x.y, rg); rg = fmaf(x.z, x.z, rg); rg = fmaf(x.w, x.w, rg);
-        rg = fmaf(y.x, y.x, rg); rg = fmaf(y.y, y.y, rg); rg = fmaf(y.z, y.z, rg); rg = fmaf(y.w, y.w, rg);
+        rg = add_squares(rg, u0[e], p0[e]);
     }
     rg = mi_wave_sum(rg);
     if (lane == 0) {
@@ -77,7 +70,7 @@ __global__ __launch_bounds__(refsum::kBlock) void inbatch_chunk_kernel(
     const int64_t n_ref = 2 * batch;
     const refsum::Chunk c = refsum::open_chunk(keys, n_ref);
     if (c.n_here == 0) return;
-    SlotRow term;
+    refsum::SlotRow term;
     if (c.lane < c.n_here) {
         term.src = refs[c.j0 + c.lane];
         if (reg_w) {
@@ -89,11 +82,6 @@ __global__ __launch_bounds__(refsum::kBlock) void inbatch_chunk_kernel(
 }
 
 // ------------------------------------------------------------------ host ---------------------------------------------------
-bool args_in_range(int64_t batch, int64_t d, int32_t group) {
-    return batch >= 1 && 2 * batch < INT32_MAX && d >= 4 && d % 4 == 0 && d <= kMaxD && group >= kMinGroup &&
-           group <= kMaxGroup && group % kTile == 0;
-}
-
 struct Workspace {
     float *u_img, *v_img, *g_slot, *lq, *lse, *term, *reg;
     int32_t *uid, *pid;
@@ -151,7 +139,7 @@ int mi_inbatch_softmax_fwd_bwd_f32(int64_t batch, int32_t group, int64_t d, int6
     if (!w.ok()) return MI_ERR_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     const int64_t n_ref = 2 * batch, n_tiles = mi_ceil_div(batch, kTile);
-    const int d4 = (int)(d / 4), nq = (d4 + 1) / 2;
+    const int d4 = (int)(d / 4), nq = (int)mi_align_up((size_t)(d4 + 1) / 2, kLoadGroup);   // k steps: whole groups
     const size_t lds = (size_t)kTile * (2 * nq + 1) * sizeof(float4);   // 33 280 bytes at d = 256
     refsum::Sort sorted;
     if (g_final) {

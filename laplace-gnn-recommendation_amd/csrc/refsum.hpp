@@ -1,5 +1,6 @@
 // Sum of weighted source rows by destination row over a list of references, without float atomics: the end of every loss
-// path of the LightGCN trainer (train.hip: bpr_chunk_kernel, rank_chunk_kernel; inbatch.hip: inbatch_chunk_kernel).
+// path of the LightGCN trainer (train.hip: bpr_chunk_kernel, rank_chunk_kernel; inbatch.hip, contrastive.hip and
+// fullsoftmax.hip: their chunk kernels).
 //
 // A reference is (key, r): key names the destination row of g_final, r is the caller's (what it adds is the caller's term
 // list: source rows and weights).  The caller writes keys and references in the order it wants the sums taken; then
@@ -162,6 +163,14 @@ __device__ __forceinline__ void walk_references(const Chunk& c, const Term& term
         }
     }
 }
+
+// The Term of a reference that adds one row as it stands: row `src` of `rows`, unweighted.
+struct SlotRow {
+    static constexpr int kTerms = 1;
+    int64_t src = 0;
+    __device__ __forceinline__ int64_t row(int, int q) const { return __shfl(src, q, MI_WAVE); }
+    __device__ __forceinline__ float weight(int, int) const { return 1.f; }
+};
 
 // ---- kernels ----------------------------------------------------------------------------------------------------------------
 // One wavefront per chunk whose trailing run starts in it and runs on: tail partial + the head partials of the following

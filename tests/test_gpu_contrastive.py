@@ -16,6 +16,7 @@ with a density of about 18 per unit around zero, some 30 of them below 1e-6 in a
 on the CPU: 1.2e-8 to 1.9e-7).  The test's table is therefore the model's with the sign of column c set to (-1)^c and 0.05
 added to every magnitude: A has no negative entry, so every propagated element of a node with an edge keeps its column's sign
 at a magnitude the six steps (lr 1e-3: at most 6e-3 per entry) cannot bring near zero, and both signs are exercised."""
+import json
 import math
 import os
 import sys
@@ -175,6 +176,28 @@ def test_contrast_gradient_scales(B, G, d, duplicated):
     loss, g_a, g_b = _device_contrast(c, g_scale_a=0.25, g_scale_b=2.0)
     assert _loss_close(loss, want)                       # the scales do not touch the loss value
     assert _added_close(g_a, _prefill(c["a"].shape, 1), 0.25 * wa) and _added_close(g_b, _prefill(c["b"].shape, 3), 2.0 * wb)
+
+
+def _loss_bits_tool():
+    """tools/record_loss_bits.py: the cases of tests/golden/tile_loss_bits.json and the function that records one."""
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import record_loss_bits
+    return record_loss_bits
+
+
+@pytest.mark.parametrize("B", E.BATCHES)
+def test_every_shape_gives_its_recorded_bits(B):
+    """Loss, g_a, g_b (zero on entry, g_scale_a = 1/3, g_scale_b = 1) and the loss-only form's loss of every group, width and
+    kind of ids at batch B, against the bits recorded at the commit tests/golden/tile_loss_bits.json names.  The cases and
+    the recording are the tool's: neither side changes alone."""
+    tool = _loss_bits_tool()
+    with open(os.path.join(ROOT, "tests", "golden", "tile_loss_bits.json")) as f:
+        rec = json.load(f)["contrastive"]
+    assert len(rec) == len(E.BATCHES) * len(E.GROUPS) * len(E.WIDTHS) * 2
+    cases = tool.contrastive_cases(B)
+    assert len(cases) == len(E.GROUPS) * len(E.WIDTHS) * 2
+    for c in cases:
+        assert tool.contrastive_record(c) == rec[c["key"]], c["key"]
 
 
 def test_autograd_function_over_gathered_blocks():

@@ -7,6 +7,7 @@ Tolerances are the project's (tests/test_gpu_lightgcn.py): loss 1e-6 * max(1, |l
 trained embeddings <= 1e-4.
 
 Measured maxima on an MI355X are in profiles/full_softmax.md."""
+import json
 import math
 import os
 import sys
@@ -137,6 +138,27 @@ def test_loss_only_form_and_second_call_give_equal_bits(i):
     only = _device_call(c, 1e-2, want_grad=False)
     assert t.equal(only[0], a[0])
     assert float(a[1].abs().max()) > 0.0 or c["I"] == 1
+
+
+def _loss_bits_tool():
+    """tools/record_loss_bits.py: the cases of tests/golden/tile_loss_bits.json and the function that records one."""
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import record_loss_bits
+    return record_loss_bits
+
+
+@pytest.mark.parametrize("i", range(len(T.SHAPES)))
+def test_every_shape_gives_its_recorded_bits(i):
+    """Loss, g_final, reg_w and the loss-only form's loss of every shape of the twin over lam in LAMS at g_scale = 1/3,
+    against the bits recorded at the commit tests/golden/tile_loss_bits.json names.  The cases and the recording are the
+    tool's: neither side changes alone."""
+    tool = _loss_bits_tool()
+    assert tool.FULL_LAMS == LAMS and tool.full_softmax_shapes() == len(T.SHAPES)
+    with open(os.path.join(ROOT, "tests", "golden", "tile_loss_bits.json")) as f:
+        rec = json.load(f)["full_softmax"]
+    assert len(rec) == len(LAMS) * len(T.SHAPES)
+    for c in tool.full_softmax_cases(i):
+        assert tool.full_softmax_record(c) == rec[c["key"]], c["key"]
 
 
 # ---------------------------------------------------------------------------- 5: against the other softmax kernels

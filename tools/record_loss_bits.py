@@ -10,8 +10,14 @@ It also writes tests/golden/loss_path_bits.json: the same for every other loss p
 D and node map on four kinds of batch; ops.inbatch_softmax_fwd_bwd over the twin's shapes and two more), recorded at the
 commit that file names, before the paths shared csrc/refsum.hpp.  Both GPU test files take these cases and their records
 from the functions below.
+
+And tests/golden/tile_loss_bits.json: the full-catalogue softmax (ops.full_softmax_fwd_bwd) and the noise-view contrastive
+term (ops.contrastive_fwd_bwd) on the shapes of their twins, recorded at the commit that file names, before they shared
+csrc/loss_tiles.hpp with the in-batch softmax.  tests/test_gpu_full_softmax.py and tests/test_gpu_contrastive.py take their
+cases and records from here in the same way.
     python3 tools/record_loss_bits.py --commit <short hash of the tree that runs> [--out tests/golden/bpr_entry_bits.json]
-                                      [--paths-out tests/golden/loss_path_bits.json]"""
+                                      [--paths-out tests/golden/loss_path_bits.json]
+                                      [--tiles-out tests/golden/tile_loss_bits.json]"""
 import argparse
 import hashlib
 import json
@@ -186,6 +192,57 @@ def loss_paths():
     return rank, inb
 
 
+# ---- the losses on 32 x 32 score tiles against their own past: tests/golden/tile_loss_bits.json -------------------------------
+# The full-catalogue softmax and the noise-view contrastive term, which share the tile routines of csrc/loss_tiles.hpp with
+# the in-batch softmax above.  tests/test_gpu_full_softmax.py and tests/test_gpu_contrastive.py take the cases and the
+# records from the functions below.
+FULL_LAMS = (0.0, 1e-2)                  # LAMS of tests/test_gpu_full_softmax.py
+
+
+def full_softmax_shapes():
+    import full_softmax_twin as T
+    return len(T.SHAPES)
+
+
+def full_softmax_cases(i):
+    return [dict(i=i, lam=lam, key=f"shape{i}_lam{li}") for li, lam in enumerate(FULL_LAMS)]
+
+
+def full_softmax_record(c):
+    import full_softmax_twin as T
+    s = T.cases()[c["i"]]
+    U, I, d = s["U"], s["I"], s["d"]
+    ud, pd, fd, e0d = s["users"].to(DEV), s["pos"].to(DEV), s["final"].to(DEV), s["e0"].to(DEV)
+    gf, rw = t.zeros(U + I, d, device=DEV), t.zeros(U + I, device=DEV)
+    loss = ops.full_softmax_fwd_bwd(ud, pd, fd, e0d, U, c["lam"], g_final=gf, reg_w=rw, g_scale=1.0 / 3)
+    only = ops.full_softmax_fwd_bwd(ud, pd, fd, e0d, U, c["lam"])
+    return {"loss_bits": bits(loss), "g_final_sha256": digest(gf), "reg_w_sha256": digest(rw), "loss_only_bits": bits(only)}
+
+
+def contrastive_cases(B):
+    """The cases of one batch size of contrastive_emulation: every group, width and kind of ids."""
+    import contrastive_emulation as E
+    return [dict(B=B, G=G, d=d, duplicated=dup, key=f"B{B}_G{G}_d{d}_dup{int(dup)}")
+            for G in E.GROUPS for d in E.WIDTHS for dup in (False, True)]
+
+
+def contrastive_record(c):
+    import contrastive_emulation as E
+    s = E.case(c["B"], c["G"], c["d"], c["duplicated"])
+    a, b, ids = s["a"].to(DEV), s["b"].to(DEV), s["ids"].to(DEV)
+    g_a, g_b = t.zeros_like(a), t.zeros_like(b)
+    loss = ops.contrastive_fwd_bwd(ids, a, b, tau=E.TAU, group=c["G"], g_a=g_a, g_b=g_b, g_scale_a=1.0 / 3, g_scale_b=1.0)
+    only = ops.contrastive_fwd_bwd(ids, a, b, tau=E.TAU, group=c["G"])
+    return {"loss_bits": bits(loss), "g_a_sha256": digest(g_a), "g_b_sha256": digest(g_b), "loss_only_bits": bits(only)}
+
+
+def tile_losses():
+    import contrastive_emulation as E
+    full = {c["key"]: full_softmax_record(c) for i in range(full_softmax_shapes()) for c in full_softmax_cases(i)}
+    con = {c["key"]: contrastive_record(c) for B in E.BATCHES for c in contrastive_cases(B)}
+    return full, con
+
+
 def write_json(path, out):
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     with open(path, "w") as f:
@@ -198,7 +255,18 @@ if __name__ == "__main__":
     ap.add_argument("--commit", required=True, help="short hash of the tree that runs; written into the file")
     ap.add_argument("--out", default=os.path.join(ROOT, "tests", "golden", "bpr_entry_bits.json"))
     ap.add_argument("--paths-out", default=os.path.join(ROOT, "tests", "golden", "loss_path_bits.json"))
+    ap.add_argument("--tiles-out", default=os.path.join(ROOT, "tests", "golden", "tile_loss_bits.json"))
     args = ap.parse_args()
+    full_sm, con = tile_losses()
+    write_json(args.tiles_out, {
+        "recorded_at_commit": args.commit,
+        "what": "ops.full_softmax_fwd_bwd (full_softmax: shape of full_softmax_twin.SHAPES, lam; g_scale 1/3) and "
+                "ops.contrastive_fwd_bwd (contrastive: B, G, d, duplicated ids of contrastive_emulation; tau 0.15, gradient "
+                "tables zero on entry, g_scale_a 1/3, g_scale_b 1) on the cases of tools/record_loss_bits.py.  fp32 bit "
+                "patterns in hex (loss, and the loss of the loss-only form), SHA-256 of the bytes of g_final and reg_w, "
+                "or of g_a and g_b.",
+        "full_softmax": full_sm, "contrastive": con})
+    print(f"{len(full_sm)} full-softmax and {len(con)} contrastive cases -> {args.tiles_out}")
     rank, inb = loss_paths()
     write_json(args.paths_out, {
         "recorded_at_commit": args.commit,
