@@ -1110,6 +1110,34 @@ int    mi_ranker_step_f32(const mi_ranker_model* model, const mi_ranker_batch* b
  * would be declined.  Enqueues nothing and reads no device memory (host-side walk of the two descriptors), so data-parallel
  * callers can agree on taking or declining a batch BEFORE any rank enters the gradient all-reduce (round 4). */
 int    mi_ranker_step_check(const mi_ranker_model* model, const mi_ranker_batch* batch, void* ws, size_t ws_bytes);
+/* mi_ranker_step_f32 that also says which launch forms it took.  Where the customer-side and the article-side twin of a step
+ * share a kernel instantiation the executor issues them as ONE launch; otherwise, and always with an auxiliary stream, as two
+ * single launches.  Both forms compute the same bits, so nothing but this report tells them apart.  `report` is zeroed at
+ * entry and filled on the host before the call returns (the launch pass only: a declined call leaves it zero); null = plain
+ * mi_ranker_step_f32.  One count per DECISION, not per kernel:
+ *   merged[kind]: how often the one-launch form took the work;  single[kind]: how often the separate launches ran instead.
+ *   EMBED               the two embedding lookups
+ *   PREP_DROPOUT        the first encoder layer's two input dropouts: merged = inside the prep launch (p > 0, L > 1 only)
+ *   DROPOUT             a later encoder layer's two input dropouts (forward)
+ *   SPMM_FWD, SPMM_BWD  the two relations' aggregations of a layer (backward: layers above the first only)
+ *   BN_FWD, BN_BWD      the two BatchNorms
+ *   GATHER_CAT_DROPOUT  merged = the decoder's gather writes the dropped rows itself; single = the plain gather launch
+ *   LINEAR1_BWD         merged = the last decoder layer's backward with its reduction in the same launch; single = two launches
+ *   GATHER_CAT_BWD      the two sums of the gather's backward
+ *   WGRAD               merged = launches of the transposed-product kernel (one for all layers when L <= 2, else one per
+ *                       layer); single = layers whose weight gradients went through the grouped GEMM instead */
+enum {
+    MI_RANKER_LAUNCH_EMBED = 0, MI_RANKER_LAUNCH_PREP_DROPOUT = 1, MI_RANKER_LAUNCH_DROPOUT = 2, MI_RANKER_LAUNCH_SPMM_FWD = 3,
+    MI_RANKER_LAUNCH_BN_FWD = 4, MI_RANKER_LAUNCH_GATHER_CAT_DROPOUT = 5, MI_RANKER_LAUNCH_LINEAR1_BWD = 6,
+    MI_RANKER_LAUNCH_GATHER_CAT_BWD = 7, MI_RANKER_LAUNCH_BN_BWD = 8, MI_RANKER_LAUNCH_SPMM_BWD = 9, MI_RANKER_LAUNCH_WGRAD = 10,
+    MI_RANKER_LAUNCH_KINDS = 11
+};
+typedef struct mi_ranker_launches {
+    int32_t merged[MI_RANKER_LAUNCH_KINDS];
+    int32_t single[MI_RANKER_LAUNCH_KINDS];
+} mi_ranker_launches;
+int    mi_ranker_step_report_f32(const mi_ranker_model* model, const mi_ranker_batch* batch, void* ws, size_t ws_bytes,
+                                 mi_stream_t stream, mi_ranker_launches* report);
 /* The update alone, for data-parallel callers: run mi_ranker_step_f32 with apply_adam = 0, all-reduce(sum) the gradient
  * buffers (params[i].g; the host side keeps them in ONE flat allocation so that is one collective), then this:
  * Adam (a9's arithmetic, model->lr/beta/eps/step) over model->params with every gradient multiplied by grad_scale

@@ -149,6 +149,19 @@ class RankerBatch(Structure):
                 ("logits", c_void_p)]
 
 
+# mi_ranker_launches: which launch form each twin step of the last mi_ranker_step_report_f32 took (the enum of laplace_hip.h)
+RANKER_LAUNCH_KINDS = ("EMBED", "PREP_DROPOUT", "DROPOUT", "SPMM_FWD", "BN_FWD", "GATHER_CAT_DROPOUT", "LINEAR1_BWD",
+                       "GATHER_CAT_BWD", "BN_BWD", "SPMM_BWD", "WGRAD")
+
+
+class RankerLaunches(Structure):
+    _fields_ = [("merged", c_int32 * len(RANKER_LAUNCH_KINDS)), ("single", c_int32 * len(RANKER_LAUNCH_KINDS))]
+
+    def as_dict(self) -> dict:
+        """{kind: (merged, single)}"""
+        return {k: (int(self.merged[i]), int(self.single[i])) for i, k in enumerate(RANKER_LAUNCH_KINDS)}
+
+
 MI_PINSAGE_MAX_LAYERS = 4
 
 
@@ -347,6 +360,7 @@ _PROTOTYPES = {
     "mi_ranker_step_workspace_bytes": (c_size_t, [POINTER(RankerModel), POINTER(RankerBatch)]),
     "mi_ranker_step_f32": (c_int32, [POINTER(RankerModel), POINTER(RankerBatch), P, c_size_t, P]),
     "mi_ranker_step_check": (c_int32, [POINTER(RankerModel), POINTER(RankerBatch), P, c_size_t]),
+    "mi_ranker_step_report_f32": (c_int32, [POINTER(RankerModel), POINTER(RankerBatch), P, c_size_t, P, POINTER(RankerLaunches)]),
     "mi_ranker_adam_f32": (c_int32, [POINTER(RankerModel), ctypes.c_float, P]),
     "mi_match_same_location_i32": (c_int32, [c_int64, P, P, P, P, P, P, c_int32, P, P, P]),
     "mi_cooc_items_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int32]),

@@ -113,9 +113,11 @@ struct Exec {
     hipStream_t cur;      // where the helpers below enqueue
     int rc = 0;
     bool oom = false;
+    mi_ranker_launches* rep;   // nullable: which launch forms the LAUNCH pass took (mi_ranker_step_report_f32)
 
-    Exec(const mi_ranker_model& m, const mi_ranker_batch& b, void* ws, size_t cap, Mode md, hipStream_t st)
-        : M(m), B(b), ar(ws, cap), mode(md), s(st), s2(st), cur(st) {
+    Exec(const mi_ranker_model& m, const mi_ranker_batch& b, void* ws, size_t cap, Mode md, hipStream_t st,
+         mi_ranker_launches* report = nullptr)
+        : M(m), B(b), ar(ws, cap), mode(md), s(st), s2(st), cur(st), rep(md == LAUNCH ? report : nullptr) {
         if (b.aux_stream && b.ev_fork && b.ev_join) s2 = (hipStream_t)b.aux_stream;
     }
     // Pairs of launches that do not depend on each other (customer / article twins: embeddings, dropout, the two
@@ -202,15 +204,25 @@ struct Exec {
     // an auxiliary stream (the twins then run side by side anyway); MI_ERR_UNSUPPORTED from a pair launcher = the pair does not
     // share a kernel instantiation: the two single launches are issued instead.  Same device code per element either way.
     bool twin() const { return s2 == s; }
-    bool paired(int prc) {   // true: the pair launch took the work
-        if (prc == 0) return true;
+    bool paired(int kind, int prc) {   // true: the pair launch took the work
+        if (prc == 0) {
+            if (rep) rep->merged[kind] += 1;
+            return true;
+        }
         if (prc != MI_ERR_UNSUPPORTED) ok(prc);
         return prc != MI_ERR_UNSUPPORTED;
     }
-    void dropout2(const float* xa, float* ya, int64_t na, uint32_t site_a, const float* xb, float* yb, int64_t nb, uint32_t site_b) {
+    void merged(int kind, int code) {   // a launch that is the one-launch form by construction
+        ok(code);
+        if (code == 0 && rep) rep->merged[kind] += 1;
+    }
+    void singles(int kind) { if (rep && go()) rep->single[kind] += 1; }   // the separate launches ran instead
+    void dropout2(int kind, const float* xa, float* ya, int64_t na, uint32_t site_a, const float* xb, float* yb, int64_t nb,
+                  uint32_t site_b) {
         if (mode == CHECK && (na % 4 != 0 || nb % 4 != 0)) fail(MI_ERR_UNSUPPORTED);
         if (!go()) return;
         if (!twin() || na == 0 || nb == 0) {
+            singles(kind);
             on(0); dropout(xa, ya, na, site_a);
             on(1); dropout(xb, yb, nb, site_b);
             return;
@@ -221,14 +233,15 @@ struct Exec {
         const unsigned ga = (unsigned)mi_ceil_div(a.n4, kBlock), gb = (unsigned)mi_ceil_div(b.n4, kBlock);
         hipLaunchKernelGGL(dropout_pair_kernel, dim3(ga + gb), dim3(kBlock), 0, s, a, b, ga, p, 1.0f / (1.0f - p), (uint32_t)B.seed,
                            (uint32_t)(B.seed >> 32), (uint32_t)B.step);
-        ok(mi_launch_status());
+        merged(kind, mi_launch_status());
     }
     // two plan-less products (rows = destinations of relation r); in place: S = addend + acc
-    void spmm2(const mi_pairs::SpmmSide (&q)[2], const int (&stream_of)[2]) {
+    void spmm2(int kind, const mi_pairs::SpmmSide (&q)[2], const int (&stream_of)[2]) {
         for (int r = 0; r < 2; ++r)
             if (mode == CHECK && (q[r].d % 4 != 0 || q[r].d > 512)) fail(MI_ERR_UNSUPPORTED);
         if (!go()) return;
-        if (twin() && paired(mi_pairs::spmm_planless_pair(q[0], q[1], s))) return;
+        if (twin() && paired(kind, mi_pairs::spmm_planless_pair(q[0], q[1], s))) return;
+        singles(kind);
         for (int r = 0; r < 2; ++r) {
             on(stream_of[r]);
             ok(mi_spmm_csr_ex_f32(q[r].n_rows, q[r].d, q[r].rowptr, q[r].col, q[r].val, q[r].X, q[r].d, q[r].Y, q[r].d, q[r].addend, q[r].d,
@@ -319,8 +332,9 @@ int Exec::run() {
         if (go() && twin()) {
             const mi_pairs::EmbedSide ea{n[0], M.n_cols[0], B.x[0], M.tables[0], M.table_rows[0], M.dims[0], x0[0], width[0]};
             const mi_pairs::EmbedSide eb{n[1], M.n_cols[1], B.x[1], M.tables[1], M.table_rows[1], M.dims[1], x0[1], width[1]};
-            done = paired(mi_pairs::embed_concat_pair(ea, eb, M.max_norm, s));
+            done = paired(MI_RANKER_LAUNCH_EMBED, mi_pairs::embed_concat_pair(ea, eb, M.max_norm, s));
         }
+        if (!done) singles(MI_RANKER_LAUNCH_EMBED);
         for (int t = 0; t < kTypes && !done; ++t) {
             on(t);
             if (go())
@@ -360,10 +374,11 @@ int Exec::run() {
             const unsigned ga = (unsigned)mi_ceil_div(da.n4, kBlock), gb = (unsigned)mi_ceil_div(db.n4, kBlock);
             hipLaunchKernelGGL(ranker_prep_dropout_kernel, dim3(gp + ga + gb), dim3(kBlock), 0, s, pa, gp, da, db, ga, p, 1.0f / (1.0f - p),
                                (uint32_t)B.seed, (uint32_t)(B.seed >> 32), (uint32_t)B.step);
+            merged(MI_RANKER_LAUNCH_PREP_DROPOUT, mi_launch_status());
         } else {
             hipLaunchKernelGGL(ranker_prep_kernel, dim3(gp), dim3(kBlock), 0, s, pa);
+            ok(mi_launch_status());
         }
-        ok(mi_launch_status());
     }
     const float* fval[2] = {v_art, v_cus};     // forward values of relation r (CSR by destination)
     const float* bval[2] = {vt_cus, vt_art};   // backward values of relation r (CSR by source)
@@ -383,7 +398,8 @@ int Exec::run() {
             if (!last && drop) xin[l][t] = l == 0 ? xin0[t] : take(n[t], cw[t]);
         }
         if (!last && drop && !(l == 0 && merged0))
-            dropout2(xcur[0], xin[l][0], n[0] * cw[0], (uint32_t)(l * 2 + 0), xcur[1], xin[l][1], n[1] * cw[1], (uint32_t)(l * 2 + 1));
+            dropout2(l == 0 ? MI_RANKER_LAUNCH_PREP_DROPOUT : MI_RANKER_LAUNCH_DROPOUT, xcur[0], xin[l][0], n[0] * cw[0],
+                     (uint32_t)(l * 2 + 0), xcur[1], xin[l][1], n[1] * cw[1], (uint32_t)(l * 2 + 1));
         on(1);
         join();    // each aggregation reads the OTHER type's input
         fork();
@@ -402,7 +418,7 @@ int Exec::run() {
                          cv.b_l, last ? 0 : 1);
             pr[r].k2 = cv.c_dst; pr[r].A2 = xin[l][dt]; pr[r].lda2 = cv.c_dst; pr[r].B2 = cv.w_r; pr[r].ldb2 = cv.c_dst;
         }
-        spmm2(fq, dst_of);   // relation 1 (destination: customers) is the small one
+        spmm2(MI_RANKER_LAUNCH_SPMM_FWD, fq, dst_of);   // relation 1 (destination: customers) is the small one
         on(1);
         join();
         products(pr, 2);
@@ -439,8 +455,9 @@ int Exec::run() {
                 q[t] = mi_pairs::BnSide{n[t], zpre[t], bn.gamma, bn.beta, bn.running_mean, bn.running_var, bn.momentum, bn.eps,
                                         bn_mean[t], bn_inv[t], z[t], nullptr, nullptr, nullptr, nullptr, bn_ws[t]};
             }
-            done = paired(mi_pairs::batchnorm_fwd_pair(q[0], q[1], C, s));
+            done = paired(MI_RANKER_LAUNCH_BN_FWD, mi_pairs::batchnorm_fwd_pair(q[0], q[1], C, s));
         }
+        if (!done) singles(MI_RANKER_LAUNCH_BN_FWD);
         for (int t = 0; t < kTypes && !done; ++t) {
             const mi_ranker_norm& bn = M.norm[t];
             on(t);
@@ -457,9 +474,13 @@ int Exec::run() {
     // the undropped concatenation has no other reader): one launch instead of gather + dropout
     bool gc_fused = false;
     if (go() && drop && LD > 1)
-        gc_fused = paired(mi_pairs::gather_cat_dropout(nl, C, C, B.label_row, B.label_col, z[0], z[1], h, M.p_dropout, B.seed, 64u,
+        gc_fused = paired(MI_RANKER_LAUNCH_GATHER_CAT_DROPOUT,
+                          mi_pairs::gather_cat_dropout(nl, C, C, B.label_row, B.label_col, z[0], z[1], h, M.p_dropout, B.seed, 64u,
                                                        (uint32_t)B.step, s));
-    if (go() && !gc_fused) ok(mi_gather_cat_f32(nl, C, C, B.label_row, B.label_col, z[0], C, z[1], C, h, 2 * C, (mi_stream_t)s));
+    if (go() && !gc_fused) {
+        singles(MI_RANKER_LAUNCH_GATHER_CAT_DROPOUT);
+        ok(mi_gather_cat_f32(nl, C, C, B.label_row, B.label_col, z[0], C, z[1], C, h, 2 * C, (mi_stream_t)s));
+    }
     float* din[MI_RANKER_MAX_LAYERS];
     float* dout[MI_RANKER_MAX_LAYERS];
     int64_t hw = 2 * C;
@@ -507,10 +528,12 @@ int Exec::run() {
         if (last && ln.out == 1) {   // Linear(in, 1): mi_linear1_bwd_f32 (as FusedRankerStep does)
             const size_t need = mi_linear1_bwd_workspace_bytes(nl, ln.in);
             char* w = take_bytes(need);
-            if (go() && !paired(mi_pairs::linear1_bwd_lastblock(nl, ln.in, dh, ln.w, din[j], dx, ln.gw, ln.b ? ln.gb : nullptr, w, need,
-                                                                 counters + 0, s)))
+            if (go() && !paired(MI_RANKER_LAUNCH_LINEAR1_BWD, mi_pairs::linear1_bwd_lastblock(nl, ln.in, dh, ln.w, din[j], dx, ln.gw,
+                                                                                               ln.b ? ln.gb : nullptr, w, need, counters + 0, s))) {
+                singles(MI_RANKER_LAUNCH_LINEAR1_BWD);
                 ok(mi_linear1_bwd_f32(nl, ln.in, dh, ln.w, din[j], ln.in, dx, ln.in, ln.gw, ln.b ? ln.gb : nullptr, w, need,
                                       (mi_stream_t)s));
+            }
             dh = dx;
             continue;   // the last layer has no dropout in front of its output and no relu behind it
         }
@@ -531,7 +554,10 @@ int Exec::run() {
     float* dz[2] = {dz_early[0], dz_early[1]};   // zero-filled by the prep launch
     fork();
     {
-        const bool done = go() && twin() && paired(mi_pairs::gather_cat_bwd_pair(nl, C, B.label_row, B.label_col, dh, 2 * C, dz[0], dz[1], s));
+        const bool done = go() && twin() &&
+                          paired(MI_RANKER_LAUNCH_GATHER_CAT_BWD,
+                                 mi_pairs::gather_cat_bwd_pair(nl, C, B.label_row, B.label_col, dh, 2 * C, dz[0], dz[1], s));
+        if (!done) singles(MI_RANKER_LAUNCH_GATHER_CAT_BWD);
         for (int t = 0; t < kTypes && !done; ++t) {
             on(t);
             if (go())
@@ -550,8 +576,9 @@ int Exec::run() {
                 q[t] = mi_pairs::BnSide{n[t], zpre[t], bn.gamma, nullptr, nullptr, nullptr, 0.f, 0.f, bn_mean[t], bn_inv[t], nullptr,
                                         dz[t], dxb[t], bn.gamma ? bn.g_gamma : nullptr, bn.gamma ? bn.g_beta : nullptr, bn_ws[t]};
             }
-            done = paired(mi_pairs::batchnorm_bwd_pair(q[0], q[1], C, s));
+            done = paired(MI_RANKER_LAUNCH_BN_BWD, mi_pairs::batchnorm_bwd_pair(q[0], q[1], C, s));
         }
+        if (!done) singles(MI_RANKER_LAUNCH_BN_BWD);
         for (int t = 0; t < kTypes; ++t) {
             const mi_ranker_norm& bn = M.norm[t];
             on(t);
@@ -597,7 +624,7 @@ int Exec::run() {
                 const int st = src_of[r];
                 bq[r] = mi_pairs::SpmmSide{n[st], cv.c_src, bptr[r], bcol[r], bval[r], dagg[r], nullptr, dxn[st], dxn[st]};
             }
-            spmm2(bq, src_of);
+            spmm2(MI_RANKER_LAUNCH_SPMM_BWD, bq, src_of);
             on(1);
         }
         // the weight gradients need nothing of the aggregations above: they run beside them.  Round 3: both relations'
@@ -620,7 +647,7 @@ int Exec::run() {
             } else {
                 const size_t need = mi_sage_wgrad_workspace_bytes(wq, 2);
                 char* w = take_bytes(need);
-                if (go()) ok(mi_sage_wgrad_f32(wq, 2, w, need, (mi_stream_t)s));
+                if (go()) merged(MI_RANKER_LAUNCH_WGRAD, mi_sage_wgrad_f32(wq, 2, w, need, (mi_stream_t)s));
             }
             if (need_x) {
                 for (int t = 0; t < kTypes; ++t) {
@@ -646,6 +673,7 @@ int Exec::run() {
             }
             pw[nw++] = prob(1, 0, cv.c_out, cv.c_dst, n[dt], dy[r], cv.c_out, xin[l][dt], cv.c_dst, cv.gw_r, cv.c_dst, mask[r]);
         }
+        singles(MI_RANKER_LAUNCH_WGRAD);
         products(pw, nw);
         if (need_x) {
             for (int t = 0; t < kTypes; ++t) {
@@ -661,7 +689,7 @@ int Exec::run() {
     if (n_wq > 0) {
         const size_t need = mi_sage_wgrad_workspace_bytes(wq_all, n_wq);
         char* w = take_bytes(need);
-        if (go()) ok(mi_sage_wgrad_f32(wq_all, n_wq, w, need, (mi_stream_t)s));
+        if (go()) merged(MI_RANKER_LAUNCH_WGRAD, mi_sage_wgrad_f32(wq_all, n_wq, w, need, (mi_stream_t)s));
     }
     if (oom) return MI_ERR_WORKSPACE;
     if (rc) return rc;
@@ -697,6 +725,7 @@ extern "C" int64_t mi_ranker_sizeof(int32_t which) {
         case 3: return (int64_t)sizeof(mi_ranker_norm);
         case 4: return (int64_t)sizeof(mi_ranker_linear);
         case 5: return (int64_t)sizeof(mi_ranker_param);
+        case 6: return (int64_t)sizeof(mi_ranker_launches);
         default: return -1;
     }
 }
@@ -715,16 +744,22 @@ extern "C" int mi_ranker_step_check(const mi_ranker_model* model, const mi_ranke
     return chk.run();
 }
 
-extern "C" int mi_ranker_step_f32(const mi_ranker_model* model, const mi_ranker_batch* batch, void* ws, size_t ws_bytes,
-                                  mi_stream_t stream) {
+extern "C" int mi_ranker_step_report_f32(const mi_ranker_model* model, const mi_ranker_batch* batch, void* ws, size_t ws_bytes,
+                                         mi_stream_t stream, mi_ranker_launches* report) {
+    if (report) memset(report, 0, sizeof(*report));
     MI_CHECK_ARG(model && batch && ws && mi_aligned16(ws));
     {
         Exec chk(*model, *batch, ws, ws_bytes, CHECK, (hipStream_t)stream);
         const int rc = chk.run();
         if (rc) return rc;
     }
-    Exec run(*model, *batch, ws, ws_bytes, LAUNCH, (hipStream_t)stream);
+    Exec run(*model, *batch, ws, ws_bytes, LAUNCH, (hipStream_t)stream, report);
     return run.run();
+}
+
+extern "C" int mi_ranker_step_f32(const mi_ranker_model* model, const mi_ranker_batch* batch, void* ws, size_t ws_bytes,
+                                  mi_stream_t stream) {
+    return mi_ranker_step_report_f32(model, batch, ws, ws_bytes, stream, nullptr);
 }
 
 extern "C" int mi_ranker_adam_f32(const mi_ranker_model* model, float grad_scale, mi_stream_t stream) {

@@ -166,10 +166,14 @@ class NativeRankerStep:
         self._ws_dims = None       # the largest (customers, articles, edges, label edges) the workspace was sized for
         self._adam_step = 0
         self.declined: Optional[str] = None
+        self._launches = _lib.RankerLaunches()     # filled by every step: mi_ranker_step_report_f32
+        self._launches_ref = ctypes.byref(self._launches)
+        self._reported = False
         # a second stream for the customer-side twins of independent launch pairs (mi_ranker_batch.aux_stream).  OFF by
         # default: measured at the H&M shape, 24 users per batch (round 3): 0.775 ms per iteration with it against 0.750
         # without — eight fork / join event pairs per iteration cost more than running 5-20 us kernels side by side returns.
-        # LAPLACE_RANKER_AUX=1 switches it on (results are identical either way: tests/test_gpu_ranker.py).
+        # LAPLACE_RANKER_AUX=1 switches it on (results are identical either way, bit for bit: tests/test_gpu_ranker_pairs.py
+        # runs every case of tests/ranker_step_cases.py both ways).
         self._aux = None
         if os.environ.get("LAPLACE_RANKER_AUX", "0") == "1":
             dev = next(model.parameters()).device
@@ -231,6 +235,12 @@ class NativeRankerStep:
     @classmethod
     def supports(cls, model, optimizer) -> bool:
         return cls.unsupported_reason(model, optimizer) is None
+
+    @property
+    def last_launches(self) -> Optional[Dict[str, tuple]]:
+        """{kind: (merged, single)} of the last step — which of its twin steps went out as one launch and which as two single
+        launches (include/laplace_hip.h: mi_ranker_launches) — or None when that step was declined."""
+        return self._launches.as_dict() if self._reported else None
 
     # ------------------------------------------------------------------------------------------
     def _build(self) -> RankerModel:
@@ -364,6 +374,7 @@ class NativeRankerStep:
         rank the decision is collective (native_binding): every rank returns None when ANY rank's batch is declined, so all of
         them take the caller's fallback together (`declined` then names the local reason, or says that a peer declined)."""
         self.declined = None       # why the last call returned None (diagnostics)
+        self._reported = False
         prep, go = collective_prepare(self._world(), lambda mine: self._all_ranks_take_it(mine, next(self.model.parameters()).device),
                                       lambda: self._prepare(x_dict, edge_index_dict, edge_label_index, labels))
         if not go:
@@ -373,16 +384,19 @@ class NativeRankerStep:
         d, b, loss, steps, _keep = prep
         group = self.optimizer.param_groups[0]
         L = _lib.lib()
-        rc = L.mi_ranker_step_f32(ctypes.byref(d), ctypes.byref(b), self._ws.data_ptr(), self._ws.numel(), _lib.current_stream())
+        rc = L.mi_ranker_step_report_f32(ctypes.byref(d), ctypes.byref(b), self._ws.data_ptr(), self._ws.numel(), _lib.current_stream(),
+                                         self._launches_ref)
         if rc == _lib.MI_ERR_WORKSPACE:        # (found by the validation pass: nothing enqueued) the skipped counting pass after all
             self._recount_workspace(d, b)
-            rc = L.mi_ranker_step_f32(ctypes.byref(d), ctypes.byref(b), self._ws.data_ptr(), self._ws.numel(), _lib.current_stream())
+            rc = L.mi_ranker_step_report_f32(ctypes.byref(d), ctypes.byref(b), self._ws.data_ptr(), self._ws.numel(),
+                                             _lib.current_stream(), self._launches_ref)
         if rc == _lib.MI_ERR_UNSUPPORTED:
             if self._world() > 1:              # cannot happen: mi_ranker_step_check took the same descriptors
                 raise _lib.MiError("mi_ranker_step_f32 declined a batch its own validation pass had accepted")
             self.declined = "mi_ranker_step_f32: MI_ERR_UNSUPPORTED (shape outside the executor's)"
             return None
         _lib.check(rc, "mi_ranker_step_f32")
+        self._reported = True
         self.iteration += 1
         if self.before_step is not None:       # gradients are in param.grad: exchange them, then torch's own update
             self.before_step()

@@ -72,12 +72,20 @@ def hetero_reduce(outs: List[Tensor], aggr: str) -> Tensor:
     return out
 
 
+def _dropout(x: Tensor, p: Optional[float], training: bool, fixed: Optional[Dict[int, Tensor]], site: int) -> Tensor:
+    """F.dropout, or — with `fixed` (RankerRef.set_dropout_masks) — the multiplication by the given multiplier of this site."""
+    if fixed is not None and training:
+        return x * fixed[site]
+    return F.dropout(x, p=p, training=training)
+
+
 class HeteroEncoderRef(nn.Module):
     def __init__(self, dims: List[Dict[str, Tuple[int, int, int]]], aggr_conv: str, aggr_hetero: str,
                  p_dropout_features: Optional[float]):
         """dims[l][key] = (in_src, in_dst, out) for layer l and relation key."""
         super().__init__()
         self.aggr_hetero, self.p = aggr_hetero, p_dropout_features
+        self.fixed_masks, self.type_index = None, {}     # RankerRef.set_dropout_masks
         self.layers = nn.ModuleList([nn.ModuleDict({k: SAGEConvRef(a, b, c, aggr_conv) for k, (a, b, c) in layer.items()})
                                      for layer in dims])
 
@@ -86,7 +94,8 @@ class HeteroEncoderRef(nn.Module):
         for index, convs in enumerate(self.layers):
             last = index == n - 1
             if not last and self.p is not None:
-                x_dict = {k: F.dropout(v, p=self.p, training=self.training) for k, v in x_dict.items()}
+                x_dict = {k: _dropout(v, self.p, self.training, self.fixed_masks, 2 * index + self.type_index.get(k, 0))
+                          for k, v in x_dict.items()}
             by_dst: Dict[str, List[Tensor]] = {}
             for et, ei in edge_index_dict.items():
                 if _key(et) not in convs:
@@ -103,6 +112,7 @@ class DecoderRef(nn.Module):
         super().__init__()
         self.layers = nn.ModuleList([nn.Linear(a, b) for a, b in sizes])
         self.p, self.user_key, self.item_key = p, user_key, item_key
+        self.fixed_masks = None                          # RankerRef.set_dropout_masks
 
     def forward(self, z_dict, edge_label_index):
         ci, ai = edge_label_index
@@ -112,7 +122,7 @@ class DecoderRef(nn.Module):
                 z = layer(z)
             else:
                 if self.p is not None:
-                    z = F.dropout(z, p=self.p, training=self.training)
+                    z = _dropout(z, self.p, self.training, self.fixed_masks, 64 + i)
                 z = layer(z).relu()
         return z.view(-1)
 
@@ -140,6 +150,13 @@ class RankerRef(nn.Module):
                     e.weight.requires_grad_(False)
                     mods.append(e)
                 self.embedding_layers[k] = mods
+
+    def set_dropout_masks(self, masks: Optional[Dict[int, Tensor]]) -> None:
+        """Training-mode dropouts multiply by masks[site] (0 where dropped, 1 / (1 - p) where kept; the input's shape) instead
+        of drawing from torch's generator; None restores F.dropout.  Sites as the native executor numbers them: 2 l + t in
+        front of encoder layer l for node type t (0 = customer, 1 = article), 64 + j in front of decoder layer j."""
+        self.encoder.fixed_masks = self.decoder.fixed_masks = masks
+        self.encoder.type_index = {self.user_key: 0, self.item_key: 1}
 
     def embed(self, x_dict):
         out = dict(x_dict)
