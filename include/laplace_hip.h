@@ -1892,6 +1892,61 @@ int     mi_als_solve_rows_f32(int64_t n_rows, int64_t d, const int32_t* ptr, con
                               const int32_t* row_list, int64_t n_list, int32_t* n_failed, void* ws, size_t ws_bytes,
                               mi_stream_t stream);
 
+/* ------------------------------------------------------------------------------------
+ * iALS block  implicit-feedback ALS, block row solver (additive to ABI 14; csrc/als_block.hip).
+ * replaces: nothing in the reference.  The iALS entry above forms and factorises one d x d system per row; this entry
+ *           minimises the same row quadratic 1/2 x^T A x - b^T x (A and b of the iALS entry) exactly over one block of
+ *           B coordinates at a time, as iALS++ does (Rendle, Krichene, Zhang and Koren, RecSys 2021): the largest system is
+ *           B x B, the width goes to 256, and a row of n entries costs about 2 n d B + 2 d^2 + d B^2 / 3 flop per sweep.
+ *           It is a ROW-LOCAL variant.  The paper's outer loop runs over blocks, with all users and then all items inside
+ *           it, and keeps the predictions of all pairs in memory between steps; here a half-sweep walks all blocks of one row
+ *           before the next row, which makes it one launch, and the predictions p_e never outlive the row's wavefront.
+ * Inputs.  As the iALS entry: a CSR over Y [n_cols, d] (ldy), G [d, d] of which only G[j][k] with k <= j is read
+ *   (G(j, k) below is G[max(j, k)][min(j, k)]), alpha >= 0, reg > 0; and block B in {16, 32, 64}, sweeps in 1 .. 64, from_zero.
+ *   X [n_work, d] (ldx) is IN/OUT: a row starts from its current content of X (from the place its result goes to, i.e. by list
+ *   position with a row_list), or from 0 when from_zero is not 0 (X is then not read).
+ * The rule, per row r with entries e_0 .. e_{n-1} in CSR order (y_e = Y[idx[e], :]) and start x, restated in float64 and in
+ * float32 by tests/als_block_emulation.py.  "dot16(u, v, m)" for vectors over m columns is: 16 chains t_c, c = 0 .. 15,
+ * t_c = fmaf(u[c + 16 i], v[c + 16 i], t_c) from 0 over i ascending while c + 16 i < m, then added pairwise as a tree at
+ * distances 8, 4, 2, 1 (t_c + t_{c ^ 8}, ...).
+ *   start     p_e = dot16(y_e, x, d) for every entry; exactly 0 under from_zero.
+ *   for t in 0 .. sweeps-1, for c in 0 .. ceil(d / B)-1, pi = [c B, min((c + 1) B, d)) (the last block may be partial):
+ *     w_e     = fmaf(alpha, p_e, -(1.0f + alpha))
+ *     q[j]    = sum_k G(j, k) x[k], j in pi, over ALL k < d, from the CURRENT x: 64 / B chains, chain m = fmaf(G(j, k), x[k],
+ *               acc) from 0 over the groups of four columns k = 4 u .. 4 u + 3, u = m, m + 64 / B, .. ascending, the chains
+ *               added in ascending m.
+ *     gs[j]   = sum_e w_e y_e[j], ONE chain acc = fmaf(y_e[j], w_e, acc) from 0 over ALL the row's entries in order.
+ *     g[j]    = fmaf(reg, x[j], gs[j] + q[j])
+ *     S[j][k] = sum_e y_e[j] y_e[k], ONE chain acc = fmaf(y_e[j], y_e[k], acc) from 0 over ALL the row's entries in order;
+ *     H[j][k] = fmaf(alpha, S[j][k], G(j, k)), + reg on the diagonal (H[j][j] = fmaf(..) + reg),   j, k in pi
+ *     delta   solves H delta = -g by an f32 Cholesky of the |pi| x |pi| system; the order inside it is the kernel's and NOT part
+ *               of the rule.
+ *     x[j]    = x[j] + delta[j], j in pi;   p_e = p_e + dot16(y_e[pi], delta, |pi|)   (not after the very last step)
+ *   There are no chunks in any sum: a row is walked by one wavefront, so the order is a function of (the row's entries in
+ *   order, d, B, sweeps) alone, never of the device, the grid or the other rows.  mi_als_block_chunk(d, B) is the one
+ *   constant that changes the kernel's PATH: a row of at most that many entries keeps its factor rows and p_e on chip, a
+ *   longer one re-gathers its block columns per block and keeps p_e in the workspace, by entry position.  Both paths run
+ *   the sums above in the same order and give the same bits.
+ *   empty row x_r = 0 (also with a start).
+ *   pivot     A pivot that is not a positive finite number, in any block step: x_r = 0 and *n_failed is incremented by one (an
+ *             int32 device counter the CALLER zeroes; an integer atomic).
+ * No float atomics anywhere: two calls give equal bits, and a row alone gives the bits it has in a batch or through row_list.
+ * row_list / n_list: as the iALS entry (distinct ids; X compact by list position; an id outside [0, n_rows) gives a zero row).
+ * Guards.  idx[e] outside [0, n_cols) contributes a zero row y_e.  A rowptr that runs past nnz is treated as a failed pivot.
+ * Workspace: mi_als_block_rows_workspace_bytes(n_work, nnz, d, block) = d * d * 4 bytes (G(j, k) written out as a full
+ *   matrix by a first small kernel) and 4 bytes per entry (at least one), each rounded up to 256.
+ * Returned before anything is enqueued: MI_ERR_BAD_ARG (d % 4 != 0, d < 4 or d > 256, block not 16, 32 or 64, sweeps outside
+ *   1 .. 64, and everything the iALS entry refuses), MI_ERR_WORKSPACE (ws null or short).  Zero rows: 0, nothing enqueued.
+ * mi_als_block_chunk: 0 for a shape the entry refuses.
+ * ---------------------------------------------------------------------------------- */
+int32_t mi_als_block_chunk(int64_t d, int64_t block);
+size_t  mi_als_block_rows_workspace_bytes(int64_t n_work, int64_t nnz, int64_t d, int64_t block);
+int     mi_als_block_rows_f32(int64_t n_rows, int64_t d, int64_t block, int64_t sweeps, const int32_t* ptr,
+                              const int32_t* idx, int64_t nnz, int64_t n_cols, const float* Y, int64_t ldy, const float* G,
+                              float alpha, float reg, float* X /* in/out */, int64_t ldx, int32_t from_zero,
+                              const int32_t* row_list, int64_t n_list, int32_t* n_failed, void* ws, size_t ws_bytes,
+                              mi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,9 +7,13 @@ topk_for_users, ops.rank_of_items, get_full_rank_metrics_lightgcn, save_predicti
 unchanged.  A half-sweep is ONE launch of ops.als_solve_rows (csrc/als.hip; the rule is stated in include/laplace_hip.h) after
 one d x d Gram product (ops.gemm): with the other table Y fixed, row r becomes the solution of
     (Y^T Y + alpha * sum_e y_e y_e^T + reg I) x = (1 + alpha) * sum_e y_e        over the entries e of row r.
+With solver="block" the one launch is ops.als_block_rows (csrc/als_block.hip, "iALS block" in the header) instead: a row-local
+iALS++ (Rendle et al., RecSys 2021) that warm-starts from the table and minimises the same row quadratic exactly over one
+block of `block` coordinates at a time, `block_sweeps` passes per half-sweep; it is the only solver for dim > 128 (up to 256).
 
-Not built: frequency-scaled regularisation, per-edge confidences, the CG and iALS++ block solvers, dim > 128, a sharded form,
-bf16, and the matcher's entry in get_matchers / tools/e2e_hm_scale.py's chain.
+Not built: frequency-scaled regularisation, per-edge confidences, the CG solver, the paper's block-outer schedule of iALS++
+(all rows inside one block step, predictions of all pairs kept between steps), hub rows split over workgroups, dim > 256, a
+sharded form, bf16, and the matcher's entry in get_matchers / tools/e2e_hm_scale.py's chain.
 """
 from __future__ import annotations
 
@@ -23,6 +27,7 @@ from .interactions import Interactions
 from .reporting.types import Stats
 
 SIDES = ("users", "items")
+SOLVERS = ("cholesky", "block")
 
 
 class ImplicitALS(t.nn.Module):
@@ -31,9 +36,21 @@ class ImplicitALS(t.nn.Module):
     deduplicated."""
 
     def __init__(self, num_users: int, num_items: int, dim: int = 64, alpha: float = 1.0, reg: float = 20.0, seed: int = 0,
-                 init_std: float = 0.1):
+                 init_std: float = 0.1, solver: str = "cholesky", block: int = 16, block_sweeps: int = 1,
+                 fold_in_sweeps: int = 4):
         super().__init__()
-        ops.check_als(dim, alpha, reg)
+        if solver not in SOLVERS:
+            raise ValueError(f"solver must be one of {SOLVERS}, got {solver!r}")
+        if solver == "block":
+            ops.check_als_block(dim, block, block_sweeps, alpha, reg)
+            ops.check_als_block(dim, block, fold_in_sweeps, alpha, reg)
+        else:
+            if isinstance(dim, int) and dim > ops.ALS_MAX_DIM:
+                raise ValueError(f"dim {dim} > {ops.ALS_MAX_DIM} requires solver=\"block\" (the Cholesky solver holds one "
+                                 f"dim x dim system per workgroup in LDS)")
+            ops.check_als(dim, alpha, reg)
+        self.solver, self.block = solver, int(block)
+        self.block_sweeps, self.fold_in_sweeps = int(block_sweeps), int(fold_in_sweeps)
         self.num_users, self.num_items, self.dim = int(num_users), int(num_items), int(dim)
         self.alpha, self.reg = float(alpha), float(reg)
         gen = t.Generator().manual_seed(int(seed))   # drawn on the host: the same tables whatever the device
@@ -63,7 +80,11 @@ class ImplicitALS(t.nn.Module):
         return mine.weight.data, other.weight.data
 
     def _solve(self, csr: ops.DeviceCSR, fixed: Tensor, out: Optional[Tensor]) -> Tuple[Tensor, Tensor]:
+        """`out` is the table of a half-sweep (the block solver's start as well) or None for a fold-in (a zero start)."""
         gram = ops.gemm(fixed, fixed, trans_a=True, trans_b=False)
+        if self.solver == "block":
+            return ops.als_block_rows(csr, fixed, gram, alpha=self.alpha, reg=self.reg, block=self.block, x=out,
+                                      sweeps=self.block_sweeps if out is not None else self.fold_in_sweeps)
         return ops.als_solve_rows(csr, fixed, gram, alpha=self.alpha, reg=self.reg, out=out)
 
     def half_sweep(self, side: str, interactions: Optional[Interactions] = None) -> Tensor:
@@ -93,7 +114,8 @@ class ImplicitALS(t.nn.Module):
 
     def fold_in(self, ptr: Tensor, idx: Tensor) -> Tensor:
         """Vectors [len(ptr) - 1, dim] for rows that are not in the model — an int32 CSR (ptr, idx) over ITEM ids — against
-        the current item table: a user half-sweep on another CSR, so a new interaction is seen at once."""
+        the current item table: a user half-sweep on another CSR, so a new interaction is seen at once.  The block solver
+        starts these rows from zero and makes fold_in_sweeps passes over them."""
         csr = ops.DeviceCSR(int(ptr.numel()) - 1, self.num_items, ptr, idx)
         x, failed = self._solve(csr, self.items_emb.weight.data, None)
         n = int(failed.item())
@@ -121,7 +143,8 @@ class ImplicitALS(t.nn.Module):
 
 def train(config, *, edge_index: Tensor, num_users: int, num_articles: int, dim: int = 64, alpha: float = 1.0,
           reg: float = 20.0, epochs: int = 3, seed: int = 0, device: str = "cuda", save_dir: Optional[str] = None,
-          full_rank_ks: Optional[Tuple[int, ...]] = (12, 100), verbose: bool = True) -> Stats:
+          full_rank_ks: Optional[Tuple[int, ...]] = (12, 100), verbose: bool = True, solver: str = "cholesky",
+          block: int = 16, block_sweeps: int = 1) -> Stats:
     """run_pipeline_lightgcn.train with iALS in the trainer's place: the same split (create_dataloaders_lightgcn), the ranking
     metrics @ config.k on validation and test, evaluation_full_rank on the test split and save_predictions — the same three
     files (lightgcn_output.pt and the two tables) that data.matching.LightGCNMatcher consumes.  Stats.loss is the objective
@@ -131,7 +154,8 @@ def train(config, *, edge_index: Tensor, num_users: int, num_articles: int, dim:
     from .utils.metrics_lightgcn import get_metrics_lightgcn
     (_, _, _, train_edges, val_edges, test_edges, all_edges, num_users,
      num_articles) = create_dataloaders_lightgcn(edge_index, num_users, num_articles, compat="bipartite", device=device)
-    model = ImplicitALS(num_users, num_articles, dim=dim, alpha=alpha, reg=reg, seed=seed).to(device)
+    model = ImplicitALS(num_users, num_articles, dim=dim, alpha=alpha, reg=reg, seed=seed, solver=solver, block=block,
+                        block_sweeps=block_sweeps).to(device)
     inter = Interactions(train_edges, num_users, num_articles)
 
     def log(epoch: int, m: ImplicitALS) -> None:

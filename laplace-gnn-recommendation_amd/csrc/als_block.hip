@@ -1,0 +1,391 @@
+// Implicit ALS, block row solver (include/laplace_hip.h "iALS block", additive to ABI 14): a row-local iALS++ (Rendle et al.,
+// RecSys 2021).  Instead of one d x d system per row (csrc/als.hip) a row's quadratic is minimised exactly over one block of
+// B coordinates at a time: the largest system on chip is B x B, the width goes to 256, and a short row costs about
+// 2 n d B + 2 d^2 + d B^2 / 3 flop per sweep instead of 2 n d^2 + d^3 / 3.  The numerics (the order of every sum) are the
+// header's rule; this comment is about the layout.
+//
+// One WAVEFRONT per row, four rows per workgroup, no workgroup barrier anywhere: everything a row needs is private to its
+// wavefront (its quarter of the LDS), so a step of the small factorisation costs a wavefront-scope fence instead of a
+// barrier with three other wavefronts waiting on it, and four short rows share a workgroup.  A hub row is walked by its
+// one wavefront (profiles/als_block.md has the tail that causes).
+//
+// Factor rows.  A row of at most R = mi_als_block_chunk(d, B) entries is RESIDENT: its factor rows are gathered once, with
+// 16-byte loads, into the wavefront's 16 KiB area as [entry][LDR] floats, and its predictions p_e live in LDS.  A longer row
+// STREAMS: per block it re-gathers the block's B columns of KT entries at a time (64-byte pieces of a row at B = 16) into the
+// same area as [entry][LDB], once for the Gram pass and once for the prediction update, and keeps p_e in the workspace at
+// the entry's position in idx.  Both forms run the same arithmetic in the same order, so the bits do not depend on which one
+// a row took.  LDR and LDB are 16 mod 32 floats: the 16 columns x 2 entries that a half-wave of a ds_read_b32 touches fall
+// on 32 different banks.
+//
+// Block step.  v_mfma_f32_16x16x4_f32 takes A[i = lane & 15][k = lane >> 4] and B[k = lane >> 4][j = lane & 15].  With the
+// ENTRIES as k, the operand of tile row ti is one ds_read_b32 (column 16 ti + i of entry 4 step + k) and serves as A of the
+// tiles (ti, .) and as B of the tiles (., ti): the lower-triangle tiles of the block Gram (1, 3 or 10 at B = 16, 32, 64) are
+// one fmaf chain over the row's entries each.  The gradient's sum_e w_e y_e[j] rides on the same instruction: the B operand
+// is w_e for every column, so every column of the result tile holds the sum.  q = G[pi, :] x is B x (64 / B) lanes of
+// partial chains over rows of G with 16-byte loads from L2: a first small kernel writes G(j, k) = G[max][min] out as a full
+// matrix into the workspace, so that a row of it is contiguous (the caller's upper triangle is never read).  The B x B
+// Cholesky runs in the wavefront's LDS, lanes as a B x (64 / B) grid over (row, column group), the right-hand side carried in
+// one register per lane (forward substitution inside the factorisation's step, x_k handed round by a lane shuffle, as the
+// backward substitution).
+#include "common.hpp"
+
+namespace {
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+constexpr int AB_WAVES = 4;       // rows per workgroup, one wavefront each
+constexpr int AB_AREA = 4096;     // floats of LDS per wavefront for factor rows
+constexpr int AB_MAX_D = 256;
+constexpr int AB_MAX_RES = 256;   // entries of p_e kept in LDS
+
+// the smallest stride >= w that is 16 mod 32
+__host__ __device__ constexpr int ab_ld(int w) { return (w + 15) / 32 * 32 + 16; }
+__host__ __device__ constexpr int ab_res_of(int d) {
+    return (AB_AREA / ab_ld(d) & ~3) < AB_MAX_RES ? (AB_AREA / ab_ld(d) & ~3) : AB_MAX_RES;
+}
+
+struct AbArgs {
+    int n_rows, d, n_cols, n_work, nnz, sweeps, from_zero;
+    const int32_t* ptr;
+    const int32_t* idx;
+    const float* Y;
+    int64_t ldy;
+    float alpha, reg;
+    float* X;
+    int64_t ldx;
+    const int32_t* row_list;
+    int32_t* n_failed;
+    float* Gs;   // workspace: G(j, k) as a full symmetric matrix
+    float* pw;   // workspace: p_e of the streaming rows, by entry position
+};
+
+__global__ void als_block_sym_kernel(const float* G, float* Gs, int d) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= d * d) return;
+    const int j = i / d, k = i - j * d;
+    Gs[i] = G[k <= j ? j * d + k : k * d + j];
+}
+
+// What one lane wrote (LDS, or the row's own workspace entries) is read by the other lanes of ITS wavefront behind this.
+__device__ __forceinline__ void ab_wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// Entries [q0, q0 + cnt) of idx, columns [col0, col0 + 4 W4) of their factor rows, to dst[e][ld]; columns at or beyond d,
+// entries with an id outside the table and the entries from cnt up to the next multiple of 4 are staged as zeros.
+__device__ __forceinline__ void ab_gather(const AbArgs& a, int q0, int cnt, int col0, int W4, float* dst, int ld) {
+    const int lane = mi_lane();
+    const int slots = ((cnt + 3) & ~3) * W4;
+    for (int f = lane; f < slots; f += MI_WAVE) {
+        const int e = f / W4, c4 = f - e * W4;
+        float4 v = mi_f4_zero();
+        if (e < cnt && col0 + 4 * c4 < a.d) {
+            const int col = a.idx[q0 + e];
+            if ((unsigned)col < (unsigned)a.n_cols) v = *reinterpret_cast<const float4*>(a.Y + (int64_t)col * a.ldy + col0 + 4 * c4);
+        }
+        *reinterpret_cast<float4*>(dst + e * ld + 4 * c4) = v;
+    }
+}
+
+// t_e = sum over the first 16 nt columns of src[e][.] * vec[.] for the staged entries e < cnt: 16 lanes per entry, lane c a
+// chain over columns c, c + 16, ..; the 16 chains added pairwise at lane distances 8, 4, 2, 1.  sink(e, t_e) on one lane.
+template <class F>
+__device__ __forceinline__ void ab_dots(const float* src, int ld, int cnt, const float* vec, int nt, F&& sink) {
+    const int lane = mi_lane(), c = lane & 15;
+    for (int e4 = 0; e4 < cnt; e4 += 4) {
+        const int e = e4 + (lane >> 4);
+        float tsum = 0.f;
+        for (int i = 0; i < nt; ++i) tsum = fmaf(src[e * ld + c + 16 * i], vec[c + 16 * i], tsum);
+        tsum += __shfl_xor(tsum, 8, MI_WAVE);
+        tsum += __shfl_xor(tsum, 4, MI_WAVE);
+        tsum += __shfl_xor(tsum, 2, MI_WAVE);
+        tsum += __shfl_xor(tsum, 1, MI_WAVE);
+        if (c == 0 && e < cnt) sink(e, tsum);
+    }
+}
+
+template <int B>
+__global__ __launch_bounds__(AB_WAVES * MI_WAVE) void als_block_kernel(AbArgs a) {
+    constexpr int TB = B / 16, JG = 64 / B, HB = B + 1;
+    constexpr int LDB = ab_ld(B), KT = B == 64 ? 48 : 64;
+    static_assert(KT * LDB <= AB_AREA && KT % 4 == 0, "a streamed chunk fits the area");
+    __shared__ __align__(16) float s_area[AB_WAVES][AB_AREA];
+    __shared__ float s_h[AB_WAVES][B * HB];
+    __shared__ __align__(16) float s_x[AB_WAVES][AB_MAX_D];
+    __shared__ float s_p[AB_WAVES][AB_MAX_RES];
+    __shared__ float s_dl[AB_WAVES][64];
+    __shared__ float s_gt[AB_WAVES][64];
+    const int wave = threadIdx.x >> 6, lane = mi_lane();
+    const int pos = blockIdx.x * AB_WAVES + wave;
+    if (pos >= a.n_work) return;
+    float* area = s_area[wave];
+    float* Hs = s_h[wave];
+    float* xs = s_x[wave];
+    float* ps = s_p[wave];
+    float* dl = s_dl[wave];
+    float* gt = s_gt[wave];
+    const int d = a.d, LDR = ab_ld(d), RES = ab_res_of(d), d16 = (d + 15) & ~15;
+    const int r = a.row_list ? a.row_list[pos] : pos;
+    float* xout = a.X + (int64_t)pos * a.ldx;
+    int p0 = 0, n = 0;
+    if ((unsigned)r < (unsigned)a.n_rows) {
+        p0 = a.ptr[r];
+        n = a.ptr[r + 1] - p0;
+    }
+    if (n <= 0) {
+        for (int k = lane; k < d; k += MI_WAVE) xout[k] = 0.f;
+        return;
+    }
+    bool failed = p0 < 0 || n > a.nnz - p0;   // a rowptr that disagrees with nnz: nothing of idx is read for this row
+    const bool resident = n <= RES;
+    const float c1 = -(1.0f + a.alpha);
+    if (!failed) {
+        for (int k = lane; k < d16; k += MI_WAVE) xs[k] = (k < d && !a.from_zero) ? xout[k] : 0.f;
+        if (resident) ab_gather(a, p0, n, 0, LDR / 4, area, LDR);
+        ab_wave_sync();
+        // p_e = y_e . x
+        if (a.from_zero) {
+            for (int e = lane; e < n; e += MI_WAVE) {
+                if (resident) ps[e] = 0.f; else a.pw[p0 + e] = 0.f;
+            }
+        } else if (resident) {
+            ab_dots(area, LDR, n, xs, d16 / 16, [&](int e, float v) { ps[e] = v; });
+        } else {
+            for (int c0 = 0; c0 < n; c0 += RES) {
+                const int cnt = min(RES, n - c0);
+                ab_gather(a, p0 + c0, cnt, 0, LDR / 4, area, LDR);
+                ab_wave_sync();
+                ab_dots(area, LDR, cnt, xs, d16 / 16, [&](int e, float v) { ps[e] = v; });
+                ab_wave_sync();
+                for (int e = lane; e < cnt; e += MI_WAVE) a.pw[p0 + c0 + e] = ps[e];
+                ab_wave_sync();
+            }
+        }
+        ab_wave_sync();
+    }
+    const int nblk = (d + B - 1) / B;
+    const int arow = lane >> 4, acol = lane & 15;
+    for (int t = 0; t < a.sweeps && !failed; ++t) {
+        for (int c = 0; c < nblk && !failed; ++c) {
+            const int cB = c * B, bw = min(B, d - cB), bt = (bw + 15) >> 4;
+            // the block's own part of G, in the C layout of the tiles: in flight under everything up to the Gram pass
+            f32x4 gb[TB][TB];
+#pragma unroll
+            for (int ti = 0; ti < TB; ++ti) {
+#pragma unroll
+                for (int tj = 0; tj <= ti; ++tj) {
+#pragma unroll
+                    for (int g = 0; g < 4; ++g) {
+                        const int row = 16 * ti + 4 * arow + g, col = 16 * tj + acol;
+                        gb[ti][tj][g] = (row < bw && col <= row) ? a.Gs[(cB + row) * d + cB + col] : 0.f;
+                    }
+                }
+            }
+            // q[j] = sum_k G(j, k) x[k]: lane (j, kg) takes the groups of four columns kg, kg + JG, .. as one chain; the JG
+            // chains are added in ascending kg
+            const int j = lane & (B - 1), kg = lane / B;
+            float qv = 0.f;
+            if (j < bw) {
+                const float4* grow = reinterpret_cast<const float4*>(a.Gs + (cB + j) * d);
+                const float4* x4 = reinterpret_cast<const float4*>(xs);
+#pragma unroll 8
+                for (int k4 = kg; k4 < d / 4; k4 += JG) {
+                    const float4 gv = grow[k4], xv = x4[k4];
+                    qv = fmaf(gv.x, xv.x, qv);
+                    qv = fmaf(gv.y, xv.y, qv);
+                    qv = fmaf(gv.z, xv.z, qv);
+                    qv = fmaf(gv.w, xv.w, qv);
+                }
+            }
+            float q = __shfl(qv, j, MI_WAVE);
+#pragma unroll
+            for (int g = 1; g < JG; ++g) q += __shfl(qv, j + B * g, MI_WAVE);
+            // the block Gram and sum_e w_e y_e[j], the entries as k of the matrix instruction
+            f32x4 acc[TB][TB], gacc[TB];
+#pragma unroll
+            for (int ti = 0; ti < TB; ++ti) {
+                gacc[ti] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int tj = 0; tj < TB; ++tj) acc[ti][tj] = f32x4{0.f, 0.f, 0.f, 0.f};
+            }
+            auto gram = [&](const float* src, int ld, int col0, int cnt) {   // p_e of the staged entries is ps[e]
+                for (int e4 = 0; e4 < cnt; e4 += 4) {
+                    const int e = e4 + arow;
+                    float w = 0.f;
+                    if (e < cnt) w = fmaf(a.alpha, ps[e], c1);
+                    float op[TB];
+#pragma unroll
+                    for (int ti = 0; ti < TB; ++ti) op[ti] = ti < bt ? src[e * ld + col0 + 16 * ti + acol] : 0.f;
+#pragma unroll
+                    for (int ti = 0; ti < TB; ++ti) {
+                        if (ti < bt) {
+#pragma unroll
+                            for (int tj = 0; tj <= ti; ++tj)
+                                acc[ti][tj] = __builtin_amdgcn_mfma_f32_16x16x4f32(op[ti], op[tj], acc[ti][tj], 0, 0, 0);
+                            gacc[ti] = __builtin_amdgcn_mfma_f32_16x16x4f32(op[ti], w, gacc[ti], 0, 0, 0);
+                        }
+                    }
+                }
+            };
+            if (resident) {
+                gram(area, LDR, cB, n);
+            } else {
+                for (int c0 = 0; c0 < n; c0 += KT) {
+                    const int cnt = min(KT, n - c0);
+                    ab_gather(a, p0 + c0, cnt, cB, B / 4, area, LDB);
+                    if (lane < cnt) ps[lane] = a.pw[p0 + c0 + lane];
+                    ab_wave_sync();
+                    gram(area, LDB, 0, cnt);
+                    ab_wave_sync();
+                }
+            }
+            // H = fmaf(alpha, S, G) + reg I (lower triangle) and the gradient, to LDS
+#pragma unroll
+            for (int ti = 0; ti < TB; ++ti) {
+                if (ti >= bt) continue;
+#pragma unroll
+                for (int tj = 0; tj <= ti; ++tj) {
+                    const int col = 16 * tj + acol;
+#pragma unroll
+                    for (int g = 0; g < 4; ++g) {
+                        const int row = 16 * ti + 4 * arow + g;
+                        if (row < bw && col <= row) {
+                            float v = fmaf(a.alpha, acc[ti][tj][g], gb[ti][tj][g]);
+                            if (row == col) v = v + a.reg;
+                            Hs[row * HB + col] = v;
+                        }
+                    }
+                }
+                if (acol == 0) {
+#pragma unroll
+                    for (int g = 0; g < 4; ++g) gt[16 * ti + 4 * arow + g] = gacc[ti][g];
+                }
+            }
+            ab_wave_sync();
+            // H delta = -g: right-looking Cholesky, lane (i, jg) updates row i's columns k + 1 + jg, + JG, ..; lane l < bw
+            // carries element l of the right-hand side through the forward and the backward substitution
+            float v = lane < bw ? -fmaf(a.reg, xs[cB + lane], gt[lane] + q) : 0.f;
+            float myinv = 0.f;
+            const int i = j, jg = kg;
+            for (int k = 0; k < bw; ++k) {
+                const float pv = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(Hs[k * HB + k])));
+                if (!(pv > 0.f && pv < INFINITY)) {
+                    failed = true;   // the same word for every lane: the whole wavefront leaves here
+                    break;
+                }
+                const float inv = 1.0f / sqrtf(pv);
+                if (lane == k) myinv = inv;
+                const bool below = i > k && i < bw;
+                const float li = below ? Hs[i * HB + k] * inv : 0.f;
+                const float yk = __shfl(v, k, MI_WAVE) * inv;
+                if (lane == k) v = yk;
+                else if (lane > k && lane < bw) v = fmaf(-li, yk, v);
+                if (below) {   // four columns at a time: their eight LDS reads are in flight together
+                    for (int jb = k + 1 + jg; jb <= i; jb += 4 * JG) {
+                        float lj[4], h[4];
+#pragma unroll
+                        for (int u = 0; u < 4; ++u) {
+                            const int jc = jb + u * JG;
+                            lj[u] = jc <= i ? Hs[jc * HB + k] : 0.f;
+                            h[u] = jc <= i ? Hs[i * HB + jc] : 0.f;
+                        }
+#pragma unroll
+                        for (int u = 0; u < 4; ++u) {
+                            const int jc = jb + u * JG;
+                            if (jc <= i) Hs[i * HB + jc] = fmaf(-li, lj[u] * inv, h[u]);
+                        }
+                    }
+                }
+                if (below && jg == 0) Hs[i * HB + k] = li;
+                ab_wave_sync();
+            }
+            if (failed) break;
+            for (int k = bw - 1; k >= 0; --k) {
+                const float dk = __shfl(v * myinv, k, MI_WAVE);
+                if (lane == k) v = dk;
+                else if (lane < k) v = fmaf(-Hs[k * HB + lane], dk, v);
+            }
+            if (lane < bw) xs[cB + lane] = xs[cB + lane] + v;
+            dl[lane] = lane < bw ? v : 0.f;
+            ab_wave_sync();
+            if (t == a.sweeps - 1 && c == nblk - 1) break;   // nobody reads the predictions after the last step
+            // p_e += sum_{j in pi} y_e[j] delta[j]
+            if (resident) {
+                ab_dots(area + cB, LDR, n, dl, bt, [&](int e, float s) { ps[e] = ps[e] + s; });
+            } else {
+                for (int c0 = 0; c0 < n; c0 += KT) {
+                    const int cnt = min(KT, n - c0);
+                    ab_gather(a, p0 + c0, cnt, cB, B / 4, area, LDB);
+                    if (lane < cnt) ps[lane] = a.pw[p0 + c0 + lane];
+                    ab_wave_sync();
+                    ab_dots(area, LDB, cnt, dl, bt, [&](int e, float s) { ps[e] = ps[e] + s; });
+                    ab_wave_sync();
+                    if (lane < cnt) a.pw[p0 + c0 + lane] = ps[lane];
+                    ab_wave_sync();
+                }
+            }
+            ab_wave_sync();
+        }
+    }
+    if (failed) {
+        for (int k = lane; k < d; k += MI_WAVE) xout[k] = 0.f;
+        if (lane == 0) atomicAdd(a.n_failed, 1);
+        return;
+    }
+    for (int k = lane; k < d; k += MI_WAVE) xout[k] = xs[k];
+}
+
+inline bool ab_shape_ok(int64_t d, int64_t block) {
+    return d >= 4 && d <= AB_MAX_D && d % 4 == 0 && (block == 16 || block == 32 || block == 64);
+}
+
+inline size_t ab_ws_g(int64_t d) { return mi_align_up((size_t)(d * d) * 4, 256); }
+inline size_t ab_ws_bytes(int64_t nnz, int64_t d) { return ab_ws_g(d) + mi_align_up((size_t)(nnz > 0 ? nnz : 1) * 4, 256); }
+
+}  // namespace
+
+extern "C" {
+
+int32_t mi_als_block_chunk(int64_t d, int64_t block) { return ab_shape_ok(d, block) ? ab_res_of((int)d) : 0; }
+
+size_t mi_als_block_rows_workspace_bytes(int64_t n_work, int64_t nnz, int64_t d, int64_t block) {
+    if (n_work < 0 || nnz < 0 || nnz >= ((int64_t)1 << 31) || !ab_shape_ok(d, block)) return 0;
+    return ab_ws_bytes(nnz, d);
+}
+
+int mi_als_block_rows_f32(int64_t n_rows, int64_t d, int64_t block, int64_t sweeps, const int32_t* ptr, const int32_t* idx,
+                          int64_t nnz, int64_t n_cols, const float* Y, int64_t ldy, const float* G, float alpha, float reg,
+                          float* X, int64_t ldx, int32_t from_zero, const int32_t* row_list, int64_t n_list, int32_t* n_failed,
+                          void* ws, size_t ws_bytes, mi_stream_t stream) {
+    const int64_t lim = (int64_t)1 << 31;
+    MI_CHECK_ARG(ab_shape_ok(d, block));
+    MI_CHECK_ARG(sweeps >= 1 && sweeps <= 64);
+    MI_CHECK_ARG(n_rows >= 0 && n_rows < lim && n_cols >= 0 && n_cols < lim && nnz >= 0 && nnz < lim);
+    MI_CHECK_ARG(alpha >= 0.f && alpha < INFINITY && reg > 0.f && reg < INFINITY);
+    const int64_t n_work = row_list ? n_list : n_rows;
+    MI_CHECK_ARG(n_work >= 0 && n_work < lim);
+    MI_CHECK_ARG(n_failed != nullptr);
+    if (n_work == 0) return 0;
+    MI_CHECK_ARG(ptr && (idx || nnz == 0) && Y && G && X);
+    MI_CHECK_ARG(mi_aligned16(Y) && ldy >= d && ldy % 4 == 0 && ldx >= d);
+    if (!ws || ws_bytes < ab_ws_bytes(nnz, d)) return MI_ERR_WORKSPACE;
+    AbArgs a;
+    a.n_rows = (int)n_rows; a.d = (int)d; a.n_cols = (int)n_cols; a.n_work = (int)n_work; a.nnz = (int)nnz;
+    a.sweeps = (int)sweeps; a.from_zero = from_zero != 0;
+    a.ptr = ptr; a.idx = idx; a.Y = Y; a.ldy = ldy; a.alpha = alpha; a.reg = reg; a.X = X; a.ldx = ldx;
+    a.row_list = row_list; a.n_failed = n_failed;
+    a.Gs = static_cast<float*>(ws);
+    a.pw = reinterpret_cast<float*>(static_cast<char*>(ws) + ab_ws_g(d));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(als_block_sym_kernel, dim3((unsigned)mi_ceil_div(d * d, 256)), dim3(256), 0, st, G, a.Gs, (int)d);
+    MI_HIP(hipGetLastError());
+    const dim3 grid((unsigned)mi_ceil_div(n_work, AB_WAVES)), blk(AB_WAVES * MI_WAVE);
+    if (block == 16) hipLaunchKernelGGL(als_block_kernel<16>, grid, blk, 0, st, a);
+    else if (block == 32) hipLaunchKernelGGL(als_block_kernel<32>, grid, blk, 0, st, a);
+    else hipLaunchKernelGGL(als_block_kernel<64>, grid, blk, 0, st, a);
+    return mi_launch_status();
+}
+
+}  // extern "C"

@@ -1940,6 +1940,73 @@ def als_solve_rows(a: DeviceCSR, Y: Tensor, G: Tensor, *, alpha: float, reg: flo
     return out, n_failed
 
 
+ALS_BLOCK_MAX_DIM = 256
+ALS_BLOCKS = (16, 32, 64)
+ALS_BLOCK_MAX_SWEEPS = 64
+
+
+def check_als_block(d, block, sweeps, alpha, reg) -> None:
+    """The argument rules of the block row solver (include/laplace_hip.h, iALS block): ValueError naming the constraint.
+    Needs no device; ops.als_block_rows and als.ImplicitALS share it."""
+    if isinstance(d, bool) or not isinstance(d, numbers.Integral):
+        raise ValueError(f"dim must be an integer, got {d!r}")
+    if d % 4 != 0:
+        raise ValueError(f"dim must be a multiple of 4 (factor rows are read as float4), got {d}")
+    if not 4 <= d <= ALS_BLOCK_MAX_DIM:
+        raise ValueError(f"dim must lie in 4 .. {ALS_BLOCK_MAX_DIM} for the block solver, got {d}")
+    if isinstance(block, bool) or block not in ALS_BLOCKS:
+        raise ValueError(f"block must be one of {ALS_BLOCKS}, got {block!r}")
+    if isinstance(sweeps, bool) or not isinstance(sweeps, numbers.Integral) or not 1 <= sweeps <= ALS_BLOCK_MAX_SWEEPS:
+        raise ValueError(f"sweeps must be an integer in 1 .. {ALS_BLOCK_MAX_SWEEPS}, got {sweeps!r}")
+    check_als(4, alpha, reg)
+
+
+def als_block_chunk(d: int, block: int) -> int:
+    """The longest row that the block solver keeps on chip at width d (mi_als_block_chunk); 0 for a refused shape."""
+    return int(_lib.lib().mi_als_block_chunk(int(d), int(block)))
+
+
+def als_block_rows(a: DeviceCSR, Y: Tensor, G: Tensor, *, alpha: float, reg: float, block: int = 16, sweeps: int = 1,
+                   x: Optional[Tensor] = None, row_list: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+    """iALS block — for every row r of `a` (a CSR over the rows of Y [n_cols, d]), `sweeps` passes over the blocks of `block`
+    coordinates, each step the exact minimiser over its block of the row's quadratic
+    1/2 x^T (G + alpha * sum_e y_e y_e^T + reg I) x - (1 + alpha) * sum_e y_e . x; one wavefront per row; the rule is stated
+    in include/laplace_hip.h.  x [n_rows, d] (or [len(row_list), d], compact by list position) is the start and is UPDATED
+    IN PLACE; x=None starts from zero into a fresh tensor.  Returns (X, n_failed) as als_solve_rows does."""
+    _need(a.rowptr, t.int32, "a.rowptr")
+    _need(a.col, t.int32, "a.col")
+    ldy = _rows_ok(Y, "Y")
+    _need(G, t.float32, "G")
+    if Y.shape[0] != a.n_cols:
+        raise ValueError(f"Y must have one row per column of a: {a.n_cols}, got {Y.shape[0]}")
+    d = int(Y.shape[1])
+    check_als_block(d, block, sweeps, alpha, reg)
+    if tuple(G.shape) != (d, d):
+        raise ValueError(f"G must be [{d}, {d}], got {tuple(G.shape)}")
+    if a.rowptr.numel() != a.n_rows + 1:
+        raise ValueError("a.rowptr needs n_rows + 1 entries")
+    if row_list is not None:
+        _need(row_list, t.int32, "row_list")
+    n_work = int(row_list.numel()) if row_list is not None else a.n_rows
+    from_zero = x is None
+    if from_zero:
+        x = t.empty(n_work, d, dtype=t.float32, device=Y.device)
+    ldx = _rows_ok(x, "x")
+    if tuple(x.shape) != (n_work, d):
+        raise ValueError(f"x must be [{n_work}, {d}], got {tuple(x.shape)}")
+    n_failed = t.zeros(1, dtype=t.int32, device=Y.device)
+    if n_work == 0 or a.nnz == 0:   # nothing to solve: every row is empty
+        return x.zero_(), n_failed
+    L = _lib.lib()
+    ws_bytes = L.mi_als_block_rows_workspace_bytes(n_work, a.nnz, d, int(block))
+    ws = _ws_reused(ws_bytes, Y.device)
+    check(L.mi_als_block_rows_f32(a.n_rows, d, int(block), int(sweeps), a.rowptr.data_ptr(), _ptr(a.col), a.nnz, a.n_cols,
+                                  Y.data_ptr(), ldy, G.data_ptr(), float(alpha), float(reg), x.data_ptr(), ldx, int(from_zero),
+                                  row_list.data_ptr() if row_list is not None else None, n_work if row_list is not None else 0,
+                                  n_failed.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "mi_als_block_rows_f32")
+    return x, n_failed
+
+
 _BN_WS = {}
 BATCHNORM_MAX_CHANNELS = 512   # kBnMaxC of csrc/norm.hip: mi_batchnorm_*_f32 return MI_ERR_UNSUPPORTED beyond it
 

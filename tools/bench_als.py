@@ -3,11 +3,18 @@ at d = 64 and 128: the median of 11 epochs after warm-up, HIP events around each
 one process.  For each half-sweep the achieved rate of 2 d^2 nnz + rows d^3 / 3 flop is set against the 157 TF/s f32 matrix
 peak.  One dense C2 LightGCN step (d = 128, 3 layers, batch 16 384) is timed in the same process for scale.
     python3 tools/bench_als.py [--shapes planted,c2,c3] [--dims 64,128] [--epochs 11] [--warmup 2] [--no-lightgcn]
-One JSON line per (shape, d); nothing here is compared with a target: there is no earlier implementation."""
+                               [--solver cholesky|block|both] [--block 16,32] [--sweeps 1,2] [--dim D] [--fold-in]
+--solver block / both adds one line per (block, sweeps) with the block row solver (ops.als_block_rows) from the SAME initial
+tables as the Cholesky line of that (shape, d) — the yardstick, timed in the same run; d > 128 has the block lines only.  A
+block line also carries hub_ms: the one longest item row alone through row_list, i.e. the one wavefront the item
+half-sweep cannot end before.  --dim D is --dims D.  --fold-in adds, per (shape, d, block), what a fold-in from zero leaves
+after 1, 2, 4 and 8 sweeps on the first 4 096 users: the relative distance to the same rows after 64 sweeps.
+One JSON line per (shape, d, solver); the flop model of every line is the full solve's, so TF/s of a block line is a
+speed-up in disguise, not a rate."""
 import argparse, json, os, statistics, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch as t
-from laplace_amd import synthetic as S
+from laplace_amd import ops, synthetic as S
 from laplace_amd.als import ImplicitALS
 from laplace_amd.interactions import Interactions
 
@@ -18,10 +25,17 @@ SHAPES = {"planted": PLANTED, "c2": S.C2, "c3": S.C3}
 ap = argparse.ArgumentParser()
 ap.add_argument("--shapes", default="planted,c2,c3")
 ap.add_argument("--dims", default="64,128")
+ap.add_argument("--dim", type=int, default=None)
 ap.add_argument("--epochs", type=int, default=11)
 ap.add_argument("--warmup", type=int, default=2)
 ap.add_argument("--no-lightgcn", action="store_true")
+ap.add_argument("--solver", default="cholesky", choices=["cholesky", "block", "both"])
+ap.add_argument("--block", default="16")
+ap.add_argument("--sweeps", default="1")
+ap.add_argument("--fold-in", action="store_true")
 args = ap.parse_args()
+dims = [args.dim] if args.dim is not None else [int(x) for x in args.dims.split(",")]
+block_cfgs = [(int(b), int(s)) for b in args.block.split(",") for s in args.sweeps.split(",")]
 
 
 def half_sweep_ms(model, side):
@@ -32,6 +46,20 @@ def half_sweep_ms(model, side):
     return a, b, failed
 
 
+def timed(fn, reps):
+    fn()
+    t.cuda.synchronize()
+    ms = []
+    for _ in range(reps):
+        a, b = t.cuda.Event(enable_timing=True), t.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        t.cuda.synchronize()
+        ms.append(a.elapsed_time(b))
+    return statistics.median(ms)
+
+
 for name in args.shapes.split(","):
     spec = SHAPES[name]
     t0 = time.perf_counter()
@@ -39,28 +67,61 @@ for name in args.shapes.split(","):
     gen_s = time.perf_counter() - t0
     inter = Interactions(ei.cuda(), spec.num_users, spec.num_items)
     nnz = inter.num_edges
-    for d in [int(x) for x in args.dims.split(",")]:
-        model = ImplicitALS(spec.num_users, spec.num_items, dim=d, alpha=1.0, reg=20.0, seed=0).cuda()
+    for d in dims:
+        cfgs = [("cholesky", 16, 1)] if args.solver != "block" and d <= ops.ALS_MAX_DIM else []
+        if args.solver != "cholesky":
+            cfgs += [("block", b, s) for b, s in block_cfgs]
+        model = ImplicitALS(spec.num_users, spec.num_items, dim=d, alpha=1.0, reg=20.0, seed=0, solver="block").cuda()
         model.bind(inter)
-        for _ in range(args.warmup):
-            model.half_sweep("users"), model.half_sweep("items")
-        t.cuda.synchronize()
-        events, failed = [], 0
-        for _ in range(args.epochs):
-            events.append((half_sweep_ms(model, "users"), half_sweep_ms(model, "items")))
-        t.cuda.synchronize()
-        out = {"shape": name, "users": spec.num_users, "items": spec.num_items, "nnz": nnz, "d": d, "epochs": args.epochs,
-               "generate_s": round(gen_s, 1)}
-        for k, (side, rows) in enumerate((("users", spec.num_users), ("items", spec.num_items))):
-            ms = statistics.median(e[k][0].elapsed_time(e[k][1]) for e in events)
-            failed += sum(int(e[k][2].item()) for e in events)
-            flop = 2.0 * d * d * nnz + rows * d ** 3 / 3.0
-            out[f"{side}_ms"] = round(ms, 3)
-            out[f"{side}_tflops"] = round(flop / (ms * 1e-3) / 1e12, 3)
-            out[f"{side}_of_peak"] = round(flop / (ms * 1e-3) / 1e12 / PEAK_TF, 4)
-        out["epoch_ms"] = round(out["users_ms"] + out["items_ms"], 3)
-        out["failed_rows"] = failed
-        print(json.dumps(out), flush=True)
+        start = (model.users_emb.weight.clone(), model.items_emb.weight.clone())
+        for solver, block, sweeps in cfgs:
+            model.solver, model.block, model.block_sweeps = solver, block, sweeps
+            model.users_emb.weight.copy_(start[0])
+            model.items_emb.weight.copy_(start[1])
+            for _ in range(args.warmup):
+                model.half_sweep("users"), model.half_sweep("items")
+            t.cuda.synchronize()
+            events, failed = [], 0
+            for _ in range(args.epochs):
+                events.append((half_sweep_ms(model, "users"), half_sweep_ms(model, "items")))
+            t.cuda.synchronize()
+            out = {"shape": name, "users": spec.num_users, "items": spec.num_items, "nnz": nnz, "d": d, "solver": solver,
+                   "epochs": args.epochs, "generate_s": round(gen_s, 1)}
+            if solver == "block":
+                out.update(block=block, sweeps=sweeps)
+            for k, (side, rows) in enumerate((("users", spec.num_users), ("items", spec.num_items))):
+                ms = statistics.median(e[k][0].elapsed_time(e[k][1]) for e in events)
+                failed += sum(int(e[k][2].item()) for e in events)
+                flop = 2.0 * d * d * nnz + rows * d ** 3 / 3.0
+                out[f"{side}_ms"] = round(ms, 3)
+                out[f"{side}_tflops"] = round(flop / (ms * 1e-3) / 1e12, 3)
+                out[f"{side}_of_peak"] = round(flop / (ms * 1e-3) / 1e12 / PEAK_TF, 4)
+            out["epoch_ms"] = round(out["users_ms"] + out["items_ms"], 3)
+            out["failed_rows"] = failed
+            out["objective"] = round(model.objective(inter), 2) if name == "planted" else None
+            if solver == "block":
+                by_item = model._bound[2]
+                deg = by_item.rowptr[1:] - by_item.rowptr[:-1]
+                hub = deg.argmax().to(t.int32).reshape(1)
+                X, G = model.users_emb.weight.data, ops.gemm(model.users_emb.weight.data, model.users_emb.weight.data,
+                                                             trans_a=True, trans_b=False)
+                x1 = model.items_emb.weight.data[hub.long()].clone()
+                out["hub_entries"] = int(deg.max().item())
+                out["hub_ms"] = round(timed(lambda: ops.als_block_rows(by_item, X, G, alpha=1.0, reg=20.0, block=block,
+                                                                       sweeps=sweeps, x=x1, row_list=hub), 5), 3)
+            print(json.dumps(out), flush=True)
+            if solver == "block" and args.fold_in and sweeps == block_cfgs[0][1]:
+                by_user = model._bound[1]
+                rl = t.arange(min(4096, spec.num_users), dtype=t.int32, device="cuda")
+                Y = model.items_emb.weight.data
+                G = ops.gemm(Y, Y, trans_a=True, trans_b=False)
+                ref = ops.als_block_rows(by_user, Y, G, alpha=1.0, reg=20.0, block=block, sweeps=64, row_list=rl)[0]
+                left = {}
+                for s in (1, 2, 4, 8):
+                    x = ops.als_block_rows(by_user, Y, G, alpha=1.0, reg=20.0, block=block, sweeps=s, row_list=rl)[0]
+                    rel = (x - ref).norm(dim=1) / ref.norm(dim=1).clamp_min(1e-30)
+                    left[str(s)] = {"median": float(rel.median()), "max": float(rel.max())}
+                print(json.dumps({"shape": name, "d": d, "block": block, "fold_in_relative_distance_to_64_sweeps": left}), flush=True)
         del model
     del inter
     t.cuda.empty_cache()
