@@ -247,6 +247,42 @@ typedef struct mi_spmm_sweep {
                                    L2 hit rate only: results do not depend on it                                          */
 } mi_spmm_sweep;
 
+/* TILES form of the hub rows (the longest split rows of an adjacency whose columns are far more than the L2s hold: the
+ * item rows of a [users; items] graph).  A hub row has an entry in almost every tile of 64 or 128 consecutive rows of X, so
+ * its gathers need no cache at all: P workgroups each own a contiguous run of whole tiles, stream every tile that holds a hub
+ * entry through LDS ONCE, and add its entries into accumulators that stay in registers from the first tile to the last.
+ * Layout, built once per adjacency (host: ops.build_hub_tiles_plan):
+ *   slots      a slot is one accumulator: a hub row, or class j % k of the entries of a hub row (entry j of the row, k classes)
+ *              where the row is heavier than the mean load of a sub-group — no slot is heavier than total hub entries / 32;
+ *   sub-groups a workgroup is 32 sub-groups (one row of X wide: d / 4 lanes rounded up to 8, 16 or 32) of 16 accumulators;
+ *              slots are assigned by longest-processing-time over their entry counts, slot_of[sg * 16 + a] (< 0 = unused);
+ *   ranges     workgroup w owns the loaded tiles [wg_ptr[w], wg_ptr[w + 1]) of the list tile_id (tiles without a hub entry
+ *              are not listed and never loaded); the cuts balance a modelled cost, not row counts;
+ *   entries    tile j of the list owns entries [tile_ent[j], tile_ent[j + 1]) of ecol (column minus the tile's first) / eval,
+ *              sorted by (sub-group, accumulator, column); cnt[(j * 32 + sg) * 16 + a] of them belong to accumulator a of
+ *              sub-group sg, the sub-group's first is sg_off[j * 32 + sg] entries into the tile's run.
+ * Reproducibility: everything is static.  Partial row (slot, w) = the slot's entries in w's range, added one by one in column
+ * order; they sit at [slot * n_wg + w] IN FRONT of the work items' partial rows, plan->item_ptr / long_rows list the hub rows
+ * first (item_ptr[i] = n_wg * first slot of hub row i), and the one fix-up kernel reduces them with every other split row in
+ * its fixed order: no float atomics, nothing between workgroups, bitwise the same run to run and on one or two streams.
+ * eval holds VALUES: re-copy it when the CSR's val changes.  Dense launches only (no x_map, no row_list), d <= 128. */
+typedef struct mi_spmm_tiles {
+    const uint8_t* ecol;        /* uint8[n_entries]                                                                      */
+    const float*   eval;        /* float[n_entries]                                                                      */
+    const int32_t* tile_id;     /* int32[n_listed]: tile number (first row of X = tile_id * tile), ascending              */
+    const int32_t* tile_ent;    /* int32[n_listed + 1]                                                                   */
+    const uint8_t* cnt;         /* uint8[n_listed * 32 * 16], 16-byte aligned                                            */
+    const int32_t* sg_off;      /* int32[n_listed * 32]                                                                  */
+    const int32_t* wg_ptr;      /* int32[n_wg + 1]                                                                       */
+    const int32_t* slot_of;     /* int32[32 * 16]                                                                        */
+    int32_t        n_wg;        /* P: workgroups = partial rows per slot                                                 */
+    int32_t        n_slots;     /* 1 .. 512                                                                              */
+    int32_t        tile;        /* 64 or 128                                                                             */
+    int32_t        nt;          /* != 0: the streamed loads (X rows, entries) use the non-temporal policy                 */
+    int64_t        n_cols;      /* rows of X                                                                             */
+    int32_t        max_tile_entries;  /* largest tile_ent[j + 1] - tile_ent[j]; beyond 96 * sub-group lanes: MI_ERR_UNSUPPORTED */
+} mi_spmm_tiles;
+
 typedef struct mi_spmm_ex {
     const int32_t* x_map;
     const int32_t* addend_map;
@@ -302,6 +338,12 @@ typedef struct mi_spmm_ex {
     int32_t        slice_rows;      /* with row_slices: > 0 = only rows [0, slice_rows) run in the sliced form, the rows behind them
                                        in the plain one (a [users; items] adjacency: the item rows are long and gather from the
                                        user table, which has no popular part); 0 = all rows; < 0 is MI_ERR_BAD_ARG */
+    const mi_spmm_tiles* tiles;     /* nullable (and null in a zero-initialised struct): the plan's hub rows run in TILES form, see
+                                       mi_spmm_tiles; the plan's n_items then counts n_wg * n_slots partial rows in front of the
+                                       work items'.  Not with x_map, row_list or a sweep (MI_ERR_BAD_ARG); d > 128, or an LDS size
+                                       the device refuses: MI_ERR_UNSUPPORTED, returned BEFORE anything is enqueued when the call
+                                       computes the split rows (parts = 0 or MI_SPMM_SPLIT_ROWS): relaunch with the adjacency's
+                                       plan without tiles */
 } mi_spmm_ex;
 #define MI_SPMM_SHORT_ROWS 1
 #define MI_SPMM_SPLIT_ROWS 2

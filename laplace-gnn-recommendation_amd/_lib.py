@@ -43,12 +43,18 @@ class SpmmSweepStruct(Structure):
                 ("n_streams", c_int32), ("n_slots", c_int32), ("progress", c_void_p), ("epoch", c_int32), ("slack", c_int32)]
 
 
+class SpmmTilesStruct(Structure):
+    _fields_ = [("ecol", c_void_p), ("eval", c_void_p), ("tile_id", c_void_p), ("tile_ent", c_void_p), ("cnt", c_void_p),
+                ("sg_off", c_void_p), ("wg_ptr", c_void_p), ("slot_of", c_void_p), ("n_wg", c_int32), ("n_slots", c_int32),
+                ("tile", c_int32), ("nt", c_int32), ("n_cols", c_int64), ("max_tile_entries", c_int32)]
+
+
 class SpmmExStruct(Structure):
     _fields_ = [("x_map", c_void_p), ("addend_map", c_void_p), ("row_list", c_void_p), ("n_list_dev", c_void_p),
                 ("n_list", c_int64), ("adam", POINTER(AdamArgs)), ("parts", c_int32), ("hot_rows", c_int32),
                 ("sweep", POINTER(SpmmSweepStruct)), ("hot_base", c_int32), ("hot_threads", c_int32),
                 ("x_bits", c_void_p), ("thin_rows", c_void_p), ("n_thin", c_int32), ("row_slices", c_int32),
-                ("slice_rows", c_int32)]
+                ("slice_rows", c_int32), ("tiles", POINTER(SpmmTilesStruct))]
 
 
 MI_SPMM_SHORT_ROWS, MI_SPMM_SPLIT_ROWS = 1, 2

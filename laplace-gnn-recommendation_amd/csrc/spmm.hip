@@ -1134,6 +1134,128 @@ __global__ __launch_bounds__(1024) void spmm_sweep_kernel(mi_spmm_sweep sw, int 
     }
 }
 
+// Split rows, TILES form (mi_spmm_tiles): the hub rows never gather.  Workgroup w owns a contiguous run of tiles of T rows of
+// X; it stages each tile that holds a hub entry — the rows, and the tile's entry list — in LDS once and every sub-group adds
+// the entries of its 16 slots into 16 accumulators that stay in registers from the first tile to the last.  Two LDS buffers,
+// one tile in registers on its way: the loads of tile i + 2 are issued before the barrier that ends tile i and are written to
+// LDS after tile i + 1 was summed, so a tile's bytes are in flight for the time another tile takes to compute.  One barrier per
+// tile, executed by every thread; all trip counts come from the plan.  No atomics, nothing between workgroups: a slot's
+// partial row (slot, w) is the chained sum of its entries in w's range in column order.
+#define MI_HUB_SG 32    // sub-groups per workgroup
+#define MI_HUB_ACC 16   // accumulators (slots) per sub-group
+#define MI_HUB_EPT 3    // entries of a tile staged per thread: a tile holds at most 3 * 32 * LPR entries
+template <int LPR, int TPT, bool NT>
+__global__ __launch_bounds__(MI_HUB_SG * LPR) void spmm_hub_tiles_kernel(mi_spmm_tiles tl, int d4, const float4* __restrict__ X4,
+                                                                        int64_t ldx4, float4* __restrict__ partial, bool streaming) {
+    extern __shared__ float4 hub_lds[];  // 2 x { T rows of LPR float4 | CAP values | CAP local columns }
+    constexpr int THREADS = MI_HUB_SG * LPR, T = 32 * TPT, CAP = MI_HUB_EPT * THREADS;
+    constexpr int BUF_F4 = T * LPR + CAP * 5 / 16;
+    static_assert((CAP * 5) % 16 == 0 && T <= 256, "buffers stay 16-byte aligned; a local column is one byte");
+    const int tid = threadIdx.x;
+    const int li = tid % LPR, sg = tid / LPR;   // LPR divides the wavefront: sub-groups do not straddle wavefronts
+    const int w = blockIdx.x;
+    const int j0 = tl.wg_ptr[w], n_t = tl.wg_ptr[w + 1] - j0;   // block-uniform: every barrier below is reached by all threads
+    float4 acc[MI_HUB_ACC];
+#pragma unroll
+    for (int a = 0; a < MI_HUB_ACC; ++a) acc[a] = mi_f4_zero();
+    float4 xr[TPT];
+    float ev[MI_HUB_EPT];
+    uint32_t ec[MI_HUB_EPT];
+    uint4 cw_next = make_uint4(0, 0, 0, 0), cw = cw_next;
+    int32_t off_next = 0, off = 0;
+
+    auto load = [&](int j) {   // tile j of the launch -> registers
+        const int64_t row0 = (int64_t)tl.tile_id[j] * T;
+        const int32_t e0 = tl.tile_ent[j];
+        const int32_t ne = min(tl.tile_ent[j + 1] - e0, CAP);
+#pragma unroll
+        for (int k = 0; k < TPT; ++k) {
+            const int64_t r = row0 + sg + 32 * k;
+            xr[k] = mi_f4_zero();
+            if (r < tl.n_cols && li < d4) {
+                const float4* p = X4 + r * ldx4 + li;
+                if (NT) {
+                    mi_f4v x = __builtin_nontemporal_load(reinterpret_cast<const mi_f4v*>(p));
+                    xr[k] = make_float4(x.x, x.y, x.z, x.w);
+                } else {
+                    xr[k] = *p;
+                }
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < MI_HUB_EPT; ++k) {
+            const int i = tid + k * THREADS;
+            ev[k] = 0.f;
+            ec[k] = 0;
+            if (i < ne) {
+                ev[k] = NT ? __builtin_nontemporal_load(tl.eval + e0 + i) : tl.eval[e0 + i];
+                ec[k] = NT ? __builtin_nontemporal_load(tl.ecol + e0 + i) : tl.ecol[e0 + i];
+            }
+        }
+        cw_next = reinterpret_cast<const uint4*>(tl.cnt)[(int64_t)j * MI_HUB_SG + sg];
+        off_next = tl.sg_off[(int64_t)j * MI_HUB_SG + sg];
+    };
+    auto stage = [&](int b) {   // registers -> buffer b
+        float4* Xs = hub_lds + b * BUF_F4;
+        float* vs = reinterpret_cast<float*>(Xs + T * LPR);
+        uint8_t* cs = reinterpret_cast<uint8_t*>(vs + CAP);
+#pragma unroll
+        for (int k = 0; k < TPT; ++k) Xs[(sg + 32 * k) * LPR + li] = xr[k];
+#pragma unroll
+        for (int k = 0; k < MI_HUB_EPT; ++k) {
+            vs[tid + k * THREADS] = ev[k];
+            cs[tid + k * THREADS] = (uint8_t)ec[k];
+        }
+        // copied by moves the compiler cannot fold into the loads: with cw / off as load targets of the first tile, the wait it
+        // places at the head of the tile loop for them also retires the NEXT tile's loads, which then overlap nothing
+        asm volatile("v_mov_b32 %0, %1" : "=v"(cw.x) : "v"(cw_next.x));
+        asm volatile("v_mov_b32 %0, %1" : "=v"(cw.y) : "v"(cw_next.y));
+        asm volatile("v_mov_b32 %0, %1" : "=v"(cw.z) : "v"(cw_next.z));
+        asm volatile("v_mov_b32 %0, %1" : "=v"(cw.w) : "v"(cw_next.w));
+        asm volatile("v_mov_b32 %0, %1" : "=v"(off) : "v"(off_next));
+    };
+    if (n_t > 0) {
+        load(j0);
+        stage(0);
+        if (n_t > 1) load(j0 + 1);
+    }
+    __syncthreads();
+    for (int i = 0; i < n_t; ++i) {
+        const float4* Xs = hub_lds + (i & 1) * BUF_F4;
+        const float* vs = reinterpret_cast<const float*>(Xs + T * LPR);
+        const uint8_t* cs = reinterpret_cast<const uint8_t*>(vs + CAP);
+        const uint32_t cnt[4] = {cw.x, cw.y, cw.z, cw.w};
+        // the sub-group's entries of the tile are one run, slot after slot: entry e + 1 is read under the row load of entry e
+        int e = min(off, CAP - 1);
+        uint32_t c = cs[e];
+        float v = vs[e];
+#pragma unroll
+        for (int a = 0; a < MI_HUB_ACC; ++a) {   // static accumulator index: acc stays in registers
+            const int n = (int)((cnt[a / 4] >> (8 * (a % 4))) & 255u);
+            // no cross-lane operation inside: the sub-groups of a wavefront may leave the loop at their own counts
+#pragma unroll 1
+            for (const int end = min(e + n, CAP); e < end;) {
+                const float4 x = Xs[(c & (T - 1)) * LPR + li];
+                const float wt = v;
+                e += 1;
+                const int en = min(e, CAP - 1);
+                c = cs[en];
+                v = vs[en];
+                mi_f4_fma(acc[a], wt, x);
+            }
+        }
+        if (i + 1 < n_t) stage((i + 1) & 1);   // last read of that buffer: tile i - 1, a barrier ago
+        if (i + 2 < n_t) load(j0 + i + 2);
+        __syncthreads();
+    }
+#pragma unroll
+    for (int a = 0; a < MI_HUB_ACC; ++a) {
+        const int32_t slot = tl.slot_of[sg * MI_HUB_ACC + a];
+        if (slot >= 0 && slot < tl.n_slots && li < d4)
+            mi_store4<1>(partial + ((int64_t)slot * tl.n_wg + w) * d4 + li, acc[a], streaming);
+    }
+}
+
 // One 256-thread block per split row.  Its 4 wavefronts x NB sub-groups stride over the row's
 // partial sums (several loads in flight each), then combine through LDS in a fixed order, so the
 // result does not depend on scheduling.  Wave 0 applies the epilogue.
@@ -1536,7 +1658,8 @@ struct HotLaunch { int state = 0; int cus = 0; size_t lds_cap = 0; int occ_key =
 template <int LPR, int VPL, bool SPARSE, bool ADAM>
 int launch_spmm_mode(int64_t n_rows, int d4, const int32_t* rowptr, const int32_t* col, const float* val,
                      const float4* X4, int64_t ldx4, const Epilogue& ep, const mi_spmm_plan* plan,
-                     float4* partial, const Ex& ex, int64_t n_list, hipStream_t s, const mi_spmm_sweep* sweep) {
+                     float4* partial, const Ex& ex, int64_t n_list, hipStream_t s, const mi_spmm_sweep* sweep,
+                     const mi_spmm_tiles* tiles) {
     constexpr int UNROLL = (VPL == 1) ? MI_SPMM_UNROLL : 4;                                        // work items, sweep
     constexpr int UNROLL_ROWS = (VPL == 1) ? (ADAM ? MI_SPMM_UNROLL_ADAM : MI_SPMM_UNROLL) : 4;   // the short-row kernel (the one that carries the Adam epilogue)
     constexpr int UNROLL_THIN = (VPL == 1) ? MI_SPMM_UNROLL_THIN : 4;                             // whole thin rows
@@ -1568,10 +1691,37 @@ int launch_spmm_mode(int64_t n_rows, int d4, const int32_t* rowptr, const int32_
             return MI_ERR_UNSUPPORTED;
         }
     }
+    if (do_split && plan && plan->n_items > 0 && tiles) {
+        if constexpr (!SPARSE && VPL == 1 && LPR <= 32) {
+            const mi_spmm_tiles& tl = *tiles;
+            constexpr int threads = MI_HUB_SG * LPR, cap = MI_HUB_EPT * threads;
+            if (tl.max_tile_entries > cap) return MI_ERR_UNSUPPORTED;
+            const size_t lds = 2 * ((size_t)tl.tile * LPR * sizeof(float4) + (size_t)cap * 5);
+            const int which = (tl.tile == 128 ? 2 : 0) + (tl.nt ? 1 : 0);
+            using HubKernel = void (*)(mi_spmm_tiles, int, const float4*, int64_t, float4*, bool);
+            const HubKernel kern = which == 0 ? spmm_hub_tiles_kernel<LPR, 2, false>
+                                 : which == 1 ? spmm_hub_tiles_kernel<LPR, 2, true>
+                                 : which == 2 ? spmm_hub_tiles_kernel<LPR, 4, false> : spmm_hub_tiles_kernel<LPR, 4, true>;
+            // per instantiation and per process, as for the sweep kernel above: the library drives one device per process
+            // (one rank per GPU) and plans are built and launched from one thread
+            static bool attr_set[4] = {false, false, false, false};
+            if (!attr_set[which]) {
+                if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                        (int)lds) != hipSuccess) {
+                    (void)hipGetLastError();
+                    return MI_ERR_UNSUPPORTED;
+                }
+                attr_set[which] = true;
+            }
+            hipLaunchKernelGGL(kern, dim3((unsigned)tl.n_wg), dim3(threads), lds, s, tl, d4, X4, ldx4, partial, ep.streaming);
+        } else {
+            return MI_ERR_UNSUPPORTED;
+        }
+    }
     bool xmap_form = false;   // the work items ran as spmm_items_xscan_kernel: their live flags are valid
     // HYBRID plan (round 4): the hub rows in SWEEP form AND the remaining split rows as banded work items — `items` is
     // then non-null beside the sweep, its slots are absolute (they start behind the sweep's 8 * n_slots partial rows)
-    if (do_split && plan && plan->n_items > 0 && (!sweep || plan->items)) {  // row_list mode still reduces every split row: hubs are few and almost always wanted
+    if (do_split && plan && plan->n_items > 0 && ((!sweep && !tiles) || plan->items)) {  // row_list mode still reduces every split row: hubs are few and almost always wanted
         const int64_t n_launch = plan->n_launch;
         dim3 gi((unsigned)mi_ceil_div(n_launch, SG * ITEMS_RPS));
         const int32_t* ecol = plan->epos ? plan->ecol : col;   // packed plan: the work items read the plan's launch-ordered copies
@@ -1659,8 +1809,8 @@ int launch_spmm_mode(int64_t n_rows, int d4, const int32_t* rowptr, const int32_
             // rows behind slice_rows (the item rows of a [users; items] adjacency: long rows that gather from a table without a
             // popular part) stay with the plain kernel: the same launch on shifted pointers
             const int64_t n_sl = ex.slice_rows > 0 ? std::min<int64_t>(ex.slice_rows, n_out) : n_out;
-            const int64_t tiles = mi_ceil_div(n_sl, kSliceTile);
-            const dim3 gs((unsigned)(mi_ceil_div(tiles, 8 / sl) * 8));  // blockIdx.x & 7 = the XCD, as for the banded plan
+            const int64_t n_sl_tiles = mi_ceil_div(n_sl, kSliceTile);
+            const dim3 gs((unsigned)(mi_ceil_div(n_sl_tiles, 8 / sl) * 8));  // blockIdx.x & 7 = the XCD, as for the banded plan
             // sub-groups of LPR / SL lanes: d4 / sl of them active (d4 <= LPR)
             if (sl == 2)
                 hipLaunchKernelGGL((spmm_rows_kernel<LPR / 2, 1, MI_SPMM_SLICE_UNROLL, 1, SPARSE, ADAM, 2>), gs, dim3(kBlock), 0, s, n_sl, d4,
@@ -1709,10 +1859,11 @@ int launch_spmm_mode(int64_t n_rows, int d4, const int32_t* rowptr, const int32_
 template <int LPR, int VPL>
 int launch_spmm(int64_t n_rows, int d4, const int32_t* rowptr, const int32_t* col, const float* val,
                 const float4* X4, int64_t ldx4, const Epilogue& ep, const mi_spmm_plan* plan,
-                float4* partial, const Ex& ex, int64_t n_list, hipStream_t s, const mi_spmm_sweep* sweep) {
+                float4* partial, const Ex& ex, int64_t n_list, hipStream_t s, const mi_spmm_sweep* sweep,
+                const mi_spmm_tiles* tiles) {
     const bool sparse = ex.x_map || ex.row_list;
 #define MI_SPMM_GO(SP, AD) \
-    return launch_spmm_mode<LPR, VPL, SP, AD>(n_rows, d4, rowptr, col, val, X4, ldx4, ep, plan, partial, ex, n_list, s, sweep)
+    return launch_spmm_mode<LPR, VPL, SP, AD>(n_rows, d4, rowptr, col, val, X4, ldx4, ep, plan, partial, ex, n_list, s, sweep, tiles)
     if (ep.p) {
         if (sparse) MI_SPMM_GO(true, true);
         MI_SPMM_GO(false, true);
@@ -1968,10 +2119,22 @@ int mi_spmm_csr_ex_f32(int64_t n_rows, int64_t d, const int32_t* rowptr, const i
         MI_CHECK_ARG(sweep->slack >= 0);
         if (d > 128) return MI_ERR_UNSUPPORTED;
     }
+    const mi_spmm_tiles* tiles = exh ? exh->tiles : nullptr;
+    if (tiles) {
+        MI_CHECK_ARG(plan && plan->n_items > 0 && !sweep && !ex.x_map && !ex.row_list);
+        MI_CHECK_ARG(tiles->ecol && tiles->eval && tiles->tile_id && tiles->tile_ent && tiles->cnt && tiles->sg_off && tiles->wg_ptr &&
+                     tiles->slot_of && mi_aligned16(tiles->cnt));
+        MI_CHECK_ARG(tiles->n_wg > 0 && tiles->n_slots > 0 && tiles->n_slots <= MI_HUB_SG * MI_HUB_ACC &&
+                     (tiles->tile == 64 || tiles->tile == 128) && tiles->n_cols > 0 && tiles->max_tile_entries >= 0);
+        MI_CHECK_ARG(plan->items ? plan->n_items > (int64_t)tiles->n_wg * tiles->n_slots
+                                 : plan->n_items == (int64_t)tiles->n_wg * tiles->n_slots);
+        if (d > 128) return MI_ERR_UNSUPPORTED;
+    }
     float4* partial = nullptr;
     if (plan && plan->n_items > 0) {
-        const int64_t own_items = (int64_t)plan->n_items - (sweep ? 8 * (int64_t)sweep->n_slots : 0);  // the work items' partial rows
-        MI_CHECK_ARG(plan->item_ptr && plan->long_rows && (sweep || plan->items));
+        const int64_t own_items = (int64_t)plan->n_items - (sweep ? 8 * (int64_t)sweep->n_slots : 0) -
+                                  (tiles ? (int64_t)tiles->n_wg * tiles->n_slots : 0);  // the work items' partial rows
+        MI_CHECK_ARG(plan->item_ptr && plan->long_rows && (sweep || tiles || plan->items));
         MI_CHECK_ARG(!plan->items || plan->n_launch >= own_items);
         MI_CHECK_ARG(!plan->items || plan->band == 0 || plan->n_launch % (8 * kPlanGroup) == 0);
         MI_CHECK_ARG(!plan->epos || (plan->items && plan->ecol && plan->eval));
@@ -2009,11 +2172,11 @@ int mi_spmm_csr_ex_f32(int64_t n_rows, int64_t d, const int32_t* rowptr, const i
     const float4* X4 = reinterpret_cast<const float4*>(X);
     const int d4 = (int)(d / 4);
     hipStream_t s = (hipStream_t)stream;
-    if (d4 <= 8)   return launch_spmm<8, 1>(n_rows, d4, rowptr, col, val, X4, ldx / 4, ep, plan, partial, ex, n_list, s, sweep);
-    if (d4 <= 16)  return launch_spmm<16, 1>(n_rows, d4, rowptr, col, val, X4, ldx / 4, ep, plan, partial, ex, n_list, s, sweep);
-    if (d4 <= 32)  return launch_spmm<32, 1>(n_rows, d4, rowptr, col, val, X4, ldx / 4, ep, plan, partial, ex, n_list, s, sweep);
-    if (d4 <= 64)  return launch_spmm<64, 1>(n_rows, d4, rowptr, col, val, X4, ldx / 4, ep, plan, partial, ex, n_list, s, sweep);
-    return launch_spmm<64, 2>(n_rows, d4, rowptr, col, val, X4, ldx / 4, ep, plan, partial, ex, n_list, s, sweep);
+    if (d4 <= 8)   return launch_spmm<8, 1>(n_rows, d4, rowptr, col, val, X4, ldx / 4, ep, plan, partial, ex, n_list, s, sweep, tiles);
+    if (d4 <= 16)  return launch_spmm<16, 1>(n_rows, d4, rowptr, col, val, X4, ldx / 4, ep, plan, partial, ex, n_list, s, sweep, tiles);
+    if (d4 <= 32)  return launch_spmm<32, 1>(n_rows, d4, rowptr, col, val, X4, ldx / 4, ep, plan, partial, ex, n_list, s, sweep, tiles);
+    if (d4 <= 64)  return launch_spmm<64, 1>(n_rows, d4, rowptr, col, val, X4, ldx / 4, ep, plan, partial, ex, n_list, s, sweep, tiles);
+    return launch_spmm<64, 2>(n_rows, d4, rowptr, col, val, X4, ldx / 4, ep, plan, partial, ex, n_list, s, sweep, tiles);
 }
 
 int mi_spmm_csr_f32(int64_t n_rows, int64_t d, const int32_t* rowptr, const int32_t* col,

@@ -155,6 +155,8 @@ class SpmmPlan:
     thin_rows: Optional[Tensor] = None            # int32: rows with chunk < degree <= thin_max, longest first (mi_spmm_ex.thin_rows)
     thin_max: int = 0
     slice_reuse: dict = field(default_factory=dict)   # first hot row -> gathers per gathered column of the rows in front of it (spmm, ROW_SLICES)
+    tiles: Optional["_lib.SpmmTilesStruct"] = None    # hub rows in TILES form (mi_spmm_tiles); tensors kept in tiles_t (build_hub_tiles_layout)
+    tiles_t: dict = field(default_factory=dict)
 
     @property
     def n_thin_rows(self) -> int:
@@ -186,6 +188,8 @@ class DeviceCSR:
     plan: Optional[SpmmPlan] = None
     hot: Optional[Tuple[int, int]] = None   # (first row, rows) of X worth an LDS cache in dense launches: see spmm()
     plan_bf16: Optional[SpmmPlan] = None    # spmm_bf16's own work-item plan: `plan` and the f32 launches are untouched by it
+    plan_tiles: object = None               # the TILES plan of the dense launches (HUB_TILES): None = not tried, False = not applicable;
+                                            # x_map / row_list launches keep `plan`
 
     # Value generation: 0 for an adjacency whose `val` is the one it was built with, a process-wide fresh number after every
     # later assignment of `val` and every invalidate_values().  With the identity and _version of the tensor itself it is
@@ -536,6 +540,255 @@ def build_hybrid_plan(a: DeviceCSR, chunk: int = DEFAULT_CHUNK, band: Optional[i
 HYBRID_TAIL_BAND = int(_os_environ.get("LAPLACE_HYBRID_TAIL_BAND", 16384))  # columns per band of a hybrid plan's banded tail
 
 
+# HUB TILES (include/laplace_hip.h, mi_spmm_tiles; profiles/hub_tiles_c4.md): the longest split rows of an adjacency
+# under the locality order are summed from LDS-staged tiles of X into register accumulators, every row of X read once per
+# pass, instead of gathering through L2.  HUB_TILES: 0 = off, 1 = on for every dense launch of a planned adjacency with the
+# `hot` hint that has hub rows (tests, A/B), "auto" = on where the gates below hold.  LAPLACE_SPMM_HUB_TILES overrides.
+HUB_TILES = _os_environ.get("LAPLACE_SPMM_HUB_TILES", "auto")
+HUB_SLOTS = int(_os_environ.get("LAPLACE_SPMM_HUB_SLOTS", 512))      # accumulators of a workgroup: 32 sub-groups x 16
+HUB_FLOOR = int(_os_environ.get("LAPLACE_SPMM_HUB_FLOOR", 8192))     # hub rows have at least this many entries
+HUB_TILE = int(_os_environ.get("LAPLACE_SPMM_HUB_TILE", 128))        # rows of X per tile: 64 or 128
+# 1 = the kernel's streamed loads use the nt policy.  In-step A/B on C4, alternated three times: nt 46.09, 46.18, 45.80 ms per step,
+# plain 45.79, 45.82, 45.30 (profiles/hub_tiles_c4.md, section 6): plain loads, bitwise the same result.
+HUB_NT = int(_os_environ.get("LAPLACE_SPMM_HUB_NT", 0))
+HUB_WGS = int(_os_environ.get("LAPLACE_SPMM_HUB_WGS", 0))            # workgroups (user ranges); 0 = the device's CU count
+HUB_MIN_COLS = 1 << 20    # "auto": narrower operands sit in the L2s / the Infinity Cache and have nothing to stream for
+# "auto": hub entries per streamed row of X.  A streamed row costs 512 B at D = 128; a hub entry's gather missed L2 for about
+# 290 B on C4 (23.6 GB fetched for 81 M entries), so the stream pays from about 2 entries per row; the bar leaves a margin.
+HUB_MIN_REUSE = float(_os_environ.get("LAPLACE_SPMM_HUB_MIN_REUSE", 4))
+HUB_SG, HUB_ACC = 32, 16  # sub-groups per workgroup, accumulators per sub-group (csrc/spmm.hip, spmm_hub_tiles_kernel)
+HUB_LOAD_COST = 6         # modelled cost of loading one row of a tile, in entries (user-range cuts): C4 averages 7 entries per row
+
+
+def hub_tiles_slots(deg_desc, n_slots: int = 512, floor: int = 8192, n_sg: int = HUB_SG):
+    """Which of the rows (degrees, longest first) become hub rows and into how many slots each is cut: (rows taken, parts per
+    row, bound).  A row heavier than the mean load of a sub-group (bound = total hub entries // n_sg) is cut into
+    k = ceil(deg / bound) classes — entry j of the row belongs to class j % k — so no slot is heavier than bound; rows are
+    dropped from the short end until the slots fit n_slots.  Host arithmetic on at most n_slots numbers."""
+    ds = [int(x) for x in deg_desc[:n_slots] if int(x) >= floor]
+    while ds:
+        bound = max(1, sum(ds) // n_sg)
+        parts = [-(-x // bound) for x in ds]
+        if sum(parts) <= n_slots:
+            return len(ds), parts, bound
+        ds.pop()
+    return 0, [], 0
+
+
+def hub_tiles_assign(loads, n_sg: int = HUB_SG, n_acc: int = HUB_ACC):
+    """Longest-processing-time assignment of slots (entry counts) to sub-groups of n_acc accumulators: slot -> (sub-group,
+    accumulator).  Ties by slot number: static."""
+    import heapq
+    order = sorted(range(len(loads)), key=lambda s: (-loads[s], s))
+    heap = [(0, k, 0) for k in range(n_sg)]
+    heapq.heapify(heap)
+    where = [None] * len(loads)
+    for s in order:
+        while True:
+            load, k, cnt = heapq.heappop(heap)
+            if cnt < n_acc:
+                break
+        where[s] = (k, cnt)
+        heapq.heappush(heap, (load + loads[s], k, cnt + 1))
+    return where
+
+
+def hub_tiles_ranges(tile_entries: Tensor, tile: int, n_wg: int) -> Tensor:
+    """Cuts of the tiles into n_wg contiguous runs of about equal modelled cost: int64[n_wg + 1], tile numbers.  A tile
+    without hub entries is never loaded and costs nothing; any other costs max(loading its rows, its entries)."""
+    cost = t.where(tile_entries > 0, t.clamp(tile_entries, min=HUB_LOAD_COST * tile), t.zeros_like(tile_entries))
+    cum = t.cumsum(cost, 0)
+    total = int(cum[-1]) if cum.numel() else 0
+    targets = (t.arange(1, n_wg, device=cum.device, dtype=t.int64) * total) // n_wg
+    cuts = t.searchsorted(cum, targets, right=False) + 1   # the tile that crosses the target stays with the earlier workgroup
+    z = t.zeros(1, dtype=t.int64, device=cum.device)
+    return t.cat([z, t.clamp(cuts, max=cum.numel()), z + cum.numel()])
+
+
+def build_hub_tiles_layout(a: DeviceCSR, hub_rows: Tensor, parts, n_wg: int, tile: int):
+    """The tiles layout of the hub rows' entries (mi_spmm_tiles): a dict of tensors.  hub_rows: int64, parts[i] slots of row i.
+    Torch ops on the adjacency's device (or the CPU, for the layout tests); set-up time only."""
+    dev = a.rowptr.device
+    n_hub = int(hub_rows.numel())
+    deg = (a.rowptr[1:] - a.rowptr[:-1]).to(t.int64)
+    dl = deg[hub_rows]
+    total = int(dl.sum())
+    parts_t = t.tensor(parts, dtype=t.int64, device=dev)
+    base_t = t.cumsum(parts_t, 0) - parts_t
+    n_slots = int(parts_t.sum())
+    row_i = t.repeat_interleave(t.arange(n_hub, device=dev), dl)
+    first = t.cumsum(dl, 0) - dl
+    rank = t.arange(total, device=dev) - first[row_i]                                    # entry j of its row
+    e = a.rowptr[hub_rows].to(t.int64)[row_i] + rank                                    # position in a.col / a.val
+    c = a.col[e].to(t.int64)
+    slot = base_t[row_i] + rank % parts_t[row_i]
+    loads = t.bincount(slot, minlength=n_slots).cpu().tolist()
+    where = hub_tiles_assign(loads)
+    sg_t = t.tensor([w[0] for w in where], dtype=t.int64, device=dev)
+    q_t = t.tensor([w[1] for w in where], dtype=t.int64, device=dev)
+    slot_of = t.full((HUB_SG * HUB_ACC,), -1, dtype=t.int32, device=dev)
+    slot_of[sg_t * HUB_ACC + q_t] = t.arange(n_slots, dtype=t.int32, device=dev)
+    tl = c // tile
+    n_tiles = (a.n_cols + tile - 1) // tile
+    key = (tl * HUB_SG + sg_t[slot]) * HUB_ACC + q_t[slot]
+    order = t.argsort(key, stable=True)                                                 # columns stay ascending within a slot
+    key = key[order]
+    tile_entries = t.bincount(tl, minlength=n_tiles)
+    live = t.nonzero(tile_entries > 0).view(-1)                                         # the tiles that are loaded
+    comp = t.full((n_tiles,), -1, dtype=t.int64, device=dev)
+    comp[live] = t.arange(live.numel(), device=dev)
+    n_live = int(live.numel())
+    cnt = t.bincount(comp[key // (HUB_SG * HUB_ACC)] * (HUB_SG * HUB_ACC) + key % (HUB_SG * HUB_ACC),
+                     minlength=n_live * HUB_SG * HUB_ACC).view(n_live, HUB_SG, HUB_ACC)
+    per_sg = cnt.sum(2)
+    sg_off = (t.cumsum(per_sg, 1) - per_sg).to(t.int32).contiguous()                   # first entry of the sub-group within its tile
+    te = tile_entries[live]
+    tile_ent = t.zeros(n_live + 1, dtype=t.int64, device=dev)
+    tile_ent[1:] = t.cumsum(te, 0)
+    cuts = hub_tiles_ranges(tile_entries, tile, n_wg)
+    before = t.zeros(n_tiles + 1, dtype=t.int64, device=dev)
+    before[1:] = t.cumsum((tile_entries > 0).to(t.int64), 0)
+    src = e[order].to(t.int32).contiguous()
+    return dict(ecol=(c[order] % tile).to(t.uint8).contiguous(), src=src, eval=a.val[src.long()].contiguous(),
+                tile_id=live.to(t.int32).contiguous(), tile_ent=tile_ent.to(t.int32).contiguous(),
+                cnt=cnt.to(t.uint8).contiguous(), sg_off=sg_off, wg_ptr=before[cuts].to(t.int32).contiguous(),
+                wg_tiles=cuts, slot_of=slot_of, slot_loads=loads, n_slots=n_slots, item_ptr=(n_wg * t.cat([base_t, base_t.new_tensor([n_slots])])).to(t.int32).contiguous(),
+                max_tile_entries=int(te.max()) if n_live else 0, tile=tile, n_wg=n_wg, cnt_max=int(cnt.max()) if n_live else 0)
+
+
+def hub_tiles_entry_cap(tile: int, d: int = 128) -> int:
+    """Entries of one tile that the kernel's LDS holds (csrc/spmm.hip: 3 entries staged per thread)."""
+    lpr = 8 if d <= 32 else 16 if d <= 64 else 32
+    return 3 * HUB_SG * lpr
+
+
+def build_hub_tiles_plan(a: DeviceCSR, chunk: int = DEFAULT_CHUNK, n_slots: Optional[int] = None, floor: Optional[int] = None,
+                         n_wg: Optional[int] = None, tile: Optional[int] = None) -> Optional[SpmmPlan]:
+    """TILES plan: the hub rows (hub_tiles_slots) in the tiles layout, their n_wg partial rows per slot in front of the work
+    items' slots; every other row as in build_spmm_plan's banded default (thin rows, banded work items up to the hub rows'
+    degree), long_rows / item_ptr merged as the hybrid plan merges them.  None when the adjacency has no hub rows or a tile
+    holds more entries than the kernel stages."""
+    n_slots = HUB_SLOTS if n_slots is None else n_slots
+    floor = HUB_FLOOR if floor is None else floor
+    tile = HUB_TILE if tile is None else tile
+    if n_wg is None:
+        n_wg = HUB_WGS or t.cuda.get_device_properties(a.device).multi_processor_count
+    if a.val is None or a.nnz == 0 or tile not in (64, 128) or not 0 < n_slots <= HUB_SG * HUB_ACC or n_wg < 1:
+        return None
+    dev = a.device
+    deg = a.rowptr[1:] - a.rowptr[:-1]
+    floor = max(floor, chunk + 1)
+    cand = t.nonzero(deg >= floor).view(-1)
+    if cand.numel() == 0:
+        return None
+    cand = cand[t.argsort(deg[cand], descending=True, stable=True)][:n_slots]
+    n_hub, parts, _ = hub_tiles_slots(deg[cand].cpu().tolist(), n_slots, floor)
+    if n_hub == 0:
+        return None
+    cand = cand[:n_hub]
+    max_deg = int(deg[cand[-1]]) - 1                     # every row longer than this is a hub row ...
+    hub_rows = t.nonzero(deg > max_deg).view(-1)         # ... ties of the shortest included
+    if hub_rows.numel() != n_hub:
+        hub_rows = hub_rows[t.argsort(deg[hub_rows], descending=True, stable=True)]
+        n_hub, parts, _ = hub_tiles_slots(deg[hub_rows].cpu().tolist(), HUB_SG * HUB_ACC, floor)
+        if n_hub != hub_rows.numel():
+            return None                                  # a tie that does not fit: leave the adjacency to the banded plan
+    else:
+        hub_rows = cand
+    lay = build_hub_tiles_layout(a, hub_rows.to(t.int64), parts, n_wg, tile)
+    if lay["cnt_max"] > 255:                                      # duplicate entries beyond what a count byte holds
+        return None
+    if lay["max_tile_entries"] > hub_tiles_entry_cap(tile, 128):  # narrower products have smaller workgroups: checked per launch
+        return None
+    tl = _lib.SpmmTilesStruct(lay["ecol"].data_ptr(), lay["eval"].data_ptr(), lay["tile_id"].data_ptr(), lay["tile_ent"].data_ptr(),
+                              lay["cnt"].data_ptr(), lay["sg_off"].data_ptr(), lay["wg_ptr"].data_ptr(), lay["slot_of"].data_ptr(),
+                              n_wg, lay["n_slots"], tile, HUB_NT, a.n_cols, lay["max_tile_entries"])
+    off = n_wg * lay["n_slots"]                           # the hub rows' partial rows come first
+    hub32 = hub_rows.to(t.int32).contiguous()
+    # the rest: thin rows and banded work items of the rows with chunk < degree <= max_deg
+    L = _lib.lib()
+    band = DEFAULT_BAND if a.n_cols >= MIN_BANDED_COLS else 0
+    thin_max = THIN_PER_BAND * ((a.n_cols + band - 1) // band) if band > 0 else 0
+    if thin_max <= chunk or thin_max > max_deg:
+        thin_max = 0
+    st = SpmmPlanStruct()
+    plan = None
+    nl = 0
+    if max_deg > chunk:
+        ws = _ws(L.mi_spmm_plan_workspace_bytes(a.n_rows, a.nnz), dev)
+        info = _lib.SpmmPlanInfo()
+        check(L.mi_spmm_plan_count_thin(a.n_rows, a.n_cols, _ptr(a.rowptr), _ptr(a.col), chunk, thin_max, max_deg, band,
+                                        ws.data_ptr(), ws.numel(), ctypes.byref(info), _stream()), "mi_spmm_plan_count_thin")
+        nl, nlaunch = int(info.n_long_rows), int(info.n_launch)
+    long_index = t.full((max(a.n_rows, 1),), -1, dtype=t.int32, device=dev)
+    if nl > 0:
+        long_rows_b = t.empty(nl, dtype=t.int32, device=dev)
+        item_ptr_b = t.empty(nl + 1, dtype=t.int32, device=dev)
+        items = t.empty(4 * max(nlaunch, 1), dtype=t.int32, device=dev)
+        st_b = SpmmPlanStruct()
+        st_b.long_rows, st_b.item_ptr, st_b.items, st_b.long_index = long_rows_b.data_ptr(), item_ptr_b.data_ptr(), items.data_ptr(), None
+        check(L.mi_spmm_plan_fill(a.n_rows, _ptr(a.rowptr), ctypes.byref(info), ctypes.byref(st_b), ws.data_ptr(), ws.numel(),
+                                  _stream()), "mi_spmm_plan_fill")
+        del ws
+        it = items.view(-1, 4)
+        it[:, 3] += (it[:, 3] >= 0).to(t.int32) * off    # padding slots stay negative
+        long_rows = t.cat([hub32, long_rows_b]).contiguous()
+        item_ptr = t.cat([lay["item_ptr"][:-1], item_ptr_b + off]).contiguous()
+        st.n_items, st.n_launch = off + int(info.n_items), nlaunch
+        st.items = items.data_ptr()
+        st.band, st.n_bands = int(info.band), int(info.n_bands)
+    else:
+        items = None
+        long_rows, item_ptr = hub32, lay["item_ptr"]
+        st.n_items, st.n_launch = off, 0
+        st.items = None
+    long_index[long_rows.long()] = t.arange(long_rows.numel(), dtype=t.int32, device=dev)
+    st.chunk, st.n_long_rows = chunk, int(long_rows.numel())
+    st.long_rows, st.item_ptr, st.long_index = long_rows.data_ptr(), item_ptr.data_ptr(), long_index.data_ptr()
+    plan = SpmmPlan(st, long_rows, item_ptr, items, long_index)
+    plan.tiles, plan.tiles_t = tl, lay
+    plan.thin_max = thin_max
+    if thin_max > 0:
+        rows = t.nonzero((deg > chunk) & (deg <= thin_max)).view(-1)
+        if rows.numel() > 0:
+            rows = rows[t.argsort(deg[rows], descending=True, stable=True)]
+            long_index[rows] = -2
+            plan.thin_rows = rows.to(t.int32).contiguous()
+    if nl > 0:
+        plan.nnz_long = int(info.nnz_long)
+        if PACK_ENTRIES and nlaunch > 0 and plan.nnz_long > 0:
+            # the work items' begin / end index the CSR arrays: the pack pass reads them as they are
+            _pack_plan_entries(a, plan, values_only=False)
+    plan.values_of = _values_key(a)
+    return plan
+
+
+def _hub_tiles_plan_for(a: DeviceCSR, d: int) -> Optional[SpmmPlan]:
+    """The adjacency's tiles plan for a dense launch of width d, or None: the module switch, the gates of "auto", one build
+    per adjacency (a.plan_tiles; False = tried and not applicable)."""
+    if HUB_TILES in ("0", "", 0, None, False) or a.hot is None or d > 128 or d % 4:
+        return None
+    key = (str(HUB_TILES), HUB_SLOTS, HUB_FLOOR, HUB_TILE, HUB_NT, HUB_WGS, HUB_MIN_REUSE, id(a.plan))
+    if a.__dict__.get("_plan_tiles_key") != key:      # another a.plan (rebuilt with another chunk) or other switches: build again
+        object.__setattr__(a, "_plan_tiles_key", key)
+        a.plan_tiles = None
+    if a.plan_tiles is None:
+        plan = None
+        ok = a.nnz >= PLAN_MIN_NNZ or str(HUB_TILES) == "1"
+        if ok and str(HUB_TILES) != "1":
+            ok = a.n_cols >= HUB_MIN_COLS and a.plan is not None and a.plan.sweep is None
+        if ok:
+            plan = build_hub_tiles_plan(a, chunk=int(a.plan.struct.chunk) if a.plan is not None else DEFAULT_CHUNK)
+        if plan is not None and str(HUB_TILES) != "1":
+            if int(plan.tiles_t["tile_ent"][-1]) < HUB_MIN_REUSE * a.n_cols:
+                plan = None
+        a.plan_tiles = plan if plan is not None else False
+    plan = a.plan_tiles or None
+    if plan is not None and plan.tiles_t["max_tile_entries"] > hub_tiles_entry_cap(plan.tiles_t["tile"], d):
+        return None                                       # this width's workgroup stages fewer entries per tile: today's path
+    return plan
+
+
 import os as _os
 SWEEP = _os.environ.get("LAPLACE_SWEEP", "1") != "0"  # module switch (A/B): off keeps the banded work-item plans
 SWEEP_BAND = int(_os.environ.get("LAPLACE_SWEEP_BAND", SWEEP_BAND))
@@ -629,6 +882,9 @@ def _sync_plan_values(a: DeviceCSR, plan: SpmmPlan) -> None:
         raise ValueError(f"val has {v.numel()} entries, the adjacency {a.nnz}")
     if plan.packed:
         _pack_plan_entries(a, plan, values_only=True)
+    if plan.tiles is not None:
+        ev = plan.tiles_t["eval"]
+        check(_lib.lib().mi_gather_f32(ev.numel(), _ptr(v), _ptr(plan.tiles_t["src"]), _ptr(ev), _stream()), "mi_gather_f32")
     if plan.sweep is not None:
         val_s = plan.sweep_t[1]
         check(_lib.lib().mi_gather_f32(val_s.numel(), _ptr(v), _ptr(plan.sweep_src), _ptr(val_s), _stream()), "mi_gather_f32")
@@ -715,6 +971,8 @@ def spmm(a: DeviceCSR, X: Tensor, *, Y: Optional[Tensor] = None, addend: Optiona
     if a.plan is None and (a.nnz >= PLAN_MIN_NNZ or row_list is not None):
         a.plan = build_spmm_plan(a)
     plan = a.plan
+    if plan is not None and x_map is None and row_list is None:
+        plan = _hub_tiles_plan_for(a, d) or plan          # dense launches: the hub rows from LDS-staged tiles (HUB_TILES)
     if plan is not None and plan.sweep is not None and d > 128:  # the sweep form stops at 128 floats per row
         if plan.wide is None:
             plan.wide = build_spmm_plan(a, chunk=int(plan.struct.chunk), sweep=False, thin_max=0)
@@ -759,22 +1017,36 @@ def spmm(a: DeviceCSR, X: Tensor, *, Y: Optional[Tensor] = None, addend: Optiona
     if row_slices and not _row_slices_pay(a, plan, slice_rows):
         row_slices = slice_rows = 0
 
-    def launch(parts: int, stream: int) -> None:
+    def launch(parts: int, stream: int, raw: bool = False):
         exs = None
         if (x_map is not None or addend_map is not None or row_list is not None or adam_args is not None or parts
-                or sweep is not None or hot_rows != 0 or HOT_THREADS or n_thin or row_slices):
+                or sweep is not None or hot_rows != 0 or HOT_THREADS or n_thin or row_slices or (plan is not None and plan.tiles is not None)):
             exs = SpmmExStruct(_ptr(x_map), _ptr(addend_map), _ptr(row_list), _ptr(n_list_dev),
                                row_list.numel() if row_list is not None else 0,
                                ctypes.pointer(adam_args) if adam_args is not None else None, parts, hot_rows,
                                ctypes.pointer(sweep) if sweep is not None else None, hot_base, HOT_THREADS, _ptr(x_bits),
-                               _ptr(plan.thin_rows) if n_thin else None, n_thin, row_slices, slice_rows)
-        check(L.mi_spmm_csr_ex_f32(a.n_rows, d, _ptr(a.rowptr), col_ptr, val_ptr, X.data_ptr(), ldx,
-                                   _ptr(Y), ldy, _ptr(addend), lda, _ptr(S), lds, float(scale),
-                                   ctypes.byref(plan.struct) if plan is not None else None,
-                                   ctypes.byref(exs) if exs is not None else None, ws_ptr, ws_bytes,
-                                   stream), "mi_spmm_csr_ex_f32")
+                               _ptr(plan.thin_rows) if n_thin else None, n_thin, row_slices, slice_rows,
+                               ctypes.pointer(plan.tiles) if plan is not None and plan.tiles is not None else None)
+        rc = L.mi_spmm_csr_ex_f32(a.n_rows, d, _ptr(a.rowptr), col_ptr, val_ptr, X.data_ptr(), ldx,
+                                  _ptr(Y), ldy, _ptr(addend), lda, _ptr(S), lds, float(scale),
+                                  ctypes.byref(plan.struct) if plan is not None else None,
+                                  ctypes.byref(exs) if exs is not None else None, ws_ptr, ws_bytes, stream)
+        if raw:
+            return rc
+        check(rc, "mi_spmm_csr_ex_f32")
 
-    if SPMM_TWO_STREAMS and plan is not None and (plan.n_items > 0 or n_thin > 0):
+    if plan is not None and plan.tiles is not None and d not in plan.tiles_t.setdefault("widths_ok", set()):
+        # The first product of a tiles plan at this width is ONE whole launch on the current stream: the library tries the
+        # tiles kernel's LDS size before it enqueues anything, so a device that refuses it (MI_ERR_UNSUPPORTED) has done no
+        # work yet — the adjacency then gives up the form for good and the product is redone with its other plan.
+        rc = launch(0, _stream(), raw=True)
+        if rc == _lib.MI_ERR_UNSUPPORTED:
+            a.plan_tiles = False
+            return spmm(a, X, Y=Y, addend=addend, S=S, scale=scale, x_map=x_map, addend_map=addend_map, row_list=row_list,
+                        n_list_dev=n_list_dev, adam=adam, x_rare=x_rare)
+        check(rc, "mi_spmm_csr_ex_f32")
+        plan.tiles_t["widths_ok"].add(d)
+    elif SPMM_TWO_STREAMS and plan is not None and (plan.n_items > 0 or n_thin > 0):
         # short rows beside the split rows' work items + fix-up: disjoint output rows, joined before returning
         cur = t.cuda.current_stream()
         side = _side_stream(a.device)
