@@ -1989,6 +1989,67 @@ int     mi_als_block_rows_f32(int64_t n_rows, int64_t d, int64_t block, int64_t 
                               const int32_t* row_list, int64_t n_list, int32_t* n_failed, void* ws, size_t ws_bytes,
                               mi_stream_t stream);
 
+/* ------------------------------------------------------------------------------------
+ * iALS weighted  the iALS entry with a confidence per entry and a regulariser per row (additive to ABI 14; csrc/als.hip).
+ * replaces: nothing in the reference.  Hu, Koren and Volinsky's c_ui = 1 + alpha r_ui (the caller passes a_e = alpha r_e) and
+ *           the frequency-scaled regulariser of Rendle et al. (RecSys 2022, section 4) as a value per row.  The iALS entry
+ *           above keeps its signature, its code and its bits; this one solves, per row r,
+ *               (G + sum_e a_e y_e y_e^T + reg_r I) x = sum_e (1 + a_e) y_e.
+ * Inputs.  As the iALS entry, with `conf` [nnz] (f32; a_e by ENTRY POSITION in idx) in the place of alpha and
+ *   `reg_rows` [n_rows] (f32; indexed by ROW ID, never by list position; null = the scalar `reg` for every row).
+ *   a_e must be finite and >= 0; the entry does not scan conf.
+ * The rule, per row r with entries e in CSR order, y_e = Y[idx[e], :], a_e = conf[e], c_e = 1.0f + a_e (one rounding),
+ * reg_r = reg_rows ? reg_rows[r] : reg; restated in float64 and float32 by tests/als_weighted_emulation.py:
+ *   z         z_e[k] = a_e * y_e[k], ONE f32 product per element.
+ *   chunks    As the iALS entry: chunk c is entries [c L, (c + 1) L) of the row, L = mi_als_chunk(d).
+ *   per chunk S_c[j][k] = ONE chain acc = fmaf(y_e[j], z_e[k], acc) from 0 in entry order, for k <= j (the row index is
+ *             the y side, the column index the z side);  s_c[j] = ONE chain acc = fmaf(c_e, y_e[j], acc) from 0 in entry order.
+ *   across    S = ((S_0 + S_1) + S_2) ... in ascending c, one f32 addition each; s likewise.
+ *   system    A[j][k] = G[j][k] + S[j][k] (one addition), then reg_r added on the diagonal (A[j][j] = (G + S) + reg_r);
+ *             b[j] = s[j].
+ *   solve, empty row, pivot: as the iALS entry.
+ *   reg_r     A reg_rows[r] that is not a positive finite number makes row r a failed row: x_r = 0, counted in *n_failed; an
+ *             EMPTY row is zero and not counted whatever its reg_rows.
+ *   conf      A negative or non-finite a_e may cost the row its definiteness and is then handled by the pivot rule (zero row,
+ *             counted); a NaN that reaches x is the caller's.  Nothing is read or written out of bounds on any such input.
+ * Duplicates, determinism, row_list / n_list, guards, workspace (mi_als_solve_rows_w_workspace_bytes, the same size and
+ *   layout): as the iALS entry; with a row_list, conf is still by entry position and reg_rows by row id.
+ * Returned before anything is enqueued: everything the iALS entry refuses (alpha apart), MI_ERR_BAD_ARG for a null conf, and
+ *   for reg <= 0 or not finite when reg_rows is null (with reg_rows given, reg is not looked at).
+ * ---------------------------------------------------------------------------------- */
+size_t  mi_als_solve_rows_w_workspace_bytes(int64_t n_work, int64_t nnz, int64_t d);
+int     mi_als_solve_rows_w_f32(int64_t n_rows, int64_t d, const int32_t* ptr, const int32_t* idx, int64_t nnz,
+                                int64_t n_cols, const float* Y, int64_t ldy, const float* G, const float* conf,
+                                const float* reg_rows /* nullable */, float reg, float* X, int64_t ldx,
+                                const int32_t* row_list, int64_t n_list, int32_t* n_failed, void* ws, size_t ws_bytes,
+                                mi_stream_t stream);
+
+/* ------------------------------------------------------------------------------------
+ * iALS block weighted  the iALS block entry with the same two additions (additive to ABI 14; csrc/als_block.hip).
+ * Minimises the row quadratic of the "iALS weighted" entry, 1/2 x^T A x - b^T x, over one block of B coordinates at a time.
+ * Inputs.  As the iALS block entry, with conf [nnz] and reg_rows [n_rows] (nullable) as in the iALS weighted entry.
+ * The rule is the "iALS block" rule with these changes (a_e = conf[e], c_e = 1.0f + a_e, reg_r as above), restated in
+ * float64 and float32 by tests/als_weighted_emulation.py:
+ *     w_e     = fmaf(a_e, p_e, -c_e)
+ *     g[j]    = fmaf(reg_r, x[j], gs[j] + q[j])            (gs and q as in the iALS block rule, gs with this w_e)
+ *     S[j][k] = ONE chain acc = fmaf(y_e[j], z_e[k], acc) from 0 over ALL the row's entries in order, z_e[k] = a_e * y_e[k]
+ *               (one f32 product), k <= j
+ *     H[j][k] = G(j, k) + S[j][k] (one addition), + reg_r on the diagonal,   j, k in pi
+ *   Start, q, delta, the update of x and p_e, the absence of chunks, the empty row and the pivot rule are unchanged.  A row of
+ *   at most min(mi_als_block_chunk(d, B), 128) entries (the 128 binds at d <= 16 only) keeps a_e on chip beside p_e; a longer
+ *   one re-reads conf with every streamed piece (conf is not copied into the workspace).  Both paths give the same bits.
+ *   A reg_rows[r] that is not a positive finite number: a failed row (zero, counted), as in the iALS weighted entry.
+ * Workspace: mi_als_block_rows_w_workspace_bytes, the size of the iALS block entry's.
+ * Returned before anything is enqueued: everything the iALS block entry refuses (alpha apart), a null conf, and reg <= 0 or
+ *   not finite when reg_rows is null.
+ * ---------------------------------------------------------------------------------- */
+size_t  mi_als_block_rows_w_workspace_bytes(int64_t n_work, int64_t nnz, int64_t d, int64_t block);
+int     mi_als_block_rows_w_f32(int64_t n_rows, int64_t d, int64_t block, int64_t sweeps, const int32_t* ptr,
+                                const int32_t* idx, int64_t nnz, int64_t n_cols, const float* Y, int64_t ldy, const float* G,
+                                const float* conf, const float* reg_rows /* nullable */, float reg, float* X /* in/out */,
+                                int64_t ldx, int32_t from_zero, const int32_t* row_list, int64_t n_list, int32_t* n_failed,
+                                void* ws, size_t ws_bytes, mi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

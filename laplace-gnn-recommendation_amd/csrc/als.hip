@@ -39,6 +39,12 @@
 // A pivot that is not a positive finite number is seen by every thread at once (all read the same word): the workgroup writes a
 // zero row, thread 0 counts it, everybody leaves.  Nothing of that touches memory outside the row's own x.
 //
+// Weighted entry ("iALS weighted" in the header: a confidence a_e per entry, a regulariser per row).  The same kernels with
+// W = true: als_accumulate_w stages a second image z = a y beside y (the B operand of every tile; same stride, same banks) and
+// c_e = 1 + a_e for the s chain; A = (G + S) + reg_r I, b = s.  The system still aliases both images (64 staged rows <= d + 1
+// rows at d >= 64; at d <= 32 the staging is the larger and the kernel's LDS doubles).  The W = false instantiations compile
+// to the instructions they had before the parameter existed.  Measured: profiles/als_weighted.md.
+//
 // Measured rates and where this is poor (a user half-sweep is all factorisation: one barrier per column with four wavefronts
 // waiting on it; the d <= 32 classes run one row per workgroup): profiles/als.md.
 #include "common.hpp"
@@ -62,6 +68,7 @@ struct AlsCfg {
     static constexpr int F4 = DP / 4;
     static constexpr int U = ALS_KT * F4 / NT;
     static constexpr int SM_ROWS = (DP + 1) > ALS_KT ? (DP + 1) : ALS_KT;
+    static constexpr int SM_ROWS_W = (DP + 1) > 2 * ALS_KT ? (DP + 1) : 2 * ALS_KT;   // weighted: a second staged image (z)
     static_assert(ALS_KT * F4 % NT == 0, "whole float4 slots per thread");
 };
 
@@ -82,6 +89,8 @@ struct AlsArgs {
     int32_t* chunk_base;   // [n_work]  first slot of a long row, -1 = none left
     float* part;           // [cap][d * d + d]
     int cap;
+    const float* conf;     // weighted entries only: a_e by entry position
+    const float* reg_rows; // weighted entries only: reg by ROW ID, or null (the scalar reg)
 };
 
 __device__ __forceinline__ void als_tile_of(int q, int& ti, int& tj) {
@@ -136,6 +145,66 @@ __device__ __forceinline__ void als_accumulate(const AlsArgs& a, int p0, int p1,
     }
 }
 
+// The weighted sibling ("iALS weighted" in the header): S_c[j][k] = sum_e y_e[j] z_e[k] with z_e = a_e * y_e (one f32 product per
+// element, made once while staging), s_c[j] = sum_e c_e y_e[j] with c_e = 1.0f + a_e.  `stage` holds TWO images of ALS_KT
+// rows, y then z, both with the stride C::LDA: the A operand of tile (ti, tj) is read from y, the B operand from z.  a_e comes
+// in with the same ALS_KT prefetch as idx; an entry past the end of the row is staged as y = z = 0 with c = 0.
+template <class C>
+__device__ __forceinline__ void als_accumulate_w(const AlsArgs& a, int p0, int p1, float* stage, float* cs, const int (&ti)[C::TPW],
+                                                 const int (&tj)[C::TPW], const bool (&live)[C::TPW], f32x4 (&acc)[C::TPW],
+                                                 float& s_sum) {
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int d = a.d;
+    float* stagez = stage + ALS_KT * C::LDA;
+    float4 pre[C::U];
+    float prea[C::U];
+    auto fetch = [&](int q0) {
+#pragma unroll
+        for (int u = 0; u < C::U; ++u) {
+            const int f = tid + C::NT * u, e = f / C::F4, c4 = f % C::F4;
+            float4 v = mi_f4_zero();
+            float w = 0.f;
+            if (q0 + e < p1) {
+                w = a.conf[q0 + e];
+                if (4 * c4 < d) {
+                    const int col = a.idx[q0 + e];
+                    if ((unsigned)col < (unsigned)a.n_cols) v = *reinterpret_cast<const float4*>(a.Y + (int64_t)col * a.ldy + 4 * c4);
+                }
+            }
+            pre[u] = v;
+            prea[u] = w;
+        }
+    };
+    fetch(p0);
+    const int arow = lane >> 4, acol = lane & 15;
+    for (int q0 = p0; q0 < p1; q0 += ALS_KT) {
+#pragma unroll
+        for (int u = 0; u < C::U; ++u) {
+            const int f = tid + C::NT * u, e = f / C::F4, c4 = f % C::F4;
+            const float4 v = pre[u];
+            const float w = prea[u];
+            *reinterpret_cast<float4*>(stage + e * C::LDA + 4 * c4) = v;
+            *reinterpret_cast<float4*>(stagez + e * C::LDA + 4 * c4) = make_float4(w * v.x, w * v.y, w * v.z, w * v.w);
+            if (c4 == 0) cs[e] = q0 + e < p1 ? 1.0f + w : 0.f;
+        }
+        __syncthreads();
+        if (q0 + ALS_KT < p1) fetch(q0 + ALS_KT);
+        const int ne = min(ALS_KT, p1 - q0), steps = (ne + 3) >> 2;
+        for (int ks = 0; ks < steps; ++ks) {
+            const float* row = stage + (4 * ks + arow) * C::LDA + acol;
+            const float* rowz = stagez + (4 * ks + arow) * C::LDA + acol;
+#pragma unroll
+            for (int s = 0; s < C::TPW; ++s) {
+                if (live[s]) acc[s] = __builtin_amdgcn_mfma_f32_16x16x4f32(row[16 * ti[s]], rowz[16 * tj[s]], acc[s], 0, 0, 0);
+            }
+        }
+        if (tid < d) {
+            for (int e = 0; e < ne; ++e) s_sum = fmaf(cs[e], stage[e * C::LDA + tid], s_sum);
+        }
+        __syncthreads();
+    }
+}
+
 template <class C>
 __device__ __forceinline__ void als_tiles(int d, int (&ti)[C::TPW], int (&tj)[C::TPW], bool (&live)[C::TPW]) {
     const int wave = threadIdx.x >> 6;
@@ -170,9 +239,9 @@ __global__ void als_plan_kernel(AlsArgs a, int L) {
     a.chunk_base[pos] = base;
 }
 
-template <class C>
+template <class C, bool W>
 __global__ __launch_bounds__(C::NT) void als_partial_kernel(AlsArgs a) {
-    __shared__ __align__(16) float sm[ALS_KT * C::LDA];
+    __shared__ __align__(16) float sm[(W ? 2 : 1) * ALS_KT * C::LDA];
     const int slot = blockIdx.x;
     const int pos = a.chunk_row[slot];
     if (pos < 0) return;
@@ -188,7 +257,12 @@ __global__ __launch_bounds__(C::NT) void als_partial_kernel(AlsArgs a) {
 #pragma unroll
     for (int s = 0; s < C::TPW; ++s) acc[s] = f32x4{0.f, 0.f, 0.f, 0.f};
     float s_sum = 0.f;
-    als_accumulate<C>(a, p0, p1, sm, ti, tj, live, acc, s_sum);
+    if constexpr (W) {
+        __shared__ float cs[ALS_KT];
+        als_accumulate_w<C>(a, p0, p1, sm, cs, ti, tj, live, acc, s_sum);
+    } else {
+        als_accumulate<C>(a, p0, p1, sm, ti, tj, live, acc, s_sum);
+    }
     float* out = a.part + (int64_t)slot * (d * d + d);
 #pragma unroll
     for (int s = 0; s < C::TPW; ++s) {
@@ -203,9 +277,9 @@ __global__ __launch_bounds__(C::NT) void als_partial_kernel(AlsArgs a) {
     if (tid < d) out[d * d + tid] = s_sum;
 }
 
-template <class C>
+template <class C, bool W>
 __global__ __launch_bounds__(C::NT) void als_solve_kernel(AlsArgs a) {
-    __shared__ __align__(16) float sm[C::SM_ROWS * C::LDA];   // the staged entries, then A with b as row d
+    __shared__ __align__(16) float sm[(W ? C::SM_ROWS_W : C::SM_ROWS) * C::LDA];   // the staged entries, then A with b as row d
     __shared__ float cb[2][C::DP + 1];                         // column k (unscaled) of the step that reads it
     __shared__ float dinv[C::DP];                              // 1 / L[k][k]
     const int tid = threadIdx.x, lane = tid & 63;
@@ -223,6 +297,11 @@ __global__ __launch_bounds__(C::NT) void als_solve_kernel(AlsArgs a) {
         return;
     }
     bool failed = p0 < 0 || n > a.nnz - p0;   // a rowptr that disagrees with nnz: nothing of idx is read for this row
+    float reg_r = a.reg;
+    if constexpr (W) {
+        if (a.reg_rows) reg_r = a.reg_rows[r];   // by row id; r is inside [0, n_rows) here
+        failed = failed || !(reg_r > 0.f && reg_r < INFINITY);
+    }
     int ti[C::TPW], tj[C::TPW];
     bool live[C::TPW];
     f32x4 acc[C::TPW];
@@ -232,7 +311,12 @@ __global__ __launch_bounds__(C::NT) void als_solve_kernel(AlsArgs a) {
     float s_sum = 0.f;
     if (failed) {
     } else if (n <= L) {
-        als_accumulate<C>(a, p0, p0 + n, sm, ti, tj, live, acc, s_sum);
+        if constexpr (W) {
+            __shared__ float cs[ALS_KT];
+            als_accumulate_w<C>(a, p0, p0 + n, sm, cs, ti, tj, live, acc, s_sum);
+        } else {
+            als_accumulate<C>(a, p0, p0 + n, sm, ti, tj, live, acc, s_sum);
+        }
     } else {
         const int base = a.cap > 0 ? a.chunk_base[pos] : -1;   // -1: no slots left (a row listed twice); counted as failed
         failed = base < 0;
@@ -252,7 +336,7 @@ __global__ __launch_bounds__(C::NT) void als_solve_kernel(AlsArgs a) {
             if (tid < d) s_sum = s_sum + part[d * d + tid];
         }
     }
-    // A = fmaf(alpha, S, G) + reg I (lower triangle), b = (1 + alpha) s as row d
+    // A = fmaf(alpha, S, G) + reg I (lower triangle), b = (1 + alpha) s as row d; weighted: A = (G + S) + reg_r I, b = s
     if (!failed) {
 #pragma unroll
         for (int s = 0; s < C::TPW; ++s) {
@@ -262,15 +346,17 @@ __global__ __launch_bounds__(C::NT) void als_solve_kernel(AlsArgs a) {
             for (int g = 0; g < 4; ++g) {
                 const int row = 16 * ti[s] + 4 * (lane >> 4) + g;
                 if (row < d && col <= row) {
-                    float v = fmaf(a.alpha, acc[s][g], a.G[row * d + col]);
-                    if (row == col) v = v + a.reg;
+                    float v;
+                    if constexpr (W) v = a.G[row * d + col] + acc[s][g];
+                    else v = fmaf(a.alpha, acc[s][g], a.G[row * d + col]);
+                    if (row == col) v = v + reg_r;
                     sm[row * C::LDA + col] = v;
                     if (col == 0) cb[0][row] = v;
                 }
             }
         }
         if (tid < d) {
-            const float bj = (1.0f + a.alpha) * s_sum;
+            const float bj = W ? s_sum : (1.0f + a.alpha) * s_sum;
             sm[d * C::LDA + tid] = bj;
             if (tid == 0) cb[0][d] = bj;
         }
@@ -376,14 +462,60 @@ inline AlsLayout als_layout(int64_t n_work, int64_t nnz, int64_t d) {
 
 inline bool als_width_ok(int64_t d) { return d >= 4 && d <= 128 && d % 4 == 0; }
 
-template <class C>
+template <class C, bool W>
 int als_launch(const AlsArgs& a, hipStream_t st) {
     if (a.cap > 0) {
-        hipLaunchKernelGGL((als_partial_kernel<C>), dim3(a.cap), dim3(C::NT), 0, st, a);
+        hipLaunchKernelGGL((als_partial_kernel<C, W>), dim3(a.cap), dim3(C::NT), 0, st, a);
         MI_HIP(hipGetLastError());
     }
-    hipLaunchKernelGGL((als_solve_kernel<C>), dim3(a.n_work), dim3(C::NT), 0, st, a);
+    hipLaunchKernelGGL((als_solve_kernel<C, W>), dim3(a.n_work), dim3(C::NT), 0, st, a);
     return mi_launch_status();
+}
+
+// The body of both entries: conf == null is the unweighted one (alpha, reg), otherwise (conf, reg_rows or reg).
+template <bool W>
+int als_run(int64_t n_rows, int64_t d, const int32_t* ptr, const int32_t* idx, int64_t nnz, int64_t n_cols, const float* Y,
+            int64_t ldy, const float* G, float alpha, const float* conf, const float* reg_rows, float reg, float* X, int64_t ldx,
+            const int32_t* row_list, int64_t n_list, int32_t* n_failed, void* ws, size_t ws_bytes, mi_stream_t stream) {
+    const int64_t lim = (int64_t)1 << 31;
+    MI_CHECK_ARG(als_width_ok(d));
+    MI_CHECK_ARG(n_rows >= 0 && n_rows < lim && n_cols >= 0 && n_cols < lim && nnz >= 0 && nnz < lim);
+    if (W) {
+        MI_CHECK_ARG(conf != nullptr);
+        MI_CHECK_ARG(reg_rows != nullptr || (reg > 0.f && reg < INFINITY));
+    } else {
+        MI_CHECK_ARG(alpha >= 0.f && alpha < INFINITY && reg > 0.f && reg < INFINITY);
+    }
+    const int64_t n_work = row_list ? n_list : n_rows;
+    MI_CHECK_ARG(n_work >= 0 && n_work < lim);
+    MI_CHECK_ARG(n_failed != nullptr);
+    if (n_work == 0) return 0;
+    MI_CHECK_ARG(ptr && (idx || nnz == 0) && Y && G && X);
+    MI_CHECK_ARG(mi_aligned16(Y) && ldy >= d && ldy % 4 == 0 && ldx >= d);
+    const AlsLayout lay = als_layout(n_work, nnz, d);
+    if (!ws || ws_bytes < lay.total) return MI_ERR_WORKSPACE;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    char* w = static_cast<char*>(ws);
+    AlsArgs a;
+    a.n_rows = (int)n_rows; a.d = (int)d; a.n_cols = (int)n_cols; a.n_work = (int)n_work; a.nnz = (int)nnz;
+    a.ptr = ptr; a.idx = idx; a.Y = Y; a.ldy = ldy; a.G = G; a.alpha = alpha; a.reg = reg; a.X = X; a.ldx = ldx;
+    a.row_list = row_list; a.n_failed = n_failed;
+    a.conf = conf; a.reg_rows = reg_rows;
+    a.counter = reinterpret_cast<int32_t*>(w + lay.counter);
+    a.chunk_row = reinterpret_cast<int32_t*>(w + lay.chunk_row);
+    a.chunk_base = reinterpret_cast<int32_t*>(w + lay.chunk_base);
+    a.part = reinterpret_cast<float*>(w + lay.part);
+    a.cap = (int)als_cap(nnz, als_chunk_of((int)d));
+    if (a.cap > 0) {
+        MI_HIP(hipMemsetAsync(a.counter, 0, 256, st));
+        MI_HIP(hipMemsetAsync(a.chunk_row, 0xFF, (size_t)a.cap * 4, st));
+        hipLaunchKernelGGL(als_plan_kernel, dim3((unsigned)mi_ceil_div(n_work, 256)), dim3(256), 0, st, a, als_chunk_of((int)d));
+        MI_HIP(hipGetLastError());
+    }
+    if (d <= 16) return als_launch<AlsCfg<16, 1>, W>(a, st);
+    if (d <= 32) return als_launch<AlsCfg<32, 1>, W>(a, st);
+    if (d <= 64) return als_launch<AlsCfg<64, 4>, W>(a, st);
+    return als_launch<AlsCfg<128, 4>, W>(a, st);
 }
 
 }  // namespace
@@ -401,39 +533,20 @@ int mi_als_solve_rows_f32(int64_t n_rows, int64_t d, const int32_t* ptr, const i
                           const float* Y, int64_t ldy, const float* G, float alpha, float reg, float* X, int64_t ldx,
                           const int32_t* row_list, int64_t n_list, int32_t* n_failed, void* ws, size_t ws_bytes,
                           mi_stream_t stream) {
-    const int64_t lim = (int64_t)1 << 31;
-    MI_CHECK_ARG(als_width_ok(d));
-    MI_CHECK_ARG(n_rows >= 0 && n_rows < lim && n_cols >= 0 && n_cols < lim && nnz >= 0 && nnz < lim);
-    MI_CHECK_ARG(alpha >= 0.f && alpha < INFINITY && reg > 0.f && reg < INFINITY);
-    const int64_t n_work = row_list ? n_list : n_rows;
-    MI_CHECK_ARG(n_work >= 0 && n_work < lim);
-    MI_CHECK_ARG(n_failed != nullptr);
-    if (n_work == 0) return 0;
-    MI_CHECK_ARG(ptr && (idx || nnz == 0) && Y && G && X);
-    MI_CHECK_ARG(mi_aligned16(Y) && ldy >= d && ldy % 4 == 0 && ldx >= d);
-    const AlsLayout lay = als_layout(n_work, nnz, d);
-    if (!ws || ws_bytes < lay.total) return MI_ERR_WORKSPACE;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    char* w = static_cast<char*>(ws);
-    AlsArgs a;
-    a.n_rows = (int)n_rows; a.d = (int)d; a.n_cols = (int)n_cols; a.n_work = (int)n_work; a.nnz = (int)nnz;
-    a.ptr = ptr; a.idx = idx; a.Y = Y; a.ldy = ldy; a.G = G; a.alpha = alpha; a.reg = reg; a.X = X; a.ldx = ldx;
-    a.row_list = row_list; a.n_failed = n_failed;
-    a.counter = reinterpret_cast<int32_t*>(w + lay.counter);
-    a.chunk_row = reinterpret_cast<int32_t*>(w + lay.chunk_row);
-    a.chunk_base = reinterpret_cast<int32_t*>(w + lay.chunk_base);
-    a.part = reinterpret_cast<float*>(w + lay.part);
-    a.cap = (int)als_cap(nnz, als_chunk_of((int)d));
-    if (a.cap > 0) {
-        MI_HIP(hipMemsetAsync(a.counter, 0, 256, st));
-        MI_HIP(hipMemsetAsync(a.chunk_row, 0xFF, (size_t)a.cap * 4, st));
-        hipLaunchKernelGGL(als_plan_kernel, dim3((unsigned)mi_ceil_div(n_work, 256)), dim3(256), 0, st, a, als_chunk_of((int)d));
-        MI_HIP(hipGetLastError());
-    }
-    if (d <= 16) return als_launch<AlsCfg<16, 1>>(a, st);
-    if (d <= 32) return als_launch<AlsCfg<32, 1>>(a, st);
-    if (d <= 64) return als_launch<AlsCfg<64, 4>>(a, st);
-    return als_launch<AlsCfg<128, 4>>(a, st);
+    return als_run<false>(n_rows, d, ptr, idx, nnz, n_cols, Y, ldy, G, alpha, nullptr, nullptr, reg, X, ldx, row_list, n_list,
+                          n_failed, ws, ws_bytes, stream);
+}
+
+size_t mi_als_solve_rows_w_workspace_bytes(int64_t n_work, int64_t nnz, int64_t d) {
+    return mi_als_solve_rows_workspace_bytes(n_work, nnz, d);
+}
+
+int mi_als_solve_rows_w_f32(int64_t n_rows, int64_t d, const int32_t* ptr, const int32_t* idx, int64_t nnz, int64_t n_cols,
+                            const float* Y, int64_t ldy, const float* G, const float* conf, const float* reg_rows, float reg,
+                            float* X, int64_t ldx, const int32_t* row_list, int64_t n_list, int32_t* n_failed, void* ws,
+                            size_t ws_bytes, mi_stream_t stream) {
+    return als_run<true>(n_rows, d, ptr, idx, nnz, n_cols, Y, ldy, G, 0.f, conf, reg_rows, reg, X, ldx, row_list, n_list,
+                         n_failed, ws, ws_bytes, stream);
 }
 
 }  // extern "C"

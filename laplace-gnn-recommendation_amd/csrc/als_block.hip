@@ -37,6 +37,7 @@ constexpr int AB_WAVES = 4;       // rows per workgroup, one wavefront each
 constexpr int AB_AREA = 4096;     // floats of LDS per wavefront for factor rows
 constexpr int AB_MAX_D = 256;
 constexpr int AB_MAX_RES = 256;   // entries of p_e kept in LDS
+constexpr int AB_MAX_RES_W = 128;  // weighted: entries of p_e and of a_e kept in LDS, together the size of the unweighted p_e
 
 // the smallest stride >= w that is 16 mod 32
 __host__ __device__ constexpr int ab_ld(int w) { return (w + 15) / 32 * 32 + 16; }
@@ -57,6 +58,8 @@ struct AbArgs {
     int32_t* n_failed;
     float* Gs;   // workspace: G(j, k) as a full symmetric matrix
     float* pw;   // workspace: p_e of the streaming rows, by entry position
+    const float* conf;       // weighted entry only: a_e by entry position
+    const float* reg_rows;   // weighted entry only: reg by ROW ID, or null (the scalar reg)
 };
 
 __global__ void als_block_sym_kernel(const float* G, float* Gs, int d) {
@@ -106,7 +109,12 @@ __device__ __forceinline__ void ab_dots(const float* src, int ld, int cnt, const
     }
 }
 
-template <int B>
+// W: the weighted entry ("iALS block weighted" in the header).  a_e sits beside p_e: in LDS (as[e]) for a resident row, re-read
+// from conf with every streamed chunk otherwise, never copied into the workspace.  The B operand of the Gram tiles is
+// z_e = a_e * y_e, one f32 product made in registers from the operand that the A side reads: no second staged image.
+// p_e and a_e share the LDS that p_e alone has in the unweighted kernel (two workgroups per CU at B = 16 either way), so a
+// weighted row is resident up to min(R, AB_MAX_RES_W) entries: fewer than R only at d <= 16.
+template <int B, bool W>
 __global__ __launch_bounds__(AB_WAVES * MI_WAVE) void als_block_kernel(AbArgs a) {
     constexpr int TB = B / 16, JG = 64 / B, HB = B + 1;
     constexpr int LDB = ab_ld(B), KT = B == 64 ? 48 : 64;
@@ -114,7 +122,7 @@ __global__ __launch_bounds__(AB_WAVES * MI_WAVE) void als_block_kernel(AbArgs a)
     __shared__ __align__(16) float s_area[AB_WAVES][AB_AREA];
     __shared__ float s_h[AB_WAVES][B * HB];
     __shared__ __align__(16) float s_x[AB_WAVES][AB_MAX_D];
-    __shared__ float s_p[AB_WAVES][AB_MAX_RES];
+    __shared__ float s_p[AB_WAVES][W ? AB_MAX_RES_W : AB_MAX_RES];
     __shared__ float s_dl[AB_WAVES][64];
     __shared__ float s_gt[AB_WAVES][64];
     const int wave = threadIdx.x >> 6, lane = mi_lane();
@@ -126,7 +134,12 @@ __global__ __launch_bounds__(AB_WAVES * MI_WAVE) void als_block_kernel(AbArgs a)
     float* ps = s_p[wave];
     float* dl = s_dl[wave];
     float* gt = s_gt[wave];
-    const int d = a.d, LDR = ab_ld(d), RES = ab_res_of(d), d16 = (d + 15) & ~15;
+    float* as = nullptr;
+    if constexpr (W) {
+        __shared__ float s_a[AB_WAVES][AB_MAX_RES_W];
+        as = s_a[wave];
+    }
+    const int d = a.d, LDR = ab_ld(d), RES = W ? min(ab_res_of(d), AB_MAX_RES_W) : ab_res_of(d), d16 = (d + 15) & ~15;
     const int r = a.row_list ? a.row_list[pos] : pos;
     float* xout = a.X + (int64_t)pos * a.ldx;
     int p0 = 0, n = 0;
@@ -141,9 +154,19 @@ __global__ __launch_bounds__(AB_WAVES * MI_WAVE) void als_block_kernel(AbArgs a)
     bool failed = p0 < 0 || n > a.nnz - p0;   // a rowptr that disagrees with nnz: nothing of idx is read for this row
     const bool resident = n <= RES;
     const float c1 = -(1.0f + a.alpha);
+    float reg_r = a.reg;
+    if constexpr (W) {
+        if (a.reg_rows) reg_r = a.reg_rows[r];   // by row id; r is inside [0, n_rows) here
+        failed = failed || !(reg_r > 0.f && reg_r < INFINITY);
+    }
     if (!failed) {
         for (int k = lane; k < d16; k += MI_WAVE) xs[k] = (k < d && !a.from_zero) ? xout[k] : 0.f;
         if (resident) ab_gather(a, p0, n, 0, LDR / 4, area, LDR);
+        if constexpr (W) {
+            if (resident) {
+                for (int e = lane; e < n; e += MI_WAVE) as[e] = a.conf[p0 + e];
+            }
+        }
         ab_wave_sync();
         // p_e = y_e . x
         if (a.from_zero) {
@@ -213,17 +236,27 @@ __global__ __launch_bounds__(AB_WAVES * MI_WAVE) void als_block_kernel(AbArgs a)
             auto gram = [&](const float* src, int ld, int col0, int cnt) {   // p_e of the staged entries is ps[e]
                 for (int e4 = 0; e4 < cnt; e4 += 4) {
                     const int e = e4 + arow;
-                    float w = 0.f;
-                    if (e < cnt) w = fmaf(a.alpha, ps[e], c1);
+                    float w = 0.f, ae = 0.f;
+                    if constexpr (W) {
+                        if (e < cnt) {
+                            ae = as[e];
+                            w = fmaf(ae, ps[e], -(1.0f + ae));
+                        }
+                    } else {
+                        if (e < cnt) w = fmaf(a.alpha, ps[e], c1);
+                    }
                     float op[TB];
 #pragma unroll
                     for (int ti = 0; ti < TB; ++ti) op[ti] = ti < bt ? src[e * ld + col0 + 16 * ti + acol] : 0.f;
+                    float oz[TB];
+#pragma unroll
+                    for (int ti = 0; ti < TB; ++ti) oz[ti] = W ? ae * op[ti] : op[ti];
 #pragma unroll
                     for (int ti = 0; ti < TB; ++ti) {
                         if (ti < bt) {
 #pragma unroll
                             for (int tj = 0; tj <= ti; ++tj)
-                                acc[ti][tj] = __builtin_amdgcn_mfma_f32_16x16x4f32(op[ti], op[tj], acc[ti][tj], 0, 0, 0);
+                                acc[ti][tj] = __builtin_amdgcn_mfma_f32_16x16x4f32(op[ti], oz[tj], acc[ti][tj], 0, 0, 0);
                             gacc[ti] = __builtin_amdgcn_mfma_f32_16x16x4f32(op[ti], w, gacc[ti], 0, 0, 0);
                         }
                     }
@@ -236,12 +269,15 @@ __global__ __launch_bounds__(AB_WAVES * MI_WAVE) void als_block_kernel(AbArgs a)
                     const int cnt = min(KT, n - c0);
                     ab_gather(a, p0 + c0, cnt, cB, B / 4, area, LDB);
                     if (lane < cnt) ps[lane] = a.pw[p0 + c0 + lane];
+                    if constexpr (W) {
+                        if (lane < cnt) as[lane] = a.conf[p0 + c0 + lane];
+                    }
                     ab_wave_sync();
                     gram(area, LDB, 0, cnt);
                     ab_wave_sync();
                 }
             }
-            // H = fmaf(alpha, S, G) + reg I (lower triangle) and the gradient, to LDS
+            // H = fmaf(alpha, S, G) + reg I (lower triangle) and the gradient, to LDS; weighted: H = (G + S) + reg_r I
 #pragma unroll
             for (int ti = 0; ti < TB; ++ti) {
                 if (ti >= bt) continue;
@@ -252,8 +288,10 @@ __global__ __launch_bounds__(AB_WAVES * MI_WAVE) void als_block_kernel(AbArgs a)
                     for (int g = 0; g < 4; ++g) {
                         const int row = 16 * ti + 4 * arow + g;
                         if (row < bw && col <= row) {
-                            float v = fmaf(a.alpha, acc[ti][tj][g], gb[ti][tj][g]);
-                            if (row == col) v = v + a.reg;
+                            float v;
+                            if constexpr (W) v = gb[ti][tj][g] + acc[ti][tj][g];
+                            else v = fmaf(a.alpha, acc[ti][tj][g], gb[ti][tj][g]);
+                            if (row == col) v = v + reg_r;
                             Hs[row * HB + col] = v;
                         }
                     }
@@ -266,7 +304,7 @@ __global__ __launch_bounds__(AB_WAVES * MI_WAVE) void als_block_kernel(AbArgs a)
             ab_wave_sync();
             // H delta = -g: right-looking Cholesky, lane (i, jg) updates row i's columns k + 1 + jg, + JG, ..; lane l < bw
             // carries element l of the right-hand side through the forward and the backward substitution
-            float v = lane < bw ? -fmaf(a.reg, xs[cB + lane], gt[lane] + q) : 0.f;
+            float v = lane < bw ? -fmaf(reg_r, xs[cB + lane], gt[lane] + q) : 0.f;
             float myinv = 0.f;
             const int i = j, jg = kg;
             for (int k = 0; k < bw; ++k) {
@@ -344,6 +382,47 @@ inline bool ab_shape_ok(int64_t d, int64_t block) {
 inline size_t ab_ws_g(int64_t d) { return mi_align_up((size_t)(d * d) * 4, 256); }
 inline size_t ab_ws_bytes(int64_t nnz, int64_t d) { return ab_ws_g(d) + mi_align_up((size_t)(nnz > 0 ? nnz : 1) * 4, 256); }
 
+// The body of both entries: W = false is the unweighted one (alpha, reg), W = true takes (conf, reg_rows or reg).
+template <bool W>
+int ab_run(int64_t n_rows, int64_t d, int64_t block, int64_t sweeps, const int32_t* ptr, const int32_t* idx, int64_t nnz,
+           int64_t n_cols, const float* Y, int64_t ldy, const float* G, float alpha, const float* conf, const float* reg_rows,
+           float reg, float* X, int64_t ldx, int32_t from_zero, const int32_t* row_list, int64_t n_list, int32_t* n_failed,
+           void* ws, size_t ws_bytes, mi_stream_t stream) {
+    const int64_t lim = (int64_t)1 << 31;
+    MI_CHECK_ARG(ab_shape_ok(d, block));
+    MI_CHECK_ARG(sweeps >= 1 && sweeps <= 64);
+    MI_CHECK_ARG(n_rows >= 0 && n_rows < lim && n_cols >= 0 && n_cols < lim && nnz >= 0 && nnz < lim);
+    if (W) {
+        MI_CHECK_ARG(conf != nullptr);
+        MI_CHECK_ARG(reg_rows != nullptr || (reg > 0.f && reg < INFINITY));
+    } else {
+        MI_CHECK_ARG(alpha >= 0.f && alpha < INFINITY && reg > 0.f && reg < INFINITY);
+    }
+    const int64_t n_work = row_list ? n_list : n_rows;
+    MI_CHECK_ARG(n_work >= 0 && n_work < lim);
+    MI_CHECK_ARG(n_failed != nullptr);
+    if (n_work == 0) return 0;
+    MI_CHECK_ARG(ptr && (idx || nnz == 0) && Y && G && X);
+    MI_CHECK_ARG(mi_aligned16(Y) && ldy >= d && ldy % 4 == 0 && ldx >= d);
+    if (!ws || ws_bytes < ab_ws_bytes(nnz, d)) return MI_ERR_WORKSPACE;
+    AbArgs a;
+    a.n_rows = (int)n_rows; a.d = (int)d; a.n_cols = (int)n_cols; a.n_work = (int)n_work; a.nnz = (int)nnz;
+    a.sweeps = (int)sweeps; a.from_zero = from_zero != 0;
+    a.ptr = ptr; a.idx = idx; a.Y = Y; a.ldy = ldy; a.alpha = alpha; a.reg = reg; a.X = X; a.ldx = ldx;
+    a.row_list = row_list; a.n_failed = n_failed;
+    a.conf = conf; a.reg_rows = reg_rows;
+    a.Gs = static_cast<float*>(ws);
+    a.pw = reinterpret_cast<float*>(static_cast<char*>(ws) + ab_ws_g(d));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(als_block_sym_kernel, dim3((unsigned)mi_ceil_div(d * d, 256)), dim3(256), 0, st, G, a.Gs, (int)d);
+    MI_HIP(hipGetLastError());
+    const dim3 grid((unsigned)mi_ceil_div(n_work, AB_WAVES)), blk(AB_WAVES * MI_WAVE);
+    if (block == 16) hipLaunchKernelGGL((als_block_kernel<16, W>), grid, blk, 0, st, a);
+    else if (block == 32) hipLaunchKernelGGL((als_block_kernel<32, W>), grid, blk, 0, st, a);
+    else hipLaunchKernelGGL((als_block_kernel<64, W>), grid, blk, 0, st, a);
+    return mi_launch_status();
+}
+
 }  // namespace
 
 extern "C" {
@@ -359,33 +438,20 @@ int mi_als_block_rows_f32(int64_t n_rows, int64_t d, int64_t block, int64_t swee
                           int64_t nnz, int64_t n_cols, const float* Y, int64_t ldy, const float* G, float alpha, float reg,
                           float* X, int64_t ldx, int32_t from_zero, const int32_t* row_list, int64_t n_list, int32_t* n_failed,
                           void* ws, size_t ws_bytes, mi_stream_t stream) {
-    const int64_t lim = (int64_t)1 << 31;
-    MI_CHECK_ARG(ab_shape_ok(d, block));
-    MI_CHECK_ARG(sweeps >= 1 && sweeps <= 64);
-    MI_CHECK_ARG(n_rows >= 0 && n_rows < lim && n_cols >= 0 && n_cols < lim && nnz >= 0 && nnz < lim);
-    MI_CHECK_ARG(alpha >= 0.f && alpha < INFINITY && reg > 0.f && reg < INFINITY);
-    const int64_t n_work = row_list ? n_list : n_rows;
-    MI_CHECK_ARG(n_work >= 0 && n_work < lim);
-    MI_CHECK_ARG(n_failed != nullptr);
-    if (n_work == 0) return 0;
-    MI_CHECK_ARG(ptr && (idx || nnz == 0) && Y && G && X);
-    MI_CHECK_ARG(mi_aligned16(Y) && ldy >= d && ldy % 4 == 0 && ldx >= d);
-    if (!ws || ws_bytes < ab_ws_bytes(nnz, d)) return MI_ERR_WORKSPACE;
-    AbArgs a;
-    a.n_rows = (int)n_rows; a.d = (int)d; a.n_cols = (int)n_cols; a.n_work = (int)n_work; a.nnz = (int)nnz;
-    a.sweeps = (int)sweeps; a.from_zero = from_zero != 0;
-    a.ptr = ptr; a.idx = idx; a.Y = Y; a.ldy = ldy; a.alpha = alpha; a.reg = reg; a.X = X; a.ldx = ldx;
-    a.row_list = row_list; a.n_failed = n_failed;
-    a.Gs = static_cast<float*>(ws);
-    a.pw = reinterpret_cast<float*>(static_cast<char*>(ws) + ab_ws_g(d));
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(als_block_sym_kernel, dim3((unsigned)mi_ceil_div(d * d, 256)), dim3(256), 0, st, G, a.Gs, (int)d);
-    MI_HIP(hipGetLastError());
-    const dim3 grid((unsigned)mi_ceil_div(n_work, AB_WAVES)), blk(AB_WAVES * MI_WAVE);
-    if (block == 16) hipLaunchKernelGGL(als_block_kernel<16>, grid, blk, 0, st, a);
-    else if (block == 32) hipLaunchKernelGGL(als_block_kernel<32>, grid, blk, 0, st, a);
-    else hipLaunchKernelGGL(als_block_kernel<64>, grid, blk, 0, st, a);
-    return mi_launch_status();
+    return ab_run<false>(n_rows, d, block, sweeps, ptr, idx, nnz, n_cols, Y, ldy, G, alpha, nullptr, nullptr, reg, X, ldx,
+                         from_zero, row_list, n_list, n_failed, ws, ws_bytes, stream);
+}
+
+size_t mi_als_block_rows_w_workspace_bytes(int64_t n_work, int64_t nnz, int64_t d, int64_t block) {
+    return mi_als_block_rows_workspace_bytes(n_work, nnz, d, block);
+}
+
+int mi_als_block_rows_w_f32(int64_t n_rows, int64_t d, int64_t block, int64_t sweeps, const int32_t* ptr, const int32_t* idx,
+                            int64_t nnz, int64_t n_cols, const float* Y, int64_t ldy, const float* G, const float* conf,
+                            const float* reg_rows, float reg, float* X, int64_t ldx, int32_t from_zero, const int32_t* row_list,
+                            int64_t n_list, int32_t* n_failed, void* ws, size_t ws_bytes, mi_stream_t stream) {
+    return ab_run<true>(n_rows, d, block, sweeps, ptr, idx, nnz, n_cols, Y, ldy, G, 0.f, conf, reg_rows, reg, X, ldx, from_zero,
+                        row_list, n_list, n_failed, ws, ws_bytes, stream);
 }
 
 }  // extern "C"

@@ -2166,18 +2166,49 @@ def check_als(d, alpha, reg) -> None:
             raise ValueError(f"{name} must be a finite number {'> 0' if strict else '>= 0'}, got {v!r}")
 
 
+def check_als_weights(nnz: int, n_rows: int, conf, reg_rows) -> None:
+    """Shape and dtype of the per-entry confidences and per-row regularisers of the weighted row solves (include/laplace_hip.h,
+    iALS weighted): conf float32 [nnz] by entry position, reg_rows float32 [n_rows] by row id; None passes.  ValueError
+    naming which.  Needs no device and reads no value: the kernels treat a bad VALUE as a failed row."""
+    for name, x, n, what in (("conf", conf, nnz, "nnz"), ("reg_rows", reg_rows, n_rows, "n_rows")):
+        if x is None:
+            continue
+        if not isinstance(x, Tensor) or x.dtype != t.float32:
+            raise ValueError(f"{name} must be a float32 tensor [{what}], got {getattr(x, 'dtype', type(x))}")
+        if x.dim() != 1 or x.numel() != n:
+            raise ValueError(f"{name} must have shape [{what}] = [{n}], got {tuple(x.shape)}")
+
+
+def _als_weights(a: "DeviceCSR", conf, reg_rows, alpha: float, device) -> Tuple[Tensor, Optional[Tensor]]:
+    """The device operands of a weighted call: conf filled with alpha where only reg_rows was given."""
+    if conf is None:
+        conf = t.full((a.nnz,), float(alpha), dtype=t.float32, device=device)
+    _need(conf, t.float32, "conf")
+    if reg_rows is not None:
+        _need(reg_rows, t.float32, "reg_rows")
+    return conf, reg_rows
+
+
 def als_chunk(d: int) -> int:
     """L of the iALS rule for width d: entries per chunk of a row's rank-n update (mi_als_chunk)."""
     return int(_lib.lib().mi_als_chunk(int(d)))
 
 
 def als_solve_rows(a: DeviceCSR, Y: Tensor, G: Tensor, *, alpha: float, reg: float, out: Optional[Tensor] = None,
-                   row_list: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+                   row_list: Optional[Tensor] = None, conf: Optional[Tensor] = None,
+                   reg_rows: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
     """iALS — for every row r of `a` (a CSR over the rows of Y [n_cols, d]) the solution of
     (G + alpha * sum_e y_e y_e^T + reg I) x = (1 + alpha) * sum_e y_e, f32 Cholesky, one workgroup per row; the rule is stated in
     include/laplace_hip.h.  G [d, d] is the caller's (the trainer passes gemm(Y, Y, trans_a=True, trans_b=False)).  Returns
     (X, n_failed): X [n_rows, d], or [len(row_list), d] compact by list position; n_failed an int32 device scalar counting the
-    rows whose factorisation met a non-positive or non-finite pivot (those rows are zero).  Empty rows are zero and not counted."""
+    rows whose factorisation met a non-positive or non-finite pivot (those rows are zero).  Empty rows are zero and not counted.
+    conf [nnz] (a_e by entry position of a.col) and / or reg_rows [n_rows] (by row id, also with a row_list) select the weighted
+    entry, (G + sum_e a_e y_e y_e^T + reg_r I) x = sum_e (1 + a_e) y_e ("iALS weighted" in the header): conf=None is a_e = alpha,
+    reg_rows=None is reg_r = reg; with conf given alpha is checked and not used.  With both None this is the unweighted
+    entry, its call and its bits."""
+    weighted = conf is not None or reg_rows is not None
+    if weighted:
+        check_als_weights(a.nnz, a.n_rows, conf, reg_rows)
     _need(a.rowptr, t.int32, "a.rowptr")
     _need(a.col, t.int32, "a.col")
     ldy = _rows_ok(Y, "Y")
@@ -2202,6 +2233,15 @@ def als_solve_rows(a: DeviceCSR, Y: Tensor, G: Tensor, *, alpha: float, reg: flo
     if n_work == 0 or a.nnz == 0:   # nothing to solve: every row is empty
         return out.zero_(), n_failed
     L = _lib.lib()
+    if weighted:
+        conf, reg_rows = _als_weights(a, conf, reg_rows, alpha, Y.device)
+        ws = _ws_reused(L.mi_als_solve_rows_w_workspace_bytes(n_work, a.nnz, d), Y.device)
+        check(L.mi_als_solve_rows_w_f32(a.n_rows, d, a.rowptr.data_ptr(), _ptr(a.col), a.nnz, a.n_cols, Y.data_ptr(), ldy,
+                                        G.data_ptr(), conf.data_ptr(), _ptr(reg_rows), float(reg), out.data_ptr(), ldx,
+                                        row_list.data_ptr() if row_list is not None else None,
+                                        n_work if row_list is not None else 0, n_failed.data_ptr(), ws.data_ptr(), ws.numel(),
+                                        _stream()), "mi_als_solve_rows_w_f32")
+        return out, n_failed
     ws_bytes = L.mi_als_solve_rows_workspace_bytes(n_work, a.nnz, d)
     ws = _ws_reused(ws_bytes, Y.device)
     # a pointer that is never dereferenced where the tensor is empty (no entries, no listed rows) keeps the null check simple
@@ -2239,12 +2279,17 @@ def als_block_chunk(d: int, block: int) -> int:
 
 
 def als_block_rows(a: DeviceCSR, Y: Tensor, G: Tensor, *, alpha: float, reg: float, block: int = 16, sweeps: int = 1,
-                   x: Optional[Tensor] = None, row_list: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+                   x: Optional[Tensor] = None, row_list: Optional[Tensor] = None, conf: Optional[Tensor] = None,
+                   reg_rows: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
     """iALS block — for every row r of `a` (a CSR over the rows of Y [n_cols, d]), `sweeps` passes over the blocks of `block`
     coordinates, each step the exact minimiser over its block of the row's quadratic
     1/2 x^T (G + alpha * sum_e y_e y_e^T + reg I) x - (1 + alpha) * sum_e y_e . x; one wavefront per row; the rule is stated
     in include/laplace_hip.h.  x [n_rows, d] (or [len(row_list), d], compact by list position) is the start and is UPDATED
-    IN PLACE; x=None starts from zero into a fresh tensor.  Returns (X, n_failed) as als_solve_rows does."""
+    IN PLACE; x=None starts from zero into a fresh tensor.  Returns (X, n_failed) as als_solve_rows does.  conf / reg_rows: as
+    in als_solve_rows, selecting the "iALS block weighted" entry; with both None the unweighted entry, its call and its bits."""
+    weighted = conf is not None or reg_rows is not None
+    if weighted:
+        check_als_weights(a.nnz, a.n_rows, conf, reg_rows)
     _need(a.rowptr, t.int32, "a.rowptr")
     _need(a.col, t.int32, "a.col")
     ldy = _rows_ok(Y, "Y")
@@ -2270,6 +2315,15 @@ def als_block_rows(a: DeviceCSR, Y: Tensor, G: Tensor, *, alpha: float, reg: flo
     if n_work == 0 or a.nnz == 0:   # nothing to solve: every row is empty
         return x.zero_(), n_failed
     L = _lib.lib()
+    if weighted:
+        conf, reg_rows = _als_weights(a, conf, reg_rows, alpha, Y.device)
+        ws = _ws_reused(L.mi_als_block_rows_w_workspace_bytes(n_work, a.nnz, d, int(block)), Y.device)
+        check(L.mi_als_block_rows_w_f32(a.n_rows, d, int(block), int(sweeps), a.rowptr.data_ptr(), _ptr(a.col), a.nnz,
+                                        a.n_cols, Y.data_ptr(), ldy, G.data_ptr(), conf.data_ptr(), _ptr(reg_rows), float(reg),
+                                        x.data_ptr(), ldx, int(from_zero), row_list.data_ptr() if row_list is not None else None,
+                                        n_work if row_list is not None else 0, n_failed.data_ptr(), ws.data_ptr(), ws.numel(),
+                                        _stream()), "mi_als_block_rows_w_f32")
+        return x, n_failed
     ws_bytes = L.mi_als_block_rows_workspace_bytes(n_work, a.nnz, d, int(block))
     ws = _ws_reused(ws_bytes, Y.device)
     check(L.mi_als_block_rows_f32(a.n_rows, d, int(block), int(sweeps), a.rowptr.data_ptr(), _ptr(a.col), a.nnz, a.n_cols,

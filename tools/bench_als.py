@@ -4,11 +4,16 @@ one process.  For each half-sweep the achieved rate of 2 d^2 nnz + rows d^3 / 3 
 peak.  One dense C2 LightGCN step (d = 128, 3 layers, batch 16 384) is timed in the same process for scale.
     python3 tools/bench_als.py [--shapes planted,c2,c3] [--dims 64,128] [--epochs 11] [--warmup 2] [--no-lightgcn]
                                [--solver cholesky|block|both] [--block 16,32] [--sweeps 1,2] [--dim D] [--fold-in]
+                               [--weighted] [--reg-power NU]
 --solver block / both adds one line per (block, sweeps) with the block row solver (ops.als_block_rows) from the SAME initial
 tables as the Cholesky line of that (shape, d) — the yardstick, timed in the same run; d > 128 has the block lines only.  A
 block line also carries hub_ms: the one longest item row alone through row_list, i.e. the one wavefront the item
 half-sweep cannot end before.  --dim D is --dims D.  --fold-in adds, per (shape, d, block), what a fold-in from zero leaves
 after 1, 2, 4 and 8 sweeps on the first 4 096 users: the relative distance to the same rows after 64 sweeps.
+--weighted adds, after every line, the same configuration from the same initial tables through the WEIGHTED entries: first
+with a_e == alpha on every edge (weights "constant": the same operands as the unweighted line, so the ratio of the two is the
+cost of the weighted kernels alone), then with a random weight per edge in [0.1, 30] / alpha and --reg-power NU (weights
+"random").  Each weighted line carries users_vs_unweighted / items_vs_unweighted, its time over the unweighted line's.
 One JSON line per (shape, d, solver); the flop model of every line is the full solve's, so TF/s of a block line is a
 speed-up in disguise, not a rate."""
 import argparse, json, os, statistics, sys, time
@@ -33,6 +38,8 @@ ap.add_argument("--solver", default="cholesky", choices=["cholesky", "block", "b
 ap.add_argument("--block", default="16")
 ap.add_argument("--sweeps", default="1")
 ap.add_argument("--fold-in", action="store_true")
+ap.add_argument("--weighted", action="store_true")
+ap.add_argument("--reg-power", type=float, default=0.5)
 args = ap.parse_args()
 dims = [args.dim] if args.dim is not None else [int(x) for x in args.dims.split(",")]
 block_cfgs = [(int(b), int(s)) for b in args.block.split(",") for s in args.sweeps.split(",")]
@@ -74,8 +81,18 @@ for name in args.shapes.split(","):
         model = ImplicitALS(spec.num_users, spec.num_items, dim=d, alpha=1.0, reg=20.0, seed=0, solver="block").cuda()
         model.bind(inter)
         start = (model.users_emb.weight.clone(), model.items_emb.weight.clone())
-        for solver, block, sweeps in cfgs:
+        base = {}
+        modes = [("none", None, 0.0)]
+        if args.weighted:
+            gen = t.Generator(device="cuda").manual_seed(1)
+            lo, hi = t.log(t.tensor(0.1)).item(), t.log(t.tensor(30.0)).item()
+            w_rand = t.exp(t.rand(nnz, generator=gen, device="cuda", dtype=t.float64) * (hi - lo) + lo) / model.alpha
+            modes += [("constant", t.ones(nnz, dtype=t.float32, device="cuda"), 0.0), ("random", w_rand, args.reg_power)]
+        for (solver, block, sweeps), (weights, conf, nu) in ((c, m) for c in cfgs for m in modes):
             model.solver, model.block, model.block_sweeps = solver, block, sweeps
+            model.reg_power = nu
+            model.reg = 20.0 if nu == 0.0 else 20.0 / (spec.num_items + nnz / spec.num_users) ** nu   # about 20 on a mean user row
+            model.bind(inter, conf)
             model.users_emb.weight.copy_(start[0])
             model.items_emb.weight.copy_(start[1])
             for _ in range(args.warmup):
@@ -89,6 +106,8 @@ for name in args.shapes.split(","):
                    "epochs": args.epochs, "generate_s": round(gen_s, 1)}
             if solver == "block":
                 out.update(block=block, sweeps=sweeps)
+            if args.weighted:
+                out.update(weights=weights, reg_power=nu)
             for k, (side, rows) in enumerate((("users", spec.num_users), ("items", spec.num_items))):
                 ms = statistics.median(e[k][0].elapsed_time(e[k][1]) for e in events)
                 failed += sum(int(e[k][2].item()) for e in events)
@@ -97,9 +116,14 @@ for name in args.shapes.split(","):
                 out[f"{side}_tflops"] = round(flop / (ms * 1e-3) / 1e12, 3)
                 out[f"{side}_of_peak"] = round(flop / (ms * 1e-3) / 1e12 / PEAK_TF, 4)
             out["epoch_ms"] = round(out["users_ms"] + out["items_ms"], 3)
+            if weights == "none":
+                base = {side: out[f"{side}_ms"] for side in ("users", "items")}
+            else:
+                for side in ("users", "items"):
+                    out[f"{side}_vs_unweighted"] = round(out[f"{side}_ms"] / base[side], 3)
             out["failed_rows"] = failed
             out["objective"] = round(model.objective(inter), 2) if name == "planted" else None
-            if solver == "block":
+            if solver == "block" and weights == "none":
                 by_item = model._bound[2]
                 deg = by_item.rowptr[1:] - by_item.rowptr[:-1]
                 hub = deg.argmax().to(t.int32).reshape(1)
@@ -110,7 +134,7 @@ for name in args.shapes.split(","):
                 out["hub_ms"] = round(timed(lambda: ops.als_block_rows(by_item, X, G, alpha=1.0, reg=20.0, block=block,
                                                                        sweeps=sweeps, x=x1, row_list=hub), 5), 3)
             print(json.dumps(out), flush=True)
-            if solver == "block" and args.fold_in and sweeps == block_cfgs[0][1]:
+            if solver == "block" and weights == "none" and args.fold_in and sweeps == block_cfgs[0][1]:
                 by_user = model._bound[1]
                 rl = t.arange(min(4096, spec.num_users), dtype=t.int32, device="cuda")
                 Y = model.items_emb.weight.data

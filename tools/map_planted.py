@@ -5,7 +5,8 @@ reference's, F8) vs propagated embeddings vs the popularity predictor, at checkp
 "map_at_12": the layer-0 tables (default) or the propagated embeddings the loss trains.
 --model als: the same protocol with iALS (als.ImplicitALS; --alpha, --reg) in the trainer's place, scored after each epoch count
 of --als-epochs; --als-solver block (--als-block, --als-sweeps) trains it with the block row solver, the only one for
---dim > 128.  --init als: LightGCN's tables start from the iALS factors after max(--als-epochs) epochs.  --seed moves the
+--dim > 128; --als-reg-power NU trains it with the frequency-scaled regulariser reg * (n_cols + sum_e a_e)^NU (--reg must be
+retuned with NU: it multiplies a factor in the thousands at NU = 1).  --init als: LightGCN's tables start from the iALS factors after max(--als-epochs) epochs.  --seed moves the
 model's initial tables and the trainer's sampler (the graph and the held-out pairs stay the recipe's).  Every line also carries
 map@12, mrr and recall@100 of the full-catalogue ranks (utils.metrics_lightgcn.full_rank_metrics) of the held-out pairs."""
 import argparse, json, os, sys
@@ -42,6 +43,7 @@ ap.add_argument("--reg", type=float, default=20.0)
 ap.add_argument("--als-solver", default="cholesky", choices=["cholesky", "block"])
 ap.add_argument("--als-block", type=int, default=16)
 ap.add_argument("--als-sweeps", type=int, default=1)
+ap.add_argument("--als-reg-power", type=float, default=0.0)
 ap.add_argument("--seed", type=int, default=0)
 args = ap.parse_args()
 spec = S.SyntheticSpec(args.users, args.items, args.edges, seed=5, communities=args.communities, community_mix=args.mix,
@@ -70,13 +72,15 @@ def popularity():
 als = None
 if args.model == "als" or args.init == "als":
     als = ImplicitALS(args.users, args.items, dim=args.dim, alpha=args.alpha, reg=args.reg, seed=args.seed,
-                      solver=args.als_solver, block=args.als_block, block_sweeps=args.als_sweeps).to("cuda")
+                      solver=args.als_solver, block=args.als_block, block_sweeps=args.als_sweeps,
+                      reg_power=args.als_reg_power).to("cuda")
     done = 0
     for cp in (als_epochs if args.model == "als" else [max(als_epochs)]):
         als.fit(inter, cp - done)
         done = cp
         if args.model == "als":
-            print(cp, json.dumps({"model": "als", "solver": args.als_solver, "dim": args.dim, "seed": args.seed, **full_rank(als),
+            print(cp, json.dumps({"model": "als", "solver": args.als_solver, "dim": args.dim, "seed": args.seed, "reg": args.reg,
+                                  "reg_power": args.als_reg_power, **full_rank(als),
                                   "objective": round(als.objective(inter), 2)}), flush=True)
 if args.model == "als":
     print("popularity", json.dumps(popularity()), flush=True)
