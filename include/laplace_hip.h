@@ -2050,6 +2050,72 @@ int     mi_als_block_rows_w_f32(int64_t n_rows, int64_t d, int64_t block, int64_
                                 int64_t ldx, int32_t from_zero, const int32_t* row_list, int64_t n_list, int32_t* n_failed,
                                 void* ws, size_t ws_bytes, mi_stream_t stream);
 
+/* ------------------------------------------------------------------------------------
+ * iALS block hub  the two iALS block entries with hub rows taken from an assembled system (additive to ABI 14;
+ *                 csrc/als_block.hip, the Gram code shared with csrc/als.hip through csrc/als_gram.hpp).
+ * replaces: nothing in the reference.  One wavefront walks a row in the block entries, so a row of half a million entries
+ *           is a half-sweep of its own.  For n >> d the block form's 2 n d B flop per block times d / B blocks IS the full
+ *           Gram: here a row with MORE THAN hub_threshold entries has its d x d system formed once, over one workgroup per
+ *           chunk of its entries, and the block steps run on that system.  Every other row is the block entry's, bit for bit.
+ * Inputs.  As the iALS block entry (the _w_ pair: as the iALS block weighted entry), and hub_threshold >= 1, n_hub_rows,
+ *   n_hub_chunks: the caller's counts, over the rows the call works on, of the rows with n > hub_threshold entries and of
+ *   sum ceil(n / L_h) over them (counts over the whole CSR are upper bounds for a row_list of distinct rows).
+ * The rule for a hub row r (entries e in CSR order, y_e, a_e, c_e, reg_r as in the entries named), restated in float64 and
+ * float32 by tests/als_hub_emulation.py:
+ *   chunks    Chunk c is entries [c L_h, (c + 1) L_h) of the row, L_h = mi_als_block_hub_chunk(d): a compile-time constant
+ *             of d alone (256 up to d = 64, 512 beyond: shorter than the iALS entry's L, because a hub row's answer is as
+ *             good as its Gram — the block rule refines through p_e, this one cannot — and a chain's error grows with its
+ *             length).
+ *   per chunk S_c[j][k], k <= j, ONE fmaf chain from 0 in entry order, and s_c[j], one chain from 0 in entry order: exactly
+ *             the "per chunk" line of the iALS entry, and for the _w_ pair of the iALS weighted entry (z_e = a_e * y_e,
+ *             S_c[j][k] = chain of fmaf(y_e[j], z_e[k], acc); s_c[j] = chain of fmaf(c_e, y_e[j], acc), c_e = 1.0f + a_e).
+ *   across    S = ((S_0 + S_1) + S_2) ... in ascending c, one f32 addition each; s likewise.
+ *   system    exactly the "system" line of the iALS entry (A[j][k] = fmaf(alpha, S[j][k], G[j][k]), + reg on the diagonal,
+ *             b[j] = (1.0f + alpha) * s[j]) or of the iALS weighted entry (A = G + S, + reg_r on the diagonal, b = s), for
+ *             k <= j;  A(j, k) below is A[max(j, k)][min(j, k)].
+ *   start     x from X, or 0 under from_zero, as in the block entry.
+ *   for t in 0 .. sweeps-1, for c in 0 .. ceil(d / B)-1, pi = [c B, min((c + 1) B, d)):
+ *     u[j]    = sum_k A(j, k) x[k], j in pi, over ALL k < d, from the CURRENT x, in the chain layout of the block rule's q:
+ *               64 / B chains, chain m = fmaf(A(j, k), x[k], acc) from 0 over the groups of four columns k = 4 u .. 4 u + 3,
+ *               u = m, m + 64 / B, .. ascending, the chains added in ascending m.
+ *     g[j]    = u[j] - b[j]
+ *     H       = A[pi, pi]
+ *     delta   solves H delta = -g by an f32 Cholesky whose inner order is the kernel's and NOT part of the rule.
+ *     x[j]    = x[j] + delta[j], j in pi
+ *   In exact arithmetic this is the block rule's own iteration (p_e = y_e . x, so sum_e w_e y_e + G x + reg x = A x - b).
+ *   empty row, pivot, reg_rows, guards (idx out of range, a rowptr that runs past nnz, n_failed): exactly the block entry's.
+ *   no slot   A hub row that found no workspace slot (n_hub_rows or n_hub_chunks too small, a row listed twice) is a failed
+ *             row: zero, counted.  Nothing is read or written out of bounds.
+ * No float atomics.  A hub row's bits are a function of (its entries in order, Y, G, alpha or conf, reg, the start, d, B,
+ *   sweeps) alone: not of the device, the grid, the other rows, row_list, or of hub_threshold beyond which side of it the row
+ *   falls on.  Which workspace slot a row or a chunk gets (integer atomics) may differ from run to run; what is written into
+ *   it does not.  A row with at most hub_threshold entries has the bits the iALS block (weighted) entry gives it.
+ * Workspace: mi_als_block_rows_hub_workspace_bytes(n_work, nnz, d, block, n_hub_rows, n_hub_chunks) = the block entry's
+ *   bytes + 256 + 4 n_work + 8 n_hub_rows + 4 n_hub_chunks + 4 n_hub_chunks (256 T + 16 ceil(d / 16)) + 4 n_hub_rows (d d + d),
+ *   every term rounded up to 256, T = ceil(d / 16) (ceil(d / 16) + 1) / 2 the 16 x 16 tiles of a lower triangle: a chunk slot
+ *   holds the lower triangle only, a row slot A as a full symmetric matrix and b.  It grows with the hub rows that exist.
+ * Returned before anything is enqueued: everything the block entry refuses, MI_ERR_BAD_ARG for hub_threshold < 1 or a count
+ *   that is negative or 2^31 or more, MI_ERR_WORKSPACE (ws null or short).  Zero rows: 0, nothing enqueued.
+ * mi_als_block_hub_chunk: L_h of a width, 0 for a width the entry refuses.  The size queries return 0 for refused arguments.
+ * ---------------------------------------------------------------------------------- */
+int32_t mi_als_block_hub_chunk(int64_t d);
+size_t  mi_als_block_rows_hub_workspace_bytes(int64_t n_work, int64_t nnz, int64_t d, int64_t block, int64_t n_hub_rows,
+                                              int64_t n_hub_chunks);
+int     mi_als_block_rows_hub_f32(int64_t n_rows, int64_t d, int64_t block, int64_t sweeps, const int32_t* ptr,
+                                  const int32_t* idx, int64_t nnz, int64_t n_cols, const float* Y, int64_t ldy,
+                                  const float* G, float alpha, float reg, float* X /* in/out */, int64_t ldx,
+                                  int32_t from_zero, const int32_t* row_list, int64_t n_list, int64_t hub_threshold,
+                                  int64_t n_hub_rows, int64_t n_hub_chunks, int32_t* n_failed, void* ws, size_t ws_bytes,
+                                  mi_stream_t stream);
+size_t  mi_als_block_rows_hub_w_workspace_bytes(int64_t n_work, int64_t nnz, int64_t d, int64_t block, int64_t n_hub_rows,
+                                                int64_t n_hub_chunks);
+int     mi_als_block_rows_hub_w_f32(int64_t n_rows, int64_t d, int64_t block, int64_t sweeps, const int32_t* ptr,
+                                    const int32_t* idx, int64_t nnz, int64_t n_cols, const float* Y, int64_t ldy,
+                                    const float* G, const float* conf, const float* reg_rows /* nullable */, float reg,
+                                    float* X /* in/out */, int64_t ldx, int32_t from_zero, const int32_t* row_list,
+                                    int64_t n_list, int64_t hub_threshold, int64_t n_hub_rows, int64_t n_hub_chunks,
+                                    int32_t* n_failed, void* ws, size_t ws_bytes, mi_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -446,6 +446,15 @@ _PROTOTYPES = {
     "mi_als_block_rows_w_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int64]),
     "mi_als_block_rows_w_f32": (c_int32, [c_int64, c_int64, c_int64, c_int64, P, P, c_int64, c_int64, P, c_int64, P, P, P,
                                           c_float, P, c_int64, c_int32, P, c_int64, P, P, c_size_t, P]),
+    "mi_als_block_hub_chunk": (c_int32, [c_int64]),
+    "mi_als_block_rows_hub_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int64, c_int64, c_int64]),
+    "mi_als_block_rows_hub_f32": (c_int32, [c_int64, c_int64, c_int64, c_int64, P, P, c_int64, c_int64, P, c_int64, P, c_float,
+                                            c_float, P, c_int64, c_int32, P, c_int64, c_int64, c_int64, c_int64, P, P,
+                                            c_size_t, P]),
+    "mi_als_block_rows_hub_w_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int64, c_int64, c_int64]),
+    "mi_als_block_rows_hub_w_f32": (c_int32, [c_int64, c_int64, c_int64, c_int64, P, P, c_int64, c_int64, P, c_int64, P, P, P,
+                                              c_float, P, c_int64, c_int32, P, c_int64, c_int64, c_int64, c_int64, P, P,
+                                              c_size_t, P]),
 }
 
 _LIB = None

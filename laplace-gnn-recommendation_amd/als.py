@@ -10,6 +10,9 @@ one d x d Gram product (ops.gemm): with the other table Y fixed, row r becomes t
 With solver="block" the one launch is ops.als_block_rows (csrc/als_block.hip, "iALS block" in the header) instead: a row-local
 iALS++ (Rendle et al., RecSys 2021) that warm-starts from the table and minimises the same row quadratic exactly over one
 block of `block` coordinates at a time, `block_sweeps` passes per half-sweep; it is the only solver for dim > 128 (up to 256).
+One wavefront walks a row there, so a popular item's row is a half-sweep of its own: hub_threshold=T (opt-in, block solver
+only) takes every row with more than T entries from its dim x dim system instead, assembled once over one workgroup per chunk
+of the row ("iALS block hub" in the header); the other rows, and hub_threshold=None, keep every bit.
 
 Per-edge confidences (Hu, Koren and Volinsky: c_ui = 1 + alpha r_ui) and frequency-scaled regularisation (Rendle et al.,
 RecSys 2022, section 4) are opt-in: bind / fit / fold_in take a `confidence` per edge and the model a `reg_power`; with either
@@ -18,8 +21,9 @@ solves (Y^T Y + sum_e a_e y_e y_e^T + reg_r I) x = sum_e (1 + a_e) y_e with a_e 
 and every bit is the unweighted entry's.
 
 Not built: the CG solver, the paper's block-outer schedule of iALS++ (all rows inside one block step, predictions of all
-pairs kept between steps), hub rows split over workgroups, dim > 256, a sharded form, bf16, negative or missing-preference
-(p = 0) observed entries, and the matcher's entry in get_matchers / tools/e2e_hm_scale.py's chain.
+pairs kept between steps), a second stream for the hub rows, an automatic hub_threshold, dim > 256, a sharded form, bf16,
+negative or missing-preference (p = 0) observed entries, and the matcher's entry in get_matchers / tools/e2e_hm_scale.py's
+chain.
 """
 from __future__ import annotations
 
@@ -88,15 +92,20 @@ class ImplicitALS(t.nn.Module):
     project's scaling, where an unobserved pair weighs 1 and an observed one 1 + a_e: the paper's weights are alpha0 and 1, so
     the two agree up to the constant alpha0^nu with alpha0 = 1 / alpha.  The factor is between n_cols^nu and (n_cols + mass)^nu,
     i.e. in the thousands at nu = 1: `reg` MUST be rescaled (retuned) with nu; a reg tuned at nu = 0 is far too strong at
-    nu > 0.  nu = 0 (the default) is the one reg of every row."""
+    nu > 0.  nu = 0 (the default) is the one reg of every row.
+
+    hub_threshold (solver="block" only; None = off): every half_sweep, fit and fold_in takes the rows with more entries than
+    this from their assembled system (ops.als_block_rows(hub_threshold=)).  profiles/als_hub.md has what it buys."""
 
     def __init__(self, num_users: int, num_items: int, dim: int = 64, alpha: float = 1.0, reg: float = 20.0, seed: int = 0,
                  init_std: float = 0.1, solver: str = "cholesky", block: int = 16, block_sweeps: int = 1,
-                 fold_in_sweeps: int = 4, reg_power: float = 0.0):
+                 fold_in_sweeps: int = 4, reg_power: float = 0.0, hub_threshold: Optional[int] = None):
         super().__init__()
         self.reg_power = check_reg_power(reg_power)
         if solver not in SOLVERS:
             raise ValueError(f"solver must be one of {SOLVERS}, got {solver!r}")
+        ops.check_als_hub_threshold(hub_threshold, solver)
+        self.hub_threshold = None if hub_threshold is None else int(hub_threshold)
         if solver == "block":
             ops.check_als_block(dim, block, block_sweeps, alpha, reg)
             ops.check_als_block(dim, block, fold_in_sweeps, alpha, reg)
@@ -169,7 +178,7 @@ class ImplicitALS(t.nn.Module):
         if self.solver == "block":
             return ops.als_block_rows(csr, fixed, gram, alpha=self.alpha, reg=self.reg, block=self.block, x=out,
                                       sweeps=self.block_sweeps if out is not None else self.fold_in_sweeps,
-                                      conf=conf, reg_rows=reg_rows)
+                                      conf=conf, reg_rows=reg_rows, hub_threshold=self.hub_threshold)
         return ops.als_solve_rows(csr, fixed, gram, alpha=self.alpha, reg=self.reg, out=out, conf=conf, reg_rows=reg_rows)
 
     def half_sweep(self, side: str, interactions: Optional[Interactions] = None, confidence: Optional[Tensor] = None
@@ -257,11 +266,11 @@ class ImplicitALS(t.nn.Module):
 def train(config, *, edge_index: Tensor, num_users: int, num_articles: int, dim: int = 64, alpha: float = 1.0,
           reg: float = 20.0, epochs: int = 3, seed: int = 0, device: str = "cuda", save_dir: Optional[str] = None,
           full_rank_ks: Optional[Tuple[int, ...]] = (12, 100), verbose: bool = True, solver: str = "cholesky",
-          block: int = 16, block_sweeps: int = 1, reg_power: float = 0.0) -> Stats:
+          block: int = 16, block_sweeps: int = 1, reg_power: float = 0.0, hub_threshold: Optional[int] = None) -> Stats:
     """run_pipeline_lightgcn.train with iALS in the trainer's place: the same split (create_dataloaders_lightgcn), the ranking
     metrics @ config.k on validation and test, evaluation_full_rank on the test split and save_predictions — the same three
     files (lightgcn_output.pt and the two tables) that data.matching.LightGCNMatcher consumes.  Stats.loss is the objective
-    on the training edges.  reg_power goes to the model.  There is no `confidence` here: the loader's split returns the three
+    on the training edges.  reg_power and hub_threshold go to the model.  There is no `confidence` here: the loader's split returns the three
     edge sets without the permutation that cut them, so a weight per edge of `edge_index` could not be cut alike; split
     first and call ImplicitALS.fit(interactions, epochs, confidence=) for per-edge weights."""
     from .data.lightgcn_loader import create_dataloaders_lightgcn
@@ -270,7 +279,7 @@ def train(config, *, edge_index: Tensor, num_users: int, num_articles: int, dim:
     (_, _, _, train_edges, val_edges, test_edges, all_edges, num_users,
      num_articles) = create_dataloaders_lightgcn(edge_index, num_users, num_articles, compat="bipartite", device=device)
     model = ImplicitALS(num_users, num_articles, dim=dim, alpha=alpha, reg=reg, seed=seed, solver=solver, block=block,
-                        block_sweeps=block_sweeps, reg_power=reg_power).to(device)
+                        block_sweeps=block_sweeps, reg_power=reg_power, hub_threshold=hub_threshold).to(device)
     inter = Interactions(train_edges, num_users, num_articles)
 
     def log(epoch: int, m: ImplicitALS) -> None:

@@ -190,6 +190,7 @@ class DeviceCSR:
     plan_bf16: Optional[SpmmPlan] = None    # spmm_bf16's own work-item plan: `plan` and the f32 launches are untouched by it
     plan_tiles: object = None               # the TILES plan of the dense launches (HUB_TILES): None = not tried, False = not applicable;
                                             # x_map / row_list launches keep `plan`
+    hub_counts: dict = field(default_factory=dict)   # (hub_threshold, chunk) -> (hub rows, hub chunks): als_hub_counts
 
     # Value generation: 0 for an adjacency whose `val` is the one it was built with, a process-wide fresh number after every
     # later assignment of `val` and every invalidate_values().  With the identity and _version of the tensor itself it is
@@ -2278,15 +2279,48 @@ def als_block_chunk(d: int, block: int) -> int:
     return int(_lib.lib().mi_als_block_chunk(int(d), int(block)))
 
 
+def check_als_hub_threshold(hub_threshold, solver: str = "block") -> None:
+    """hub_threshold of the block row solver (include/laplace_hip.h, iALS block hub): None, or an integer >= 1, and None for
+    any solver but "block".  ValueError naming the argument; needs no device."""
+    if hub_threshold is None:
+        return
+    if isinstance(hub_threshold, bool) or not isinstance(hub_threshold, numbers.Integral) or hub_threshold < 1:
+        raise ValueError(f"hub_threshold must be None or an integer >= 1, got {hub_threshold!r}")
+    if solver != "block":
+        raise ValueError(f"hub_threshold is the block solver's: it must be None with solver={solver!r}, got {hub_threshold!r}")
+
+
+def als_block_hub_chunk(d: int) -> int:
+    """L_h of the hub rule for width d: entries per chunk of a hub row's Gram (mi_als_block_hub_chunk); 0 for a refused width."""
+    return int(_lib.lib().mi_als_block_hub_chunk(int(d)))
+
+
+def als_hub_counts(a: DeviceCSR, hub_threshold: int, d: int) -> Tuple[int, int]:
+    """(rows of `a` with more than hub_threshold entries, sum over them of ceil(n / L_h)): what the hub entries size their
+    workspace by.  One device reduction and one read-back per (CSR, threshold, chunk), kept on the CSR like its plans."""
+    L = als_block_hub_chunk(d)
+    key = (int(hub_threshold), L)
+    if key not in a.hub_counts:
+        n = (a.rowptr[1:] - a.rowptr[:-1]).long()
+        hub = n > int(hub_threshold)
+        chunks = t.where(hub, (n + (L - 1)) // L, t.zeros_like(n))
+        a.hub_counts[key] = tuple(int(v) for v in t.stack([hub.sum(), chunks.sum()]).tolist())
+    return a.hub_counts[key]
+
+
 def als_block_rows(a: DeviceCSR, Y: Tensor, G: Tensor, *, alpha: float, reg: float, block: int = 16, sweeps: int = 1,
                    x: Optional[Tensor] = None, row_list: Optional[Tensor] = None, conf: Optional[Tensor] = None,
-                   reg_rows: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+                   reg_rows: Optional[Tensor] = None, hub_threshold: Optional[int] = None) -> Tuple[Tensor, Tensor]:
     """iALS block — for every row r of `a` (a CSR over the rows of Y [n_cols, d]), `sweeps` passes over the blocks of `block`
     coordinates, each step the exact minimiser over its block of the row's quadratic
     1/2 x^T (G + alpha * sum_e y_e y_e^T + reg I) x - (1 + alpha) * sum_e y_e . x; one wavefront per row; the rule is stated
     in include/laplace_hip.h.  x [n_rows, d] (or [len(row_list), d], compact by list position) is the start and is UPDATED
     IN PLACE; x=None starts from zero into a fresh tensor.  Returns (X, n_failed) as als_solve_rows does.  conf / reg_rows: as
-    in als_solve_rows, selecting the "iALS block weighted" entry; with both None the unweighted entry, its call and its bits."""
+    in als_solve_rows, selecting the "iALS block weighted" entry; with both None the unweighted entry, its call and its bits.
+    hub_threshold: None launches exactly that; an integer >= 1 selects the "iALS block hub" entries, which take every row with
+    MORE entries from its d x d system, assembled once over one workgroup per chunk of the row (als_hub_counts sizes the
+    workspace: one read-back per CSR and threshold); the other rows keep their bits."""
+    check_als_hub_threshold(hub_threshold)
     weighted = conf is not None or reg_rows is not None
     if weighted:
         check_als_weights(a.nnz, a.n_rows, conf, reg_rows)
@@ -2315,6 +2349,26 @@ def als_block_rows(a: DeviceCSR, Y: Tensor, G: Tensor, *, alpha: float, reg: flo
     if n_work == 0 or a.nnz == 0:   # nothing to solve: every row is empty
         return x.zero_(), n_failed
     L = _lib.lib()
+    rl_ptr, n_list = (row_list.data_ptr(), n_work) if row_list is not None else (None, 0)
+    if hub_threshold is not None:
+        thr = min(int(hub_threshold), (1 << 31) - 1)
+        hub_rows, hub_chunks = als_hub_counts(a, thr, d)   # over the whole CSR: upper bounds for a list of distinct rows
+        if weighted:
+            conf, reg_rows = _als_weights(a, conf, reg_rows, alpha, Y.device)
+            ws = _ws_reused(L.mi_als_block_rows_hub_w_workspace_bytes(n_work, a.nnz, d, int(block), hub_rows, hub_chunks),
+                            Y.device)
+            check(L.mi_als_block_rows_hub_w_f32(a.n_rows, d, int(block), int(sweeps), a.rowptr.data_ptr(), _ptr(a.col), a.nnz,
+                                                a.n_cols, Y.data_ptr(), ldy, G.data_ptr(), conf.data_ptr(), _ptr(reg_rows),
+                                                float(reg), x.data_ptr(), ldx, int(from_zero), rl_ptr, n_list, thr, hub_rows,
+                                                hub_chunks, n_failed.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
+                  "mi_als_block_rows_hub_w_f32")
+            return x, n_failed
+        ws = _ws_reused(L.mi_als_block_rows_hub_workspace_bytes(n_work, a.nnz, d, int(block), hub_rows, hub_chunks), Y.device)
+        check(L.mi_als_block_rows_hub_f32(a.n_rows, d, int(block), int(sweeps), a.rowptr.data_ptr(), _ptr(a.col), a.nnz,
+                                          a.n_cols, Y.data_ptr(), ldy, G.data_ptr(), float(alpha), float(reg), x.data_ptr(), ldx,
+                                          int(from_zero), rl_ptr, n_list, thr, hub_rows, hub_chunks, n_failed.data_ptr(),
+                                          ws.data_ptr(), ws.numel(), _stream()), "mi_als_block_rows_hub_f32")
+        return x, n_failed
     if weighted:
         conf, reg_rows = _als_weights(a, conf, reg_rows, alpha, Y.device)
         ws = _ws_reused(L.mi_als_block_rows_w_workspace_bytes(n_work, a.nnz, d, int(block)), Y.device)

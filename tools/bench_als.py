@@ -4,7 +4,7 @@ one process.  For each half-sweep the achieved rate of 2 d^2 nnz + rows d^3 / 3 
 peak.  One dense C2 LightGCN step (d = 128, 3 layers, batch 16 384) is timed in the same process for scale.
     python3 tools/bench_als.py [--shapes planted,c2,c3] [--dims 64,128] [--epochs 11] [--warmup 2] [--no-lightgcn]
                                [--solver cholesky|block|both] [--block 16,32] [--sweeps 1,2] [--dim D] [--fold-in]
-                               [--weighted] [--reg-power NU]
+                               [--weighted] [--reg-power NU] [--hub-threshold none,256,1024,4096]
 --solver block / both adds one line per (block, sweeps) with the block row solver (ops.als_block_rows) from the SAME initial
 tables as the Cholesky line of that (shape, d) — the yardstick, timed in the same run; d > 128 has the block lines only.  A
 block line also carries hub_ms: the one longest item row alone through row_list, i.e. the one wavefront the item
@@ -14,6 +14,10 @@ after 1, 2, 4 and 8 sweeps on the first 4 096 users: the relative distance to th
 with a_e == alpha on every edge (weights "constant": the same operands as the unweighted line, so the ratio of the two is the
 cost of the weighted kernels alone), then with a random weight per edge in [0.1, 30] / alpha and --reg-power NU (weights
 "random").  Each weighted line carries users_vs_unweighted / items_vs_unweighted, its time over the unweighted line's.
+--hub-threshold LIST repeats every block line per entry of the list: "none" is the block entry as it was (the yardstick, in the
+same run), an integer T takes the rows with more than T entries through the hub entries (ops.als_block_rows(hub_threshold=T)).
+Such a line carries hub_threshold, the hub rows and chunks of both sides, the larger of the two workspaces in bytes, and its
+hub_ms is the longest item row alone through row_list WITH that threshold.
 One JSON line per (shape, d, solver); the flop model of every line is the full solve's, so TF/s of a block line is a
 speed-up in disguise, not a rate."""
 import argparse, json, os, statistics, sys, time
@@ -40,9 +44,11 @@ ap.add_argument("--sweeps", default="1")
 ap.add_argument("--fold-in", action="store_true")
 ap.add_argument("--weighted", action="store_true")
 ap.add_argument("--reg-power", type=float, default=0.5)
+ap.add_argument("--hub-threshold", default="none")
 args = ap.parse_args()
 dims = [args.dim] if args.dim is not None else [int(x) for x in args.dims.split(",")]
-block_cfgs = [(int(b), int(s)) for b in args.block.split(",") for s in args.sweeps.split(",")]
+hub_thresholds = [None if x.strip().lower() == "none" else int(x) for x in args.hub_threshold.split(",")]
+block_cfgs = [(int(b), int(s), h) for b in args.block.split(",") for s in args.sweeps.split(",") for h in hub_thresholds]
 
 
 def half_sweep_ms(model, side):
@@ -75,9 +81,9 @@ for name in args.shapes.split(","):
     inter = Interactions(ei.cuda(), spec.num_users, spec.num_items)
     nnz = inter.num_edges
     for d in dims:
-        cfgs = [("cholesky", 16, 1)] if args.solver != "block" and d <= ops.ALS_MAX_DIM else []
+        cfgs = [("cholesky", 16, 1, None)] if args.solver != "block" and d <= ops.ALS_MAX_DIM else []
         if args.solver != "cholesky":
-            cfgs += [("block", b, s) for b, s in block_cfgs]
+            cfgs += [("block", b, s, h) for b, s, h in block_cfgs]
         model = ImplicitALS(spec.num_users, spec.num_items, dim=d, alpha=1.0, reg=20.0, seed=0, solver="block").cuda()
         model.bind(inter)
         start = (model.users_emb.weight.clone(), model.items_emb.weight.clone())
@@ -88,8 +94,8 @@ for name in args.shapes.split(","):
             lo, hi = t.log(t.tensor(0.1)).item(), t.log(t.tensor(30.0)).item()
             w_rand = t.exp(t.rand(nnz, generator=gen, device="cuda", dtype=t.float64) * (hi - lo) + lo) / model.alpha
             modes += [("constant", t.ones(nnz, dtype=t.float32, device="cuda"), 0.0), ("random", w_rand, args.reg_power)]
-        for (solver, block, sweeps), (weights, conf, nu) in ((c, m) for c in cfgs for m in modes):
-            model.solver, model.block, model.block_sweeps = solver, block, sweeps
+        for (solver, block, sweeps, hub_thr), (weights, conf, nu) in ((c, m) for c in cfgs for m in modes):
+            model.solver, model.block, model.block_sweeps, model.hub_threshold = solver, block, sweeps, hub_thr
             model.reg_power = nu
             model.reg = 20.0 if nu == 0.0 else 20.0 / (spec.num_items + nnz / spec.num_users) ** nu   # about 20 on a mean user row
             model.bind(inter, conf)
@@ -105,7 +111,15 @@ for name in args.shapes.split(","):
             out = {"shape": name, "users": spec.num_users, "items": spec.num_items, "nnz": nnz, "d": d, "solver": solver,
                    "epochs": args.epochs, "generate_s": round(gen_s, 1)}
             if solver == "block":
-                out.update(block=block, sweeps=sweeps)
+                out.update(block=block, sweeps=sweeps, hub_threshold=hub_thr)
+                if hub_thr is not None:
+                    L, ws = ops._lib.lib(), 0
+                    for side, k in (("users", 1), ("items", 2)):
+                        csr = model._bound[k]
+                        hr, hc = ops.als_hub_counts(csr, hub_thr, d)
+                        out[f"{side}_hub_rows"], out[f"{side}_hub_chunks"] = hr, hc
+                        ws = max(ws, int(L.mi_als_block_rows_hub_workspace_bytes(csr.n_rows, csr.nnz, d, block, hr, hc)))
+                    out["hub_workspace_bytes"] = ws
             if args.weighted:
                 out.update(weights=weights, reg_power=nu)
             for k, (side, rows) in enumerate((("users", spec.num_users), ("items", spec.num_items))):
@@ -132,9 +146,10 @@ for name in args.shapes.split(","):
                 x1 = model.items_emb.weight.data[hub.long()].clone()
                 out["hub_entries"] = int(deg.max().item())
                 out["hub_ms"] = round(timed(lambda: ops.als_block_rows(by_item, X, G, alpha=1.0, reg=20.0, block=block,
-                                                                       sweeps=sweeps, x=x1, row_list=hub), 5), 3)
+                                                                       sweeps=sweeps, x=x1, row_list=hub,
+                                                                       hub_threshold=hub_thr), 5), 3)
             print(json.dumps(out), flush=True)
-            if solver == "block" and weights == "none" and args.fold_in and sweeps == block_cfgs[0][1]:
+            if solver == "block" and weights == "none" and args.fold_in and sweeps == block_cfgs[0][1] and hub_thr is None:
                 by_user = model._bound[1]
                 rl = t.arange(min(4096, spec.num_users), dtype=t.int32, device="cuda")
                 Y = model.items_emb.weight.data
